@@ -35,6 +35,8 @@ WORKLOADS = {
     "gabls1_slab8": ("gabls1", 1024, 128, 256, "one rank's share (1024x128x256) of gabls1 1024x1024x256 fp32 on 8 GPUs, run alone, RHS only"),
 }
 FP32_RHS_ONLY = ("gabls1_1024", "gabls1_slab8")
+DUMP_BYTES = 60_000_000     # --dump-outputs: all arrays together stay under 64 MB
+DUMP_SEED = 20250           # --dump-outputs: the cells sampled from an interior too large to write whole
 
 
 def cpu_baseline(case, sample=(256, 256, 256), reps=3, with_pres=True):
@@ -150,6 +152,51 @@ def recorded_traffic(workload, igc=None):
             os.path.relpath(best[0], ROOT) + " (recorded by rocprofv3 PMC passes on these sources, not measured in this run)")
 
 
+def output_sample(hp, rhs_only, world):
+    """What the timed path leaves to its caller after a step, on this rank: the tendencies (with the pressure gradient removed
+    unless the workload is RHS only), the eddy viscosity of Smagorinsky cases and the pressure. Interior cells only. An interior
+    that fits the --dump-outputs budget comes whole, shape (kmax, jmax, imax); a larger one as the cells at a fixed, seeded set of
+    flat interior indices (sorted, the same on every rank and in every run with the same grid). Returns (arrays, description)."""
+    import torch
+    from microhh_amd.grid import DIFF_SMAG2
+    g = hp.grid
+    fields = [("ut", hp.ut), ("vt", hp.vt), ("wt", hp.wt)] + [("st%d" % n, t) for n, t in enumerate(hp.st)]
+    if hp.cfg["diff"] == DIFF_SMAG2:
+        fields.append(("evisc", hp.evisc))
+    if not rhs_only:
+        fields.append(("p", hp.p))
+    n = g.kmax * g.jmax * g.imax
+    cap = DUMP_BYTES // (len(fields) * g.np_dtype.itemsize * world)
+    hp.sync()
+    if n <= cap:
+        return {name: t.view(g.shape3)[g.interior].cpu().numpy().copy() for name, t in fields}, "whole interior, (ktot, jtot, itot)"
+    idx = np.unique(np.random.RandomState(DUMP_SEED).randint(0, n, size=cap))
+    k, j, i = idx // (g.jmax * g.imax), (idx // g.imax) % g.jmax, idx % g.imax
+    flat = torch.from_numpy((k + g.kstart) * g.ijcells + (j + g.jstart) * g.icells + (i + g.istart)).to(hp.device)
+    out = {name: t.reshape(-1).index_select(0, flat).cpu().numpy() for name, t in fields}
+    return out, ("%d cells of each rank's interior at flat indices np.unique(RandomState(%d).randint(0, %d, %d)), rank after rank"
+                 % (idx.size, DUMP_SEED, n, cap))
+
+
+def dump_outputs(path, arrays, world, rank):
+    """Rank 0 writes path/<name>.npy; with N ranks each array is the ranks' parts in rank order (slabs joined along y)."""
+    import torch.distributed as dist
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, arrays)
+    else:
+        parts = [arrays]
+    if rank != 0:
+        return None
+    os.makedirs(path, exist_ok=True)
+    shapes = {}
+    for name in arrays:
+        a = np.concatenate([p[name] for p in parts], axis=1 if arrays[name].ndim == 3 else 0)
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 SAMPLER = r"""
 import json, re, subprocess, sys, time
 for line in sys.stdin:
@@ -238,7 +285,12 @@ def main():
                     "calls Grid::set_minimum_ghost_cells (src/grid.cxx:435-439); 16 = rows of whole 128-byte lines at itot = 512 fp64. A second, NAMED line: "
                     "the headline stays on the reference default")
     ap.add_argument("--force-slab", action="store_true", help="N=1 only: run the slab code path (halo pack/unpack, split pressure solve) with local copies as exchanges")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (tendencies, eddy viscosity, pressure) as DIR/<name>.npy: "
+                         "the whole interior where it fits in 60 MB in all, a fixed seeded sample of its cells where not")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.build == "fma":
         os.environ["MHH_LIB"] = os.path.join(ROOT, "microhh_amd", "libmhh_hip_fma.so")
@@ -349,6 +401,11 @@ def main():
         tt = torch.tensor([elapsed], device=("cuda" if on_gpu and not args.share_gpu else "cpu"), dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    dumped = None
+    if args.dump_outputs:                # before anything after the timed region launches kernels on these fields
+        arrays, how = output_sample(hp, rhs_only, world)
+        shapes = dump_outputs(args.dump_outputs, arrays, world, rank)
+        dumped = {"dir": args.dump_outputs, "arrays": shapes, "cells": how}
     ms = 1e3 * elapsed / args.steps
     cells = itot * jtot * ktot
     rhs_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in events]))   # fused RHS kernel, this rank, ms per launch
@@ -378,6 +435,8 @@ def main():
         "alg_bytes_per_cell_full_step": hp.alg_bytes_rhs() + hp.alg_bytes_visc() + (0 if rhs_only else hp.alg_bytes_pres()),
         "hbm_frac_full_step": (hp.alg_bytes_rhs() + hp.alg_bytes_visc() + (0 if rhs_only else hp.alg_bytes_pres())) * local_cells / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
     }
+    if dumped:
+        out["outputs"] = dumped
     if not rhs_only:
         # self-check of the solve on the state the timed steps left behind (before anything else launches kernels on these fields) (every rank takes part: halos + MAX over ranks):
         # Pres::input -- the divergence of u/dt + ut, which Pres::exec has just removed -- beside the same of u, v, w alone

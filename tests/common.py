@@ -139,15 +139,15 @@ SMALL_GRIDS_2 = [
 ]
 
 
-def grid_2nd(itot=16, jtot=12, ktot=10, gc=(3, 3, 1), dtype=np.float64, stretched=True, **kw):
-    z = None
-    if stretched:
+def grid_2nd(itot=16, jtot=12, ktot=10, gc=(3, 3, 1), dtype=np.float64, stretched=True, z=None, **kw):
+    """z: a stored stretched profile instead of moser_z's (whose last bits follow the host's numpy)."""
+    if z is None and stretched:
         z = moser_z(ktot, 1200.)
     return Grid(itot, jtot, ktot, 3200., 3200., 1200., order=2, igc=gc[0], jgc=gc[1], kgc=gc[2], z=z, dtype=dtype, **kw)
 
 
-def grid_4th(itot=16, jtot=12, ktot=12, dtype=np.float64, **kw):
-    return Grid(itot, jtot, ktot, 2*np.pi, np.pi, 2., order=4, z=moser_z(ktot, 2.), dtype=dtype, **kw)
+def grid_4th(itot=16, jtot=12, ktot=12, dtype=np.float64, z=None, **kw):
+    return Grid(itot, jtot, ktot, 2*np.pi, np.pi, 2., order=4, z=moser_z(ktot, 2.) if z is None else z, dtype=dtype, **kw)
 
 
 def limiter_inputs(c, dtype):

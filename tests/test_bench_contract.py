@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 import backends as B
@@ -59,3 +60,18 @@ def test_bench_overlapped_path_two_ranks():
         else:
             os.environ["MHH_OVERLAP"] = env_was
     assert d["config"]["halo_overlap"] is False and d["value"] > 0
+
+
+def test_bench_dump_outputs_repeat(tmp_path):
+    """--dump-outputs DIR: what the last timed step computed, as DIR/<name>.npy (the rehearsal grid's interior is small enough to
+    come whole), and bit for bit the same in a second run with the same arguments."""
+    one, two = tmp_path / "one", tmp_path / "two"
+    d = _run(1, extra=["--dump-outputs", str(one)])
+    _run(1, extra=["--dump-outputs", str(two)])
+    names = sorted(os.listdir(one))
+    assert names == sorted(n + ".npy" for n in ("ut", "vt", "wt", "st0", "evisc", "p")), names
+    assert d["outputs"]["arrays"]["p"] == [10, 24, 16]
+    for n in names:
+        a, b = np.load(one / n), np.load(two / n)
+        assert a.dtype == np.float64 and a.shape == (10, 24, 16) and np.isfinite(a).all() and np.abs(a).max() > 0, n
+        assert np.array_equal(a, b), n
