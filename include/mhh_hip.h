@@ -313,7 +313,7 @@ int mhh_halo_pack_rows  (const mhh_grid* g, void* const* fields, int nfields, in
                          void* send_south, void* send_north, void* stream);
 int mhh_halo_unpack_rows(const mhh_grid* g, void* const* fields, int nfields, int rows_south, int rows_north,
                          const void* recv_from_south, const void* recv_from_north, void* stream);
-/* pres_2 split at the transposes. All-to-all buffers hold mhh_pres_slab_xbuf_elems() COMPLEX elements,
+/* pres_2 (and pres_4, below) split at the transposes. All-to-all buffers hold mhh_pres_slab_xbuf_elems() COMPLEX elements,
  * laid out [peer][k][jl][kxl] so that one equal-split all_to_all moves them.                               */
 typedef struct mhh_pres_slab_plan mhh_pres_slab_plan;
 int  mhh_pres_slab_plan_create(const mhh_grid* g, const void* host_dz, const void* host_dzhi,
@@ -343,6 +343,26 @@ int mhh_pres_solve_y         (mhh_pres_slab_plan* plan, const mhh_grid* g, void*
 int mhh_pres_bwd_y_chunk     (mhh_pres_slab_plan* plan, const mhh_grid* g, void* sendbuf, int c, void* stream);
 int mhh_pres_bwd_x_chunk     (mhh_pres_slab_plan* plan, const mhh_grid* g, void* recvbuf, int c, void* stream);
 int mhh_pres_unpack_output_slab(mhh_pres_slab_plan* plan, const mhh_grid* g, const mhh_fields* f, void* stream);
+/* pres_4 on the slab (src/pres_4.cxx:64-140; the reference's MPI decomposition swaps the mode indices after the x/y transpose as
+ * Pres_2 does, src/pres_4.cxx:327-470). mhh_pres_slab_plan_create_order is the slab counterpart of mhh_pres_plan_create
+ * (Pres_4::set_values, src/pres_4.cxx:179-252, from the HOST metrics dzi4 / dzhi4; order 2 reads dz, dzhi, rhoref, rhorefh and gives
+ * the plan of mhh_pres_slab_plan_create). Order 4 needs jgc >= 2, kgc >= 2, igc >= 2, kmax >= 4 and a 3-D grid (jtot > 1). Its plan
+ * keeps the LU factors of the 7-band system of every column of the rank (src/pres_4.cxx:358-470, 574-730): 7*(kmax+4)*nxb*jtot
+ * values, nxb = ceil((itot/2+1)/npy). Call order per solve (order 4):
+ *   north-south halo of vt, rows_south = 2, rows_north = 1 (the input reads vt[j-1..j+2], src/pres_4.cxx:312-315);
+ *   mhh_pres_input_packed(g, 4) into mhh_pres_slab_packed;  fwd_x_pack -> all-to-all -> fwd_y_solve_bwd_y -> all-to-all -> bwd_x_unpack
+ *   (or, k-sliced: the chunk calls above with solve_y, then mhh_pres_unpack_slab);
+ *   halo of p, rows_south = 1, rows_north = 2 (the output reads p[j-2..j+1], src/pres_4.cxx:555-569);  mhh_pres_output_order(g, 4).
+ * The unpack writes p's interior rows, its x halo and the four mirrored vertical ghost levels (src/pres_4.cxx:481-528). The fused
+ * Pres_2::output entry points (bwd_x_unpack_output, unpack_output_slab) and the LDS x stages (mhh_pres_slab_lds_*) refuse an order-4
+ * plan, mhh_pres_slab_has_lds returns 0 for it; mhh_pres_output_south_row takes no plan and is part of the order-2 sequence only. */
+int mhh_pres_slab_plan_create_order(const mhh_grid* g, int order /*2|4*/, const void* host_dz, const void* host_dzhi,
+                                    const void* host_dzi4, const void* host_dzhi4, const void* host_rhoref, const void* host_rhorefh,
+                                    mhh_pres_slab_plan** out);
+int mhh_pres_slab_order(const mhh_pres_slab_plan* plan);
+/* the unpack of mhh_pres_bwd_x_unpack alone (either order): the packed solution of the last bwd_x_chunk into p (src/pres_2.cxx:333-362,
+ * src/pres_4.cxx:481-528) */
+int mhh_pres_unpack_slab(mhh_pres_slab_plan* plan, const mhh_grid* g, const mhh_fields* f, void* stream);
 /* The x stages of the slab solve with the transforms in LDS (csrc/pres_lds.h; power-of-two itot, jmax a multiple of 8;
  * mhh_pres_slab_has_lds tells): Pres_2::input + the transform along x (src/pres_2.cxx:156-196, src/fft.cxx:451-497) of k-slice c
  * written straight into segment c of the send buffer of Transpose::exec_xy (src/transpose.cxx:170-193), and the transform back

@@ -122,6 +122,9 @@ SIGNATURES = {
     "mhh_pres_slab_lds_bwd": (ci, [PLAN, GP, vp, FP, ci, vp]),
     "mhh_pres_slab_lds_fwd_y": (ci, [PLAN, GP, vp, ci, vp]),
     "mhh_pres_slab_lds_bwd_y": (ci, [PLAN, GP, vp, ci, vp]),
+    "mhh_pres_slab_plan_create_order": (ci, [GP, ci, vp, vp, vp, vp, vp, vp, C.POINTER(PLAN)]),
+    "mhh_pres_slab_order": (ci, [PLAN]),
+    "mhh_pres_unpack_slab": (ci, [PLAN, GP, FP, vp]),
 }
 
 

@@ -60,34 +60,10 @@ struct mhh_pres_plan
 template<class TF> struct alignas(2*sizeof(TF)) C2 { TF x, y; };
 #include "pres_lds.h"
 #include "pres_lds4.h"
+#include "pres4_bands.h"
 
-// ---- host-side coefficient tables (Pres_2::set_values src/pres_2.cxx:125-153; Pres_4::set_values src/pres_4.cxx:179-252)
-template<class TF>
-static void host_bmat(int order, const mhh_grid* g, std::vector<TF>& bi, std::vector<TF>& bj)
-{
-    const int itot = g->itot, jtot = g->jtot;
-    const TF dx = TF(g->dx), dy = TF(g->dy);
-    const TF dxidxi = 1./(dx*dx), dyidyi = 1./(dy*dy);
-    const TF pi = std::acos(-1.);
-    bi.resize(itot); bj.resize(jtot);
-    if (order == 2)
-    {
-        for (int j=0; j<jtot/2+1; ++j) bj[j] = 2. * (std::cos(2.*pi*(TF)j/(TF)jtot)-1.) * dyidyi;
-        for (int i=0; i<itot/2+1; ++i) bi[i] = 2. * (std::cos(2.*pi*(TF)i/(TF)itot)-1.) * dxidxi;
-    }
-    else
-    {
-        for (int j=0; j<jtot/2+1; j++)
-            bj[j] = ( 2.* (1./576.) * std::cos(6.*pi*(double)j/(double)jtot) - 2.* (54./576.) * std::cos(4.*pi*(double)j/(double)jtot)
-                    + 2.* (783./576.) * std::cos(2.*pi*(double)j/(double)jtot) - (1460./576.) ) * dyidyi;
-        for (int i=0; i<itot/2+1; i++)
-            bi[i] = ( 2.* (1./576.) * std::cos(6.*pi*(double)i/(double)itot) - 2.* (54./576.) * std::cos(4.*pi*(double)i/(double)itot)
-                    + 2.* (783./576.) * std::cos(2.*pi*(double)i/(double)itot) - (1460./576.) ) * dxidxi;
-    }
-    for (int j=jtot/2+1; j<jtot; ++j) bj[j] = bj[jtot-j];
-    for (int i=itot/2+1; i<itot; ++i) bi[i] = bi[itot-i];
-}
-
+// ---- host-side coefficient tables (Pres_2::set_values src/pres_2.cxx:125-153; Pres_4::set_values src/pres_4.cxx:179-252):
+// host_bmat, host_pres4_bands (pres4_bands.h, shared with the slab plan)
 template<class TF>
 static int upload(void** dst, const std::vector<TF>& v)
 {
@@ -104,7 +80,7 @@ static int plan_tables(mhh_pres_plan* P, const mhh_grid* g, const void* hdz, con
     host_bmat<TF>(P->order, g, bi, bj);
     if (int e = upload(&P->bmati, bi)) return e;
     if (int e = upload(&P->bmatj, bj)) return e;
-    const int kmax = g->kmax, kgc = g->kgc, kstart = g->kstart;
+    const int kmax = g->kmax, kgc = g->kgc;
     if (P->order == 2)
     {
         const TF* dz = cp<TF>(hdz); const TF* dzhi = cp<TF>(hdzhi); const TF* rhoh = cp<TF>(hrhoh); const TF* rho = cp<TF>(hrho);
@@ -122,37 +98,9 @@ static int plan_tables(mhh_pres_plan* P, const mhh_grid* g, const void* hdz, con
     }
     else
     {
-        const TF* dzi4 = cp<TF>(hdzi4); const TF* h = cp<TF>(hdzhi4);
-        std::vector<TF> m1(kmax), m2(kmax), m3(kmax), m4(kmax), m5(kmax), m6(kmax), m7(kmax);
-        int k = 0, kc = kstart;
-        m1[k] = 0.;
-        m2[k] = (1./576.) * (               -  27.*h[kc]                            ) * dzi4[kc];
-        m3[k] = (1./576.) * ( -1.*h[kc+1] + 729.*h[kc] +  27.*h[kc+1]               ) * dzi4[kc];
-        m4[k] = (1./576.) * ( 27.*h[kc+1] - 729.*h[kc] - 729.*h[kc+1] -  1.*h[kc+2] ) * dzi4[kc];
-        m5[k] = (1./576.) * (-27.*h[kc+1] +  27.*h[kc] + 729.*h[kc+1] + 27.*h[kc+2] ) * dzi4[kc];
-        m6[k] = (1./576.) * (  1.*h[kc+1]              -  27.*h[kc+1] - 27.*h[kc+2] ) * dzi4[kc];
-        m7[k] = (1./576.) * (                                         +  1.*h[kc+2] ) * dzi4[kc];
-        for (k=1; k<kmax-1; k++)
-        {
-            kc = kstart+k;
-            m1[k] = (1./576.) * (   1.*h[kc-1]                                           ) * dzi4[kc];
-            m2[k] = (1./576.) * ( -27.*h[kc-1] -  27.*h[kc]                              ) * dzi4[kc];
-            m3[k] = (1./576.) * (  27.*h[kc-1] + 729.*h[kc] +  27.*h[kc+1]               ) * dzi4[kc];
-            m4[k] = (1./576.) * (  -1.*h[kc-1] - 729.*h[kc] - 729.*h[kc+1] -  1.*h[kc+2] ) * dzi4[kc];
-            m5[k] = (1./576.) * (              +  27.*h[kc] + 729.*h[kc+1] + 27.*h[kc+2] ) * dzi4[kc];
-            m6[k] = (1./576.) * (                           -  27.*h[kc+1] - 27.*h[kc+2] ) * dzi4[kc];
-            m7[k] = (1./576.) * (                                          +  1.*h[kc+2] ) * dzi4[kc];
-        }
-        k = kmax-1; kc = kstart+k;
-        m1[k] = (1./576.) * (   1.*h[kc-1]                                         ) * dzi4[kc];
-        m2[k] = (1./576.) * ( -27.*h[kc-1] -  27.*h[kc]                +  1.*h[kc] ) * dzi4[kc];
-        m3[k] = (1./576.) * (  27.*h[kc-1] + 729.*h[kc] +  27.*h[kc+1] - 27.*h[kc] ) * dzi4[kc];
-        m4[k] = (1./576.) * (  -1.*h[kc-1] - 729.*h[kc] - 729.*h[kc+1] + 27.*h[kc] ) * dzi4[kc];
-        m5[k] = (1./576.) * (              +  27.*h[kc] + 729.*h[kc+1] -  1.*h[kc] ) * dzi4[kc];
-        m6[k] = (1./576.) * (                           -  27.*h[kc+1]             ) * dzi4[kc];
-        m7[k] = 0.;
-        std::vector<TF>* mm[7] = {&m1, &m2, &m3, &m4, &m5, &m6, &m7};
-        for (int n=0; n<7; ++n) if (int e = upload(&P->m[n], *mm[n])) return e;
+        std::vector<TF> m[7];
+        host_pres4_bands<TF>(g, cp<TF>(hdzi4), cp<TF>(hdzhi4), m);
+        for (int n=0; n<7; ++n) if (int e = upload(&P->m[n], m[n])) return e;
     }
     return MHH_OK;
 }
@@ -436,56 +384,7 @@ static int tdma_factor(mhh_pres_plan* P)
 // (hdma_factor_kernel, the reference's elimination order) and kept: band n (0..6) at W[(n*(kmax+4) + k)*ncol + col].
 // Every solve is then the two substitution sweeps (hdma_solve_kernel), in place on the spectral array.
 // =======================================================================================================
-// one column: Wc = the column's element of band 0, row 0; row r of band n at Wc[n*bstride + r*ncol]
-template<class TF>
-__device__ __forceinline__ void hdma_factor_column(TF* __restrict__ Wc, size_t ncol, size_t bstride, TF bi, TF bj, bool mean,
-                                                   const TF* __restrict__ M1, const TF* __restrict__ M2, const TF* __restrict__ M3, const TF* __restrict__ M4,
-                                                   const TF* __restrict__ M5, const TF* __restrict__ M6, const TF* __restrict__ M7, int kmax)
-{
-    TF* __restrict__ m1 = Wc;             TF* __restrict__ m2 = Wc + bstride;   TF* __restrict__ m3 = Wc + 2*bstride; TF* __restrict__ m4 = Wc + 3*bstride;
-    TF* __restrict__ m5 = Wc + 4*bstride; TF* __restrict__ m6 = Wc + 5*bstride; TF* __restrict__ m7 = Wc + 6*bstride;
-#define A(arr, k) arr[(size_t)(k)*ncol]
-    // fill (rows 0,1: bottom bc; 2..kmax+1: interior; kmax+2, kmax+3: top bc)
-    A(m1,0)=0; A(m2,0)=0; A(m3,0)=0; A(m4,0)=1; A(m5,0)=0;  A(m6,0)=0; A(m7,0)=-1;
-    A(m1,1)=0; A(m2,1)=0; A(m3,1)=0; A(m4,1)=1; A(m5,1)=-1; A(m6,1)=0; A(m7,1)=0;
-    for (int k=0; k<kmax; ++k)
-    {
-        A(m1,k+2)=M1[k]; A(m2,k+2)=M2[k]; A(m3,k+2)=M3[k]; A(m4,k+2)=M4[k] + bi + bj;
-        A(m5,k+2)=M5[k]; A(m6,k+2)=M6[k]; A(m7,k+2)=M7[k];
-    }
-    const int t = kmax+2;
-    if (mean) { A(m1,t)=TF(0.);    A(m2,t)=TF(-1/3.); A(m3,t)=TF(2.);  A(m4,t)=TF(1.);
-                A(m1,t+1)=TF(-2.); A(m2,t+1)=TF(9.);  A(m3,t+1)=TF(0.); A(m4,t+1)=TF(1.); }
-    else      { A(m1,t)=TF(0.);    A(m2,t)=TF(0.);    A(m3,t)=TF(-1.); A(m4,t)=TF(1.);
-                A(m1,t+1)=TF(-1.); A(m2,t+1)=TF(0.);  A(m3,t+1)=TF(0.); A(m4,t+1)=TF(1.); }
-    A(m5,t)=0; A(m6,t)=0; A(m7,t)=0;
-    A(m5,t+1)=0; A(m6,t+1)=0; A(m7,t+1)=0;
-    // LU
-    int k = 0;
-    A(m1,k)=1; A(m2,k)=1; A(m3,k)=TF(1.)/A(m4,k); A(m4,k)=1; A(m5,k)=A(m5,k)*A(m3,k); A(m6,k)=A(m6,k)*A(m3,k); A(m7,k)=A(m7,k)*A(m3,k);
-    k = 1;
-    A(m1,k)=1; A(m2,k)=1; A(m3,k)=A(m3,k)/A(m4,k-1);
-    A(m4,k)=A(m4,k)-A(m3,k)*A(m5,k-1); A(m5,k)=A(m5,k)-A(m3,k)*A(m6,k-1); A(m6,k)=A(m6,k)-A(m3,k)*A(m7,k-1);
-    k = 2;
-    A(m1,k)=1; A(m2,k)=A(m2,k)/A(m4,k-2);
-    A(m3,k)=( A(m3,k) - A(m2,k)*A(m5,k-2) ) / A(m4,k-1);
-    A(m4,k)=A(m4,k) - A(m3,k)*A(m5,k-1) - A(m2,k)*A(m6,k-2);
-    A(m5,k)=A(m5,k) - A(m3,k)*A(m6,k-1) - A(m2,k)*A(m7,k-2);
-    A(m6,k)=A(m6,k) - A(m3,k)*A(m7,k-1);
-    for (k=3; k<kmax+4; ++k)
-    {
-        if (k == kmax+2) A(m7,kmax+1) = TF(1.);
-        A(m1,k)=( A(m1,k) ) / A(m4,k-3);
-        A(m2,k)=( A(m2,k) - A(m1,k)*A(m5,k-3) ) / A(m4,k-2);
-        A(m3,k)=( A(m3,k) - A(m2,k)*A(m5,k-2) - A(m1,k)*A(m6,k-3) ) / A(m4,k-1);
-        A(m4,k)=  A(m4,k) - A(m3,k)*A(m5,k-1) - A(m2,k)*A(m6,k-2) - A(m1,k)*A(m7,k-3);
-        if (k < kmax+3) A(m5,k)= A(m5,k) - A(m3,k)*A(m6,k-1) - A(m2,k)*A(m7,k-2);
-        if (k < kmax+2) A(m6,k)= A(m6,k) - A(m3,k)*A(m7,k-1);
-        if (k == kmax+2) { A(m6,k)=TF(1.); A(m7,k)=TF(1.); }
-        if (k == kmax+3) { A(m5,k)=TF(1.); A(m6,k)=TF(1.); A(m7,k)=TF(1.); }
-    }
-#undef A
-}
+// one column: hdma_factor_column (pres4_bands.h, shared with the slab plan)
 template<class TF>
 __global__ void __launch_bounds__(64) hdma_factor_kernel(TF* __restrict__ W,
                                                   const TF* __restrict__ bmati, const TF* __restrict__ bmatj,

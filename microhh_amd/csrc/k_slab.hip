@@ -11,6 +11,7 @@
 #include "fft_lifetime.h"
 #include "k_common.h"
 #include "pres_lds_slab.h"
+#include "pres4_bands.h"
 
 using namespace mhh;
 
@@ -91,7 +92,7 @@ MHH_API unsigned long long mhh_halo_buffer_elems(const mhh_grid* g, int nf)
 }
 
 // =======================================================================================================
-// Slab pressure solver (pres_2). Layouts, all complex interleaved, nxh = itot/2+1, nxb = ceil(nxh/npy):
+// Slab pressure solver (pres_2, pres_4). Layouts, all complex interleaved, nxh = itot/2+1, nxb = ceil(nxh/npy):
 //   specx [k][jl][kx]            after the local x transform (jl in this rank's jmax rows)
 //   xbuf  [q][k][jl][kxl]        all-to-all buffer, q = destination / source rank, kx = q*nxb + kxl (zero padded)
 //   specy [k][kxl][j]            after the exchange, j over the full jtot, unit stride for the y transform
@@ -100,9 +101,10 @@ template<class TF> struct alignas(2*sizeof(TF)) C2 { TF x, y; };   // naturally 
 
 struct mhh_pres_slab_plan
 {
-    int dtype = 0, itot = 0, jtot = 0, ktot = 0, jmax = 0, npy = 1, rank = 0, nxh = 0, nxb = 0;
+    int order = 2, dtype = 0, itot = 0, jtot = 0, ktot = 0, jmax = 0, npy = 1, rank = 0, nxh = 0, nxb = 0;
     size_t esz = 8;
     void* bmati = nullptr; void* bmatj = nullptr; void* a = nullptr; void* c = nullptr; void* dz = nullptr; void* rhoref = nullptr;
+    void* m[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};     // pres_4: the interior rows of the seven bands
     void* packed = nullptr; void* specx = nullptr; void* specy = nullptr; void* work = nullptr;
     rocfft_plan fx = nullptr, bx = nullptr, fy = nullptr, by = nullptr;
     // the same transforms over ONE k-slice of ktot / nchunks levels (mhh_pres_slab_set_chunks): slice c of the all-to-all can
@@ -149,6 +151,18 @@ static int slab_tables(mhh_pres_slab_plan* P, const mhh_grid* g, const void* hdz
     if (int e = up(&P->dz, dzk)) return e;
     return up(&P->rhoref, rk);
 }
+// Pres_4::set_values, src/pres_4.cxx:179-252: the single-GPU plan's own host tables (pres4_bands.h)
+template<class TF>
+static int slab_tables4(mhh_pres_slab_plan* P, const mhh_grid* g, const void* hdzi4, const void* hdzhi4)
+{
+    std::vector<TF> bi, bj, m[7];
+    host_bmat<TF>(4, g, bi, bj);
+    host_pres4_bands<TF>(g, cp<TF>(hdzi4), cp<TF>(hdzhi4), m);
+    if (int e = up(&P->bmati, bi)) return e;
+    if (int e = up(&P->bmatj, bj)) return e;
+    for (int n=0; n<7; ++n) if (int e = up(&P->m[n], m[n])) return e;
+    return MHH_OK;
+}
 
 static int plan1d(rocfft_plan* plan, rocfft_transform_type type, rocfft_result_placement place, int dtype, size_t n, size_t batch,
                   rocfft_array_type in_t, rocfft_array_type out_t, size_t in_dist, size_t out_dist, size_t* wbs)
@@ -173,26 +187,41 @@ MHH_API void mhh_pres_slab_plan_destroy(mhh_pres_slab_plan* P)
     for (rocfft_plan p : {P->fx, P->bx, P->fy, P->by, P->cfx, P->cbx, P->cfy, P->cby}) if (p) rocfft_plan_destroy(p);
     if (P->info) rocfft_execution_info_destroy(P->info);
     for (void* b : {P->bmati, P->bmatj, P->a, P->c, P->dz, P->rhoref, P->packed, P->specx, P->specy, P->work, P->wb}) if (b) (void)hipFree(b);
+    for (void* b : P->m) if (b) (void)hipFree(b);
     delete P;
 }
 
-static int slab_factor(mhh_pres_slab_plan* P);     // tdma_slab_factor_kernel launch, defined with the kernel
-MHH_API int mhh_pres_slab_plan_create(const mhh_grid* g, const void* host_dz, const void* host_dzhi, const void* host_rhoref, const void* host_rhorefh,
-                                      mhh_pres_slab_plan** out)
+static int slab_factor(mhh_pres_slab_plan* P);     // tdma_slab_factor_kernel / hdma_slab_factor_kernel launch, defined with the kernels
+MHH_API int mhh_pres_slab_plan_create_order(const mhh_grid* g, int order, const void* host_dz, const void* host_dzhi, const void* host_dzi4, const void* host_dzhi4,
+                                            const void* host_rhoref, const void* host_rhorefh, mhh_pres_slab_plan** out)
 {
     if (int e = check_grid(g)) return e;
-    MHH_REQUIRE(out && host_dz && host_dzhi && host_rhoref && host_rhorefh, "null pointer");
+    MHH_REQUIRE(out != nullptr, "out");
+    MHH_REQUIRE(order == 2 || order == 4, "order must be 2 or 4");
     MHH_REQUIRE(g->npy >= 1 && g->jtot % g->npy == 0 && g->jmax == g->jtot / g->npy && g->imax == g->itot, "slab grid: jmax = jtot/npy, imax = itot");
     MHH_REQUIRE(g->mpicoordy >= 0 && g->mpicoordy < g->npy, "mpicoordy");
-    MHH_REQUIRE(g->jtot > 1 && g->kgc >= 1 && g->igc >= 1 && g->jgc >= 1, "pres_2 slab needs a 3-D grid with 1 ghost cell");
+    if (order == 2)
+    {
+        MHH_REQUIRE(host_dz && host_dzhi && host_rhoref && host_rhorefh, "null pointer");
+        MHH_REQUIRE(g->jtot > 1 && g->kgc >= 1 && g->igc >= 1 && g->jgc >= 1, "pres_2 slab needs a 3-D grid with 1 ghost cell");
+    }
+    else
+    {
+        MHH_REQUIRE(host_dzi4 && host_dzhi4, "null pointer");
+        MHH_REQUIRE(g->jtot > 1 && g->kgc >= 2 && g->igc >= 2 && g->jgc >= 2 && g->kmax >= 4, "pres_4 slab needs a 3-D grid with 2 ghost cells and kmax >= 4");
+    }
     mhh_pres_slab_plan* P = new mhh_pres_slab_plan();
-    P->dtype = g->dtype; P->itot = g->itot; P->jtot = g->jtot; P->ktot = g->ktot; P->jmax = g->jmax; P->npy = g->npy; P->rank = g->mpicoordy;
+    P->order = order; P->dtype = g->dtype; P->itot = g->itot; P->jtot = g->jtot; P->ktot = g->ktot; P->jmax = g->jmax; P->npy = g->npy; P->rank = g->mpicoordy;
     P->nxh = g->itot/2 + 1; P->nxb = (P->nxh + g->npy - 1) / g->npy; P->esz = (g->dtype == MHH_F64) ? 8 : 4;
-    int e = (g->dtype == MHH_F64) ? slab_tables<double>(P, g, host_dz, host_dzhi, host_rhoref, host_rhorefh)
-                                  : slab_tables<float>(P, g, host_dz, host_dzhi, host_rhoref, host_rhorefh);
+    int e = (order == 4) ? ((g->dtype == MHH_F64) ? slab_tables4<double>(P, g, host_dzi4, host_dzhi4) : slab_tables4<float>(P, g, host_dzi4, host_dzhi4))
+                         : ((g->dtype == MHH_F64) ? slab_tables<double>(P, g, host_dz, host_dzhi, host_rhoref, host_rhorefh)
+                                                  : slab_tables<float>(P, g, host_dz, host_dzhi, host_rhoref, host_rhorefh));
     const size_t nreal = (size_t)g->itot*g->jmax*g->ktot, nx = (size_t)P->nxh*g->jmax*g->ktot, ny = (size_t)P->nxb*g->jtot*g->ktot;
+    // the factors of every column, computed below: pres_2 the pivots w2 and the eliminated upper diagonal w3 (kmax levels each),
+    // pres_4 the seven LU bands of the kmax+4 rows
+    const size_t nwork = (order == 2) ? 2*ny : (size_t)7*(g->ktot + 4)*P->nxb*g->jtot;
     auto alloc = [&](void** p, size_t bytes) { if (e) return; hipError_t h = hipMalloc(p, bytes); if (h != hipSuccess) { set_error("hipMalloc: %s", hipGetErrorString(h)); e = MHH_ENOMEM; } };
-    alloc(&P->packed, nreal*P->esz); alloc(&P->specx, nx*2*P->esz); alloc(&P->specy, ny*2*P->esz); alloc(&P->work, 2*ny*P->esz);          // pivots w2 and eliminated upper diagonal w3 of every column, factored below
+    alloc(&P->packed, nreal*P->esz); alloc(&P->specx, nx*2*P->esz); alloc(&P->specy, ny*2*P->esz); alloc(&P->work, nwork*P->esz);
     if (!e)
     {
         fft_acquire();
@@ -210,11 +239,17 @@ MHH_API int mhh_pres_slab_plan_create(const mhh_grid* g, const void* host_dz, co
         }
     }
     if (!e) e = slab_factor(P);
-    if (!e && lds_slab_usable(g)) { e = lds_slab_twiddles(g, &P->tx_lds); if (!e) e = lds_slab_twiddles_y(g, &P->ty_lds); }      // the transforms in LDS
+    if (!e && order == 2 && lds_slab_usable(g)) { e = lds_slab_twiddles(g, &P->tx_lds); if (!e) e = lds_slab_twiddles_y(g, &P->ty_lds); }      // the transforms in LDS
     if (e) { mhh_pres_slab_plan_destroy(P); return e; }
     *out = P;
     return MHH_OK;
 }
+MHH_API int mhh_pres_slab_plan_create(const mhh_grid* g, const void* host_dz, const void* host_dzhi, const void* host_rhoref, const void* host_rhorefh,
+                                      mhh_pres_slab_plan** out)
+{
+    return mhh_pres_slab_plan_create_order(g, 2, host_dz, host_dzhi, nullptr, nullptr, host_rhoref, host_rhorefh, out);
+}
+MHH_API int mhh_pres_slab_order(const mhh_pres_slab_plan* P) { return P ? P->order : 0; }
 MHH_API unsigned long long mhh_pres_slab_xbuf_elems(const mhh_pres_slab_plan* P)   // complex elements of one all-to-all buffer
 {
     return (unsigned long long)P->npy * P->ktot * P->jmax * P->nxb;
@@ -415,31 +450,187 @@ __global__ void __launch_bounds__(128) tdma_slab_kernel(TF* __restrict__ p, cons
     }
 }
 
+// The 7-band solve of pres_4 (src/pres_4.cxx:358-470 matrix, :574-730 hdma) on the rank's (x-block, all y) columns. Latency-bound
+// like the Thomas sweep above (33 x 256 columns per rank at moser600 on 8 GPUs: a quarter of a wave per SIMD, 260 dependent rows per
+// sweep), and organised the same way:
+//   * the LU factors depend on the grid and (kx, ky) only: computed ONCE at plan creation by the single-GPU plan's own column
+//     factorisation (hdma_factor_column, pres4_bands.h) in the slab column order col = kxl*jtot + ky, band n (0..6), row r at
+//     W[(n*(kmax+4) + r)*ncol + col] -- 7*(kmax+4)*nxb*jtot values. The pivots (band 3) are kept as reciprocals (as the LDS
+//     form's pres4_lds_factor_kernel does), so that no division is left in the sweeps;
+//   * one thread per (ky, re|im) component, in place on specy [k][kxl][ky] (row r of the system = level r-2; the two boundary rows
+//     on either side carry a zero right-hand side and live in registers);
+//   * the right-hand side and the factors of the next U levels are loaded while the U current levels run through the
+//     recurrence, whose terms are ordered so that only one multiply-subtract (and the multiply by the reciprocal pivot on the way
+//     back) waits for the row before.
+template<class TF>
+__global__ void __launch_bounds__(64) hdma_slab_factor_kernel(TF* __restrict__ W, const TF* __restrict__ bmati, const TF* __restrict__ bmatj,
+                                                              const TF* __restrict__ M1, const TF* __restrict__ M2, const TF* __restrict__ M3, const TF* __restrict__ M4,
+                                                              const TF* __restrict__ M5, const TF* __restrict__ M6, const TF* __restrict__ M7,
+                                                              int nxh, int nxb, int kx0, int jtot, int kmax)
+{
+    const int ky = blockIdx.x*64 + threadIdx.x, kxl = blockIdx.y;
+    const int kx = kx0 + kxl;
+    if (ky >= jtot || kx >= nxh) return;
+    const size_t ncol = (size_t)nxb*jtot, col = (size_t)kxl*jtot + ky, bstride = (size_t)(kmax+4)*ncol;
+    TF* __restrict__ Wc = W + col;
+    hdma_factor_column(Wc, ncol, bstride, bmati[kx], bmatj[ky], kx == 0 && ky == 0, M1, M2, M3, M4, M5, M6, M7, kmax);
+    for (int r=0; r<kmax+4; ++r) Wc[3*bstride + (size_t)r*ncol] = TF(1.) / Wc[3*bstride + (size_t)r*ncol];
+}
+template<class TF>
+__global__ void __launch_bounds__(128) hdma_slab_kernel(TF* __restrict__ p, const TF* __restrict__ W, int nxh, int nxb, int kx0, int jtot, int kmax)
+{
+#ifndef MHH_SLAB4_U
+#define MHH_SLAB4_U 8          // levels in flight per thread
+#endif
+    constexpr int U = MHH_SLAB4_U;
+    const int t = blockIdx.x*128 + threadIdx.x;           // 0 .. 2*jtot-1
+    const int ky = t >> 1, comp = t & 1, kxl = blockIdx.y;
+    const int kx = kx0 + kxl;
+    if (ky >= jtot || kx >= nxh) return;
+    const size_t ncol = (size_t)nxb*jtot, col = (size_t)kxl*jtot + ky, bs = (size_t)(kmax+4)*ncol;
+    TF* __restrict__ q = p + 2*col + comp;                 // level l of this component at q[2*l*ncol]
+    const TF* __restrict__ m1 = W + col;        const TF* __restrict__ m2 = m1 + bs;   const TF* __restrict__ m3 = m1 + 2*bs;
+    const TF* __restrict__ r4 = m1 + 3*bs;      const TF* __restrict__ m5 = m1 + 4*bs; const TF* __restrict__ m6 = m1 + 5*bs;
+    const TF* __restrict__ m7 = m1 + 6*bs;
+#define A(arr, r) arr[(size_t)(r)*ncol]
+    // the factors of the two top rows (kmax+2, kmax+3), needed between the sweeps
+    const int rt = kmax+2;
+    const TF t1a = A(m1,rt), t2a = A(m2,rt), t3a = A(m3,rt), t1b = A(m1,rt+1), t2b = A(m2,rt+1), t3b = A(m3,rt+1);
+    const TF r4a = A(r4,rt), r4b = A(r4,rt+1), t5a = A(m5,rt);
+    // L y = q: y_r = q_r - m1_r y_{r-3} - m2_r y_{r-2} - m3_r y_{r-1}; rows 0 and 1 give y = 0
+    TF a1 = TF(0), a2 = TF(0), a3 = TF(0);                 // y_{r-1}, y_{r-2}, y_{r-3}
+    {
+        TF qc[U], c1[U], c2[U], c3[U];
+#pragma unroll
+        for (int u=0; u<U; ++u) { const int l = u; const bool ok = l < kmax; const int r = ok ? l+2 : 0;
+                                  qc[u] = ok ? q[2*(size_t)l*ncol] : TF(0); c1[u] = A(m1,r); c2[u] = A(m2,r); c3[u] = A(m3,r); }
+        for (int l0=0; l0<kmax; l0+=U)
+        {
+            TF qn[U], n1[U], n2[U], n3[U];
+#pragma unroll
+            for (int u=0; u<U; ++u) { const int l = l0 + U + u; const bool ok = l < kmax; const int r = ok ? l+2 : 0;
+                                      qn[u] = ok ? q[2*(size_t)l*ncol] : TF(0); n1[u] = A(m1,r); n2[u] = A(m2,r); n3[u] = A(m3,r); }
+#pragma unroll
+            for (int u=0; u<U; ++u)
+            {
+                const int l = l0 + u;
+                if (l < kmax)
+                {
+                    TF v = qc[u] - c1[u]*a3;
+                    v -= c2[u]*a2;
+                    v -= c3[u]*a1;
+                    q[2*(size_t)l*ncol] = v;
+                    a3 = a2; a2 = a1; a1 = v;
+                }
+            }
+#pragma unroll
+            for (int u=0; u<U; ++u) { qc[u] = qn[u]; c1[u] = n1[u]; c2[u] = n2[u]; c3[u] = n3[u]; }
+        }
+    }
+    TF ya = TF(0) - t1a*a3; ya -= t2a*a2; ya -= t3a*a1;    // row kmax+2
+    TF yb = TF(0) - t1b*a2; yb -= t2b*a1; yb -= t3b*ya;    // row kmax+3
+    // U x = y: x_r = (y_r - m7_r x_{r+3} - m6_r x_{r+2} - m5_r x_{r+1}) / m4_r, from the top
+    TF b2 = yb * r4b;                                      // x_{kmax+3}
+    TF b1 = (ya - t5a*b2) * r4a;                           // x_{kmax+2}
+    TF b3 = TF(0);                                         // (no row kmax+4)
+    {
+        TF qc[U], c5[U], c6[U], c7[U], c4[U];
+#pragma unroll
+        for (int u=0; u<U; ++u) { const int l = kmax-1 - u; const bool ok = l >= 0; const int r = ok ? l+2 : 0;
+                                  qc[u] = ok ? q[2*(size_t)l*ncol] : TF(0); c5[u] = A(m5,r); c6[u] = A(m6,r); c7[u] = A(m7,r); c4[u] = A(r4,r); }
+        for (int l0=kmax-1; l0>=0; l0-=U)
+        {
+            TF qn[U], n5[U], n6[U], n7[U], n4[U];
+#pragma unroll
+            for (int u=0; u<U; ++u) { const int l = l0 - U - u; const bool ok = l >= 0; const int r = ok ? l+2 : 0;
+                                      qn[u] = ok ? q[2*(size_t)l*ncol] : TF(0); n5[u] = A(m5,r); n6[u] = A(m6,r); n7[u] = A(m7,r); n4[u] = A(r4,r); }
+#pragma unroll
+            for (int u=0; u<U; ++u)
+            {
+                const int l = l0 - u;
+                if (l >= 0)
+                {
+                    TF v = qc[u] - c7[u]*b3;
+                    v -= c6[u]*b2;
+                    v -= c5[u]*b1;
+                    v *= c4[u];
+                    q[2*(size_t)l*ncol] = v;
+                    b3 = b2; b2 = b1; b1 = v;
+                }
+            }
+#pragma unroll
+            for (int u=0; u<U; ++u) { qc[u] = qn[u]; c5[u] = n5[u]; c6[u] = n6[u]; c7[u] = n7[u]; c4[u] = n4[u]; }
+        }
+    }
+#undef A
+}
+
 static int slab_factor(mhh_pres_slab_plan* P)
 {
     dim3 gf((P->jtot + 63)/64, P->nxb);
     const size_t ny = (size_t)P->nxb*P->jtot*P->ktot;
-    if (P->dtype == MHH_F64)
+    if (P->order == 4)
+    {
+#define M7(TF) cp<TF>(P->m[0]), cp<TF>(P->m[1]), cp<TF>(P->m[2]), cp<TF>(P->m[3]), cp<TF>(P->m[4]), cp<TF>(P->m[5]), cp<TF>(P->m[6])
+        if (P->dtype == MHH_F64)
+            hipLaunchKernelGGL(hdma_slab_factor_kernel<double>, gf, dim3(64), 0, 0, (double*)P->work, cp<double>(P->bmati), cp<double>(P->bmatj), M7(double),
+                               P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
+        else
+            hipLaunchKernelGGL(hdma_slab_factor_kernel<float>, gf, dim3(64), 0, 0, (float*)P->work, cp<float>(P->bmati), cp<float>(P->bmatj), M7(float),
+                               P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
+#undef M7
+    }
+    else if (P->dtype == MHH_F64)
         hipLaunchKernelGGL(tdma_slab_factor_kernel<double>, gf, dim3(64), 0, 0, (double*)P->work, (double*)P->work + ny, cp<double>(P->bmati), cp<double>(P->bmatj),
                            cp<double>(P->a), cp<double>(P->c), cp<double>(P->dz), cp<double>(P->rhoref), P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
     else
         hipLaunchKernelGGL(tdma_slab_factor_kernel<float>, gf, dim3(64), 0, 0, (float*)P->work, (float*)P->work + ny, cp<float>(P->bmati), cp<float>(P->bmatj),
                            cp<float>(P->a), cp<float>(P->c), cp<float>(P->dz), cp<float>(P->rhoref), P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
     hipError_t h = hipGetLastError(); if (h == hipSuccess) h = hipStreamSynchronize(0);
-    if (h != hipSuccess) { set_error("tdma_slab_factor: %s", hipGetErrorString(h)); return MHH_EHIP; }
+    if (h != hipSuccess) { set_error("%s: %s", P->order == 4 ? "hdma_slab_factor" : "tdma_slab_factor", hipGetErrorString(h)); return MHH_EHIP; }
+    return MHH_OK;
+}
+// the k-sweeps of every column of the rank's slab on specy: Thomas (pres_2) or the factored 7-band substitution (pres_4)
+static int slab_column_solve(mhh_pres_slab_plan* P, hipStream_t st)
+{
+    const size_t ny = (size_t)P->nxb*P->jtot*P->ktot;
+    dim3 gs((2*P->jtot + 127)/128, P->nxb);
+    if (P->order == 4)
+    {
+        if (P->dtype == MHH_F64) hipLaunchKernelGGL(hdma_slab_kernel<double>, gs, dim3(128), 0, st, (double*)P->specy, cp<double>(P->work), P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
+        else                     hipLaunchKernelGGL(hdma_slab_kernel<float>,  gs, dim3(128), 0, st, (float*)P->specy,  cp<float>(P->work),  P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
+    }
+    else if (P->dtype == MHH_F64)
+        hipLaunchKernelGGL(tdma_slab_kernel<double>, gs, dim3(128), 0, st, (double*)P->specy, cp<double>(P->work), cp<double>(P->work) + ny,
+                           cp<double>(P->a), cp<double>(P->dz), P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
+    else
+        hipLaunchKernelGGL(tdma_slab_kernel<float>, gs, dim3(128), 0, st, (float*)P->specy, cp<float>(P->work), cp<float>(P->work) + ny,
+                           cp<float>(P->a), cp<float>(P->dz), P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
+    MHH_LAUNCH_CHECK();
     return MHH_OK;
 }
 
-// packed real [k][jl][i] -> ghosted p: interior rows + x halo (wrap) + bottom ghost level; the y halo is the caller's exchange
+// packed real [k][jl][i] -> ghosted p: interior rows + x halo (wrap) + the mirrored vertical ghost levels (src/pres_2.cxx:333-362:
+// the bottom one; src/pres_4.cxx:481-528: two at the bottom, two at the top); the y halo is the caller's exchange.
+// blockIdx.z = kmax + 1 (pres_2) or kmax + 4 (pres_4) levels.
 template<class TF>
-__global__ void __launch_bounds__(256) unpack_slab_kernel(TF* __restrict__ p, const TF* __restrict__ packed, int itot, int jtot, int jmax, int kmax,
+__global__ void __launch_bounds__(256) unpack_slab_kernel(TF* __restrict__ p, const TF* __restrict__ packed, int order, int itot, int jtot, int jmax, int kmax,
                                                           int igc, int jgc, int kgc, int icells, int jcells)
 {
     const int i = blockIdx.x*256 + threadIdx.x;
     const int jl = blockIdx.y, kz = blockIdx.z;
     if (i >= icells) return;
-    const int kd = (kz < kmax) ? kz + kgc : kgc - 1;
-    const int ks = (kz < kmax) ? kz : 0;
+    int kd, ks;
+    if (kz < kmax)       { kd = kz + kgc;      ks = kz; }
+    else if (order == 2) { kd = kgc - 1;       ks = 0; }          // p[kstart-1] = p[kstart]
+    else
+    {
+        const int gidx = kz - kmax;                                 // 0..3
+        if (gidx == 0)      { kd = kgc - 1;        ks = 0; }        // p[kstart-1] = p[kstart]
+        else if (gidx == 1) { kd = kgc - 2;        ks = 1; }        // p[kstart-2] = p[kstart+1]
+        else if (gidx == 2) { kd = kgc + kmax;     ks = kmax-1; }   // p[kend]     = p[kend-1]
+        else                { kd = kgc + kmax + 1; ks = kmax-2; }   // p[kend+1]   = p[kend-2]
+    }
     int is = (i - igc) % itot; if (is < 0) is += itot;
     const TF val = packed[(size_t)is + (size_t)jl*itot + (size_t)ks*itot*jmax] / jtot / itot;
     p[(size_t)i + (size_t)(jl + jgc)*icells + (size_t)kd*icells*jcells] = val;
@@ -511,7 +702,7 @@ MHH_API int mhh_pres_fwd_x_pack(mhh_pres_slab_plan* P, const mhh_grid* g, void* 
     MHH_LAUNCH_CHECK();
     return MHH_OK;
 }
-// stage 2: after the forward all-to-all: y transform, tridiagonal solves, inverse y transform, pack for the way back
+// stage 2: after the forward all-to-all: y transform, tridiagonal (pres_2) or 7-band (pres_4) solves, inverse y transform, pack for the way back
 MHH_API int mhh_pres_fwd_y_solve_bwd_y(mhh_pres_slab_plan* P, const mhh_grid* g, void* recvbuf, void* sendbuf, void* stream)
 {
     if (int e = slab_match(P, g)) return e;
@@ -519,16 +710,13 @@ MHH_API int mhh_pres_fwd_y_solve_bwd_y(mhh_pres_slab_plan* P, const mhh_grid* g,
     hipStream_t st = as_stream(stream);
     MHH_FFT_TRY(rocfft_execution_info_set_stream(P->info, st));
     dim3 gy((unsigned)(((P->nxb + 31)/32) * ((P->jmax + 63)/64) * P->npy), P->ktot);
-    dim3 gs((2*P->jtot + 127)/128, P->nxb);
     void* io[1] = {P->specy};
     if (g->dtype == MHH_F64)
     {
         hipLaunchKernelGGL((xbuf_y_kernel<double, true>), gy, dim3(256), 0, st, (C2<double>*)P->specy, (C2<double>*)recvbuf, P->nxb, P->jmax, P->jtot, P->ktot);
         MHH_LAUNCH_CHECK();
         MHH_FFT_TRY(rocfft_execute(P->fy, io, nullptr, P->info));
-        hipLaunchKernelGGL(tdma_slab_kernel<double>, gs, dim3(128), 0, st, (double*)P->specy, cp<double>(P->work), cp<double>(P->work) + (size_t)P->nxb*P->jtot*P->ktot,
-                           cp<double>(P->a), cp<double>(P->dz), P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
-        MHH_LAUNCH_CHECK();
+        if (int e = slab_column_solve(P, st)) return e;
         MHH_FFT_TRY(rocfft_execute(P->by, io, nullptr, P->info));
         hipLaunchKernelGGL((xbuf_y_kernel<double, false>), gy, dim3(256), 0, st, (C2<double>*)P->specy, (C2<double>*)sendbuf, P->nxb, P->jmax, P->jtot, P->ktot);
     }
@@ -537,16 +725,25 @@ MHH_API int mhh_pres_fwd_y_solve_bwd_y(mhh_pres_slab_plan* P, const mhh_grid* g,
         hipLaunchKernelGGL((xbuf_y_kernel<float, true>), gy, dim3(256), 0, st, (C2<float>*)P->specy, (C2<float>*)recvbuf, P->nxb, P->jmax, P->jtot, P->ktot);
         MHH_LAUNCH_CHECK();
         MHH_FFT_TRY(rocfft_execute(P->fy, io, nullptr, P->info));
-        hipLaunchKernelGGL(tdma_slab_kernel<float>, gs, dim3(128), 0, st, (float*)P->specy, cp<float>(P->work), cp<float>(P->work) + (size_t)P->nxb*P->jtot*P->ktot,
-                           cp<float>(P->a), cp<float>(P->dz), P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
-        MHH_LAUNCH_CHECK();
+        if (int e = slab_column_solve(P, st)) return e;
         MHH_FFT_TRY(rocfft_execute(P->by, io, nullptr, P->info));
         hipLaunchKernelGGL((xbuf_y_kernel<float, false>), gy, dim3(256), 0, st, (C2<float>*)P->specy, (C2<float>*)sendbuf, P->nxb, P->jmax, P->jtot, P->ktot);
     }
     MHH_LAUNCH_CHECK();
     return MHH_OK;
 }
-// stage 3: after the backward all-to-all: inverse x transform, normalise, write p (interior rows, x halo, bottom ghost level)
+// the unpack of the packed solution into p (unpack_slab_kernel) on `st`
+static int slab_unpack(mhh_pres_slab_plan* P, const mhh_grid* g, const mhh_fields* f, hipStream_t st)
+{
+    dim3 ug((g->icells + 255)/256, g->jmax, g->kmax + (P->order == 2 ? 1 : 4));
+    if (g->dtype == MHH_F64)
+        hipLaunchKernelGGL(unpack_slab_kernel<double>, ug, dim3(256), 0, st, mp<double>(f->p), cp<double>(P->packed), P->order, g->itot, g->jtot, g->jmax, g->kmax, g->igc, g->jgc, g->kgc, g->icells, g->jcells);
+    else
+        hipLaunchKernelGGL(unpack_slab_kernel<float>, ug, dim3(256), 0, st, mp<float>(f->p), cp<float>(P->packed), P->order, g->itot, g->jtot, g->jmax, g->kmax, g->igc, g->jgc, g->kgc, g->icells, g->jcells);
+    MHH_LAUNCH_CHECK();
+    return MHH_OK;
+}
+// stage 3: after the backward all-to-all: inverse x transform, normalise, write p (interior rows, x halo, vertical ghost levels)
 MHH_API int mhh_pres_bwd_x_unpack(mhh_pres_slab_plan* P, const mhh_grid* g, void* recvbuf, const mhh_fields* f, void* stream)
 {
     if (int e = slab_match(P, g)) return e;
@@ -554,30 +751,26 @@ MHH_API int mhh_pres_bwd_x_unpack(mhh_pres_slab_plan* P, const mhh_grid* g, void
     hipStream_t st = as_stream(stream);
     MHH_FFT_TRY(rocfft_execution_info_set_stream(P->info, st));
     dim3 grid((P->npy*P->nxb + 255)/256, P->jmax, P->ktot);
-    dim3 ug((g->icells + 255)/256, g->jmax, g->kmax + 1);
     void* in[1] = {P->specx}; void* out[1] = {P->packed};
-    if (g->dtype == MHH_F64)
-    {
-        hipLaunchKernelGGL((xbuf_x_kernel<double, false>), grid, dim3(256), 0, st, (C2<double>*)P->specx, (C2<double>*)recvbuf, P->nxh, P->nxb, P->jmax, P->ktot, P->npy);
-        MHH_LAUNCH_CHECK();
-        MHH_FFT_TRY(rocfft_execute(P->bx, in, out, P->info));
-        hipLaunchKernelGGL(unpack_slab_kernel<double>, ug, dim3(256), 0, st, mp<double>(f->p), cp<double>(P->packed), g->itot, g->jtot, g->jmax, g->kmax, g->igc, g->jgc, g->kgc, g->icells, g->jcells);
-    }
-    else
-    {
-        hipLaunchKernelGGL((xbuf_x_kernel<float, false>), grid, dim3(256), 0, st, (C2<float>*)P->specx, (C2<float>*)recvbuf, P->nxh, P->nxb, P->jmax, P->ktot, P->npy);
-        MHH_LAUNCH_CHECK();
-        MHH_FFT_TRY(rocfft_execute(P->bx, in, out, P->info));
-        hipLaunchKernelGGL(unpack_slab_kernel<float>, ug, dim3(256), 0, st, mp<float>(f->p), cp<float>(P->packed), g->itot, g->jtot, g->jmax, g->kmax, g->igc, g->jgc, g->kgc, g->icells, g->jcells);
-    }
+    if (g->dtype == MHH_F64) hipLaunchKernelGGL((xbuf_x_kernel<double, false>), grid, dim3(256), 0, st, (C2<double>*)P->specx, (C2<double>*)recvbuf, P->nxh, P->nxb, P->jmax, P->ktot, P->npy);
+    else                     hipLaunchKernelGGL((xbuf_x_kernel<float, false>), grid, dim3(256), 0, st, (C2<float>*)P->specx, (C2<float>*)recvbuf, P->nxh, P->nxb, P->jmax, P->ktot, P->npy);
     MHH_LAUNCH_CHECK();
-    return MHH_OK;
+    MHH_FFT_TRY(rocfft_execute(P->bx, in, out, P->info));
+    return slab_unpack(P, g, f, st);
+}
+// the unpack alone, after the last mhh_pres_bwd_x_chunk of a k-sliced solve
+MHH_API int mhh_pres_unpack_slab(mhh_pres_slab_plan* P, const mhh_grid* g, const mhh_fields* f, void* stream)
+{
+    if (int e = slab_match(P, g)) return e;
+    MHH_REQUIRE(f && f->p, "buffers");
+    return slab_unpack(P, g, f, as_stream(stream));
 }
 // stage 3, fused form: inverse x transform, then unpack + Pres_2::output in one kernel for everything but vt on the southernmost
 // row; the caller exchanges the one-row halo of p and finishes with mhh_pres_output_south_row.
 MHH_API int mhh_pres_bwd_x_unpack_output(mhh_pres_slab_plan* P, const mhh_grid* g, void* recvbuf, const mhh_fields* f, void* stream)
 {
     if (int e = slab_match(P, g)) return e;
+    MHH_REQUIRE(P->order == 2, "Pres_2::output only: a pres_4 plan takes mhh_pres_bwd_x_unpack, the halo of p and mhh_pres_output_order(g, 4)");
     MHH_REQUIRE(recvbuf && f && f->p && f->ut && f->vt && f->wt, "buffers");
     hipStream_t st = as_stream(stream);
     MHH_FFT_TRY(rocfft_execution_info_set_stream(P->info, st));
@@ -692,20 +885,11 @@ MHH_API int mhh_pres_fwd_y_chunk(mhh_pres_slab_plan* P, const mhh_grid* g, void*
     MHH_FFT_TRY(rocfft_execute(P->cfy, io, nullptr, P->info));
     return MHH_OK;
 }
-// all slices in: the tridiagonal solves over k
+// all slices in: the tridiagonal (pres_2) or 7-band (pres_4) solves over k
 MHH_API int mhh_pres_solve_y(mhh_pres_slab_plan* P, const mhh_grid* g, void* stream)
 {
     if (int e = slab_match(P, g)) return e;
-    hipStream_t st = as_stream(stream);
-    dim3 gs((2*P->jtot + 127)/128, P->nxb);
-    if (g->dtype == MHH_F64)
-        hipLaunchKernelGGL(tdma_slab_kernel<double>, gs, dim3(128), 0, st, (double*)P->specy, cp<double>(P->work), cp<double>(P->work) + (size_t)P->nxb*P->jtot*P->ktot,
-                           cp<double>(P->a), cp<double>(P->dz), P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
-    else
-        hipLaunchKernelGGL(tdma_slab_kernel<float>, gs, dim3(128), 0, st, (float*)P->specy, cp<float>(P->work), cp<float>(P->work) + (size_t)P->nxb*P->jtot*P->ktot,
-                           cp<float>(P->a), cp<float>(P->dz), P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
-    MHH_LAUNCH_CHECK();
-    return MHH_OK;
+    return slab_column_solve(P, as_stream(stream));
 }
 // slice c: inverse y transform + reorder into segment c of sendbuf
 MHH_API int mhh_pres_bwd_y_chunk(mhh_pres_slab_plan* P, const mhh_grid* g, void* sendbuf, int c, void* stream)
@@ -746,11 +930,12 @@ MHH_API int mhh_pres_bwd_x_chunk(mhh_pres_slab_plan* P, const mhh_grid* g, void*
 MHH_API int mhh_pres_slab_has_lds(const mhh_pres_slab_plan* P)
 {
     const char* e = getenv("MHH_PRES_SLAB_LDS");          // "0": the staged x stages (A/B runs, tests of both forms)
-    return (P && P->tx_lds && !(e && !strcmp(e, "0"))) ? 1 : 0;
+    return (P && P->order == 2 && P->tx_lds && !(e && !strcmp(e, "0"))) ? 1 : 0;
 }
 MHH_API int mhh_pres_slab_lds_fwd(mhh_pres_slab_plan* P, const mhh_grid* g, const mhh_fields* f, double dt, void* sendbuf, int c, void* stream)
 {
     if (int e = slab_match(P, g)) return e;
+    MHH_REQUIRE(P->order == 2, "the LDS x stages implement pres_2 only");
     MHH_REQUIRE(P->tx_lds != nullptr, "this plan has no LDS form of the x stages (power-of-two itot, jmax a multiple of 8)");
     MHH_REQUIRE(f && f->u && f->v && f->w && f->ut && f->vt && f->wt && f->rhoref && f->rhorefh && sendbuf, "null field");
     MHH_REQUIRE(dt > 0. && c >= 0 && c < P->nchunks, "dt, k-slice");
@@ -760,6 +945,7 @@ MHH_API int mhh_pres_slab_lds_fwd(mhh_pres_slab_plan* P, const mhh_grid* g, cons
 MHH_API int mhh_pres_slab_lds_bwd(mhh_pres_slab_plan* P, const mhh_grid* g, const void* recvbuf, const mhh_fields* f, int c, void* stream)
 {
     if (int e = slab_match(P, g)) return e;
+    MHH_REQUIRE(P->order == 2, "the LDS x stages implement pres_2 only");
     MHH_REQUIRE(P->tx_lds != nullptr, "this plan has no LDS form of the x stages (power-of-two itot, jmax a multiple of 8)");
     MHH_REQUIRE(f && f->p && f->ut && f->vt && f->wt && recvbuf, "null field");
     MHH_REQUIRE(c >= 0 && c < P->nchunks, "k-slice");
@@ -772,6 +958,7 @@ MHH_API int mhh_pres_slab_lds_bwd(mhh_pres_slab_plan* P, const mhh_grid* g, cons
 MHH_API int mhh_pres_slab_lds_fwd_y(mhh_pres_slab_plan* P, const mhh_grid* g, void* recvbuf, int c, void* stream)
 {
     if (int e = slab_match(P, g)) return e;
+    MHH_REQUIRE(P->order == 2, "the LDS x stages implement pres_2 only");
     MHH_REQUIRE(P->ty_lds != nullptr && recvbuf && c >= 0 && c < P->nchunks, "LDS form, buffer, k-slice");
     const int ks = P->ktot / P->nchunks;
     return lds_slab_yfft(g, true, recvbuf, P->specy, P->ty_lds, P->nxb, P->npy, ks, c*ks, (c+1)*ks, as_stream(stream));
@@ -779,6 +966,7 @@ MHH_API int mhh_pres_slab_lds_fwd_y(mhh_pres_slab_plan* P, const mhh_grid* g, vo
 MHH_API int mhh_pres_slab_lds_bwd_y(mhh_pres_slab_plan* P, const mhh_grid* g, void* sendbuf, int c, void* stream)
 {
     if (int e = slab_match(P, g)) return e;
+    MHH_REQUIRE(P->order == 2, "the LDS x stages implement pres_2 only");
     MHH_REQUIRE(P->ty_lds != nullptr && sendbuf && c >= 0 && c < P->nchunks, "LDS form, buffer, k-slice");
     const int ks = P->ktot / P->nchunks;
     return lds_slab_yfft(g, false, sendbuf, P->specy, P->ty_lds, P->nxb, P->npy, ks, c*ks, (c+1)*ks, as_stream(stream));
@@ -787,6 +975,7 @@ MHH_API int mhh_pres_slab_lds_bwd_y(mhh_pres_slab_plan* P, const mhh_grid* g, vo
 MHH_API int mhh_pres_unpack_output_slab(mhh_pres_slab_plan* P, const mhh_grid* g, const mhh_fields* f, void* stream)
 {
     if (int e = slab_match(P, g)) return e;
+    MHH_REQUIRE(P->order == 2, "Pres_2::output only: a pres_4 plan takes mhh_pres_unpack_slab, the halo of p and mhh_pres_output_order(g, 4)");
     MHH_REQUIRE(f && f->p && f->ut && f->vt && f->wt, "buffers");
     hipStream_t st = as_stream(stream);
     dim3 ug((g->icells + 255)/256, g->jmax, g->kmax + 1);

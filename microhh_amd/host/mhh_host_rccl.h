@@ -6,7 +6,8 @@
 //                           to the ring neighbours (ncclGroupStart / ncclSend / ncclRecv / ncclGroupEnd)
 //   Transpose               exec_xy / exec_yx of the spectral pressure as one  src/transpose.cxx:170-219
 //                           grouped all-to-all (every pair of ranks exchanges one block: all xGMI links busy at once)
-//   Pres_slab               Pres_2::exec around the two transposes             src/pres_2.cxx:66-94, src/fft.cxx:451-583
+//   Pres_slab               Pres_2::exec / Pres_4::exec around the two         src/pres_2.cxx:66-94, src/pres_4.cxx:64-140,
+//                           transposes                                         src/fft.cxx:451-583
 //
 // The library (include/mhh_hip.h) packs, transforms, solves and unpacks; this header only owns the message buffers and issues
 // the collectives on the caller's stream, so that kernels and messages are ordered by the stream alone (no host synchronisation
@@ -135,12 +136,15 @@ class Transpose
         Master_rccl& master;
 };
 
-// Pres_2 on a y-slab (the reference's Pres interface, include/pres.h:39-85)
+// Pres_2 / Pres_4 on a y-slab (the reference's Pres interface, include/pres.h:39-85); order as in Pres(grid, fields, order)
 template<typename TF>
 class Pres_slab
 {
     public:
-        Pres_slab(Master_rccl& m, Grid<TF>& g, Fields<TF>& f) : master(m), grid(g), fields(f), halo(m, g), transpose(m) {}
+        Pres_slab(Master_rccl& m, Grid<TF>& g, Fields<TF>& f, int orderin = 2) : master(m), grid(g), fields(f), halo(m, g), transpose(m), order(orderin)
+        {
+            if (order != 2 && order != 4) throw std::runtime_error("Pres_slab: order must be 2 or 4");
+        }
         ~Pres_slab() { clear_device(); }
         void init() {}
         void set_values() {}
@@ -150,7 +154,9 @@ class Pres_slab
         {
             const auto& gd = grid.get_grid_data();
             mhh_grid g = grid.abi();
-            mhh_check(mhh_pres_slab_plan_create(&g, gd.dz.data(), gd.dzhi.data(), fields.rhoref.data(), fields.rhorefh.data(), &plan));
+            if (order == 2) mhh_check(mhh_pres_slab_plan_create(&g, gd.dz.data(), gd.dzhi.data(), fields.rhoref.data(), fields.rhorefh.data(), &plan));
+            else            mhh_check(mhh_pres_slab_plan_create_order(&g, 4, gd.dz.data(), gd.dzhi.data(), gd.dzi4.data(), gd.dzhi4.data(),
+                                                                      fields.rhoref.data(), fields.rhorefh.data(), &plan));
             nbytes = (size_t)mhh_pres_slab_xbuf_elems(plan) * 2 * sizeof(TF);       // complex elements
             hip_check(hipMalloc(&xsend, nbytes), "hipMalloc"); hip_check(hipMalloc(&xrecv, nbytes), "hipMalloc");
         }
@@ -191,6 +197,7 @@ class Pres_slab
         void exec(double dt, Stats&)
         {
             if (!plan) throw std::runtime_error("Pres_slab::exec before prepare_device");
+            if (order == 4) { exec4(dt); return; }
             mhh_grid g = grid.abi();
             mhh_fields f = abi_fields(fields);
             void* st = master.stream;
@@ -262,12 +269,67 @@ class Pres_slab
             mhh_grid g = grid.abi();
             mhh_fields f = abi_fields(fields);
             double div = 0;
-            mhh_check(mhh_pres_check_divergence(&g, 2, &f, work, &div, master.stream));
+            mhh_check(mhh_pres_check_divergence(&g, order, &f, work, &div, master.stream));
             return static_cast<TF>(master.max(div));
         }
     private:
+        // Pres_4::exec (src/pres_4.cxx:64-140): the staged x stages (input | x transform + pack, x transform + unpack) around the
+        // transposes, the 7-band solve between them; p's y halo by exchange before Pres_4::output
+        void exec4(double dt)
+        {
+            mhh_grid g = grid.abi();
+            mhh_fields f = abi_fields(fields);
+            void* st = master.stream;
+            halo.exec_g({fields.mt.at("v")->fld_g}, 2, 1);                 // the input reads vt[j-1..j+2] (src/pres_4.cxx:312-315)
+            void* packed = mhh_pres_slab_packed(plan);
+            mhh_check(mhh_pres_input_packed(&g, 4, &f, dt, packed, st));
+            if (nchunks == 1)
+            {
+                mhh_check(mhh_pres_fwd_x_pack(plan, &g, packed, xsend, st));
+                transpose.exec(xsend, xrecv, nbytes / master.npy);            // Transpose::exec_xy
+                mhh_check(mhh_pres_fwd_y_solve_bwd_y(plan, &g, xrecv, xsend, st));
+                transpose.exec(xsend, xrecv, nbytes / master.npy);            // Transpose::exec_yx
+                mhh_check(mhh_pres_bwd_x_unpack(plan, &g, xrecv, &f, st));
+            }
+            else
+            {
+                const size_t seg = nbytes / nchunks;
+                auto exchange = [&](int c, hipEvent_t ready, hipEvent_t done)
+                {
+                    hip_check(hipEventRecord(ready, master.stream), "hipEventRecord");
+                    hip_check(hipStreamWaitEvent(comm_stream, ready, 0), "hipStreamWaitEvent");
+                    transpose.exec(static_cast<char*>(xsend) + c*seg, static_cast<char*>(xrecv) + c*seg, seg / master.npy, comm_stream);
+                    hip_check(hipEventRecord(done, comm_stream), "hipEventRecord");
+                };
+                const int n = nchunks;
+                for (int c = 0; c < n; ++c)
+                {
+                    mhh_check(mhh_pres_fwd_x_pack_chunk(plan, &g, packed, xsend, c, st));
+                    exchange(c, events[c], events[n + c]);
+                }
+                for (int c = 0; c < n; ++c)
+                {
+                    hip_check(hipStreamWaitEvent(master.stream, events[n + c], 0), "hipStreamWaitEvent");
+                    mhh_check(mhh_pres_fwd_y_chunk(plan, &g, xrecv, c, st));
+                }
+                mhh_check(mhh_pres_solve_y(plan, &g, st));
+                for (int c = 0; c < n; ++c)
+                {
+                    mhh_check(mhh_pres_bwd_y_chunk(plan, &g, xsend, c, st));
+                    exchange(c, events[2*n + c], events[3*n + c]);
+                }
+                for (int c = 0; c < n; ++c)
+                {
+                    hip_check(hipStreamWaitEvent(master.stream, events[3*n + c], 0), "hipStreamWaitEvent");
+                    mhh_check(mhh_pres_bwd_x_chunk(plan, &g, xrecv, c, st));
+                }
+                mhh_check(mhh_pres_unpack_slab(plan, &g, &f, st));
+            }
+            halo.exec_g({fields.sd.at("p")->fld_g}, 1, 2);                 // the output reads p[j-2..j+1] (src/pres_4.cxx:555-569)
+            mhh_check(mhh_pres_output_order(&g, 4, &f, st));
+        }
         Master_rccl& master; Grid<TF>& grid; Fields<TF>& fields;
-        Boundary_cyclic_slab<TF> halo; Transpose transpose;
+        Boundary_cyclic_slab<TF> halo; Transpose transpose; int order;
         mhh_pres_slab_plan* plan = nullptr; void* work = nullptr;
         void* xsend = nullptr; void* xrecv = nullptr; size_t nbytes = 0;
         int nchunks = 1; hipStream_t comm_stream = nullptr; std::vector<hipEvent_t> events;

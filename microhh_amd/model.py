@@ -98,8 +98,6 @@ class HotPath:
         if self.on_gpu and (npy > 1 or self._force_comm):
             import torch.distributed as dist
             self._host_staged = dist.is_initialized() and dist.get_backend(group) == "gloo"
-        if self.slab and cfg["pres"] != 2:
-            raise ValueError("slab decomposition implements pres_2 (BASELINE.json multi-GPU configs use pres_2)")
         z = moser_z(ktot, cfg["size"][2]) if case == "moser600" else None
         # igc: ghost cells in x beyond what the schemes need -- what the reference's grid produces when an operator calls
         # Grid::set_minimum_ghost_cells (src/grid.cxx:435-439; src/advec_2i5.cxx:42-45 uses it). igc = 16 with itot = 512 makes
@@ -174,7 +172,8 @@ class HotPath:
             self._ok(self.lib.mhh_pres_plan_create(Gh, cfg["pres"], g.dz.ctypes.data, g.dzhi.ctypes.data, g.dzi4.ctypes.data, g.dzhi4.ctypes.data,
                                                    self.rhoref_h.ctypes.data, self.rhorefh_h.ctypes.data, C.byref(self.plan)))
         else:
-            self._ok(self.lib.mhh_pres_slab_plan_create(Gh, g.dz.ctypes.data, g.dzhi.ctypes.data, self.rhoref_h.ctypes.data, self.rhorefh_h.ctypes.data, C.byref(self.plan)))
+            self._ok(self.lib.mhh_pres_slab_plan_create_order(Gh, cfg["pres"], g.dz.ctypes.data, g.dzhi.ctypes.data, g.dzi4.ctypes.data, g.dzhi4.ctypes.data,
+                                                              self.rhoref_h.ctypes.data, self.rhorefh_h.ctypes.data, C.byref(self.plan)))
             nx = int(self.lib.mhh_pres_slab_xbuf_elems(self.plan))
             self.xsend = torch.zeros(2*nx, device=self.device, dtype=td)
             self.xrecv = torch.zeros(2*nx, device=self.device, dtype=td)
@@ -398,7 +397,9 @@ class HotPath:
         if not self.slab:
             self._ok(self.lib.mhh_pres_exec(self.plan, self.G, C.byref(self.fields), self.dt, self.stream))
             return
-        import torch.distributed as dist
+        if self.cfg["pres"] == 4:
+            self._pres4_slab()
+            return
         lib, st = self.lib, self.stream
         if self.slim: self.halo([self.vt], rows_south=1, rows_north=0)      # only vt[j+1] at the north edge is read (pres_2.cxx:181,193)
         else:         self.halo([self.vt])
@@ -440,6 +441,32 @@ class HotPath:
             self.halo([self.p])
             self._ok(lib.mhh_pres_output_order(self.G, 2, C.byref(self.fields), self.stream))
 
+    # the rows of vt the pressure input reads beyond the slab (rows_south, rows_north): pres_2 vt[j+1] (src/pres_2.cxx:181,193),
+    # pres_4 vt[j-1..j+2] (src/pres_4.cxx:312-315)
+    @property
+    def _pres_vt_rows(self):
+        return (2, 1) if self.cfg["pres"] == 4 else (1, 0)
+
+    def _pres4_slab(self):
+        """Pres_4::exec on a slab (src/pres_4.cxx:64-140): the staged x stages around the two transposes, whole or in k-slices, the
+        7-band solve on the rank's spectral columns; the unpack writes p's four mirrored ghost levels and its x halo, the exchange
+        its y halo (the output reads p[j-2..j+1], src/pres_4.cxx:555-569)."""
+        lib, st, F = self.lib, self.stream, C.byref(self.fields)
+        rs, rn = self._pres_vt_rows
+        self.halo([self.vt], rows_south=rs, rows_north=rn)
+        packed = lib.mhh_pres_slab_packed(self.plan)
+        self._ok(lib.mhh_pres_input_packed(self.G, 4, F, self.dt, packed, st))
+        if self.pres_chunks > 1:
+            self._pres_sliced(packed)
+        else:
+            self._ok(lib.mhh_pres_fwd_x_pack(self.plan, self.G, packed, self.xsend.data_ptr(), st))
+            self._transpose()                                                # Transpose::exec_xy
+            self._ok(lib.mhh_pres_fwd_y_solve_bwd_y(self.plan, self.G, self.xrecv.data_ptr(), self.xsend.data_ptr(), st))
+            self._transpose()                                                # Transpose::exec_yx
+            self._ok(lib.mhh_pres_bwd_x_unpack(self.plan, self.G, self.xrecv.data_ptr(), F, st))
+        self.halo([self.p], rows_south=1, rows_north=2)
+        self._ok(lib.mhh_pres_output_order(self.G, 4, F, self.stream))
+
     def pres_rk(self, rkorder, substep, dt):
         """pres->exec(self.dt) followed by timeloop.exec() for u, v, w (src/model.cxx:411,484) with the sub-step applied in the
         kernel that stores the corrected tendencies (mhh_pres_exec_rk); on a slab: pres() + three mhh_rk_substep calls."""
@@ -451,7 +478,7 @@ class HotPath:
             self._ok(self.lib.mhh_rk_substep(self.G, rkorder, substep, dt, a.data_ptr(), at.data_ptr(), self.stream))
 
     def _pres_sliced(self, packed, lds_x=False):
-        """Pres_2::exec after the input stage, in k-slices: per slice x transform + pack, all-to-all on the exchange stream while
+        """Pres::exec after the input stage, in k-slices: per slice x transform + pack, all-to-all on the exchange stream while
         the next slice is transformed, y transform as each slice arrives; Thomas sweeps over all levels; the same on the way back.
         Same kernels per plane as the unsliced path (tests/test_slab_gloo.py compares the two)."""
         lib, torch, n = self.lib, self.torch, self.pres_chunks
@@ -497,6 +524,9 @@ class HotPath:
                 main.wait_event(self._sl_ev[3][c])
             if lds_x: self._ok(lib.mhh_pres_slab_lds_bwd(self.plan, self.G, self.xrecv.data_ptr(), F, c, self.stream))
             else:     self._ok(lib.mhh_pres_bwd_x_chunk(self.plan, self.G, self.xrecv.data_ptr(), c, self.stream))
+        if self.cfg["pres"] == 4:
+            self._ok(lib.mhh_pres_unpack_slab(self.plan, self.G, F, self.stream))    # the caller (_pres4_slab) exchanges p and applies the output
+            return
         if not lds_x:
             self._ok(lib.mhh_pres_unpack_output_slab(self.plan, self.G, F, self.stream))
         self.halo([self.p], rows_south=0, rows_north=1)
@@ -570,7 +600,8 @@ class HotPath:
         def residual(f, real):
             if self.slab:
                 if real:
-                    self.halo([self.vt], rows_south=1, rows_north=0)
+                    rs, rn = self._pres_vt_rows
+                    self.halo([self.vt], rows_south=rs, rows_north=rn)
                 self._ok(self.lib.mhh_pres_input_packed(self.G, self.cfg["pres"], C.byref(f), self.dt, buf.data_ptr(), self.stream))
             else:
                 self._ok(self.lib.mhh_pres_input(self.plan, self.G, C.byref(f), self.dt, buf.data_ptr(), self.stream))
