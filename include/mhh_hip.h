@@ -232,6 +232,9 @@ int mhh_diff_exec_viscosity_rows2(const mhh_grid* g, int scheme, const mhh_field
  * take the one-thread-per-cell kernel, same bits) */
 unsigned long long mhh_stat_visc_march_launches(void);
 unsigned long long mhh_stat_rhs44_march_launches(void);   /* same for the k-marching form of (advec_4, diff_4) in mhh_rhs_exec */
+/* same for the scalar pass of the k-marching (advec_2i5, diff_smag2) kernel: one per launch, a launch takes a batch of scalars
+ * 1, 2, ... (mhh_rhs_exec, mhh_rhs_exec_rows(2), mhh_advec_exec, mhh_diff_exec; MHH_SCALAR_IMPL=cell: the per-field kernels) */
+unsigned long long mhh_stat_scalar_march_launches(void);
 /* self test of a device primitive of exec_viscosity: the square root for arguments known to be >= 2^-767 (csrc/gfx950_prims.h,
  * sqrt_in_range) against the compiler's sqrt on n arguments drawn from `seed`; *mismatches (host memory) must come back 0 */
 int mhh_selftest_sqrt_in_range(unsigned long long n, unsigned long long seed, unsigned long long* mismatches, void* stream);
@@ -250,8 +253,9 @@ int mhh_thermo_dry_buoyancy_tend(const mhh_grid* g, int order, void* wt, const v
 int mhh_rhs_exec(const mhh_grid* g, int advec_scheme, int diff_scheme, const mhh_fields* f,
                  const mhh_diff_params* p, void* stream);
 
-/* the (advec_2i5, diff_smag2) pass over the rows [j0, j1) of the interior only; u, v, w and at most one (unlimited)
- * scalar; same bits as the whole-slab call on those rows */
+/* the (advec_2i5, diff_smag2) pass over the rows [j0, j1) of the interior only; u, v, w and up to MHH_MAX_SCALARS
+ * unlimited scalars (scalar 0 in the fused marching kernel, the others in its scalar pass over the same rows; buoyancy only
+ * as the 2nd-order form folded with scalar 0); same bits as the whole-slab call on those rows */
 int mhh_rhs_exec_rows(const mhh_grid* g, int advec_scheme, int diff_scheme, const mhh_fields* f,
                       const mhh_diff_params* p, int j0, int j1, void* stream);
 /* the same over TWO disjoint, ordered row ranges in one launch (a slab's two edge strips once its north-south halos are in) */

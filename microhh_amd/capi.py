@@ -60,6 +60,7 @@ SIGNATURES = {
     "mhh_rhs_exec_rows": (ci, [GP, ci, ci, FP, DP, ci, ci, vp]),
     "mhh_rhs_exec_rows2": (ci, [GP, ci, ci, FP, DP, ci, ci, ci, ci, vp]),
     "mhh_stat_rhs44_march_launches": (C.c_ulonglong, []),
+    "mhh_stat_scalar_march_launches": (C.c_ulonglong, []),
     "mhh_thermo_dry_buoyancy_tend": (ci, [GP, ci, vp, vp, vp, cd, vp]),
     "mhh_advec_cfl": (ci, [GP, ci, vp, vp, vp, cd, vp, C.POINTER(cd), vp]),
     "mhh_diff_c": (ci, [GP, ci, vp, vp, cd, vp]),

@@ -36,6 +36,7 @@ using namespace mhh;
 
 #ifdef MHH_FMA_BUILD     // the named FMA build (build.py): its kernels carry their own name in profiler output
 #define rhs25_march_kernel rhs25_march_fma_kernel
+#define rhs25_scalar_march_kernel rhs25_scalar_march_fma_kernel
 #endif
 
 namespace
@@ -725,9 +726,280 @@ rhs25_march_kernel(const MarchMetrics<typename lane_of<VT>::scalar> mm, const Gr
     if (tx == 0 && f.dbg) f.dbg[((size_t)blockIdx.x*NJ + ty)*8 + 5] = (unsigned long long)(ke - ks);
 #endif
 }
+// ---- The scalar pass: advec_2i5 and / or diff_smag2 of a BATCH of scalars (scalars 1, 2, ... of fields.st) in one k-march ----
+// The fused kernel above carries one scalar; every further one used to take the one-thread-per-cell kernels (mhh_advec_s,
+// mhh_smag2_diff_c), which fetch each neighbour through L1. Here a 64 x NJ block walks up a column tile as above, and per level
+//   * what the operators read of the flow is staged ONCE for the whole batch: u at faces i, i+1 and v at j, j+1 of level k, w at
+//     k+1 and evisc at k+1 of the lane's own column in registers (loaded a level ahead), the evisc plane with its +-1 halo in LDS,
+//     and the four horizontal face viscosities 0.5*(e+e')/tPr (div_known) once per level;
+//   * each scalar has its own LDS ring (two slots: the plane of level k with its +-3 halo, the copy of k+1 landing under the
+//     compute) and its own 6-level register window; its vertical faces are formed once, on the top face, and carried down.
+// The arithmetic of a scalar is the fused kernel's scalar section (above) statement for statement, in the same order of
+// accumulation: t += advec horizontal; t += advec vertical; t += diffusion -- the bits of the oracle and of the cell kernels.
+// No buoyancy here (it is folded with scalar 0 only). Tiles are copied with TileCopy (k_march_common.h); their origins lie a
+// whole 16-byte piece west of the first cell (hx / ex: 3..2+VEC, 1..VEC cells) so that any istart copies in 16-byte pieces.
+template<class TF, int NB> struct ScalarMarchFields
+{
+    const TF* __restrict__ u; const TF* __restrict__ v; const TF* __restrict__ w; const TF* __restrict__ ev;
+    const TF* __restrict__ rhoref; const TF* __restrict__ rhorefh;
+    const TF* s[NB]; TF* st[NB]; const TF* sfb[NB]; const TF* sft[NB]; TF svisc[NB];
+    int ns, sm, hx, ex;                          // scalars of this launch (<= NB), surface model, tile origins (see above)
+};
+// scalars per launch; MHH_SCALAR_BATCH=1 (run time) runs one per launch (A/B)
+#ifndef MHH_SCALAR_NB
+#define MHH_SCALAR_NB 2
+#endif
+template<class TF, int NJ, int NB, int PB, bool ADV, bool DIF>
+__global__ void __launch_bounds__(64*NJ, (sizeof(TF) == 4 ? MHH_MARCH_OCC_F32 : MHH_MARCH_OCC))
+rhs25_scalar_march_kernel(const MarchMetrics<TF> mm, const GridDev<TF> g, const ScalarMarchFields<TF, NB> f, const MarchTiling mt)
+{
+    static_assert(PB == 16 || PB == 4, "piece size of the LDS-DMA copies");
+    constexpr int VEC = 16 / (int)sizeof(TF);
+    constexpr int AL = (PB == 16) ? VEC : 1;
+    constexpr int HXM = (PB == 16) ? 2 + VEC : 3, EXM = (PB == 16) ? VEC : 1;   // largest tile origin offsets
+    constexpr int TI = ((64 + HXM + 3 + AL-1)/AL)*AL, TE = ((64 + EXM + 1 + AL-1)/AL)*AL;
+    constexpr int TJ = NJ + 6, TJE = NJ + 2, NT = 64*NJ;
+    constexpr int NTILE = TI*TJ, NETILE = TE*TJE;
+    constexpr int OS = 0, OE = OS + 2*NB*NTILE, LTOT = OE + (DIF ? 2*NETILE : 0);
+    __shared__ __attribute__((aligned(16))) TF L[LTOT];
+
+    int bx, by, kcn;
+    if (!decode_march(mt, blockIdx.x, bx, by, kcn)) return;        // whole block leaves together: no barrier hazard
+    const int jj = g.icells, kk = g.ijcells;
+    const int tx = threadIdx.x, ty = threadIdx.y, tid = ty*64 + tx;
+    int j0, jlim; march_tile_rows(mt, by, NJ, j0, jlim);
+    const int i0 = g.istart + bx*64;
+    const int kb = g.kstart + kcn*mt.kc;
+    const int ke = (kb + mt.kc < g.kend) ? kb + mt.kc : g.kend;
+    const int i = i0 + tx, j = j0 + ty;
+    const bool active = (i < g.iend) && (j < jlim);
+    const int ci = (i < g.iend) ? i : g.iend-1, cj = (j < jlim) ? j : jlim-1;   // clamped column for the column loads
+    const int col = ci + cj*jj;
+    const int l = (ty+3)*TI + (tx+f.hx), le = (ty+1)*TE + (tx+f.ex);
+    const int ns = f.ns;
+    // interior levels: every face 6th / 5th order, no wall, no surface flux (as in the fused kernel)
+    int kf0 = (kb > g.kstart+3) ? kb : g.kstart+3;
+    int kf1 = (ke < g.kend-3) ? ke : g.kend-3;
+    if (kf1 < kf0) kf1 = kf0;
+    if (kf0 > ke) kf0 = kf1 = ke;
+
+    // column values and tendencies: scalar base (plane pbase of the array) + 32-bit lane byte offset; planes clamped into
+    // [0, kcells-1] (values read from a clamped plane are never used by an updated level). Planes from kb-3 to ke+3 are read:
+    // (kc + 8) planes below 4 GB (the host checks, as for the fused kernel).
+    const int kmaxp = g.kcells - 1, ks = kb - 1;
+    const int pbase = (kb - 4 > 0) ? kb - 4 : 0;
+    auto clampk = [&](int q) { return q < 0 ? 0 : (q > kmaxp ? kmaxp : q); };
+    const unsigned kk8 = sgpr((unsigned)((size_t)kk * sizeof(TF)));
+    const unsigned colb = (unsigned)col * (unsigned)sizeof(TF);
+    auto bo = [&](int q) -> unsigned { return colb + (unsigned)(clampk(q) - pbase) * kk8; };
+    auto plane = [&](const TF* fld, int q) -> const TF* { return fld + (size_t)clampk(q)*kk; };
+    const TF* const bu = ADV ? sgpr(f.u + (size_t)pbase*kk) : nullptr;
+    const TF* const bv = ADV ? sgpr(f.v + (size_t)pbase*kk) : nullptr;
+    const TF* const bw = ADV ? sgpr(f.w + (size_t)pbase*kk) : nullptr;
+    const TF* const bev = DIF ? sgpr(f.ev + (size_t)pbase*kk) : nullptr;
+    // (the scalars' bases are formed where they are used, from the kernel arguments: as arrays of pinned pointers they went to scratch)
+    auto bs = [&](int n) -> const TF* { return f.s[n] + (size_t)pbase*kk; };
+    auto bst = [&](int n) -> TF* { return f.st[n] + (size_t)pbase*kk; };
+    const TF* const kmm = first_kernarg(reinterpret_cast<const TF&>(mm));
+    const TF* __restrict__ tdzi = sgpr(g.dzi); const TF* __restrict__ tdzhi = sgpr(g.dzhi);
+#if !defined(MHH_MARCH_NO_NT)
+    auto tld = [](const TF* base, unsigned b) -> TF { return gload_stream(base, b); };
+    auto tst = [](TF* base, unsigned b, TF v) { gstore_stream(base, b, v); };
+#else
+    auto tld = [](const TF* base, unsigned b) -> TF { return gload(base, b); };
+    auto tst = [](TF* base, unsigned b, TF v) { gstore(base, b, v); };
+#endif
+
+    // ---- tile copies: scalar planes (+-3 halo) and the evisc plane (+-1 halo) of a level, into ring slot (q - ks) & 1 ---------
+    TileCopy<TF, PB, TI, TJ, NT> tcs; tcs.init(tid, i0 - f.hx, j0 - 3, g.icells, g.jcells);
+    TileCopy<TF, PB, TE, TJE, NT> tce; if constexpr (DIF) tce.init(tid, i0 - f.ex, j0 - 1, g.icells, g.jcells);
+    auto copy_level = [&](int q) __attribute__((always_inline))
+    {
+        const int sl = (q - ks) & 1;
+#pragma unroll
+        for (int n=0; n<NB; ++n) if (n < ns) tcs.copy(plane(f.s[n], q), L + OS + (2*n + sl)*NTILE);
+        if constexpr (DIF) tce.copy(plane(f.ev, q), L + OE + sl*NETILE);
+    };
+
+    // ---- prologue: the planes and column values level ks reads, windows centred on ks ------------------------------------
+    copy_level(ks);
+    const TF zero = TF(0);
+    TF sw[NB][6];
+#pragma unroll
+    for (int n=0; n<NB; ++n)
+#pragma unroll
+        for (int m=0; m<6; ++m) sw[n][m] = (n < ns) ? gload(bs(n), bo(ks-2+m)) : zero;
+    // level k: u(i), u(i+1), v(j), v(j+1) of level k; w and evisc of level k+1 (the lane's column)
+    TF u0 = zero, ue = zero, v0 = zero, vn = zero, wp = zero, ep = zero;
+    if constexpr (ADV) { const unsigned b = bo(ks); u0 = gload(bu, b); ue = gload(bu, b + (unsigned)sizeof(TF)); v0 = gload(bv, b); vn = gload(bv, b + (unsigned)(jj*sizeof(TF))); wp = gload(bw, bo(ks+1)); }
+    if constexpr (DIF) ep = gload(bev, bo(ks+1));
+    TF cTs[NB], cGs[NB], cDs[NB], tp[NB];            // carried bottom faces; the tendency of the next level (loaded a level ahead)
+#pragma unroll
+    for (int n=0; n<NB; ++n) { cTs[n] = zero; cGs[n] = zero; cDs[n] = zero; tp[n] = zero; }
+    wait_vmem();
+    __syncthreads();
+
+    auto level = [&](const int k, auto fast_tag, auto rho1_tag, auto rot_tag) __attribute__((always_inline))
+    {
+        constexpr bool FAST = decltype(fast_tag)::value, RHO1 = decltype(rho1_tag)::value;
+        constexpr int ROT = decltype(rot_tag)::value, RR = (ROT < 0) ? 0 : ROT;
+        auto R = [](TF r, TF x) -> TF { return RHO1 ? x : r*x; };
+        // next level's planes and column values, in flight under this level's arithmetic
+        if (k + 1 < ke) copy_level(k + 1);
+        const unsigned b0 = bo(k), b1 = bo(k+1), b2 = bo(k+2), b4 = bo(k+4);
+        TF nu0 = zero, nue = zero, nv0 = zero, nvn = zero, nwp = zero, nep = zero, nsw[NB], tc[NB];
+        if constexpr (ADV) { nu0 = gload(bu, b1); nue = gload(bu, b1 + (unsigned)sizeof(TF)); nv0 = gload(bv, b1); nvn = gload(bv, b1 + (unsigned)(jj*sizeof(TF))); nwp = gload(bw, b2); }
+        if constexpr (DIF) nep = gload(bev, b2);
+#pragma unroll
+        for (int n=0; n<NB; ++n)
+        {
+            nsw[n] = (n < ns) ? gload(bs(n), b4) : zero;
+            tc[n] = tp[n];
+            if (n < ns) tp[n] = tld(bst(n), b1);      // inactive lanes sit on a clamped (valid) column: no lane mask
+        }
+        const TF* const mq = sgpr(kmm);
+        const Uniform8<TF> mg1 = uniform_load8(mq + 8);
+        const TF dxi = mg1.v[0], dyi = mg1.v[1], dxidxi = mg1.v[2], dyidyi = mg1.v[3], tPr2 = mg1.v[5], rtPr2 = mg1.v[6];
+        auto div_tpr = [&](TF x) -> TF { return div_known(x, tPr2, rtPr2); };     // 0.5*x / tPr
+        const TF rhkp = RHO1 ? TF(1) : uniform_load(f.rhorefh, k+1), rhk = RHO1 ? TF(1) : uniform_load(f.rhorefh, k), rk = RHO1 ? TF(1) : uniform_load(f.rhoref, k);
+        const TF dzi = uniform_load(tdzi, k), dzhip = uniform_load(tdzhi, k+1);
+        const bool rk1 = RHO1 || (rk == TF(1.));
+        const int otc = FAST ? 6 : order_face_c(k+1, g.kstart, g.kend);
+        const int obc = FAST ? 6 : order_face_c(k, g.kstart, g.kend);
+        const bool fb = !FAST && f.sm && (k == g.kstart), ft = !FAST && f.sm && (k == g.kend-1);
+        const bool need_dtop = FAST || (!(ft) && (k < g.kend-1 || !f.sm) && (k+1 <= g.kend));
+        const bool upd = (FAST || k >= kb) && active;
+        const int sl = (k - ks) & 1;
+        // the face viscosities of the level, shared by the batch
+        TF dT = zero, dE = zero, dW = zero, dN = zero, dS = zero;
+        if constexpr (DIF)
+        {
+            const TF* const ek = L + OE + sl*NETILE + le;
+            const TF e0 = ek[0];
+            if (need_dtop) dT = div_tpr(e0+ep);
+            if (upd) { dE = div_tpr(e0+ek[1]); dW = div_tpr(ek[-1]+e0); dN = div_tpr(e0+ek[TE]); dS = div_tpr(ek[-TE]+e0); }
+        }
+        const int ij = col;                                    // the 2-D surface arrays at the lane's column
+#pragma unroll
+        for (int n=0; n<NB; ++n)
+        {
+            if (n < ns)
+            {
+                const TF* const sk = L + OS + (2*n + sl)*NTILE + l;
+                const TF s0 = wv<RR,2>(sw[n]), s0p = wv<RR,3>(sw[n]);
+                const TF svisc = f.svisc[n];
+                TF Ts = zero, Gs = zero, Ds = zero;
+                if (ADV && otc != 0)
+                {
+                    Ts = R(rhkp, wp) * win_cen<RR>(sw[n], otc);
+                    if (otc >= 4) Gs = R(rhkp, tabs(wp)) * win_upw<RR>(sw[n], otc);
+                }
+                if (DIF && need_dtop)
+                {
+                    const TF ets = dT + svisc;
+                    Ds = R(rhkp, ets)*(s0p-s0)*dzhip;
+                }
+                if (upd)
+                {
+                    TF t = tc[n];
+                    if constexpr (ADV)
+                    {
+                        t += advec25_hor_f0(sk, s0, TI, ue, u0, vn, v0, dxi, dyi);
+                        t += vert_combine(otc, obc, Ts, cTs[n], Gs, cGs[n], rk, rk1, dzi);
+                    }
+                    if constexpr (DIF)
+                    {
+                        const TF ee = dE + svisc, ew = dW + svisc, en = dN + svisc, es = dS + svisc;
+                        const TF hor = + ( ee*(sk[1 ]-s0) - ew*(s0-sk[-1 ]) ) * dxidxi
+                                       + ( en*(sk[TI]-s0) - es*(s0-sk[-TI]) ) * dyidyi;
+                        TF ver;
+                        if (fb)      ver = div_rho( Ds + rhk * f.sfb[n][ij], rk, rk1 ) * dzi;
+                        else if (ft) ver = div_rho( -rhkp * f.sft[n][ij] - cDs[n], rk, rk1 ) * dzi;
+                        else         ver = div_rho( Ds - cDs[n], rk, rk1 ) * dzi;
+                        t += hor + ver;
+                    }
+                    tst(bst(n), b0, t);
+                }
+                cTs[n] = Ts; cGs[n] = Gs; cDs[n] = Ds;
+            }
+        }
+        u0 = nu0; ue = nue; v0 = nv0; vn = nvn; wp = nwp; ep = nep;
+        wait_vmem();                                           // this wave's copies have landed (and its stores have left)
+        __syncthreads();                                       // ... everyone's have, and everyone is done with the oldest planes
+#pragma unroll
+        for (int n=0; n<NB; ++n)
+        {
+            if constexpr (ROT < 0) shift6(sw[n], nsw[n]);
+            else sw[n][RR] = nsw[n];                           // the slot of level k-2 takes level k+4: rotation RR+1
+        }
+    };
+    using std::true_type; using std::false_type;
+    using Shift = std::integral_constant<int, -1>;
+    bool rho_one = true;
+    for (int k = ks; k <= ke; ++k) rho_one = rho_one && (f.rhoref[k] == TF(1.)) && (f.rhorefh[k] == TF(1.));
+    auto chunk = [&](auto rho1_tag) __attribute__((always_inline))
+    {
+        int k = ks;
+        for (; __builtin_expect(k < kf0, 0); ++k) level(k, false_type{}, rho1_tag, Shift{});
+        for (; k + 6 <= kf1; k += 6)
+        {
+            level(k,   true_type{}, rho1_tag, std::integral_constant<int, 0>{});
+            level(k+1, true_type{}, rho1_tag, std::integral_constant<int, 1>{});
+            level(k+2, true_type{}, rho1_tag, std::integral_constant<int, 2>{});
+            level(k+3, true_type{}, rho1_tag, std::integral_constant<int, 3>{});
+            level(k+4, true_type{}, rho1_tag, std::integral_constant<int, 4>{});
+            level(k+5, true_type{}, rho1_tag, std::integral_constant<int, 5>{});
+        }
+        for (; __builtin_expect(k < kf1, 0); ++k) level(k, true_type{}, rho1_tag, Shift{});
+        for (; __builtin_expect(k < ke, 0); ++k) level(k, false_type{}, rho1_tag, Shift{});
+    };
+    if constexpr (sizeof(TF) == 4)
+    {   // fp32: one body, as the fused kernel's fp32 form
+        for (int k = ks; k < ke; ++k) level(k, false_type{}, false_type{}, Shift{});
+    }
+    else if (__builtin_expect(rho_one, 1)) chunk(true_type{});
+    else              chunk(false_type{});
+}
+
 #ifdef MHH_MARCH_STAMP
 static unsigned long long* g_stamp_buf = nullptr; static size_t g_stamp_n = 0;
 #endif
+
+#ifndef MHH_MARCH_KC
+#define MHH_MARCH_KC 128
+#endif
+// The uniform coefficients of both marching kernels (the scalar pass reads the second group of eight; svisc: scalar 0's, which
+// only the fused kernel reads)
+template<class TF> MarchMetrics<TF> march_metrics(const GridDev<TF>& gd, const mhh_fields* f, const mhh_diff_params* p, TF svisc)
+{
+    MarchMetrics<TF> mm;
+    mm.visc = TF(f->visc); mm.svisc = svisc;
+    mm.dxi = gd.dxi_t; mm.dyi = gd.dyi_t; mm.dxih = TF(0.5)*gd.dxi_t; mm.dyih = TF(0.5)*gd.dyi_t;
+    mm.dxd = gd.dxi_d; mm.dyd = gd.dyi_d; mm.dxd2 = TF(2.)*gd.dxi_d; mm.dyd2 = TF(2.)*gd.dyi_d;
+    mm.dxidxi = gd.dxidxi_d; mm.dyidyi = gd.dyidyi_d; mm.quarter = TF(0.25); mm.pad1 = TF(0);
+    const TF tPr = p ? TF(p->tPr) : TF(1);
+    mm.tPr2 = TF(2.)*tPr; mm.rtPr2 = TF(1.)/mm.tPr2;
+    return mm;
+}
+// Levels per k-chunk of both marching kernels over the rows [j0, j1) (+ [j2, j3)), or 0 where the grid's planes are too large:
+// a strip of a few rows (mhh_rhs_exec_rows on the edge rows) takes short k-chunks, enough blocks to fill the GPU; the lanes
+// address a chunk's planes with 32-bit byte offsets from the chunk's first plane: (kc + 8) planes below 4 GB
+template<class TF> int march_chunk_levels(const mhh_grid* g, int j0, int j1, int j2, int j3)
+{
+    int kc = (j0 >= 0 && (j1 - j0 + (j2 >= 0 ? j3 - j2 : 0)) * 4 <= g->jmax) ? 16 : MHH_MARCH_KC;
+    { const char* e = getenv("MHH_MARCH_KC_RT"); if (e && atoi(e) >= 8) kc = atoi(e); }       // tuning runs: levels per chunk at run time
+    const unsigned long long plane_bytes = (unsigned long long)g->ijcells * sizeof(TF);
+    while (kc > 8 && (unsigned long long)(kc + 8) * plane_bytes >= (1ull << 32)) kc /= 2;
+    return ((unsigned long long)(kc + 8) * plane_bytes < (1ull << 32)) ? kc : 0;
+}
+// Piece size of both kernels' LDS-DMA copies: 16 bytes where the rows and every copied array are 16-byte aligned, 4 bytes
+// otherwise (MHH_MARCH_DMA=4 forces that form; same arithmetic in both)
+inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
+inline int march_piece_bytes(bool aligned)
+{
+    const char* env = getenv("MHH_MARCH_DMA");
+    return ((env && !strcmp(env, "4")) || !aligned) ? 4 : 16;
+}
 
 // mode 0: advec_2i5 + diff_smag2 (the fused pass); 1: advec_2i5 only (p may be null); 2: diff_smag2 only
 // VT = lane value type: double, float, or F2 = two fp32 cells per lane (packed arithmetic; needs an even imax)
@@ -746,26 +1018,13 @@ int march_launch(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* 
     mf.rhoref = cp<TF>(f->rhoref); mf.rhorefh = cp<TF>(f->rhorefh);
     mf.ufb = cp<TF>(f->u_fluxbot); mf.uft = cp<TF>(f->u_fluxtop); mf.vfb = cp<TF>(f->v_fluxbot); mf.vft = cp<TF>(f->v_fluxtop);
     mf.sfb = has_s ? cp<TF>(f->s_fluxbot[0]) : nullptr; mf.sft = has_s ? cp<TF>(f->s_fluxtop[0]) : nullptr;
-    MarchMetrics<TF> mm;
-    mm.visc = TF(f->visc); mm.svisc = has_s ? TF(f->svisc[0]) : TF(0); mf.sm = (p && mode != 1) ? p->surface_model : 0;
-    mm.dxi = gd.dxi_t; mm.dyi = gd.dyi_t; mm.dxih = TF(0.5)*gd.dxi_t; mm.dyih = TF(0.5)*gd.dyi_t;
-    mm.dxd = gd.dxi_d; mm.dyd = gd.dyi_d; mm.dxd2 = TF(2.)*gd.dxi_d; mm.dyd2 = TF(2.)*gd.dyi_d;
-    mm.dxidxi = gd.dxidxi_d; mm.dyidyi = gd.dyidyi_d; mm.quarter = TF(0.25); mm.pad1 = TF(0);
-    const TF tPr = p ? TF(p->tPr) : TF(1);
-    mm.tPr2 = TF(2.)*tPr; mm.rtPr2 = TF(1.)/mm.tPr2;
+    const MarchMetrics<TF> mm = march_metrics<TF>(gd, f, p, has_s ? TF(f->svisc[0]) : TF(0));
+    mf.sm = (p && mode != 1) ? p->surface_model : 0;
     MHH_REQUIRE(mode == 1 || !has_s || known_divisor_ok(mm.tPr2), "tPr must be a positive normal number whose significand is not all ones");
     const bool buoy = mode == 0 && has_s && p->buoyancy == 2 && p->th_for_N2 == 0;
     mf.threfh = buoy ? cp<TF>(p->threfh) : nullptr; mf.grav = buoy ? TF(p->grav) : TF(0);
-#ifndef MHH_MARCH_KC
-#define MHH_MARCH_KC 128
-#endif
-    // a strip of a few rows (mhh_rhs_exec_rows on the edge rows) takes short k-chunks: enough blocks to fill the GPU
-    int kc = (j0 >= 0 && (j1 - j0 + (j2 >= 0 ? j3 - j2 : 0)) * 4 <= g->jmax) ? 16 : MHH_MARCH_KC;
-    { const char* e = getenv("MHH_MARCH_KC_RT"); if (e && atoi(e) >= 8) kc = atoi(e); }       // tuning runs: levels per chunk at run time
-    // the lanes address a chunk's planes with 32-bit byte offsets from the chunk's first plane: (kc + 8) planes below 4 GB
-    const unsigned long long plane_bytes = (unsigned long long)g->ijcells * sizeof(TF);
-    while (kc > 8 && (unsigned long long)(kc + 8) * plane_bytes >= (1ull << 32)) kc /= 2;
-    MHH_REQUIRE((unsigned long long)(kc + 8) * plane_bytes < (1ull << 32), "a plane of this grid is too large for the marching kernel's 32-bit lane offsets");
+    const int kc = march_chunk_levels<TF>(g, j0, j1, j2, j3);
+    MHH_REQUIRE(kc > 0, "a plane of this grid is too large for the marching kernel's 32-bit lane offsets");
     const MarchTiling t = make_march_tiling(g, NJ, kc, j0, j1, 64*CW, j2, j3);
     const unsigned nblocks = march_blocks(t);
 #ifdef MHH_MARCH_STAMP
@@ -773,13 +1032,9 @@ int march_launch(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* 
     MHH_HIP_TRY(hipMemsetAsync(g_stamp_buf, 0, g_stamp_n*8, st));
     mf.dbg = g_stamp_buf;
 #endif
-    // 16-byte LDS-DMA needs 16-byte aligned plane rows; other layouts copy in 4-byte pieces (MHH_MARCH_DMA=4 forces that
-    // form; same arithmetic in both)
     constexpr int VEC = 16 / (int)sizeof(TF);
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
-    const char* env = getenv("MHH_MARCH_DMA");
     const bool aligned = (g->icells % VEC == 0) && al16(f->u) && al16(f->v) && al16(f->w) && (mode == 1 || al16(f->evisc)) && (!has_s || al16(f->s[0]));
-    const int pb = ((env && !strcmp(env, "4")) || !aligned) ? 4 : 16;
+    const int pb = march_piece_bytes(aligned);
 #define MHH_LAUNCH_MARCH(PBV, A, D) do { \
         if (has_s) hipLaunchKernelGGL((rhs25_march_kernel<VT, NJ, true, PBV, A, D>),  dim3(nblocks), dim3(64, NJ), 0, st, mm, gd, mf, t); \
         else       hipLaunchKernelGGL((rhs25_march_kernel<VT, NJ, false, PBV, A, D>), dim3(nblocks), dim3(64, NJ), 0, st, mm, gd, mf, t); } while (0)
@@ -792,6 +1047,62 @@ int march_launch(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* 
     else                { if (pb == 16) MHH_LAUNCH_MARCH(16, false, true); else MHH_LAUNCH_MARCH(4, false, true); }
 #undef MHH_LAUNCH_MARCH
     MHH_LAUNCH_CHECK();
+    return MHH_OK;
+}
+
+unsigned long long g_scalar_march_launches = 0;
+
+// One launch of the scalar pass over the scalars idx[0 .. ns) (ns <= NB); mode as march_launch. Rows as march_launch.
+template<class TF, int NB>
+int scalar_march_launch(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const int* idx, int ns, int j0, int j1, hipStream_t st, int mode, int j2, int j3)
+{
+    constexpr int NJ = MHH_MARCH_NJ;
+    const GridDev<TF> gd = make_grid<TF>(g);
+    ScalarMarchFields<TF, NB> sf;
+    sf.u = cp<TF>(f->u); sf.v = cp<TF>(f->v); sf.w = cp<TF>(f->w); sf.ev = (mode == 1) ? nullptr : cp<TF>(f->evisc);
+    sf.rhoref = cp<TF>(f->rhoref); sf.rhorefh = cp<TF>(f->rhorefh);
+    for (int n=0; n<NB; ++n)
+    {
+        const int m = idx[n < ns ? n : 0];              // slots past ns repeat the first scalar (never read)
+        sf.s[n] = cp<TF>(f->s[m]); sf.st[n] = mp<TF>(f->st[m]); sf.svisc[n] = TF(f->svisc[m]);
+        sf.sfb[n] = cp<TF>(f->s_fluxbot[m]); sf.sft[n] = cp<TF>(f->s_fluxtop[m]);
+    }
+    sf.ns = ns; sf.sm = (p && mode != 1) ? p->surface_model : 0;
+    const MarchMetrics<TF> mm = march_metrics<TF>(gd, f, p, TF(0));
+    MHH_REQUIRE(mode == 1 || known_divisor_ok(mm.tPr2), "tPr must be a positive normal number whose significand is not all ones");
+    const int kc = march_chunk_levels<TF>(g, j0, j1, j2, j3);
+    MHH_REQUIRE(kc > 0, "a plane of this grid is too large for the marching kernel's 32-bit lane offsets");
+    const MarchTiling t = make_march_tiling(g, NJ, kc, j0, j1, 64, j2, j3);
+    const unsigned nblocks = march_blocks(t);
+    // (u, v, w are read per column, not copied; the tile origins are put on a 16-byte piece)
+    constexpr int VEC = 16 / (int)sizeof(TF);
+    bool aligned = (g->icells % VEC == 0) && (mode == 1 || al16(f->evisc));
+    for (int n=0; n<ns; ++n) aligned = aligned && al16(f->s[idx[n]]);
+    const int pb = march_piece_bytes(aligned);
+    sf.hx = (pb == 16) ? 3 + (g->istart - 3) % VEC : 3;
+    sf.ex = (pb == 16) ? 1 + (g->istart - 1) % VEC : 1;
+#define MHH_LAUNCH_SCALAR(PBV, A, D) hipLaunchKernelGGL((rhs25_scalar_march_kernel<TF, NJ, NB, PBV, A, D>), dim3(nblocks), dim3(64, NJ), 0, st, mm, gd, sf, t)
+    if (mode == 0)      { if (pb == 16) MHH_LAUNCH_SCALAR(16, true, true);  else MHH_LAUNCH_SCALAR(4, true, true); }
+    else if (mode == 1) { if (pb == 16) MHH_LAUNCH_SCALAR(16, true, false); else MHH_LAUNCH_SCALAR(4, true, false); }
+    else                { if (pb == 16) MHH_LAUNCH_SCALAR(16, false, true); else MHH_LAUNCH_SCALAR(4, false, true); }
+#undef MHH_LAUNCH_SCALAR
+    MHH_LAUNCH_CHECK();
+    ++g_scalar_march_launches;
+    return MHH_OK;
+}
+// the scalars idx[0 .. n) in batches of MHH_SCALAR_NB (MHH_SCALAR_BATCH=1: one per launch)
+template<class TF>
+int scalar_march_batches(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const int* idx, int n, int j0, int j1, hipStream_t st, int mode, int j2, int j3)
+{
+    const char* e = getenv("MHH_SCALAR_BATCH");
+    const int nb = (e && !strcmp(e, "1")) ? 1 : MHH_SCALAR_NB;
+    for (int b = 0; b < n; b += nb)
+    {
+        const int m = (n - b < nb) ? n - b : nb;
+        const int rc = (m == 1) ? scalar_march_launch<TF, 1>(g, f, p, idx + b, 1, j0, j1, st, mode, j2, j3)
+                                : scalar_march_launch<TF, MHH_SCALAR_NB>(g, f, p, idx + b, m, j0, j1, st, mode, j2, j3);
+        if (rc) return rc;
+    }
     return MHH_OK;
 }
 } // namespace
@@ -829,3 +1140,15 @@ int mhh_rhs25_march_rows2(const mhh_grid* g, const mhh_fields* f, const mhh_diff
 // kernel with one operator's terms only -- what the two calls of an unfused time step run.
 int mhh_advec25_march(const mhh_grid* g, const mhh_fields* f, void* stream) { return march_dispatch(g, f, nullptr, -1, -1, stream, 1); }
 int mhh_diff_smag2_march(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, void* stream) { return march_dispatch(g, f, p, -1, -1, stream, 2); }
+
+// The scalar pass (inputs validated by the caller): advec_2i5 and / or diff_smag2 of the scalars idx[0 .. n) -- mode 0: both (the
+// fused pass), 1: advection only, 2: diffusion only -- over the whole interior (j0 < 0), the rows [j0, j1), or also [j2, j3).
+int mhh_scalar25_march(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const int* idx, int n, int mode, int j0, int j1, int j2, int j3, void* stream)
+{
+    if (n <= 0) return MHH_OK;
+    if (g->dtype == MHH_F64) return scalar_march_batches<double>(g, f, p, idx, n, j0, j1, as_stream(stream), mode, j2, j3);
+    return scalar_march_batches<float>(g, f, p, idx, n, j0, j1, as_stream(stream), mode, j2, j3);
+}
+// MHH_SCALAR_IMPL=cell: scalars 1, 2, ... take the per-field cell kernels instead (A/B switch, read per call)
+bool mhh_scalar_march_on() { const char* e = getenv("MHH_SCALAR_IMPL"); return !(e && !strcmp(e, "cell")); }
+MHH_API unsigned long long mhh_stat_scalar_march_launches(void) { return g_scalar_march_launches; }

@@ -17,6 +17,8 @@ int mhh_rhs25_march_rows2(const mhh_grid* g, const mhh_fields* f, const mhh_diff
 int mhh_rhs25_march_rows(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, int j0, int j1, void* stream);   // k_march.hip
 int mhh_rhs44_march(const mhh_grid* g, const mhh_fields* f, void* stream);
 int mhh_diff4_march(const mhh_grid* g, const mhh_fields* f, void* stream);                                           // k_march4.hip
+int mhh_scalar25_march(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const int* idx, int n, int mode, int j0, int j1, int j2, int j3, void* stream);   // k_march.hip
+bool mhh_scalar_march_on();
 
 // =======================================================================================================
 // Max reductions (calc_cfl / calc_dnmul / calc_divergence + Master::max). All integrands are |.| >= 0, so the
@@ -244,8 +246,8 @@ MHH_API int mhh_diff_exec(const mhh_grid* g, int scheme, const mhh_fields* f, co
     MHH_REQUIRE(scheme == MHH_DIFF_SMAG2 && p, "scheme must be 2, 4 or 22 (with params)");
     const int sm = p->surface_model;
     // u, v, w and the first scalar in one pass of the marching kernel with the diffusive terms only (k_march.hip; same bits
-    // as the per-field kernels, which MHH_DIFF22_IMPL=cell selects); further scalars per field. Needs the advec_2i5 halo
-    // (the tiles are cut for it): other layouts take the per-field kernels.
+    // as the per-field kernels, which MHH_DIFF22_IMPL=cell selects); further scalars in the scalar pass of that kernel
+    // (MHH_SCALAR_IMPL=cell: per field). Needs the advec_2i5 halo (the tiles are cut for it): other layouts take the per-field kernels.
     const char* impl = getenv("MHH_DIFF22_IMPL");
     if (!(impl && !strcmp(impl, "cell")) && g && g->igc >= 3 && g->jgc >= 3 && g->kgc >= 1 && g->ktot >= 6)
     {
@@ -255,6 +257,12 @@ MHH_API int mhh_diff_exec(const mhh_grid* g, int scheme, const mhh_fields* f, co
         for (int n=0; n<f->nscalars; ++n) MHH_REQUIRE(f->s[n] && f->st[n] && (!sm || (f->s_fluxbot[n] && f->s_fluxtop[n])), "null scalar / scalar surface fluxes");
         mhh_fields fm = *f; fm.nscalars = f->nscalars > 0 ? 1 : 0;
         if (int e = mhh_diff_smag2_march(g, &fm, p, stream)) return e;
+        if (f->nscalars > 1 && mhh_scalar_march_on())
+        {
+            int idx[MHH_MAX_SCALARS];
+            for (int n=1; n<f->nscalars; ++n) idx[n-1] = n;
+            return mhh_scalar25_march(g, f, p, idx, f->nscalars - 1, 2, -1, -1, -1, -1, stream);
+        }
         for (int n=1; n<f->nscalars; ++n)
             if (int e = mhh_smag2_diff_c(g, sm, f->st[n], f->s[n], f->evisc, f->s_fluxbot[n], f->s_fluxtop[n], f->rhoref, f->rhorefh, p->tPr, f->svisc[n], stream)) return e;
         return MHH_OK;
@@ -466,8 +474,9 @@ MHH_API int mhh_rhs_exec(const mhh_grid* g, int advec_scheme, int diff_scheme, c
             MHH_REQUIRE(f->u_fluxbot && f->u_fluxtop && f->v_fluxbot && f->v_fluxtop, "surface fluxes");
             for (int n=0; n<f->nscalars; ++n) MHH_REQUIRE(f->s_fluxbot[n] && f->s_fluxtop[n], "scalar surface fluxes");
         }
-        // default: the k-marching LDS kernel (k_march.hip) for u, v, w and scalar 0; further scalars take the
-        // per-field kernels. MHH_RHS25_IMPL=cell selects the one-thread-per-cell fused kernel (A/B measurements).
+        // default: the k-marching LDS kernel (k_march.hip) for u, v, w and scalar 0; further unlimited scalars take the scalar
+        // pass of that kernel (MHH_SCALAR_IMPL=cell: the per-field kernels), flux-limited ones the per-field kernels.
+        // MHH_RHS25_IMPL=cell selects the one-thread-per-cell fused kernel (A/B measurements).
         const bool use_cell = [] { const char* e = getenv("MHH_RHS25_IMPL"); return e && !strcmp(e, "cell"); }();   // A/B switch, read per call
         bool any_lim = false;
         for (int n=0; n<f->nscalars; ++n) any_lim = any_lim || f->s_fluxlimit[n];
@@ -488,8 +497,16 @@ MHH_API int mhh_rhs_exec(const mhh_grid* g, int advec_scheme, int diff_scheme, c
                 if (int e = mhh_rhs25_march(g, &fm, pm, stream)) return e;
             }
             else if (int e = mhh_rhs25_march(g, f, pm, stream)) return e;
+            const bool pass = !use_cell && mhh_scalar_march_on();
+            if (pass)
+            {
+                int idx[MHH_MAX_SCALARS], nq = 0;
+                for (int n=first; n<f->nscalars; ++n) if (!f->s_fluxlimit[n]) idx[nq++] = n;
+                if (int e = mhh_scalar25_march(g, f, p, idx, nq, 0, -1, -1, -1, -1, stream)) return e;
+            }
             for (int n=first; n<f->nscalars; ++n)
             {
+                if (pass && !f->s_fluxlimit[n]) continue;
                 if (f->s_fluxlimit[n]) { if (int e = mhh_advec_s_lim(g, f->st[n], f->s[n], f->u, f->v, f->w, f->rhoref, f->rhorefh, stream)) return e; }
                 else if (int e = mhh_advec_s(g, MHH_ADVEC_2I5, f->st[n], f->s[n], f->u, f->v, f->w, f->rhoref, f->rhorefh, stream)) return e;
                 if (int e = mhh_smag2_diff_c(g, p->surface_model, f->st[n], f->s[n], f->evisc, f->s_fluxbot[n], f->s_fluxtop[n], f->rhoref, f->rhorefh, p->tPr, f->svisc[n], stream)) return e;
@@ -537,37 +554,44 @@ MHH_API int mhh_rhs_exec(const mhh_grid* g, int advec_scheme, int diff_scheme, c
 }
 
 // The (advec_2i5, diff_smag2) pass over the rows [j0, j1) only: the slab driver updates the rows that need no
-// north-south halo while the halos travel and the edge rows afterwards. u, v, w and at most one scalar (in the kernel).
-MHH_API int mhh_rhs_exec_rows(const mhh_grid* g, int advec_scheme, int diff_scheme, const mhh_fields* f, const mhh_diff_params* p, int j0, int j1, void* stream)
+// north-south halo while the halos travel and the edge rows afterwards. u, v, w and scalar 0 in the fused marching kernel,
+// further scalars in its scalar pass over the same rows; no flux-limited scalar (the limiter has no row-wise form).
+static int rhs_rows_checks(const mhh_grid* g, int advec_scheme, int diff_scheme, const mhh_fields* f, const mhh_diff_params* p)
 {
-    if (int e = check_grid(g)) return e;
     MHH_REQUIRE(advec_scheme == MHH_ADVEC_2I5 && diff_scheme == MHH_DIFF_SMAG2, "row-wise pass: (advec_2i5, diff_smag2) only");
     MHH_REQUIRE(f && p && f->u && f->v && f->w && f->ut && f->vt && f->wt && f->evisc && f->rhoref && f->rhorefh, "null field");
-    MHH_REQUIRE(f->nscalars >= 0 && f->nscalars <= 1 && (f->nscalars == 0 || (f->s[0] && f->st[0] && !f->s_fluxlimit[0])), "row-wise pass: at most one, unlimited scalar");
-    MHH_REQUIRE(!p->buoyancy || (p->buoyancy == 2 && p->th_for_N2 == 0 && f->nscalars == 1 && p->threfh), "row-wise pass: buoyancy only as the in-kernel 2nd-order form of scalar 0");
+    MHH_REQUIRE(f->nscalars >= 0 && f->nscalars <= MHH_MAX_SCALARS, "nscalars");
+    for (int n=0; n<f->nscalars; ++n) MHH_REQUIRE(f->s[n] && f->st[n] && !f->s_fluxlimit[n], "row-wise pass: at most one, unlimited scalar");
+    MHH_REQUIRE(!p->buoyancy || (p->buoyancy == 2 && p->th_for_N2 == 0 && f->nscalars >= 1 && p->threfh), "row-wise pass: buoyancy only as the in-kernel 2nd-order form of scalar 0");
     MHH_REQUIRE(g->igc >= 3 && g->jgc >= 3 && g->kgc >= 1 && g->ktot >= 6, "advec_2i5 needs gc(3,3,1), ktot>=6");
-    MHH_REQUIRE(j0 >= g->jstart && j0 < j1 && j1 <= g->jend, "rows must lie in [jstart, jend)");
     if (p->surface_model)
     {
         MHH_REQUIRE(f->u_fluxbot && f->u_fluxtop && f->v_fluxbot && f->v_fluxtop, "surface fluxes");
-        if (f->nscalars) MHH_REQUIRE(f->s_fluxbot[0] && f->s_fluxtop[0], "scalar surface fluxes");
+        for (int n=0; n<f->nscalars; ++n) MHH_REQUIRE(f->s_fluxbot[n] && f->s_fluxtop[n], "scalar surface fluxes");
     }
-    return mhh_rhs25_march_rows(g, f, p, j0, j1, stream);
+    return MHH_OK;
+}
+// scalars 1, 2, ... of a row-wise call: the scalar pass over the same rows
+static int rhs_rows_scalars(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, int j0, int j1, int j2, int j3, void* stream)
+{
+    int idx[MHH_MAX_SCALARS];
+    for (int n=1; n<f->nscalars; ++n) idx[n-1] = n;
+    return mhh_scalar25_march(g, f, p, idx, f->nscalars - 1, 0, j0, j1, j2, j3, stream);
+}
+MHH_API int mhh_rhs_exec_rows(const mhh_grid* g, int advec_scheme, int diff_scheme, const mhh_fields* f, const mhh_diff_params* p, int j0, int j1, void* stream)
+{
+    if (int e = check_grid(g)) return e;
+    if (int e = rhs_rows_checks(g, advec_scheme, diff_scheme, f, p)) return e;
+    MHH_REQUIRE(j0 >= g->jstart && j0 < j1 && j1 <= g->jend, "rows must lie in [jstart, jend)");
+    if (int e = mhh_rhs25_march_rows(g, f, p, j0, j1, stream)) return e;
+    return rhs_rows_scalars(g, f, p, j0, j1, -1, -1, stream);
 }
 // the same over two row ranges in one launch (the two edge strips of a slab)
 MHH_API int mhh_rhs_exec_rows2(const mhh_grid* g, int advec_scheme, int diff_scheme, const mhh_fields* f, const mhh_diff_params* p, int j0, int j1, int j2, int j3, void* stream)
 {
     if (int e = check_grid(g)) return e;
-    MHH_REQUIRE(advec_scheme == MHH_ADVEC_2I5 && diff_scheme == MHH_DIFF_SMAG2, "row-wise pass: (advec_2i5, diff_smag2) only");
-    MHH_REQUIRE(f && p && f->u && f->v && f->w && f->ut && f->vt && f->wt && f->evisc && f->rhoref && f->rhorefh, "null field");
-    MHH_REQUIRE(f->nscalars >= 0 && f->nscalars <= 1 && (f->nscalars == 0 || (f->s[0] && f->st[0] && !f->s_fluxlimit[0])), "row-wise pass: at most one, unlimited scalar");
-    MHH_REQUIRE(!p->buoyancy || (p->buoyancy == 2 && p->th_for_N2 == 0 && f->nscalars == 1 && p->threfh), "row-wise pass: buoyancy only as the in-kernel 2nd-order form of scalar 0");
-    MHH_REQUIRE(g->igc >= 3 && g->jgc >= 3 && g->kgc >= 1 && g->ktot >= 6, "advec_2i5 needs gc(3,3,1), ktot>=6");
+    if (int e = rhs_rows_checks(g, advec_scheme, diff_scheme, f, p)) return e;
     MHH_REQUIRE(j0 >= g->jstart && j0 < j1 && j1 <= j2 && j2 < j3 && j3 <= g->jend, "two disjoint, ordered row ranges in [jstart, jend)");
-    if (p->surface_model)
-    {
-        MHH_REQUIRE(f->u_fluxbot && f->u_fluxtop && f->v_fluxbot && f->v_fluxtop, "surface fluxes");
-        if (f->nscalars) MHH_REQUIRE(f->s_fluxbot[0] && f->s_fluxtop[0], "scalar surface fluxes");
-    }
-    return mhh_rhs25_march_rows2(g, f, p, j0, j1, j2, j3, stream);
+    if (int e = mhh_rhs25_march_rows2(g, f, p, j0, j1, j2, j3, stream)) return e;
+    return rhs_rows_scalars(g, f, p, j0, j1, j2, j3, stream);
 }

@@ -341,7 +341,8 @@ class Pres_slab
 // tendencies on rows [jstart+4, jend-4); both edge strips follow in ONE launch per operator once the halos are in
 // (mhh_diff_exec_viscosity_rows2, mhh_rhs_exec_rows2). evisc on the two ghost rows next to the slab is evaluated locally from the
 // velocity halos (same operands as on the neighbour: same bits), so it is not exchanged. Row-wise calls give the bits of the
-// whole-slab calls. Needs advec_2i5 + diff_smag2, one scalar, jgc >= 3 and jmax >= 12; can_overlap() tells.
+// whole-slab calls. Needs advec_2i5 + diff_smag2, one to MHH_MAX_SCALARS scalars none of which is flux-limited (scalar 0 runs in the
+// fused marching kernel, the others in its scalar pass over the same rows), jgc >= 3 and jmax >= 12; can_overlap() tells.
 template<typename TF>
 class Substep_slab
 {
@@ -356,7 +357,8 @@ class Substep_slab
         bool can_overlap(const Advec<TF>& advec, const Diff<TF>& diff) const
         {
             const auto& gd = grid.get_grid_data();
-            return advec.get_scheme() == MHH_ADVEC_2I5 && diff.get_scheme() == MHH_DIFF_SMAG2 && fields.sp.size() == 1 && gd.jgc >= 3 && gd.jmax >= 12;
+            return advec.get_scheme() == MHH_ADVEC_2I5 && diff.get_scheme() == MHH_DIFF_SMAG2 && !fields.sp.empty() && fields.sp.size() <= MHH_MAX_SCALARS
+                   && advec.fluxlimit_list.empty() && gd.jgc >= 3 && gd.jmax >= 12;
         }
         void halo_visc_rhs(Advec<TF>& advec, Diff<TF>& diff, Thermo<TF>& thermo)
         {

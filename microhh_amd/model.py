@@ -33,9 +33,10 @@ FIELDS3 = ("u", "v", "w", "ut", "vt", "wt")
 SURF = ("u_fluxbot", "u_fluxtop", "v_fluxbot", "v_fluxtop", "s_fluxbot", "s_fluxtop", "dudz", "dvdz", "dbdz", "z0m")
 
 
-def synthetic_global(case, itot, jtot, ktot, dtype=np.float64, seed=666):
+def synthetic_global(case, itot, jtot, ktot, dtype=np.float64, seed=666, nscalars=None):
     """Global synthetic fields on the host (interior only; ghosts are filled by the halo code). For tests that
-    compare a slab-decomposed run with a single-rank run."""
+    compare a slab-decomposed run with a single-rank run. nscalars: scalars to make (None = the case's count); every
+    one follows scalar 0's recipe."""
     cfg = CASES[case]
     rs = np.random.RandomState(seed)
     n3, n2 = (ktot, jtot, itot), (jtot, itot)
@@ -43,7 +44,7 @@ def synthetic_global(case, itot, jtot, ktot, dtype=np.float64, seed=666):
            "ut": rs.uniform(0, 1e-3, n3), "vt": rs.uniform(0, 1e-3, n3), "wt": rs.uniform(0, 1e-3, n3)}
     out["w"][0] = 0; out["wt"][0] = 0
     z = (np.arange(ktot) + 0.5) * cfg["size"][2] / ktot
-    for n in range(cfg["nscalars"]):
+    for n in range(cfg["nscalars"] if nscalars is None else nscalars):
         out["s%d" % n] = 300. + 0.003*z[:, None, None] + rs.uniform(-.05, .05, n3)
         out["st%d" % n] = rs.uniform(0, 1e-4, n3)
     for k in SURF:
@@ -56,12 +57,17 @@ class HotPath:
     """Device-resident fields of ONE rank + the operator calls of one sub-step."""
 
     def __init__(self, case, itot, jtot, ktot, dtype=np.float64, device="cuda:0", seed=666, dt=1.0,
-                 lib=None, npy=1, rank=0, group=None, global_init=None, force_slab=False, slim_halos=True, overlap=None, pres_chunks=None, igc=None):
+                 lib=None, npy=1, rank=0, group=None, global_init=None, force_slab=False, slim_halos=True, overlap=None, pres_chunks=None, igc=None,
+                 nscalars=None):
         import torch
         self.torch = torch
         self.lib = lib if lib is not None else capi.lib()
         self.cfg = cfg = CASES[case]
         self.case, self.dt, self.npy, self.rank, self.group = case, dt, npy, rank, group
+        # scalars carried (None = the case's count): th plus, e.g., qt or passive tracers, each made like scalar 0
+        nsc = cfg["nscalars"] if nscalars is None else int(nscalars)
+        if not 0 <= nsc <= capi.MAX_SCALARS:
+            raise ValueError("nscalars must lie in [0, %d]" % capi.MAX_SCALARS)
         # slab code path (halo pack/unpack, split pressure solve); force_slab runs it on ONE rank with the exchanges
         # degenerated to local copies, which is how the slab kernels are exercised on a single-GPU box
         self.slab = (npy > 1) or force_slab
@@ -115,8 +121,8 @@ class HotPath:
             self.u, self.v, self.w = rnd(n3, -1, 1), rnd(n3, -1, 1), rnd(n3, -0.5, 0.5)
             self.ut, self.vt, self.wt = rnd(n3, 0, 1e-3), rnd(n3, 0, 1e-3), rnd(n3, 0, 1e-3)
             zc = torch.from_numpy(g.z.astype(np.float64)).to(self.device).to(td)
-            self.s = [(300. + 0.003*zc[:, None, None] + rnd(n3, -0.05, 0.05)).contiguous() for _ in range(cfg["nscalars"])]
-            self.st = [rnd(n3, 0, 1e-4) for _ in range(cfg["nscalars"])]
+            self.s = [(300. + 0.003*zc[:, None, None] + rnd(n3, -0.05, 0.05)).contiguous() for _ in range(nsc)]
+            self.st = [rnd(n3, 0, 1e-4) for _ in range(nsc)]
             self.surf = {k: rnd(n2, 0, 1e-2) for k in SURF}
             self.surf["dbdz"] = rnd(n2, 0, 1e-4)
             self.surf["z0m"] = torch.full(n2, 0.1, device=self.device, dtype=td)
@@ -134,8 +140,8 @@ class HotPath:
                 return t.to(self.device).contiguous()
             for n in FIELDS3:
                 setattr(self, n, put3(global_init[n]))
-            self.s = [put3(global_init["s%d" % n]) for n in range(cfg["nscalars"])]
-            self.st = [put3(global_init["st%d" % n]) for n in range(cfg["nscalars"])]
+            self.s = [put3(global_init["s%d" % n]) for n in range(nsc)]
+            self.st = [put3(global_init["st%d" % n]) for n in range(nsc)]
             self.surf = {k: put2(global_init[k]) for k in SURF}
         # solid walls: w and its tendency vanish at kstart and above kend-1
         self.w[:g.kstart+1] = 0; self.w[g.kend:] = 0
@@ -341,7 +347,7 @@ class HotPath:
     def can_overlap(self):
         g = self.grid
         return (self.slab and self.overlap and self.evisc_local_ghosts and self.cfg["advec"] == ADVEC_2I5 and self.cfg["diff"] == DIFF_SMAG2
-                and len(self.s) == 1 and g.jgc >= 3 and g.jmax >= 12)
+                and len(self.s) >= 1 and g.jgc >= 3 and g.jmax >= 12)      # 1 .. MHH_MAX_SCALARS scalars, none flux-limited (HotPath limits none): as Substep_slab::can_overlap
 
     def halo_visc_rhs(self, ev=None):
         """cyclic_prognostic + exec_viscosity + rhs of a slab rank with the halo exchange of u, v, w, th (jgc rows of four
