@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include "../../include/mhh_hip.h"
@@ -150,6 +151,8 @@ inline int launch_interior(hipStream_t st, const GridDev<TF>& g, int k0, int k1,
 }
 
 #define MHH_DISPATCH(g, CALL) ((g)->dtype == MHH_F64 ? CALL(double) : CALL(float))
+// A/B and tuning switches, read per call: is the environment variable `name` set to `value`?
+inline bool env_is(const char* name, const char* value) { const char* e = getenv(name); return e && !strcmp(e, value); }
 
 // The inverse transform's normalisation, value / jtot / itot (src/fft.cxx). Where both extents are powers of two (POW2) the
 // two divisions are two multiplications by the exact reciprocals: the same correctly rounded results, a tenth of the issue slots.

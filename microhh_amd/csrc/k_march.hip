@@ -981,37 +981,30 @@ template<class TF> MarchMetrics<TF> march_metrics(const GridDev<TF>& gd, const m
     mm.tPr2 = TF(2.)*tPr; mm.rtPr2 = TF(1.)/mm.tPr2;
     return mm;
 }
-// Levels per k-chunk of both marching kernels over the rows [j0, j1) (+ [j2, j3)), or 0 where the grid's planes are too large:
-// a strip of a few rows (mhh_rhs_exec_rows on the edge rows) takes short k-chunks, enough blocks to fill the GPU; the lanes
-// address a chunk's planes with 32-bit byte offsets from the chunk's first plane: (kc + 8) planes below 4 GB
-template<class TF> int march_chunk_levels(const mhh_grid* g, int j0, int j1, int j2, int j3)
+// Levels per k-chunk of both marching kernels over the rows, or 0 where the grid's planes are too large: the lanes address a
+// chunk's planes with 32-bit byte offsets from the chunk's first plane: (kc + 8) planes below 4 GB
+template<class TF> int march_chunk_levels(const mhh_grid* g, const MarchRows& rows)
 {
-    int kc = (j0 >= 0 && (j1 - j0 + (j2 >= 0 ? j3 - j2 : 0)) * 4 <= g->jmax) ? 16 : MHH_MARCH_KC;
-    { const char* e = getenv("MHH_MARCH_KC_RT"); if (e && atoi(e) >= 8) kc = atoi(e); }       // tuning runs: levels per chunk at run time
+    int kc = march_kc(g, rows, MHH_MARCH_KC, "MHH_MARCH_KC_RT");
     const unsigned long long plane_bytes = (unsigned long long)g->ijcells * sizeof(TF);
     while (kc > 8 && (unsigned long long)(kc + 8) * plane_bytes >= (1ull << 32)) kc /= 2;
     return ((unsigned long long)(kc + 8) * plane_bytes < (1ull << 32)) ? kc : 0;
 }
 // Piece size of both kernels' LDS-DMA copies: 16 bytes where the rows and every copied array are 16-byte aligned, 4 bytes
 // otherwise (MHH_MARCH_DMA=4 forces that form; same arithmetic in both)
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
-inline int march_piece_bytes(bool aligned)
-{
-    const char* env = getenv("MHH_MARCH_DMA");
-    return ((env && !strcmp(env, "4")) || !aligned) ? 4 : 16;
-}
+inline int march_piece_bytes(bool aligned) { return (env_is("MHH_MARCH_DMA", "4") || !aligned) ? 4 : 16; }
 
-// mode 0: advec_2i5 + diff_smag2 (the fused pass); 1: advec_2i5 only (p may be null); 2: diff_smag2 only
+// ops MARCH_ADVEC: p may be null
 // VT = lane value type: double, float, or F2 = two fp32 cells per lane (packed arithmetic; needs an even imax)
 template<class VT>
-int march_launch(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, int j0, int j1, hipStream_t st, int mode = 0, int j2 = -1, int j3 = -1)
+int march_launch(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, MarchOps ops, const MarchRows& rows, hipStream_t st)
 {
     using TF = typename lane_of<VT>::scalar;
     constexpr int CW = lane_of<VT>::cells;
     constexpr int NJ = MHH_MARCH_NJ;
     const GridDev<TF> gd = make_grid<TF>(g);
     MarchFields<TF> mf;
-    mf.u = cp<TF>(f->u); mf.v = cp<TF>(f->v); mf.w = cp<TF>(f->w); mf.ev = (mode == 1) ? nullptr : cp<TF>(f->evisc);
+    mf.u = cp<TF>(f->u); mf.v = cp<TF>(f->v); mf.w = cp<TF>(f->w); mf.ev = (ops == MARCH_ADVEC) ? nullptr : cp<TF>(f->evisc);
     mf.ut = mp<TF>(f->ut); mf.vt = mp<TF>(f->vt); mf.wt = mp<TF>(f->wt);
     const bool has_s = f->nscalars >= 1;
     mf.s = has_s ? cp<TF>(f->s[0]) : nullptr; mf.st = has_s ? mp<TF>(f->st[0]) : nullptr;
@@ -1019,13 +1012,13 @@ int march_launch(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* 
     mf.ufb = cp<TF>(f->u_fluxbot); mf.uft = cp<TF>(f->u_fluxtop); mf.vfb = cp<TF>(f->v_fluxbot); mf.vft = cp<TF>(f->v_fluxtop);
     mf.sfb = has_s ? cp<TF>(f->s_fluxbot[0]) : nullptr; mf.sft = has_s ? cp<TF>(f->s_fluxtop[0]) : nullptr;
     const MarchMetrics<TF> mm = march_metrics<TF>(gd, f, p, has_s ? TF(f->svisc[0]) : TF(0));
-    mf.sm = (p && mode != 1) ? p->surface_model : 0;
-    MHH_REQUIRE(mode == 1 || !has_s || known_divisor_ok(mm.tPr2), "tPr must be a positive normal number whose significand is not all ones");
-    const bool buoy = mode == 0 && has_s && p->buoyancy == 2 && p->th_for_N2 == 0;
+    mf.sm = (p && ops != MARCH_ADVEC) ? p->surface_model : 0;
+    MHH_REQUIRE(ops == MARCH_ADVEC || !has_s || known_divisor_ok(mm.tPr2), "tPr must be a positive normal number whose significand is not all ones");
+    const bool buoy = ops == MARCH_BOTH && has_s && p->buoyancy == 2 && p->th_for_N2 == 0;
     mf.threfh = buoy ? cp<TF>(p->threfh) : nullptr; mf.grav = buoy ? TF(p->grav) : TF(0);
-    const int kc = march_chunk_levels<TF>(g, j0, j1, j2, j3);
+    const int kc = march_chunk_levels<TF>(g, rows);
     MHH_REQUIRE(kc > 0, "a plane of this grid is too large for the marching kernel's 32-bit lane offsets");
-    const MarchTiling t = make_march_tiling(g, NJ, kc, j0, j1, 64*CW, j2, j3);
+    const MarchTiling t = make_march_tiling(g, NJ, kc, 64*CW, rows);
     const unsigned nblocks = march_blocks(t);
 #ifdef MHH_MARCH_STAMP
     if (g_stamp_n < (size_t)nblocks*NJ*8) { if (g_stamp_buf) (void)hipFree(g_stamp_buf); g_stamp_n = (size_t)nblocks*NJ*8; MHH_HIP_TRY(hipMalloc(&g_stamp_buf, g_stamp_n*8)); }
@@ -1033,33 +1026,28 @@ int march_launch(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* 
     mf.dbg = g_stamp_buf;
 #endif
     constexpr int VEC = 16 / (int)sizeof(TF);
-    const bool aligned = (g->icells % VEC == 0) && al16(f->u) && al16(f->v) && al16(f->w) && (mode == 1 || al16(f->evisc)) && (!has_s || al16(f->s[0]));
+    const bool aligned = (g->icells % VEC == 0) && al16(f->u) && al16(f->v) && al16(f->w) && (ops == MARCH_ADVEC || al16(f->evisc)) && (!has_s || al16(f->s[0]));
     const int pb = march_piece_bytes(aligned);
-#define MHH_LAUNCH_MARCH(PBV, A, D) do { \
-        if (has_s) hipLaunchKernelGGL((rhs25_march_kernel<VT, NJ, true, PBV, A, D>),  dim3(nblocks), dim3(64, NJ), 0, st, mm, gd, mf, t); \
-        else       hipLaunchKernelGGL((rhs25_march_kernel<VT, NJ, false, PBV, A, D>), dim3(nblocks), dim3(64, NJ), 0, st, mm, gd, mf, t); } while (0)
     // tile origin on a 16-byte piece where three cells west of the first cell is not one (istart = 16: rows of whole cache lines)
-    const char* ehx = getenv("MHH_MARCH_HX");
-    const bool hx4 = mode == 0 && has_s && pb == 16 && (g->istart - 3) % VEC != 0 && (g->istart - 4) % VEC == 0 && g->istart >= 4 && !(ehx && !strcmp(ehx, "3"));
+    const bool hx4 = ops == MARCH_BOTH && has_s && pb == 16 && (g->istart - 3) % VEC != 0 && (g->istart - 4) % VEC == 0 && g->istart >= 4 && !env_is("MHH_MARCH_HX", "3");
     if (hx4) hipLaunchKernelGGL((rhs25_march_kernel<VT, NJ, true, 16, true, true, 4>), dim3(nblocks), dim3(64, NJ), 0, st, mm, gd, mf, t);
-    else if (mode == 0) { if (pb == 16) MHH_LAUNCH_MARCH(16, true, true);  else MHH_LAUNCH_MARCH(4, true, true); }
-    else if (mode == 1) { if (pb == 16) MHH_LAUNCH_MARCH(16, true, false); else MHH_LAUNCH_MARCH(4, true, false); }
-    else                { if (pb == 16) MHH_LAUNCH_MARCH(16, false, true); else MHH_LAUNCH_MARCH(4, false, true); }
-#undef MHH_LAUNCH_MARCH
+    else march_variant(ops, pb, [&](auto PB, auto A, auto D) {
+        if (has_s) hipLaunchKernelGGL((rhs25_march_kernel<VT, NJ, true, PB, A, D>),  dim3(nblocks), dim3(64, NJ), 0, st, mm, gd, mf, t);
+        else       hipLaunchKernelGGL((rhs25_march_kernel<VT, NJ, false, PB, A, D>), dim3(nblocks), dim3(64, NJ), 0, st, mm, gd, mf, t); });
     MHH_LAUNCH_CHECK();
     return MHH_OK;
 }
 
 unsigned long long g_scalar_march_launches = 0;
 
-// One launch of the scalar pass over the scalars idx[0 .. ns) (ns <= NB); mode as march_launch. Rows as march_launch.
+// One launch of the scalar pass over the scalars idx[0 .. ns) (ns <= NB); ops and rows as march_launch
 template<class TF, int NB>
-int scalar_march_launch(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const int* idx, int ns, int j0, int j1, hipStream_t st, int mode, int j2, int j3)
+int scalar_march_launch(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const int* idx, int ns, MarchOps ops, const MarchRows& rows, hipStream_t st)
 {
     constexpr int NJ = MHH_MARCH_NJ;
     const GridDev<TF> gd = make_grid<TF>(g);
     ScalarMarchFields<TF, NB> sf;
-    sf.u = cp<TF>(f->u); sf.v = cp<TF>(f->v); sf.w = cp<TF>(f->w); sf.ev = (mode == 1) ? nullptr : cp<TF>(f->evisc);
+    sf.u = cp<TF>(f->u); sf.v = cp<TF>(f->v); sf.w = cp<TF>(f->w); sf.ev = (ops == MARCH_ADVEC) ? nullptr : cp<TF>(f->evisc);
     sf.rhoref = cp<TF>(f->rhoref); sf.rhorefh = cp<TF>(f->rhorefh);
     for (int n=0; n<NB; ++n)
     {
@@ -1067,40 +1055,36 @@ int scalar_march_launch(const mhh_grid* g, const mhh_fields* f, const mhh_diff_p
         sf.s[n] = cp<TF>(f->s[m]); sf.st[n] = mp<TF>(f->st[m]); sf.svisc[n] = TF(f->svisc[m]);
         sf.sfb[n] = cp<TF>(f->s_fluxbot[m]); sf.sft[n] = cp<TF>(f->s_fluxtop[m]);
     }
-    sf.ns = ns; sf.sm = (p && mode != 1) ? p->surface_model : 0;
+    sf.ns = ns; sf.sm = (p && ops != MARCH_ADVEC) ? p->surface_model : 0;
     const MarchMetrics<TF> mm = march_metrics<TF>(gd, f, p, TF(0));
-    MHH_REQUIRE(mode == 1 || known_divisor_ok(mm.tPr2), "tPr must be a positive normal number whose significand is not all ones");
-    const int kc = march_chunk_levels<TF>(g, j0, j1, j2, j3);
+    MHH_REQUIRE(ops == MARCH_ADVEC || known_divisor_ok(mm.tPr2), "tPr must be a positive normal number whose significand is not all ones");
+    const int kc = march_chunk_levels<TF>(g, rows);
     MHH_REQUIRE(kc > 0, "a plane of this grid is too large for the marching kernel's 32-bit lane offsets");
-    const MarchTiling t = make_march_tiling(g, NJ, kc, j0, j1, 64, j2, j3);
+    const MarchTiling t = make_march_tiling(g, NJ, kc, 64, rows);
     const unsigned nblocks = march_blocks(t);
     // (u, v, w are read per column, not copied; the tile origins are put on a 16-byte piece)
     constexpr int VEC = 16 / (int)sizeof(TF);
-    bool aligned = (g->icells % VEC == 0) && (mode == 1 || al16(f->evisc));
+    bool aligned = (g->icells % VEC == 0) && (ops == MARCH_ADVEC || al16(f->evisc));
     for (int n=0; n<ns; ++n) aligned = aligned && al16(f->s[idx[n]]);
     const int pb = march_piece_bytes(aligned);
     sf.hx = (pb == 16) ? 3 + (g->istart - 3) % VEC : 3;
     sf.ex = (pb == 16) ? 1 + (g->istart - 1) % VEC : 1;
-#define MHH_LAUNCH_SCALAR(PBV, A, D) hipLaunchKernelGGL((rhs25_scalar_march_kernel<TF, NJ, NB, PBV, A, D>), dim3(nblocks), dim3(64, NJ), 0, st, mm, gd, sf, t)
-    if (mode == 0)      { if (pb == 16) MHH_LAUNCH_SCALAR(16, true, true);  else MHH_LAUNCH_SCALAR(4, true, true); }
-    else if (mode == 1) { if (pb == 16) MHH_LAUNCH_SCALAR(16, true, false); else MHH_LAUNCH_SCALAR(4, true, false); }
-    else                { if (pb == 16) MHH_LAUNCH_SCALAR(16, false, true); else MHH_LAUNCH_SCALAR(4, false, true); }
-#undef MHH_LAUNCH_SCALAR
+    march_variant(ops, pb, [&](auto PB, auto A, auto D) {
+        hipLaunchKernelGGL((rhs25_scalar_march_kernel<TF, NJ, NB, PB, A, D>), dim3(nblocks), dim3(64, NJ), 0, st, mm, gd, sf, t); });
     MHH_LAUNCH_CHECK();
     ++g_scalar_march_launches;
     return MHH_OK;
 }
 // the scalars idx[0 .. n) in batches of MHH_SCALAR_NB (MHH_SCALAR_BATCH=1: one per launch)
 template<class TF>
-int scalar_march_batches(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const int* idx, int n, int j0, int j1, hipStream_t st, int mode, int j2, int j3)
+int scalar_march_batches(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const int* idx, int n, MarchOps ops, const MarchRows& rows, hipStream_t st)
 {
-    const char* e = getenv("MHH_SCALAR_BATCH");
-    const int nb = (e && !strcmp(e, "1")) ? 1 : MHH_SCALAR_NB;
+    const int nb = env_is("MHH_SCALAR_BATCH", "1") ? 1 : MHH_SCALAR_NB;
     for (int b = 0; b < n; b += nb)
     {
         const int m = (n - b < nb) ? n - b : nb;
-        const int rc = (m == 1) ? scalar_march_launch<TF, 1>(g, f, p, idx + b, 1, j0, j1, st, mode, j2, j3)
-                                : scalar_march_launch<TF, MHH_SCALAR_NB>(g, f, p, idx + b, m, j0, j1, st, mode, j2, j3);
+        const int rc = (m == 1) ? scalar_march_launch<TF, 1>(g, f, p, idx + b, 1, ops, rows, st)
+                                : scalar_march_launch<TF, MHH_SCALAR_NB>(g, f, p, idx + b, m, ops, rows, st);
         if (rc) return rc;
     }
     return MHH_OK;
@@ -1118,37 +1102,16 @@ extern "C" __attribute__((visibility("default"))) long long mhh_march_stamps(uns
 }
 #endif
 // fp32: two cells per lane with packed arithmetic where the rows are whole 128-cell tiles; MHH_MARCH_F32X2=0 keeps one cell per lane
-static bool f32x2(const mhh_grid* g)
+int mhh::march25(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, MarchOps ops, const MarchRows& rows, void* stream)
 {
-    const char* e = getenv("MHH_MARCH_F32X2");
-    return g->imax % 128 == 0 && !(e && !strcmp(e, "0"));
+    if (g->dtype == MHH_F64) return march_launch<double>(g, f, p, ops, rows, as_stream(stream));
+    if (g->imax % 128 == 0 && !env_is("MHH_MARCH_F32X2", "0")) return march_launch<F2>(g, f, p, ops, rows, as_stream(stream));
+    return march_launch<float>(g, f, p, ops, rows, as_stream(stream));
 }
-static int march_dispatch(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, int j0, int j1, void* stream, int mode, int j2 = -1, int j3 = -1)
-{
-    if (g->dtype == MHH_F64) return march_launch<double>(g, f, p, j0, j1, as_stream(stream), mode, j2, j3);
-    if (f32x2(g)) return march_launch<F2>(g, f, p, j0, j1, as_stream(stream), mode, j2, j3);
-    return march_launch<float>(g, f, p, j0, j1, as_stream(stream), mode, j2, j3);
-}
-// entry used by mhh_rhs_exec for the (advec_2i5, diff_smag2) pair: u, v, w and scalar 0 (inputs validated by the caller)
-int mhh_rhs25_march(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, void* stream) { return march_dispatch(g, f, p, -1, -1, stream, 0); }
-// the same over the rows [j0, j1) only (interior rows while the halos travel, edge rows after: mhh_rhs_exec_rows)
-int mhh_rhs25_march_rows(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, int j0, int j1, void* stream) { return march_dispatch(g, f, p, j0, j1, stream, 0); }
-// two row ranges in one launch (the two edge strips of a slab)
-int mhh_rhs25_march_rows2(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, int j0, int j1, int j2, int j3, void* stream) { return march_dispatch(g, f, p, j0, j1, stream, 0, j2, j3); }
-
-// Advec_2i5::exec / Diff_smag2::exec on their own, for u, v, w and scalar 0 (inputs validated by the caller): the marching
-// kernel with one operator's terms only -- what the two calls of an unfused time step run.
-int mhh_advec25_march(const mhh_grid* g, const mhh_fields* f, void* stream) { return march_dispatch(g, f, nullptr, -1, -1, stream, 1); }
-int mhh_diff_smag2_march(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, void* stream) { return march_dispatch(g, f, p, -1, -1, stream, 2); }
-
-// The scalar pass (inputs validated by the caller): advec_2i5 and / or diff_smag2 of the scalars idx[0 .. n) -- mode 0: both (the
-// fused pass), 1: advection only, 2: diffusion only -- over the whole interior (j0 < 0), the rows [j0, j1), or also [j2, j3).
-int mhh_scalar25_march(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const int* idx, int n, int mode, int j0, int j1, int j2, int j3, void* stream)
+int mhh::march25_scalars(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const int* idx, int n, MarchOps ops, const MarchRows& rows, void* stream)
 {
     if (n <= 0) return MHH_OK;
-    if (g->dtype == MHH_F64) return scalar_march_batches<double>(g, f, p, idx, n, j0, j1, as_stream(stream), mode, j2, j3);
-    return scalar_march_batches<float>(g, f, p, idx, n, j0, j1, as_stream(stream), mode, j2, j3);
+    if (g->dtype == MHH_F64) return scalar_march_batches<double>(g, f, p, idx, n, ops, rows, as_stream(stream));
+    return scalar_march_batches<float>(g, f, p, idx, n, ops, rows, as_stream(stream));
 }
-// MHH_SCALAR_IMPL=cell: scalars 1, 2, ... take the per-field cell kernels instead (A/B switch, read per call)
-bool mhh_scalar_march_on() { const char* e = getenv("MHH_SCALAR_IMPL"); return !(e && !strcmp(e, "cell")); }
 MHH_API unsigned long long mhh_stat_scalar_march_launches(void) { return g_scalar_march_launches; }

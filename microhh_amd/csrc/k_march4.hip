@@ -12,8 +12,6 @@
 // first, then a barrier, then the copy of plane k+2 is issued into that slot and lands while the u and v equations are
 // computed; w has a fifth slot for its copy. 13 planes of 70 x (NJ+6) doubles = 72.8 KB: two blocks per CU.
 #include <cstdint>
-#include <cstdlib>
-#include <cstring>
 #include "k_common.h"
 #include "k_march_common.h"
 #include <gfx950_prims.h>
@@ -183,7 +181,7 @@ __global__ void __launch_bounds__(64*NJ, MHH_MARCH4_OCC) rhs44_march_kernel(cons
 #define MHH_MARCH4_NJ 4
 #endif
 template<class TF>
-int march4_launch(const mhh_grid* g, const mhh_fields* f, int pb, hipStream_t st, int mode = 0)      // 0: both, 1: advec_4, 2: diff_4
+int march4_launch(const mhh_grid* g, const mhh_fields* f, int pb, MarchOps ops, hipStream_t st)
 {
     constexpr int NJ = MHH_MARCH4_NJ;
     March4Fields<TF> mf;
@@ -192,11 +190,7 @@ int march4_launch(const mhh_grid* g, const mhh_fields* f, int pb, hipStream_t st
     const MarchTiling t = make_march_tiling(g, NJ, MHH_MARCH4_KC);
     const dim3 nb(march_blocks(t)), bs(64, NJ);
     const GridDev<TF> gd = make_grid<TF>(g);
-#define MHH_L4(PBV, A, D) hipLaunchKernelGGL((rhs44_march_kernel<TF, NJ, PBV, A, D>), nb, bs, 0, st, gd, mf, t)
-    if (mode == 0)      { if (pb == 16) MHH_L4(16, true, true);  else MHH_L4(4, true, true); }
-    else if (mode == 1) { if (pb == 16) MHH_L4(16, true, false); else MHH_L4(4, true, false); }
-    else                { if (pb == 16) MHH_L4(16, false, true); else MHH_L4(4, false, true); }
-#undef MHH_L4
+    march_variant(ops, pb, [&](auto PB, auto A, auto D) { hipLaunchKernelGGL((rhs44_march_kernel<TF, NJ, PB, A, D>), nb, bs, 0, st, gd, mf, t); });
     MHH_LAUNCH_CHECK();
     return MHH_OK;
 }
@@ -205,22 +199,12 @@ static unsigned long long g_rhs44_march_launches = 0;
 
 MHH_API unsigned long long mhh_stat_rhs44_march_launches(void) { return g_rhs44_march_launches; }
 
-// Entry used by mhh_rhs_exec for (advec_4, diff_4): u, v, w only (scalars take the per-field kernels). Returns 1 when the
-// marching kernel ran, 0 when it is switched off (MHH_RHS44_IMPL=cell), < 0 on error (-code).
-static int rhs44_march_mode(const mhh_grid* g, const mhh_fields* f, void* stream, int mode);
-int mhh_rhs44_march(const mhh_grid* g, const mhh_fields* f, void* stream) { return rhs44_march_mode(g, f, stream, 0); }
-// Advec_4::exec / Diff_4::exec on their own for u, v, w (same return convention)
-int mhh_advec4_march(const mhh_grid* g, const mhh_fields* f, void* stream) { return rhs44_march_mode(g, f, stream, 1); }
-int mhh_diff4_march(const mhh_grid* g, const mhh_fields* f, void* stream) { return rhs44_march_mode(g, f, stream, 2); }
-static int rhs44_march_mode(const mhh_grid* g, const mhh_fields* f, void* stream, int mode)
+// (advec_4, diff_4), Advec_4::exec or Diff_4::exec for u, v, w (scalars take the per-field kernels)
+int mhh::march44(const mhh_grid* g, const mhh_fields* f, MarchOps ops, void* stream)
 {
-    { const char* e = getenv("MHH_RHS44_IMPL"); if (e && !strcmp(e, "cell")) return 0; }
     const int vec = (g->dtype == MHH_F64) ? 2 : 4;
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
-    if (g->igc < 3 || g->jgc < 3 || g->kgc < 3) return 0;
     // 16-byte pieces need 16-byte aligned rows and tile origin (i0 - 3 = igc - 3 + 64*bx); other layouts copy in 4-byte pieces
     const int pb = (g->icells % vec == 0 && (g->igc - 3) % vec == 0 && al16(f->u) && al16(f->v) && al16(f->w)) ? 16 : 4;
     ++g_rhs44_march_launches;
-    const int rc = (g->dtype == MHH_F64) ? march4_launch<double>(g, f, pb, as_stream(stream), mode) : march4_launch<float>(g, f, pb, as_stream(stream), mode);
-    return rc == MHH_OK ? 1 : -rc;
+    return (g->dtype == MHH_F64) ? march4_launch<double>(g, f, pb, ops, as_stream(stream)) : march4_launch<float>(g, f, pb, ops, as_stream(stream));
 }

@@ -1,12 +1,26 @@
-// k_march_common.h -- tiling shared by the k-marching kernels (k_march.hip, k_visc.hip): 64 x NJ column tiles that walk
-// up in k over chunks of kc levels, dealt to the 8 XCDs so that tiles sharing halos run next to each other on one L2.
+// k_march_common.h -- what the k-marching kernels (k_march.hip, k_march4.hip, k_visc.hip) share: 64 x NJ column tiles that
+// walk up in k over chunks of kc levels, dealt to the 8 XCDs so that tiles sharing halos run next to each other on one L2;
+// the host helpers of their launchers; their internal entry points (k_rhs.hip and k_stencil.hip call them).
 #pragma once
 #include <cstdint>
+#include <type_traits>
 #include "k_common.h"
 #include <gfx950_prims.h>
 
 namespace mhh
 {
+// The rows of a marching launch: [j0, j1), optionally a second range [j2, j3) in the same launch (the two edge strips of a
+// slab); the default, j0 < 0, is the whole interior
+struct MarchRows
+{
+    int j0 = -1, j1 = -1, j2 = -1, j3 = -1;
+    bool whole() const { return j0 < 0; }
+    bool second() const { return j2 >= 0 && j3 > j2; }
+    int count() const { return (j1 - j0) + (second() ? j3 - j2 : 0); }     // not for the whole interior
+};
+// The operators of a marching launch: both (the fused pass), advection only, diffusion only
+enum MarchOps { MARCH_BOTH = 0, MARCH_ADVEC = 1, MARCH_DIFF = 2 };
+
 // rows [jbase, jlim) are worked, in tiles from jbase; optionally a SECOND range [jbase2, jlim2) in the same launch (the two edge
 // strips of a slab once its north-south halos have arrived: one launch instead of two): tile rows by >= nby1 belong to it
 struct MarchTiling { int nbx, nby, nkc, sr, ns, kc, jbase, jlim, nby1, jbase2, jlim2; };
@@ -38,13 +52,13 @@ __device__ __forceinline__ bool decode_march(const MarchTiling& t, unsigned L, i
 // strips of sr tile rows; (strip, k-chunk) units are dealt round-robin to the XCDs; sr shrinks on thin slabs so that all
 // 8 XCDs get work
 // tw = cells of a row per tile (a wave's 64 lanes times the cells per lane)
-inline MarchTiling make_march_tiling(const mhh_grid* g, int NJ, int kc, int j0 = -1, int j1 = -1, int tw = 64, int j2 = -1, int j3 = -1)
+inline MarchTiling make_march_tiling(const mhh_grid* g, int NJ, int kc, int tw = 64, const MarchRows& rows = MarchRows{})
 {
     MarchTiling t;
-    t.jbase = (j0 < 0) ? g->jstart : j0; t.jlim = (j1 < 0) ? g->jend : j1;
+    t.jbase = rows.whole() ? g->jstart : rows.j0; t.jlim = rows.whole() ? g->jend : rows.j1;
     t.nbx = (g->imax + tw-1)/tw; t.nby1 = (t.jlim - t.jbase + NJ-1)/NJ; t.nby = t.nby1;
     t.jbase2 = t.jlim2 = t.jlim;
-    if (j2 >= 0 && j3 > j2) { t.jbase2 = j2; t.jlim2 = j3; t.nby += (j3 - j2 + NJ-1)/NJ; }
+    if (rows.second()) { t.jbase2 = rows.j2; t.jlim2 = rows.j3; t.nby += (rows.j3 - rows.j2 + NJ-1)/NJ; }
     t.kc = kc; t.nkc = (g->kmax + t.kc - 1)/t.kc;
     t.sr = (MHH_STRIP_ROWS + NJ-1)/NJ;
     if (t.sr * 8 > t.nby * t.nkc) t.sr = (t.nby * t.nkc) / 8;
@@ -56,6 +70,28 @@ inline unsigned march_blocks(const MarchTiling& t)
 {
     const int units = t.ns * t.nkc;
     return 8u * (unsigned)((units + 7)/8) * (unsigned)t.sr * t.nbx;
+}
+// Levels per k-chunk: kc, or 16 on a strip of a few rows (the slab driver's edge rows), enough blocks to fill the GPU; the
+// environment variable `tune` (>= 8) overrides both in tuning runs
+inline int march_kc(const mhh_grid* g, const MarchRows& rows, int kc, const char* tune)
+{
+    if (!rows.whole() && rows.count() * 4 <= g->jmax) kc = 16;
+    if (const char* e = getenv(tune)) if (atoi(e) >= 8) kc = atoi(e);
+    return kc;
+}
+inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
+// Calls fn(PB, ADV, DIF) with the run-time operators and piece size (4 or 16 bytes) as std::integral_constants: the template
+// arguments of a marching kernel
+template<class Fn> void march_variant(MarchOps ops, int pb, Fn&& fn)
+{
+    using std::true_type; using std::false_type;
+    auto pieces = [&](auto adv, auto dif) {
+        if (pb == 16) fn(std::integral_constant<int, 16>{}, adv, dif);
+        else          fn(std::integral_constant<int, 4>{}, adv, dif);
+    };
+    if (ops == MARCH_BOTH)       pieces(true_type{}, true_type{});
+    else if (ops == MARCH_ADVEC) pieces(true_type{}, false_type{});
+    else                         pieces(false_type{}, true_type{});
 }
 
 // LDS-DMA copy of one TI x TJ tile of a plane (origin gi0, gj0 in grid cells) into an LDS slot, in pieces of PB bytes per
@@ -104,4 +140,23 @@ struct TileCopy
             }
     }
 };
+
+// ---- internal entry points (inputs validated by the caller); each returns MHH_OK or an error code ---------------------------
+// advec_2i5 and / or diff_smag2 of u, v, w and scalar 0 (if f->nscalars >= 1) in the fused marching kernel (k_march.hip)
+int march25(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, MarchOps ops, const MarchRows& rows, void* stream);
+// the same for the scalars idx[0 .. n) in the batched scalar pass (k_march.hip)
+int march25_scalars(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const int* idx, int n, MarchOps ops, const MarchRows& rows, void* stream);
+// advec_4 and / or diff_4 of u, v, w (k_march4.hip), where march44_takes(g)
+int march44(const mhh_grid* g, const mhh_fields* f, MarchOps ops, void* stream);
+// Diff_smag2::exec_viscosity over the rows (k_visc.hip), where visc_march_takes(g)
+int visc_march(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const void* th, const MarchRows& rows, void* stream);
+// The advec_2i5 / diff_smag2 routing of every field (k_rhs.hip): u, v, w and scalar 0 to march25, further scalars to the
+// scalar pass (pass) or their own kernels
+int route25(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, MarchOps ops, const MarchRows& rows, bool pass, void* stream);
+
+// Does the marching form take the call? The A/B switches (read per call) and the ghost cells the kernels read; otherwise the
+// caller takes the one-thread-per-cell kernels. Scalars 1, 2, ...: the scalar pass unless MHH_SCALAR_IMPL=cell.
+inline bool march44_takes(const mhh_grid* g) { return !env_is("MHH_RHS44_IMPL", "cell") && g->igc >= 3 && g->jgc >= 3 && g->kgc >= 3; }
+inline bool visc_march_takes(const mhh_grid* g) { return !env_is("MHH_VISC_IMPL", "cell") && g->igc >= 1 && g->jgc >= 1 && g->kgc >= 1; }
+inline bool scalar_march_on() { return !env_is("MHH_SCALAR_IMPL", "cell"); }
 }

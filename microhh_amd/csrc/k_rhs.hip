@@ -4,21 +4,11 @@
 #include <cstring>
 #include <cstdint>
 #include "k_common.h"
+#include "k_march_common.h"
 #include <wave_reduce.h>   // angle form: the CPU emulation build (tests/emul) overrides it by include path
 
 using namespace mhh;
 
-int mhh_rhs25_march(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, void* stream);   // k_march.hip
-int mhh_diff_smag2_march(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, void* stream);   // k_march.hip
-int mhh_visc_march(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const void* th, void* stream);   // k_visc.hip
-int mhh_visc_march_rows(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const void* th, int j0, int j1, void* stream);
-int mhh_visc_march_rows2(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const void* th, int j0, int j1, int j2, int j3, void* stream);
-int mhh_rhs25_march_rows2(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, int j0, int j1, int j2, int j3, void* stream);   // k_march.hip
-int mhh_rhs25_march_rows(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, int j0, int j1, void* stream);   // k_march.hip
-int mhh_rhs44_march(const mhh_grid* g, const mhh_fields* f, void* stream);
-int mhh_diff4_march(const mhh_grid* g, const mhh_fields* f, void* stream);                                           // k_march4.hip
-int mhh_scalar25_march(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const int* idx, int n, int mode, int j0, int j1, int j2, int j3, void* stream);   // k_march.hip
-bool mhh_scalar_march_on();
 
 // =======================================================================================================
 // Max reductions (calc_cfl / calc_dnmul / calc_divergence + Master::max). All integrands are |.| >= 0, so the
@@ -153,9 +143,34 @@ struct MirrorWallOp2
     }
 };
 
-// rows [j0, j1) (j0 < 0: the interior, plus the two adjacent ghost rows when p->evisc_ghost_rows), then the wall mirror
-// and the east-west wrap over all rows
-static int viscosity_rows(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, int j0, int j1, void* stream, int j2 = -1, int j3 = -1)
+// the one-thread-per-cell form where the marching form declined (!marched); the two adjacent ghost rows of the interior when
+// p->evisc_ghost_rows, and the wall mirror
+template<class TF>
+static int viscosity_cells(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const void* th, const MarchRows& rows, bool marched, hipStream_t st)
+{
+    ViscosityOp<TF> op{make_grid<TF>(g), p->surface_model, p->neutral, mp<TF>(f->evisc), cp<TF>(f->u), cp<TF>(f->v), cp<TF>(f->w),
+                       cp<TF>(f->dudz), cp<TF>(f->dvdz), cp<TF>(f->dbdz), cp<TF>(f->z0m), cp<TF>(p->N2), cp<TF>(th), cp<TF>(p->thref), TF(p->grav), cp<TF>(p->mlen0), TF(p->tPr), cp<TF>(p->mlen2)};
+    auto rows_of = [&](int j0, int j1) { return launch_cells(st, op, g->istart, g->iend, j0, j1, g->kstart, g->kend, g->icells, g->ijcells); };
+    if (!marched)
+    {
+        if (rows.whole()) { if (int e = launch_interior(st, op.g, g->kstart, g->kend, op)) return e; }
+        else
+        {
+            if (int e = rows_of(rows.j0, rows.j1)) return e;
+            if (rows.second()) if (int e = rows_of(rows.j2, rows.j3)) return e;
+        }
+    }
+    if (rows.whole() && p->evisc_ghost_rows)
+    {
+        if (int e = rows_of(g->jstart-1, g->jstart)) return e;
+        if (int e = rows_of(g->jend, g->jend+1)) return e;
+    }
+    if (!p->surface_model) { MirrorWallOp2<TF> m{op.g, mp<TF>(f->evisc)}; if (int e = launch_cells(st, m, 0, g->icells, 0, g->jcells, 0, 1, g->icells, g->ijcells)) return e; }
+    return MHH_OK;
+}
+// the rows (whole interior: plus the two adjacent ghost rows when p->evisc_ghost_rows), then the wall mirror and the east-west
+// wrap over all rows
+static int viscosity_rows(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const MarchRows& rows, void* stream)
 {
     MHH_REQUIRE(f && p && f->evisc && f->u && f->v && f->w && p->mlen0, "null field");
     MHH_REQUIRE(!p->surface_model || (f->dudz && f->dvdz && f->z0m), "surface model inputs");
@@ -171,24 +186,12 @@ static int viscosity_rows(const mhh_grid* g, const mhh_fields* f, const mhh_diff
     }
     MHH_REQUIRE(!(p->neutral && !p->surface_model), "neutral + resolved walls: use mhh_smag2_strain2 + mhh_smag2_evisc_neutral");
     MHH_REQUIRE(!p->evisc_ghost_rows || g->jgc >= 2, "evisc_ghost_rows needs jgc >= 2");
-    hipStream_t st = as_stream(stream);
-    const bool whole = (j0 < 0);
-    const int ja = whole ? g->jstart : j0, jb = whole ? g->jend : j1;
     // the k-marching LDS kernel (k_visc.hip), or one thread per cell where it declines
-    const int marched = whole ? mhh_visc_march(g, f, p, th, stream) : mhh_visc_march_rows2(g, f, p, th, ja, jb, j2, j3, stream);
-#define CALL(TF) [&]{ ViscosityOp<TF> op{make_grid<TF>(g), p->surface_model, p->neutral, mp<TF>(f->evisc), cp<TF>(f->u), cp<TF>(f->v), cp<TF>(f->w), \
-                          cp<TF>(f->dudz), cp<TF>(f->dvdz), cp<TF>(f->dbdz), cp<TF>(f->z0m), cp<TF>(p->N2), cp<TF>(th), cp<TF>(p->thref), TF(p->grav), cp<TF>(p->mlen0), TF(p->tPr), cp<TF>(p->mlen2)}; \
-                      if (marched < 0) return -marched; \
-                      if (!marched) { if (whole) { if (int e = launch_interior(st, op.g, g->kstart, g->kend, op)) return e; } \
-                                      else { if (int e = launch_cells(st, op, g->istart, g->iend, ja, jb, g->kstart, g->kend, g->icells, g->ijcells)) return e; \
-                                             if (j2 >= 0) if (int e = launch_cells(st, op, g->istart, g->iend, j2, j3, g->kstart, g->kend, g->icells, g->ijcells)) return e; } } \
-                      if (whole && p->evisc_ghost_rows) { \
-                          if (int e = launch_cells(st, op, g->istart, g->iend, g->jstart-1, g->jstart, g->kstart, g->kend, g->icells, g->ijcells)) return e; \
-                          if (int e = launch_cells(st, op, g->istart, g->iend, g->jend, g->jend+1, g->kstart, g->kend, g->icells, g->ijcells)) return e; } \
-                      if (!p->surface_model) { MirrorWallOp2<TF> m{op.g, mp<TF>(f->evisc)}; if (int e = launch_cells(st, m, 0, g->icells, 0, g->jcells, 0, 1, g->icells, g->ijcells)) return e; } \
-                      return MHH_OK; }()
-    if (int e = MHH_DISPATCH(g, CALL)) return e;
-#undef CALL
+    const bool marched = visc_march_takes(g);
+    if (marched) if (int e = visc_march(g, f, p, th, rows, stream)) return e;
+    const int e = (g->dtype == MHH_F64) ? viscosity_cells<double>(g, f, p, th, rows, marched, as_stream(stream))
+                                        : viscosity_cells<float>(g, f, p, th, rows, marched, as_stream(stream));
+    if (e) return e;
     // slab-decomposed: only the local east-west wrap; the caller exchanges the north-south halo
     return mhh_boundary_cyclic(g, f->evisc, g->npy > 1 ? MHH_EDGE_EW : MHH_EDGE_BOTH, stream);
 }
@@ -196,7 +199,7 @@ MHH_API int mhh_diff_exec_viscosity(const mhh_grid* g, int scheme, const mhh_fie
 {
     if (int e = check_grid(g)) return e;
     if (scheme != MHH_DIFF_SMAG2) return MHH_OK;          // diff_2 / diff_4: no-op (src/diff_2.h, src/diff_4.h)
-    return viscosity_rows(g, f, p, -1, -1, stream);
+    return viscosity_rows(g, f, p, MarchRows{}, stream);
 }
 MHH_API int mhh_diff_exec_viscosity_rows(const mhh_grid* g, int scheme, const mhh_fields* f, const mhh_diff_params* p, int j0, int j1, void* stream)
 {
@@ -204,7 +207,7 @@ MHH_API int mhh_diff_exec_viscosity_rows(const mhh_grid* g, int scheme, const mh
     if (scheme != MHH_DIFF_SMAG2) return MHH_OK;
     MHH_REQUIRE(j0 >= g->jstart-1 && j0 < j1 && j1 <= g->jend+1, "rows must lie in [jstart-1, jend+1)");
     MHH_REQUIRE((j0 >= g->jstart && j1 <= g->jend) || g->jgc >= 2, "ghost rows need jgc >= 2");
-    return viscosity_rows(g, f, p, j0, j1, stream);
+    return viscosity_rows(g, f, p, MarchRows{j0, j1}, stream);
 }
 // two row ranges in ONE launch (+ one wall mirror and one east-west wrap): the two edge strips of a slab once its halos are in
 MHH_API int mhh_diff_exec_viscosity_rows2(const mhh_grid* g, int scheme, const mhh_fields* f, const mhh_diff_params* p, int j0, int j1, int j2, int j3, void* stream)
@@ -213,7 +216,42 @@ MHH_API int mhh_diff_exec_viscosity_rows2(const mhh_grid* g, int scheme, const m
     if (scheme != MHH_DIFF_SMAG2) return MHH_OK;
     MHH_REQUIRE(j0 >= g->jstart-1 && j0 < j1 && j1 <= j2 && j2 < j3 && j3 <= g->jend+1, "two disjoint, ordered row ranges in [jstart-1, jend+1)");
     MHH_REQUIRE((j0 >= g->jstart && j3 <= g->jend) || g->jgc >= 2, "ghost rows need jgc >= 2");
-    return viscosity_rows(g, f, p, j0, j1, stream, j2, j3);
+    return viscosity_rows(g, f, p, MarchRows{j0, j1, j2, j3}, stream);
+}
+
+// advec_2i5 and / or diff_smag2 (ops) of every field over the rows (inputs validated by the caller; p null for MARCH_ADVEC):
+// u, v, w and scalar 0 in the fused marching kernel; further scalars in its scalar pass where `pass` (MHH_SCALAR_IMPL=cell: no),
+// flux-limited ones per field. Diffusion ignores the limiter. The row-wise callers have no flux-limited scalar and set `pass`:
+// the per-field kernels cover the whole interior only.
+int mhh::route25(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, MarchOps ops, const MarchRows& rows, bool pass, void* stream)
+{
+    auto lim = [&](int n) { return ops != MARCH_DIFF && f->s_fluxlimit[n]; };
+    // a flux-limited scalar 0 (advec.fluxlimit_list, src/advec_2i5.cxx:921) leaves the fused kernel to u, v, w
+    const int first = (f->nscalars > 0 && lim(0)) ? 0 : 1;
+    mhh_fields fm = *f; fm.nscalars = f->nscalars < first ? f->nscalars : first;
+    // the fused kernel folds the buoyancy of scalar 0 in (2nd order); otherwise it is added first, on its own
+    const mhh_diff_params* pm = p; mhh_diff_params pnb;
+    if (ops == MARCH_BOTH && p->buoyancy && !(p->buoyancy == 2 && p->th_for_N2 == 0 && !f->s_fluxlimit[0]))
+    {
+        if (int e = mhh_thermo_dry_buoyancy_tend(g, p->buoyancy, f->wt, f->s[p->th_for_N2], p->threfh, p->grav, stream)) return e;
+        pnb = *p; pnb.buoyancy = 0; pm = &pnb;
+    }
+    if (int e = march25(g, &fm, pm, ops, rows, stream)) return e;
+    int idx[MHH_MAX_SCALARS], nq = 0;
+    for (int n=first; n<f->nscalars; ++n) if (pass && !lim(n)) idx[nq++] = n;
+    if (int e = march25_scalars(g, f, p, idx, nq, ops, rows, stream)) return e;
+    for (int n=first; n<f->nscalars; ++n)
+    {
+        if (pass && !lim(n)) continue;
+        if (ops != MARCH_DIFF)
+        {
+            if (lim(n)) { if (int e = mhh_advec_s_lim(g, f->st[n], f->s[n], f->u, f->v, f->w, f->rhoref, f->rhorefh, stream)) return e; }
+            else if (int e = mhh_advec_s(g, MHH_ADVEC_2I5, f->st[n], f->s[n], f->u, f->v, f->w, f->rhoref, f->rhorefh, stream)) return e;
+        }
+        if (ops != MARCH_ADVEC)
+            if (int e = mhh_smag2_diff_c(g, p->surface_model, f->st[n], f->s[n], f->evisc, f->s_fluxbot[n], f->s_fluxtop[n], f->rhoref, f->rhorefh, p->tPr, f->svisc[n], stream)) return e;
+    }
+    return MHH_OK;
 }
 
 // Diff::exec (src/diff_2.cxx:150-180, src/diff_4.cxx:250-300, src/diff_smag2.cxx:939-1043), unfused
@@ -229,9 +267,8 @@ MHH_API int mhh_diff_exec(const mhh_grid* g, int scheme, const mhh_fields* f, co
         {
             if (int e = check_grid(g)) return e;
             MHH_REQUIRE(f->u && f->v && f->w && f->ut && f->vt && f->wt, "null field");
-            const int rc = mhh_diff4_march(g, f, stream);
-            if (rc < 0) return -rc;
-            uvw_done = (rc == 1);
+            uvw_done = march44_takes(g);
+            if (uvw_done) if (int e = march44(g, f, MARCH_DIFF, stream)) return e;
         }
         if (!uvw_done)
         {
@@ -248,24 +285,13 @@ MHH_API int mhh_diff_exec(const mhh_grid* g, int scheme, const mhh_fields* f, co
     // u, v, w and the first scalar in one pass of the marching kernel with the diffusive terms only (k_march.hip; same bits
     // as the per-field kernels, which MHH_DIFF22_IMPL=cell selects); further scalars in the scalar pass of that kernel
     // (MHH_SCALAR_IMPL=cell: per field). Needs the advec_2i5 halo (the tiles are cut for it): other layouts take the per-field kernels.
-    const char* impl = getenv("MHH_DIFF22_IMPL");
-    if (!(impl && !strcmp(impl, "cell")) && g && g->igc >= 3 && g->jgc >= 3 && g->kgc >= 1 && g->ktot >= 6)
+    if (!env_is("MHH_DIFF22_IMPL", "cell") && g && g->igc >= 3 && g->jgc >= 3 && g->kgc >= 1 && g->ktot >= 6)
     {
         if (int e = check_grid(g)) return e;
         MHH_REQUIRE(f->u && f->v && f->w && f->ut && f->vt && f->wt && f->evisc && f->rhoref && f->rhorefh, "null field");
         if (sm) MHH_REQUIRE(f->u_fluxbot && f->u_fluxtop && f->v_fluxbot && f->v_fluxtop, "surface fluxes");
         for (int n=0; n<f->nscalars; ++n) MHH_REQUIRE(f->s[n] && f->st[n] && (!sm || (f->s_fluxbot[n] && f->s_fluxtop[n])), "null scalar / scalar surface fluxes");
-        mhh_fields fm = *f; fm.nscalars = f->nscalars > 0 ? 1 : 0;
-        if (int e = mhh_diff_smag2_march(g, &fm, p, stream)) return e;
-        if (f->nscalars > 1 && mhh_scalar_march_on())
-        {
-            int idx[MHH_MAX_SCALARS];
-            for (int n=1; n<f->nscalars; ++n) idx[n-1] = n;
-            return mhh_scalar25_march(g, f, p, idx, f->nscalars - 1, 2, -1, -1, -1, -1, stream);
-        }
-        for (int n=1; n<f->nscalars; ++n)
-            if (int e = mhh_smag2_diff_c(g, sm, f->st[n], f->s[n], f->evisc, f->s_fluxbot[n], f->s_fluxtop[n], f->rhoref, f->rhorefh, p->tPr, f->svisc[n], stream)) return e;
-        return MHH_OK;
+        return route25(g, f, p, MARCH_DIFF, MarchRows{}, scalar_march_on(), stream);
     }
     if (int e = mhh_smag2_diff_u(g, sm, f->ut, f->u, f->v, f->w, f->evisc, f->u_fluxbot, f->u_fluxtop, f->rhoref, f->rhorefh, f->visc, stream)) return e;
     if (int e = mhh_smag2_diff_v(g, sm, f->vt, f->u, f->v, f->w, f->evisc, f->v_fluxbot, f->v_fluxtop, f->rhoref, f->rhorefh, f->visc, stream)) return e;
@@ -476,43 +502,12 @@ MHH_API int mhh_rhs_exec(const mhh_grid* g, int advec_scheme, int diff_scheme, c
         }
         // default: the k-marching LDS kernel (k_march.hip) for u, v, w and scalar 0; further unlimited scalars take the scalar
         // pass of that kernel (MHH_SCALAR_IMPL=cell: the per-field kernels), flux-limited ones the per-field kernels.
-        // MHH_RHS25_IMPL=cell selects the one-thread-per-cell fused kernel (A/B measurements).
-        const bool use_cell = [] { const char* e = getenv("MHH_RHS25_IMPL"); return e && !strcmp(e, "cell"); }();   // A/B switch, read per call
+        // MHH_RHS25_IMPL=cell selects the one-thread-per-cell fused kernel (A/B measurements); a call with a flux-limited scalar
+        // still takes the marching kernel then, with every scalar from 1 on per field.
+        const bool use_cell = env_is("MHH_RHS25_IMPL", "cell");
         bool any_lim = false;
         for (int n=0; n<f->nscalars; ++n) any_lim = any_lim || f->s_fluxlimit[n];
-        if (!use_cell || any_lim)
-        {
-            // the march kernel folds the buoyancy of scalar 0 in (2nd order); otherwise it is added first, on its own
-            const mhh_diff_params* pm = p; mhh_diff_params pnb;
-            if (p->buoyancy && !(p->buoyancy == 2 && p->th_for_N2 == 0 && !f->s_fluxlimit[0]))
-            {
-                if (int e = mhh_thermo_dry_buoyancy_tend(g, p->buoyancy, f->wt, f->s[p->th_for_N2], p->threfh, p->grav, stream)) return e;
-                pnb = *p; pnb.buoyancy = 0; pm = &pnb;
-            }
-            // a flux-limited scalar 0 (advec.fluxlimit_list, src/advec_2i5.cxx:921) leaves the fused kernel to u, v, w
-            int first = 1;
-            if (f->nscalars > 0 && f->s_fluxlimit[0])
-            {
-                mhh_fields fm = *f; fm.nscalars = 0; first = 0;
-                if (int e = mhh_rhs25_march(g, &fm, pm, stream)) return e;
-            }
-            else if (int e = mhh_rhs25_march(g, f, pm, stream)) return e;
-            const bool pass = !use_cell && mhh_scalar_march_on();
-            if (pass)
-            {
-                int idx[MHH_MAX_SCALARS], nq = 0;
-                for (int n=first; n<f->nscalars; ++n) if (!f->s_fluxlimit[n]) idx[nq++] = n;
-                if (int e = mhh_scalar25_march(g, f, p, idx, nq, 0, -1, -1, -1, -1, stream)) return e;
-            }
-            for (int n=first; n<f->nscalars; ++n)
-            {
-                if (pass && !f->s_fluxlimit[n]) continue;
-                if (f->s_fluxlimit[n]) { if (int e = mhh_advec_s_lim(g, f->st[n], f->s[n], f->u, f->v, f->w, f->rhoref, f->rhorefh, stream)) return e; }
-                else if (int e = mhh_advec_s(g, MHH_ADVEC_2I5, f->st[n], f->s[n], f->u, f->v, f->w, f->rhoref, f->rhorefh, stream)) return e;
-                if (int e = mhh_smag2_diff_c(g, p->surface_model, f->st[n], f->s[n], f->evisc, f->s_fluxbot[n], f->s_fluxtop[n], f->rhoref, f->rhorefh, p->tPr, f->svisc[n], stream)) return e;
-            }
-            return MHH_OK;
-        }
+        if (!use_cell || any_lim) return route25(g, f, p, MARCH_BOTH, MarchRows{}, !use_cell && scalar_march_on(), stream);
 #define CALL(TF) [&]{ Rhs25SmagOp<TF> op{make_grid<TF>(g), make_fields<TF>(f, p)}; return launch_interior(st, op.g, g->kstart, g->kend, op); }()
         return MHH_DISPATCH(g, CALL);
 #undef CALL
@@ -522,25 +517,16 @@ MHH_API int mhh_rhs_exec(const mhh_grid* g, int advec_scheme, int diff_scheme, c
         MHH_REQUIRE(g->igc >= 3 && g->jgc >= 3 && g->kgc >= 3, "4th order needs gc(3,3,3)");
         // default: the k-marching LDS kernel (k_march4.hip) for u, v, w where the rows allow LDS-DMA; scalars and the folded
         // buoyancy then take their own kernels (same order of accumulation). MHH_RHS44_IMPL=cell selects the cell kernel.
+        if (march44_takes(g))
         {
-            const mhh_fields* fq = f;
-            const bool buoy = p && p->buoyancy;
-            // probe the layout first so that the buoyancy term is added exactly once, and before advection
-            const char* e = getenv("MHH_RHS44_IMPL");
-            const bool can = !(e && !strcmp(e, "cell"));
-            if (can)
+            if (p && p->buoyancy) if (int e = mhh_thermo_dry_buoyancy_tend(g, p->buoyancy, f->wt, f->s[p->th_for_N2], p->threfh, p->grav, stream)) return e;
+            if (int e = march44(g, f, MARCH_BOTH, stream)) return e;
+            for (int n=0; n<f->nscalars; ++n)
             {
-                if (buoy) if (int e2 = mhh_thermo_dry_buoyancy_tend(g, p->buoyancy, f->wt, f->s[p->th_for_N2], p->threfh, p->grav, stream)) return e2;
-                const int m = mhh_rhs44_march(g, fq, stream);
-                if (m < 0) return -m;
-                MHH_REQUIRE(m == 1, "internal: rhs44 march declined a layout it was probed for");
-                for (int n=0; n<f->nscalars; ++n)
-                {
-                    if (int e2 = mhh_advec_s(g, MHH_ADVEC_4, f->st[n], f->s[n], f->u, f->v, f->w, f->rhoref, f->rhorefh, stream)) return e2;
-                    if (int e2 = mhh_diff_c(g, 4, f->st[n], f->s[n], f->svisc[n], stream)) return e2;
-                }
-                return MHH_OK;
+                if (int e = mhh_advec_s(g, MHH_ADVEC_4, f->st[n], f->s[n], f->u, f->v, f->w, f->rhoref, f->rhorefh, stream)) return e;
+                if (int e = mhh_diff_c(g, 4, f->st[n], f->s[n], f->svisc[n], stream)) return e;
             }
+            return MHH_OK;
         }
 #define CALL(TF) [&]{ Rhs44Op<TF> op{make_grid<TF>(g), make_fields<TF>(f, p)}; return launch_interior(st, op.g, g->kstart, g->kend, op); }()
         return MHH_DISPATCH(g, CALL);
@@ -571,20 +557,12 @@ static int rhs_rows_checks(const mhh_grid* g, int advec_scheme, int diff_scheme,
     }
     return MHH_OK;
 }
-// scalars 1, 2, ... of a row-wise call: the scalar pass over the same rows
-static int rhs_rows_scalars(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, int j0, int j1, int j2, int j3, void* stream)
-{
-    int idx[MHH_MAX_SCALARS];
-    for (int n=1; n<f->nscalars; ++n) idx[n-1] = n;
-    return mhh_scalar25_march(g, f, p, idx, f->nscalars - 1, 0, j0, j1, j2, j3, stream);
-}
 MHH_API int mhh_rhs_exec_rows(const mhh_grid* g, int advec_scheme, int diff_scheme, const mhh_fields* f, const mhh_diff_params* p, int j0, int j1, void* stream)
 {
     if (int e = check_grid(g)) return e;
     if (int e = rhs_rows_checks(g, advec_scheme, diff_scheme, f, p)) return e;
     MHH_REQUIRE(j0 >= g->jstart && j0 < j1 && j1 <= g->jend, "rows must lie in [jstart, jend)");
-    if (int e = mhh_rhs25_march_rows(g, f, p, j0, j1, stream)) return e;
-    return rhs_rows_scalars(g, f, p, j0, j1, -1, -1, stream);
+    return route25(g, f, p, MARCH_BOTH, MarchRows{j0, j1}, true, stream);
 }
 // the same over two row ranges in one launch (the two edge strips of a slab)
 MHH_API int mhh_rhs_exec_rows2(const mhh_grid* g, int advec_scheme, int diff_scheme, const mhh_fields* f, const mhh_diff_params* p, int j0, int j1, int j2, int j3, void* stream)
@@ -592,6 +570,5 @@ MHH_API int mhh_rhs_exec_rows2(const mhh_grid* g, int advec_scheme, int diff_sch
     if (int e = check_grid(g)) return e;
     if (int e = rhs_rows_checks(g, advec_scheme, diff_scheme, f, p)) return e;
     MHH_REQUIRE(j0 >= g->jstart && j0 < j1 && j1 <= j2 && j2 < j3 && j3 <= g->jend, "two disjoint, ordered row ranges in [jstart, jend)");
-    if (int e = mhh_rhs25_march_rows2(g, f, p, j0, j1, j2, j3, stream)) return e;
-    return rhs_rows_scalars(g, f, p, j0, j1, j2, j3, stream);
+    return route25(g, f, p, MARCH_BOTH, MarchRows{j0, j1, j2, j3}, true, stream);
 }

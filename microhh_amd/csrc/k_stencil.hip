@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 #include "k_common.h"
+#include "k_march_common.h"
 
 namespace mhh
 {
@@ -275,10 +276,6 @@ MHH_API int mhh_advec_s_lim(const mhh_grid* g, void* st, const void* sc, const v
 #undef CALL
 }
 
-int mhh_advec25_march(const mhh_grid* g, const mhh_fields* f, void* stream);                    // k_march.hip
-int mhh_advec4_march(const mhh_grid* g, const mhh_fields* f, void* stream);                     // k_march4.hip
-int mhh_scalar25_march(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const int* idx, int n, int mode, int j0, int j1, int j2, int j3, void* stream);   // k_march.hip
-bool mhh_scalar_march_on();
 MHH_API int mhh_advec_exec(const mhh_grid* g, int scheme, const mhh_fields* f, void* stream)
 {
     MHH_REQUIRE(f != nullptr, "fields");
@@ -286,40 +283,21 @@ MHH_API int mhh_advec_exec(const mhh_grid* g, int scheme, const mhh_fields* f, v
     // advec_2i5: u, v, w and the first (unlimited) scalar in one pass of the marching kernel with the advective terms only
     // (k_march.hip; same bits as the per-field kernels, which MHH_ADVEC25_IMPL=cell selects); further unlimited scalars in the
     // scalar pass of that kernel (MHH_SCALAR_IMPL=cell: per field), flux-limited ones per field.
-    const char* impl = getenv("MHH_ADVEC25_IMPL");
-    if (scheme == MHH_ADVEC_2I5 && !(impl && !strcmp(impl, "cell")))
+    if (scheme == MHH_ADVEC_2I5 && !env_is("MHH_ADVEC25_IMPL", "cell"))
     {
         if (int e = check_grid(g)) return e;
         if (int e = check_advec(g, scheme)) return e;
         MHH_REQUIRE(f->u && f->v && f->w && f->ut && f->vt && f->wt && f->rhoref && f->rhorefh, "null field");
         for (int n=0; n<f->nscalars; ++n) MHH_REQUIRE(f->s[n] && f->st[n], "null scalar");
-        mhh_fields fm = *f;
-        const bool s0 = f->nscalars > 0 && !f->s_fluxlimit[0];
-        fm.nscalars = s0 ? 1 : 0;
-        if (int e = mhh_advec25_march(g, &fm, stream)) return e;
-        const bool pass = mhh_scalar_march_on();
-        if (pass)
-        {
-            int idx[MHH_MAX_SCALARS], nq = 0;
-            for (int n=(s0 ? 1 : 0); n<f->nscalars; ++n) if (!f->s_fluxlimit[n]) idx[nq++] = n;
-            if (int e = mhh_scalar25_march(g, f, nullptr, idx, nq, 1, -1, -1, -1, -1, stream)) return e;
-        }
-        for (int n=(s0 ? 1 : 0); n<f->nscalars; ++n)
-        {
-            if (pass && !f->s_fluxlimit[n]) continue;
-            if (f->s_fluxlimit[n]) { if (int e = mhh_advec_s_lim(g, f->st[n], f->s[n], f->u, f->v, f->w, f->rhoref, f->rhorefh, stream)) return e; }
-            else if (int e = mhh_advec_s(g, scheme, f->st[n], f->s[n], f->u, f->v, f->w, f->rhoref, f->rhorefh, stream)) return e;
-        }
-        return MHH_OK;
+        return route25(g, f, nullptr, MARCH_ADVEC, MarchRows{}, scalar_march_on(), stream);
     }
     bool uvw_done = false;
     if (scheme == MHH_ADVEC_4)           // u, v, w in one pass of the 4th-order marching kernel (advective terms only); scalars per field
     {
         if (int e = check_advec(g, scheme)) return e;
         MHH_REQUIRE(f->u && f->v && f->w && f->ut && f->vt && f->wt, "null field");
-        const int rc = mhh_advec4_march(g, f, stream);
-        if (rc < 0) return -rc;
-        uvw_done = (rc == 1);
+        uvw_done = march44_takes(g);
+        if (uvw_done) if (int e = march44(g, f, MARCH_ADVEC, stream)) return e;
     }
     if (!uvw_done)
     {

@@ -8,8 +8,6 @@
 // terms -- the two expressions have the same operands in the same order (src/diff_smag2.cxx:138-148), so the sum is the
 // reference's, bit for bit.
 #include <cstdint>
-#include <cstdlib>
-#include <cstring>
 #include "k_common.h"
 #include "k_march_common.h"
 #include <gfx950_prims.h>
@@ -198,7 +196,7 @@ __global__ void __launch_bounds__(64*NJ, MHH_VISC_OCC) visc_march_kernel(const G
 }
 
 template<class TF>
-int visc_launch(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const void* th, int ex, int pb, int j0, int j1, hipStream_t st, int j2 = -1, int j3 = -1)
+int visc_launch(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const void* th, int ex, int pb, const MarchRows& rows, hipStream_t st)
 {
     constexpr int NJ = 4;
     ViscFields<TF> vf;
@@ -210,9 +208,7 @@ int visc_launch(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p
 #define MHH_VISC_DIVKNOWN 1
 #endif
     vf.rtPr = (MHH_VISC_DIVKNOWN && known_divisor_ok(vf.tPr)) ? TF(1.)/vf.tPr : TF(0);
-    int kc = (j0 >= 0 && (j1 - j0 + (j2 >= 0 ? j3 - j2 : 0)) * 4 <= g->jmax) ? 16 : MHH_VISC_KC;      // few rows: short k-chunks fill the GPU
-    { const char* e = getenv("MHH_VISC_KC_RT"); if (e && atoi(e) >= 8) kc = atoi(e); }         // tuning runs
-    const MarchTiling t = make_march_tiling(g, NJ, kc, j0, j1, 64, j2, j3);
+    const MarchTiling t = make_march_tiling(g, NJ, march_kc(g, rows, MHH_VISC_KC, "MHH_VISC_KC_RT"), 64, rows);
     const dim3 nb(march_blocks(t)), bs(64, NJ);
     const GridDev<TF> gd = make_grid<TF>(g);
     if (vf.N2)
@@ -272,21 +268,11 @@ static unsigned long long g_visc_march_launches = 0;
 // diagnostics: how many times the marching form (as opposed to the one-thread-per-cell form) has been launched
 MHH_API unsigned long long mhh_stat_visc_march_launches(void) { return g_visc_march_launches; }
 
-// Entry used by mhh_diff_exec_viscosity (inputs validated there). Returns 1 when the marching kernel ran, 0 when it is
-// switched off (MHH_VISC_IMPL=cell) or the grid has no ghost cells to read (the caller then takes the cell kernel),
-// < 0 on error (-code).
-int mhh_visc_march_rows2(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const void* th, int j0, int j1, int j2, int j3, void* stream);
-int mhh_visc_march_rows(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const void* th, int j0, int j1, void* stream)
-{ return mhh_visc_march_rows2(g, f, p, th, j0, j1, -1, -1, stream); }
-int mhh_visc_march(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const void* th, void* stream)
-{ return mhh_visc_march_rows(g, f, p, th, -1, -1, stream); }
-// rows [j0, j1) only (-1, -1: the interior) and optionally [j2, j3) in the same launch; ghost rows jstart-1 and jend are legal when jgc >= 2
-int mhh_visc_march_rows2(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const void* th, int j0, int j1, int j2, int j3, void* stream)
+// Entry used by mhh_diff_exec_viscosity and its row-wise forms (inputs validated there); ghost rows jstart-1 and jend are legal
+// when jgc >= 2
+int mhh::visc_march(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const void* th, const MarchRows& rows, void* stream)
 {
-    { const char* e = getenv("MHH_VISC_IMPL"); if (e && !strcmp(e, "cell")) return 0; }     // A/B switch, read per call
     const int vec = (g->dtype == MHH_F64) ? 2 : 4;
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
-    if (g->igc < 1 || g->jgc < 1 || g->kgc < 1) return 0;
     // 16-byte pieces: tile x-origin i0 - ex (i0 = igc + 64*bx) on a 16-byte boundary, covering i-1: 1 <= ex <= igc,
     // (igc - ex) % vec == 0; any other layout copies in 4-byte pieces with ex = 1
     int ex = 0;
@@ -295,6 +281,5 @@ int mhh_visc_march_rows2(const mhh_grid* g, const mhh_fields* f, const mhh_diff_
     const int pb = ex ? 16 : 4;
     if (!ex) ex = 1;
     ++g_visc_march_launches;
-    const int rc = (g->dtype == MHH_F64) ? visc_launch<double>(g, f, p, th, ex, pb, j0, j1, as_stream(stream), j2, j3) : visc_launch<float>(g, f, p, th, ex, pb, j0, j1, as_stream(stream), j2, j3);
-    return rc == MHH_OK ? 1 : -rc;
+    return (g->dtype == MHH_F64) ? visc_launch<double>(g, f, p, th, ex, pb, rows, as_stream(stream)) : visc_launch<float>(g, f, p, th, ex, pb, rows, as_stream(stream));
 }
