@@ -11,19 +11,12 @@
 // The reference works on FFTW half-complex *real* coefficients; the complex formulation solves the same
 // real tridiagonal system per wave-number pair (the matrix is real and depends only on
 // bmati[kx]+bmatj[ky]), so results agree to rounding of the transform (DESIGN.md "Parity").
-#include <vector>
-#include <map>
-#include <mutex>
-#include <rocfft/rocfft.h>
+#include <initializer_list>
+#include <type_traits>
 #include "fft_lifetime.h"
-#include <cstring>
-#include <cstdlib>
-#include "k_common.h"
+#include "pres_lds_slab.h"
 
 using namespace mhh;
-
-#define MHH_FFT_TRY(expr) do { rocfft_status s_ = (expr); if (s_ != rocfft_status_success) { \
-    mhh::set_error("FFT error: %s returned %d (%s:%d)", #expr, (int)s_, __FILE__, __LINE__); return MHH_EFFT; } } while (0)
 
 struct mhh_pres_plan
 {
@@ -41,10 +34,6 @@ struct mhh_pres_plan
     void* work = nullptr;        // scratch of the k-sweep: work3d (pres_2) / 7 band arrays + rhs (pres_4)
     rocfft_plan fwd = nullptr, bwd = nullptr;
     rocfft_execution_info fwd_info = nullptr, bwd_info = nullptr;
-    // fused form (mhh_pres_exec): Pres::input rides in the forward transform as its load callback, the unpack in the inverse
-    // transform as its store callback; cb_data = device copy of the PresCb record the callbacks read
-    rocfft_execution_info fwd_info_cb = nullptr, bwd_info_cb = nullptr;
-    void* cb_data = nullptr; bool cb_ready = false;
     void* fwd_wb = nullptr; void* bwd_wb = nullptr;
     bool fft_setup = false;
     // the three-kernel form with the transforms in LDS (pres_lds.h): twiddle tables, w3 in its [k][kx][ky] layout
@@ -56,21 +45,12 @@ struct mhh_pres_plan
 };
 
 
-// naturally aligned (16 bytes in fp64): one ds_read_b128 / global_load_dwordx4 per number instead of two 8-byte halves
-template<class TF> struct alignas(2*sizeof(TF)) C2 { TF x, y; };
 #include "pres_lds.h"
 #include "pres_lds4.h"
 #include "pres4_bands.h"
 
 // ---- host-side coefficient tables (Pres_2::set_values src/pres_2.cxx:125-153; Pres_4::set_values src/pres_4.cxx:179-252):
 // host_bmat, host_pres4_bands (pres4_bands.h, shared with the slab plan)
-template<class TF>
-static int upload(void** dst, const std::vector<TF>& v)
-{
-    MHH_HIP_TRY(hipMalloc(dst, v.size()*sizeof(TF)));
-    MHH_HIP_TRY(hipMemcpy(*dst, v.data(), v.size()*sizeof(TF), hipMemcpyHostToDevice));
-    return MHH_OK;
-}
 
 template<class TF>
 static int plan_tables(mhh_pres_plan* P, const mhh_grid* g, const void* hdz, const void* hdzhi, const void* hdzi4, const void* hdzhi4,
@@ -140,9 +120,7 @@ MHH_API void mhh_pres_plan_destroy(mhh_pres_plan* P)
     if (P->bwd) rocfft_plan_destroy(P->bwd);
     if (P->fwd_info) rocfft_execution_info_destroy(P->fwd_info);
     if (P->bwd_info) rocfft_execution_info_destroy(P->bwd_info);
-    if (P->fwd_info_cb) rocfft_execution_info_destroy(P->fwd_info_cb);
-    if (P->bwd_info_cb) rocfft_execution_info_destroy(P->bwd_info_cb);
-    void* bufs[] = {P->tx, P->ty, P->w3l, P->a3l, P->itw, P->cb_data, P->bmati, P->bmatj, P->a, P->c, P->dz, P->rhoref, P->packed, P->spec, P->work, P->fwd_wb, P->bwd_wb,
+    void* bufs[] = {P->tx, P->ty, P->w3l, P->a3l, P->itw, P->bmati, P->bmatj, P->a, P->c, P->dz, P->rhoref, P->packed, P->spec, P->work, P->fwd_wb, P->bwd_wb,
                     P->m[0], P->m[1], P->m[2], P->m[3], P->m[4], P->m[5], P->m[6]};
     for (void* b : bufs) if (b) (void)hipFree(b);
     delete P;
@@ -150,7 +128,6 @@ MHH_API void mhh_pres_plan_destroy(mhh_pres_plan* P)
 
 static int hdma_factor(mhh_pres_plan* P);
 static int tdma_factor(mhh_pres_plan* P);
-static int pres_cb_setup(mhh_pres_plan* P);
 static int pres_lds_setup(mhh_pres_plan* P, const mhh_grid* g);
 MHH_API int mhh_pres_plan_create(const mhh_grid* g, int order, const void* host_dz, const void* host_dzhi, const void* host_dzi4, const void* host_dzhi4,
                                  const void* host_rhoref, const void* host_rhorefh, mhh_pres_plan** out)
@@ -184,7 +161,6 @@ MHH_API int mhh_pres_plan_create(const mhh_grid* g, int order, const void* host_
         P->fft_setup = true;
         e = make_fft(P, true, &P->fwd, &P->fwd_info, &P->fwd_wb);
         if (!e) e = make_fft(P, false, &P->bwd, &P->bwd_info, &P->bwd_wb);
-        if (!e) e = pres_cb_setup(P);
     }
     if (!e && order == 4) e = hdma_factor(P);
     if (!e && order == 2) e = tdma_factor(P);
@@ -712,105 +688,6 @@ MHH_API int mhh_pres_output_order(const mhh_grid* g, int order, const mhh_fields
 }
 
 // =======================================================================================================
-// Fused form of Pres::exec. rocFFT lets a transform obtain its input through a load callback and deliver its output
-// through a store callback (rocfft_execution_info_set_load_callback / _store_callback). Pres::input is such a producer
-// (one value per packed cell, from the six ghosted fields) and the unpack such a consumer (normalise, ghosted layout,
-// periodic halo and vertical ghost rows), so the packed right-hand side and the packed solution never exist in memory:
-// two array writes and two array reads less than the staged form, and two kernels less. The transforms themselves and the
-// arithmetic of both ends are the staged form's: same bits (tests: fused vs staged).
-// =======================================================================================================
-template<class TF> struct PresCb
-{
-    GridDev<TF> g; int order;
-    const TF* u; const TF* v; const TF* w; const TF* ut; const TF* vt; const TF* wt; const TF* rhoref; const TF* rhorefh;
-    TF dti2, dti4;
-    TF* p;
-};
-template<class TF>
-__device__ TF pres_load_cb(TF*, size_t offset, void* cbdata, void*)
-{
-    const PresCb<TF>& d = *static_cast<const PresCb<TF>*>(cbdata);
-    const GridDev<TF>& g = d.g;
-    const unsigned o = (unsigned)offset, ij = (unsigned)g.imax*(unsigned)g.jmax;
-    const unsigned kz = o / ij, r = o - kz*ij, jz = r / (unsigned)g.imax, iz = r - jz*(unsigned)g.imax;
-    const int k = (int)kz + g.kgc;
-    const int c = ((int)iz + g.igc) + ((int)jz + g.jgc)*g.icells + k*g.ijcells;
-    if (d.order == 2) return pres2_in(d.u, d.v, d.w, d.ut, d.vt, d.wt, c, g.icells, g.ijcells, g.dxi_t, g.dyi_t, d.dti2, d.rhoref[k], d.rhorefh[k], d.rhorefh[k+1], g.dzi[k]);
-    return pres4_in(d.u, d.v, d.w, d.ut, d.vt, d.wt, c, g.icells, g.ijcells, g.dxi_d, g.dyi_d, d.dti4, g.dzi4[k], g.dim3);
-}
-template<class TF>
-__device__ void pres_store_cb(TF*, size_t offset, TF value, void* cbdata, void*)
-{
-    const PresCb<TF>& d = *static_cast<const PresCb<TF>*>(cbdata);
-    const GridDev<TF>& g = d.g;
-    const int itot = g.imax, jtot = g.jmax, kmax = g.kend - g.kstart;
-    const unsigned o = (unsigned)offset, ij = (unsigned)itot*(unsigned)jtot;
-    const unsigned kz = o / ij, r = o - kz*ij, jz = r / (unsigned)itot, iz = r - jz*(unsigned)itot;
-    const TF val = value / jtot / itot;                              // as unpack_kernel (src/fft.cxx scales 1/jtot then 1/itot)
-    // destination levels: the interior one and the ghost rows that mirror it (src/pres_2.cxx:352-360, src/pres_4.cxx:508-525)
-    int kd[2]; int nk = 1; kd[0] = (int)kz + g.kgc;
-    if (d.order == 2) { if (kz == 0) kd[nk++] = g.kgc - 1; }
-    else
-    {
-        if (kz == 0) kd[nk++] = g.kgc - 1;
-        if (kz == 1) kd[nk++] = g.kgc - 2;
-        if ((int)kz == kmax-1) kd[nk++] = g.kgc + kmax;
-        if ((int)kz == kmax-2) kd[nk++] = g.kgc + kmax + 1;
-    }
-    for (int n=0; n<nk; ++n)
-        for (int jd = ((int)jz + g.jgc) % jtot; jd < g.jcells; jd += jtot)       // every row / column congruent to this one: the periodic halo
-            for (int id = ((int)iz + g.igc) % itot; id < g.icells; id += itot)
-                d.p[(size_t)id + (size_t)jd*g.icells + (size_t)kd[n]*g.ijcells] = val;
-}
-// the record travels as a kernel argument: stream-ordered, and no host buffer has to outlive the call
-template<class TF> __global__ void pres_cb_record(PresCb<TF>* dst, const PresCb<TF> src) { *dst = src; }
-template<class TF> __global__ void pres_cb_addresses(void** out) { out[0] = (void*)&pres_load_cb<TF>; out[1] = (void*)&pres_store_cb<TF>; }
-
-static int pres_cb_setup(mhh_pres_plan* P)
-{
-    // device addresses of the two callbacks, execution infos that carry them, the record they read
-    void** dptr = nullptr; void* h[2] = {nullptr, nullptr};
-    MHH_HIP_TRY(hipMalloc((void**)&dptr, 2*sizeof(void*)));
-    if (P->dtype == MHH_F64) hipLaunchKernelGGL(pres_cb_addresses<double>, dim3(1), dim3(1), 0, 0, dptr);
-    else                     hipLaunchKernelGGL(pres_cb_addresses<float>,  dim3(1), dim3(1), 0, 0, dptr);
-    hipError_t he = hipMemcpy(h, dptr, 2*sizeof(void*), hipMemcpyDeviceToHost);
-    (void)hipFree(dptr);
-    if (he != hipSuccess || !h[0] || !h[1]) { set_error("pres callbacks: address query failed"); return MHH_EHIP; }
-    MHH_HIP_TRY(hipMalloc(&P->cb_data, sizeof(PresCb<double>)));
-    MHH_FFT_TRY(rocfft_execution_info_create(&P->fwd_info_cb));
-    MHH_FFT_TRY(rocfft_execution_info_create(&P->bwd_info_cb));
-    size_t wf = 0, wb = 0;
-    MHH_FFT_TRY(rocfft_plan_get_work_buffer_size(P->fwd, &wf));
-    MHH_FFT_TRY(rocfft_plan_get_work_buffer_size(P->bwd, &wb));
-    if (wf) MHH_FFT_TRY(rocfft_execution_info_set_work_buffer(P->fwd_info_cb, P->fwd_wb, wf));
-    if (wb) MHH_FFT_TRY(rocfft_execution_info_set_work_buffer(P->bwd_info_cb, P->bwd_wb, wb));
-    void* lfn[1] = {h[0]}; void* sfn[1] = {h[1]}; void* dat[1] = {P->cb_data};
-    if (rocfft_execution_info_set_load_callback(P->fwd_info_cb, lfn, dat, 0) != rocfft_status_success) return MHH_OK;   // not supported: stay staged
-    if (rocfft_execution_info_set_store_callback(P->bwd_info_cb, sfn, dat, 0) != rocfft_status_success) return MHH_OK;
-    P->cb_ready = true;
-    return MHH_OK;
-}
-
-template<class TF>
-static int pres_exec_fused(mhh_pres_plan* P, const mhh_grid* g, const mhh_fields* f, double dt, hipStream_t st)
-{
-    PresCb<TF> h;
-    h.g = make_grid<TF>(g); h.order = P->order;
-    h.u = cp<TF>(f->u); h.v = cp<TF>(f->v); h.w = cp<TF>(f->w); h.ut = cp<TF>(f->ut); h.vt = cp<TF>(f->vt); h.wt = cp<TF>(f->wt);
-    h.rhoref = cp<TF>(f->rhoref); h.rhorefh = cp<TF>(f->rhorefh); h.dti2 = TF(1.)/TF(dt); h.dti4 = TF(1./TF(dt)); h.p = mp<TF>(f->p);
-    hipLaunchKernelGGL(pres_cb_record<TF>, dim3(1), dim3(1), 0, st, static_cast<PresCb<TF>*>(P->cb_data), h);
-    MHH_LAUNCH_CHECK();
-    MHH_FFT_TRY(rocfft_execution_info_set_stream(P->fwd_info_cb, st));
-    MHH_FFT_TRY(rocfft_execution_info_set_stream(P->bwd_info_cb, st));
-    void* in[1] = {P->packed}; void* out[1] = {P->spec};          // `packed` is never read or written: the callbacks stand in for it
-    MHH_FFT_TRY(rocfft_execute(P->fwd, in, out, P->fwd_info_cb));
-    if (int e = pres_column_solve(P, g, st)) return e;
-    void* in2[1] = {P->spec}; void* out2[1] = {P->packed};
-    MHH_FFT_TRY(rocfft_execute(P->bwd, in2, out2, P->bwd_info_cb));
-    return MHH_OK;
-}
-
-// =======================================================================================================
 // Pres_2::exec with the transforms in LDS (pres_lds.h): input + x transform | y transforms around the Thomas sweeps |
 // x transform + p + output. Power-of-two itot (16 .. 1024) and jtot (8 .. 1024) whose rows fit the LDS; everything else
 // takes the staged form above.
@@ -825,88 +702,133 @@ static constexpr int LDS_RG = MHH_PRES_LDS_RG;
 // y rows: jtot = 64 ... 1024 (NY = 6 ... 10); shorter rows (tests, toy grids) run the run-time-size kernels in small blocks, where
 // registers are plentiful. Launch bounds keep at least 1024 threads per CU resident. An instantiation that needs scratch on this
 // compiler is not used (hipFuncGetAttributes at plan creation): the plan then has no LDS form and takes the staged one.
-#define MHH_FOR_NX(M) M(6) M(7) M(8) M(9)
-#define MHH_FOR_NY(M) M(6) M(7) M(8) M(9) M(10)
-#define MHH_FOR_NX_T(M, T) M(T, 6) M(T, 7) M(T, 8) M(T, 9)
-#define MHH_FOR_NY_T(M, T) M(T, 6) M(T, 7) M(T, 8) M(T, 9) M(T, 10)
 // (fp64 rows of 1024 along y: the unrolled passes do not fit the 128 registers of a 1024-thread block -- 88 bytes of scratch -- so
 // that size has no instantiation and such grids take the staged form)
 template<class TF, int NY> static constexpr bool lds_has_ny() { return sizeof(TF) == 4 || NY < 10; }
 static constexpr int LDS_XS = 64, LDS_YS = 32;            // block sizes of the run-time-size forms (itot <= 64, jtot <= 32)
+static constexpr int LDS_MAX = 160*1024;                  // the dynamic-LDS ceiling of every kernel of the form
 static int ilog2(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
-// rows of the transforms + the twiddle table; the 9-row kernel (stage 3) also keeps p of the level below there (8 rows of itot reals)
-// (pres_4: its 8-row kernel keeps a carried level there, its 11-row kernel nothing)
-static size_t lds_bytes_x(const mhh_pres_plan* P, int rows) { return ((size_t)rows*(P->itot/2 + 2) + P->itot) * 2*P->esz + ((rows == 9 || (rows == 8 && P->order == 4)) ? (size_t)8*P->itot*P->esz : 0); }
-static size_t lds_bytes_y(const mhh_pres_plan* P)           { return ((size_t)8*P->jtot + P->jtot) * 2*P->esz; }
+// block size of the kernels of an instantiated x / y row length (0: the run-time-size form)
+static constexpr int lds_bt_x(int nx) { return nx ? (2 << nx) : LDS_XS; }
+static constexpr int lds_bt_y(int ny) { return ny ? (1 << ny) : LDS_YS; }
+// The instantiation that runs a row length: fn(std::integral_constant<int, N>{}) with N = 0 for the run-time-size form (itot <=
+// LDS_XS, jtot <= LDS_YS) or the instantiated log2 length (x rows: itot = 2 << N, N = 6 ... 9; y rows: jtot = 1 << N, N = 6 ... 10
+// where lds_has_ny). Returns false where the length has none.
+template<class Fn> static bool lds_x_variant(int itot, Fn&& fn)
+{
+    using std::integral_constant;
+    if (itot <= LDS_XS) { fn(integral_constant<int, 0>{}); return true; }
+    switch (ilog2(itot/2))
+    {
+        case 6: fn(integral_constant<int, 6>{}); return true;
+        case 7: fn(integral_constant<int, 7>{}); return true;
+        case 8: fn(integral_constant<int, 8>{}); return true;
+        case 9: fn(integral_constant<int, 9>{}); return true;
+    }
+    return false;
+}
+template<class TF, class Fn> static bool lds_y_variant(int jtot, Fn&& fn)
+{
+    using std::integral_constant;
+    if (jtot <= LDS_YS) { fn(integral_constant<int, 0>{}); return true; }
+    auto at = [&](auto ny) { if constexpr (lds_has_ny<TF, ny>()) { fn(ny); return true; } else return false; };
+    switch (ilog2(jtot))
+    {
+        case 6: return at(integral_constant<int, 6>{});
+        case 7: return at(integral_constant<int, 7>{});
+        case 8: return at(integral_constant<int, 8>{});
+        case 9: return at(integral_constant<int, 9>{});
+        case 10: return at(integral_constant<int, 10>{});
+    }
+    return false;
+}
+template<class K> static const void* kfn(K* kernel) { return reinterpret_cast<const void*>(kernel); }
+// LDS bytes of an x-stage kernel of `rows` rows: the rows of the transforms + the twiddle table; pres_2's 9-row kernel (stage 3) also
+// keeps p of the level below there (8 rows of itot reals), pres_4's 8-row kernel a carried level (its 11-row kernel nothing)
+static size_t lds_bytes_x(int itot, size_t esz, int order, int rows)
+{
+    return ((size_t)rows*(itot/2 + 2) + itot) * 2*esz + ((rows == 9 || (rows == 8 && order == 4)) ? (size_t)8*itot*esz : 0);
+}
+// ... of a y-stage kernel: 8 rows of jtot + the twiddle table
+static size_t lds_bytes_y(int jtot, size_t esz) { return ((size_t)8*jtot + jtot) * 2*esz; }
+// Can the form run this grid at all? Power-of-two itot (16 .. 1024) and jtot (8 .. 1024) whose kernels fit the LDS, x ghost cells
+// no wider than a row, and cell indices within the 32 bits of the x-stage kernels
+static bool lds_eligible(const mhh_grid* g, int order)
+{
+    const size_t esz = (g->dtype == MHH_F64) ? 8 : 4;
+    if (!(is_pow2(g->itot) && g->itot >= 16 && g->itot <= 1024 && is_pow2(g->jtot) && g->jtot >= 8 && g->jtot <= 1024)) return false;
+    if (lds_bytes_x(g->itot, esz, order, order == 2 ? 9 : 11) > LDS_MAX || lds_bytes_x(g->itot, esz, order, 8) > LDS_MAX || lds_bytes_y(g->jtot, esz) > LDS_MAX) return false;
+    return g->igc <= g->itot && (long long)g->icells*g->jcells*g->kcells < (1ll << 31);
+}
+// Levels per block of the x stages over nlev levels of `rows` rows: enough blocks to fill the chip several times over (8 rows x kc
+// levels each); every block re-does one level below its own. MHH_PRES_LDS_KC=n sets it (tuning runs).
+static int lds_levels_per_block(int nlev, int rows)
+{
+    const char* e = getenv("MHH_PRES_LDS_KC");
+    int kc = e ? atoi(e) : (int)(((long long)nlev * (rows/8)) / 2048);
+    if (!e) kc = kc < 4 ? 4 : (kc > 32 ? 32 : kc);
+    return kc < 1 ? 1 : (kc > nlev ? nlev : kc);
+}
+template<class TF>
+static int lds_twiddles_t(int n, void** t)
+{
+    const double pi = std::acos(-1.);
+    std::vector<TF> w(2*(size_t)n);
+    for (int m=0; m<n; ++m) { w[2*m] = (TF)std::cos(2.*pi*m/n); w[2*m+1] = (TF)(-std::sin(2.*pi*m/n)); }
+    // the quarter points exactly
+    w[0] = 1; w[1] = 0; w[n] = -1; w[n+1] = 0;
+    if (n >= 4) { w[n/2] = 0; w[n/2+1] = -1; w[3*n/2] = 0; w[3*n/2+1] = 1; }
+    return upload(t, w);
+}
+int mhh::lds_twiddles(int n, int dtype, void** t) { return (dtype == MHH_F64) ? lds_twiddles_t<double>(n, t) : lds_twiddles_t<float>(n, t); }
 template<class TF>
 static lds_fft::PresLdsSolve<TF> lds_solve_args(const mhh_pres_plan* P)
 {
     return lds_fft::PresLdsSolve<TF>{static_cast<C2<TF>*>(P->spec), cp<TF>(P->w3l), cp<TF>(P->bmati), cp<TF>(P->bmatj), cp<TF>(P->a), cp<TF>(P->c),
                                      cp<TF>(P->dz), cp<TF>(P->rhoref), static_cast<const C2<TF>*>(P->ty), P->itot/2, P->jtot, ilog2(P->jtot), P->ktot};
 }
-// the kernel of a stage for a row length: NX / NY = 0 selects the run-time-size form
-template<class TF, int NX> static const void* lds_kernel_in()  { return reinterpret_cast<const void*>(&lds_fft::pres_in_fftx_kernel<TF, LDS_RG, (NX ? (2 << NX) : LDS_XS), NX>); }
-template<class TF, int NX> static const void* lds_kernel_out() { return reinterpret_cast<const void*>(&lds_fft::pres_ifftx_out_kernel<TF, LDS_RG, (NX ? (2 << NX) : LDS_XS), NX>); }
-template<class TF, int NY> static const void* lds_kernel_y()   { return reinterpret_cast<const void*>(&lds_fft::pres_ysolve_kernel<TF, (NY ? (1 << NY) : LDS_YS), NY>); }
-template<class TF, int NX> static const void* lds4_kernel_in()  { return reinterpret_cast<const void*>(&lds_fft::pres4_in_fftx_kernel<TF, (NX ? (2 << NX) : LDS_XS), NX>); }
-template<class TF, int NX> static const void* lds4_kernel_out() { return reinterpret_cast<const void*>(&lds_fft::pres4_ifftx_out_kernel<TF, (NX ? (2 << NX) : LDS_XS), NX>); }
-template<class TF, int NY> static const void* lds4_kernel_y()   { return reinterpret_cast<const void*>(&lds_fft::pres4_ysolve_kernel<TF, (NY ? (1 << NY) : LDS_YS), NY>); }
-template<class TF, int NY, int PH> static const void* lds_kernel_ytw() { return reinterpret_cast<const void*>(&lds_fft::pres_ysolve_tw_kernel<TF, (NY ? (1 << NY) : LDS_YS), NY, PH>); }
-// once per process and kernel: the dynamic-LDS ceiling at the device's maximum (the attribute belongs to the FUNCTION, not to a
-// plan: set per plan to that plan's bytes, a small plan created after a large one lowered the ceiling under the large one), and
-// whether the instantiation needs scratch
+// At every plan creation, on the current device: the dynamic-LDS ceiling at the device's maximum, and whether the instantiation needs
+// scratch. The attribute belongs to the FUNCTION on a device, not to a plan (set per plan to that plan's bytes, a small plan created
+// after a large one lowered the ceiling under the large one); setting it to the same maximum each time is idempotent and reaches every
+// device a process creates plans on.
 static int lds_kernel_ready(const void* kernel, bool& usable)
 {
-    static std::map<const void*, bool> seen;
-    static std::mutex mtx;
-    std::lock_guard<std::mutex> lock(mtx);
-    auto it = seen.find(kernel);
-    if (it == seen.end())
+    MHH_HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
+    hipFuncAttributes fa;
+    MHH_HIP_TRY(hipFuncGetAttributes(&fa, kernel));
+    usable = (fa.localSizeBytes == 0);
+    return MHH_OK;
+}
+// Can a form run? Every kernel it needs has an instantiation (null: none) and runs without scratch.
+static int lds_kernels_ready(std::initializer_list<const void*> kernels, bool& usable)
+{
+    usable = true;
+    for (const void* k : kernels)
     {
-        MHH_HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024));
-        hipFuncAttributes fa;
-        MHH_HIP_TRY(hipFuncGetAttributes(&fa, kernel));
-        it = seen.emplace(kernel, fa.localSizeBytes == 0).first;
+        bool u = false;
+        if (!k) { usable = false; return MHH_OK; }
+        if (int e = lds_kernel_ready(k, u)) return e;
+        usable = usable && u;
     }
-    usable = it->second;
     return MHH_OK;
 }
 template<class TF>
 static int pres_lds_kernels_ready(const mhh_pres_plan* P, bool& usable)
 {
-    const int nx = ilog2(P->itot/2), ny = ilog2(P->jtot);
     const void* k[3] = {nullptr, nullptr, nullptr};
     if (P->order == 2)
     {
-        if (P->itot <= LDS_XS) { k[0] = lds_kernel_in<TF, 0>(); k[1] = lds_kernel_out<TF, 0>(); }
-        if (P->jtot <= LDS_YS) k[2] = lds_kernel_y<TF, 0>();
-#define M(N) if (nx == N) { k[0] = lds_kernel_in<TF, N>(); k[1] = lds_kernel_out<TF, N>(); }
-        MHH_FOR_NX(M)
-#undef M
-#define M(N) if (ny == N) { if constexpr (lds_has_ny<TF, N>()) k[2] = lds_kernel_y<TF, N>(); }
-        MHH_FOR_NY(M)
-#undef M
+        lds_x_variant(P->itot, [&](auto NX) { k[0] = kfn(&lds_fft::pres_in_fftx_kernel<TF, LDS_RG, lds_bt_x(NX), NX>);
+                                               k[1] = kfn(&lds_fft::pres_ifftx_out_kernel<TF, LDS_RG, lds_bt_x(NX), NX>); });
+        lds_y_variant<TF>(P->jtot, [&](auto NY) { k[2] = kfn(&lds_fft::pres_ysolve_kernel<TF, lds_bt_y(NY), NY>); });
     }
     else
     {
-        if (P->itot <= LDS_XS) { k[0] = lds4_kernel_in<TF, 0>(); k[1] = lds4_kernel_out<TF, 0>(); }
-        if (P->jtot <= LDS_YS) k[2] = lds4_kernel_y<TF, 0>();
-#define M(N) if (nx == N) { k[0] = lds4_kernel_in<TF, N>(); k[1] = lds4_kernel_out<TF, N>(); }
-        MHH_FOR_NX(M)
-#undef M
-#define M(N) if (ny == N) { if constexpr (lds_has_ny<TF, N>()) k[2] = lds4_kernel_y<TF, N>(); }
-        MHH_FOR_NY(M)
-#undef M
+        lds_x_variant(P->itot, [&](auto NX) { k[0] = kfn(&lds_fft::pres4_in_fftx_kernel<TF, lds_bt_x(NX), NX>);
+                                               k[1] = kfn(&lds_fft::pres4_ifftx_out_kernel<TF, lds_bt_x(NX), NX>); });
+        lds_y_variant<TF>(P->jtot, [&](auto NY) { k[2] = kfn(&lds_fft::pres4_ysolve_kernel<TF, lds_bt_y(NY), NY>); });
     }
-    usable = true;
-    for (int n=0; n<3; ++n)
-    {
-        if (!k[n]) { usable = false; return MHH_OK; }
-        bool u = false;
-        if (int e = lds_kernel_ready(k[n], u)) return e;
-        usable = usable && u;
-    }
-    return MHH_OK;
+    return lds_kernels_ready({k[0], k[1], k[2]}, usable);
 }
 template<class TF>
 static int pres_lds_setup_t(mhh_pres_plan* P)
@@ -914,17 +836,8 @@ static int pres_lds_setup_t(mhh_pres_plan* P)
     bool usable = false;
     if (int e = pres_lds_kernels_ready<TF>(P, usable)) return e;
     if (!usable) return MHH_OK;
-    const double pi = std::acos(-1.);
-    for (int d=0; d<2; ++d)
-    {
-        const int n = d ? P->jtot : P->itot;
-        std::vector<TF> t(2*(size_t)n);
-        for (int m=0; m<n; ++m) { t[2*m] = (TF)std::cos(2.*pi*m/n); t[2*m+1] = (TF)(-std::sin(2.*pi*m/n)); }
-        // the quarter points exactly
-        t[0] = 1; t[1] = 0; t[n] = -1; t[n+1] = 0;
-        if (n >= 4) { t[n/2] = 0; t[n/2+1] = -1; t[3*n/2] = 0; t[3*n/2+1] = 1; }
-        if (int e = upload(d ? &P->ty : &P->tx, t)) return e;
-    }
+    if (int e = lds_twiddles(P->itot, P->dtype, &P->tx)) return e;
+    if (int e = lds_twiddles(P->jtot, P->dtype, &P->ty)) return e;
     if (P->order == 2)
     {
         MHH_HIP_TRY(hipMalloc(&P->w3l, (size_t)(P->itot/2 + 1)*P->jtot*P->ktot*sizeof(TF)));
@@ -933,14 +846,11 @@ static int pres_lds_setup_t(mhh_pres_plan* P)
         // (only where pres_y_twisted() takes it by itself, or when the switch is set at plan creation: its tables are another spectral array)
         if (P->ktot >= 16 && (P->itot <= 256 || getenv("MHH_PRES_Y_TWISTED")))
         {
-            const int ny = ilog2(P->jtot);
-            const void* k2[2] = {nullptr, nullptr};
-            if (P->jtot <= LDS_YS) { k2[0] = lds_kernel_ytw<TF, 0, 1>(); k2[1] = lds_kernel_ytw<TF, 0, 2>(); }
-#define M(N) if (ny == N) { if constexpr (lds_has_ny<TF, N>()) { k2[0] = lds_kernel_ytw<TF, N, 1>(); k2[1] = lds_kernel_ytw<TF, N, 2>(); } }
-            MHH_FOR_NY(M)
-#undef M
-            bool ok2 = (k2[0] != nullptr);
-            for (int n=0; n<2 && ok2; ++n) { bool u = false; if (int e = lds_kernel_ready(k2[n], u)) return e; ok2 = u; }
+            const void* k[2] = {nullptr, nullptr};
+            lds_y_variant<TF>(P->jtot, [&](auto NY) { k[0] = kfn(&lds_fft::pres_ysolve_tw_kernel<TF, lds_bt_y(NY), NY, 1>);
+                                                      k[1] = kfn(&lds_fft::pres_ysolve_tw_kernel<TF, lds_bt_y(NY), NY, 2>); });
+            bool ok2 = false;
+            if (int e = lds_kernels_ready({k[0], k[1]}, ok2)) return e;
             if (ok2)
             {
                 P->ksplit = ((P->ktot/2 + 7)/8)*8;
@@ -965,31 +875,17 @@ static int pres_lds_setup_t(mhh_pres_plan* P)
 }
 static int pres_lds_setup(mhh_pres_plan* P, const mhh_grid* g)
 {
-    const size_t lds_max = 160*1024;
-    if (!(is_pow2(P->itot) && P->itot >= 16 && P->itot <= 1024 && is_pow2(P->jtot) && P->jtot >= 8 && P->jtot <= 1024)) return MHH_OK;
-    if (lds_bytes_x(P, P->order == 2 ? 9 : 11) > lds_max || lds_bytes_x(P, 8) > lds_max || lds_bytes_y(P) > lds_max) return MHH_OK;
-    if (g->igc > P->itot || g->jgc > P->jtot) return MHH_OK;
-    if ((long long)g->icells*g->jcells*g->kcells >= (1ll << 31)) return MHH_OK;        // the x-stage kernels index cells with 32 bits
+    if (!lds_eligible(g, P->order) || g->jgc > P->jtot) return MHH_OK;
     return (P->dtype == MHH_F64) ? pres_lds_setup_t<double>(P) : pres_lds_setup_t<float>(P);
 }
 // the y stage with two blocks per column (pres_lds.h, 2t)? MHH_PRES_Y_TWISTED=1 / 0: wherever the plan has it / never
 static bool pres_y_twisted(const mhh_pres_plan* P)
 {
-    if (!P->tw_ok || P->order != 2) return false;
-    const char* e = getenv("MHH_PRES_Y_TWISTED");
-    if (e) return !strcmp(e, "1");
+    if (!P->tw_ok || P->order != 2 || env_is("MHH_PRES_Y_TWISTED", "0")) return false;
     // measured on MI355X (profiles/r3_pres_forms.md): with fewer columns than the chip has CUs the stage is a dependent chain per block
     // and the half-length chains win (itot = 256: 0.245 -> 0.160 ms at 256^3, 0.511 -> 0.390 at 256 x 256 x 512); at itot = 512 there
     // is a block per CU already and the second launch costs more than it saves (0.93 -> 1.07 ms at 512^3)
-    return P->itot <= 256;
-}
-static int lds_levels_per_block(const mhh_pres_plan* P)
-{
-    // enough blocks to fill the chip several times over (8 rows x kc levels each); every block re-does one level below its own
-    const char* e = getenv("MHH_PRES_LDS_KC");
-    int kc = e ? atoi(e) : (int)(((long long)P->ktot * (P->jtot/8)) / 2048);
-    if (!e) kc = kc < 4 ? 4 : (kc > 32 ? 32 : kc);
-    return kc < 1 ? 1 : (kc > P->ktot ? P->ktot : kc);
+    return env_is("MHH_PRES_Y_TWISTED", "1") || P->itot <= 256;
 }
 // Pres_4::output's correction of wt (src/pres_4.cxx:565-569; k = kstart is skipped) from p with its ghost levels in place: the
 // part of the LDS form's last stage that needs the level above (pres_lds4.h)
@@ -1021,6 +917,48 @@ __global__ void __launch_bounds__(256) pres4_wt_march_kernel(const GridDev<TF> g
         pm2 = pm1; pm1 = pc; pc = pn;
     }
 }
+template<class TF>
+static int pres2_lds_stage(mhh_pres_plan* P, const mhh_grid* g, const mhh_fields* f, double dt, int stage, dim3 xgrid, int kc, hipStream_t st)
+{
+    const int nx = ilog2(P->itot/2);
+    const dim3 yb(P->jtot);
+    const size_t yl = lds_bytes_y(P->jtot, P->esz);
+    if (stage == 1)
+    {
+        MHH_REQUIRE(f && f->u && f->v && f->w && f->ut && f->vt && f->wt && f->rhoref && f->rhorefh, "null field");
+        MHH_REQUIRE(dt > 0., "dt");
+        if (int e = pres_input_halos(g, 2, f, st)) return e;
+        const lds_fft::PresLdsIn<TF> a{make_grid<TF>(g), cp<TF>(f->u), cp<TF>(f->v), cp<TF>(f->w), cp<TF>(f->ut), cp<TF>(f->vt), cp<TF>(f->wt),
+                                       cp<TF>(f->rhoref), cp<TF>(f->rhorefh), TF(1.)/TF(dt), static_cast<C2<TF>*>(P->spec), static_cast<const C2<TF>*>(P->tx), nx, kc, 0, P->ktot, P->jtot, {}};
+        const size_t xl = lds_bytes_x(P->itot, P->esz, 2, 8);
+        lds_x_variant(P->itot, [&](auto NX) { hipLaunchKernelGGL((lds_fft::pres_in_fftx_kernel<TF, LDS_RG, lds_bt_x(NX), NX>), xgrid, dim3(P->itot), xl, st, a); });
+    }
+    else if (stage == 2 && pres_y_twisted(P))
+    {
+        // two blocks per column, two launches: eliminate towards the split | solve where the halves meet and substitute outward
+        const lds_fft::PresLdsSolveTw<TF> ya{lds_solve_args<TF>(P), cp<TF>(P->a3l), static_cast<C2<TF>*>(P->itw), P->ksplit};
+        lds_y_variant<TF>(P->jtot, [&](auto NY) { hipLaunchKernelGGL((lds_fft::pres_ysolve_tw_kernel<TF, lds_bt_y(NY), NY, 1>), dim3(P->itot), yb, yl, st, ya);
+                                                  hipLaunchKernelGGL((lds_fft::pres_ysolve_tw_kernel<TF, lds_bt_y(NY), NY, 2>), dim3(P->itot), yb, yl, st, ya); });
+    }
+    else if (stage == 2)
+    {
+        const auto ya = lds_solve_args<TF>(P);
+        lds_y_variant<TF>(P->jtot, [&](auto NY) { hipLaunchKernelGGL((lds_fft::pres_ysolve_kernel<TF, lds_bt_y(NY), NY>), dim3(P->itot/2), yb, yl, st, ya); });
+    }
+    else
+    {
+        MHH_REQUIRE(f && f->p && f->ut && f->vt && f->wt, "null field");
+        const lds_fft::PresLdsOut<TF> a{make_grid<TF>(g), static_cast<const C2<TF>*>(P->spec), static_cast<const C2<TF>*>(P->tx),
+                                        mp<TF>(f->p), mp<TF>(f->ut), mp<TF>(f->vt), mp<TF>(f->wt), nx, kc, 0, P->ktot, P->jtot, {},
+                                        mp<TF>(P->rk_u), mp<TF>(P->rk_v), mp<TF>(P->rk_w), TF(P->rk_cA), TF(P->rk_cB), TF(P->rk_dt)};
+        const size_t xl = lds_bytes_x(P->itot, P->esz, 2, 9);
+        lds_x_variant(P->itot, [&](auto NX) {
+            if (P->rk_on) hipLaunchKernelGGL((lds_fft::pres_ifftx_out_kernel<TF, LDS_RG, lds_bt_x(NX), NX, false, true>), xgrid, dim3(P->itot), xl, st, a);
+            else          hipLaunchKernelGGL((lds_fft::pres_ifftx_out_kernel<TF, LDS_RG, lds_bt_x(NX), NX>), xgrid, dim3(P->itot), xl, st, a); });
+    }
+    return MHH_OK;
+}
+template<class TF>
 static int pres4_lds_stage(mhh_pres_plan* P, const mhh_grid* g, const mhh_fields* f, double dt, int stage, dim3 xgrid, int kc, hipStream_t st)
 {
     const int nx = ilog2(P->itot/2), ny = ilog2(P->jtot);
@@ -1029,55 +967,38 @@ static int pres4_lds_stage(mhh_pres_plan* P, const mhh_grid* g, const mhh_fields
         MHH_REQUIRE(f && f->u && f->v && f->w && f->ut && f->vt && f->wt, "null field");
         MHH_REQUIRE(dt > 0., "dt");
         if (int e = pres_input_halos(g, 4, f, st)) return e;
-#define M(TF, N) else if (nx == N) hipLaunchKernelGGL((lds_fft::pres4_in_fftx_kernel<TF, (2 << N), N>), xgrid, dim3(P->itot), lds_bytes_x(P, 8), st, a);
-#define CALL(TF) [&]{ lds_fft::Pres4LdsIn<TF> a{make_grid<TF>(g), cp<TF>(f->u), cp<TF>(f->v), cp<TF>(f->w), cp<TF>(f->ut), cp<TF>(f->vt), cp<TF>(f->wt), \
-                          TF(1.)/TF(dt), static_cast<C2<TF>*>(P->spec), static_cast<const C2<TF>*>(P->tx), nx, kc}; \
-                      if (P->itot <= LDS_XS) hipLaunchKernelGGL((lds_fft::pres4_in_fftx_kernel<TF, LDS_XS, 0>), xgrid, dim3(P->itot), lds_bytes_x(P, 8), st, a); \
-                      MHH_FOR_NX_T(M, TF) return MHH_OK; }()
-        if (int e = MHH_DISPATCH(g, CALL)) return e;
-#undef CALL
-#undef M
+        const lds_fft::Pres4LdsIn<TF> a{make_grid<TF>(g), cp<TF>(f->u), cp<TF>(f->v), cp<TF>(f->w), cp<TF>(f->ut), cp<TF>(f->vt), cp<TF>(f->wt),
+                                        TF(1.)/TF(dt), static_cast<C2<TF>*>(P->spec), static_cast<const C2<TF>*>(P->tx), nx, kc};
+        const size_t xl = lds_bytes_x(P->itot, P->esz, 4, 8);
+        lds_x_variant(P->itot, [&](auto NX) { hipLaunchKernelGGL((lds_fft::pres4_in_fftx_kernel<TF, lds_bt_x(NX), NX>), xgrid, dim3(P->itot), xl, st, a); });
     }
     else if (stage == 2)
     {
-#define M(TF, N) else if (ny == N) { if constexpr (lds_has_ny<TF, N>()) hipLaunchKernelGGL((lds_fft::pres4_ysolve_kernel<TF, (1 << N), N>), yg, yb, yl, st, ya); }
-#define CALL(TF) [&]{ const dim3 yg(P->itot/2), yb(P->jtot); const size_t yl = lds_bytes_y(P); \
-                      const lds_fft::Pres4LdsSolve<TF> ya{static_cast<C2<TF>*>(P->spec), cp<TF>(P->w3l), cp<TF>(P->m[6]), static_cast<const C2<TF>*>(P->ty), P->itot/2, P->jtot, ny, P->ktot}; \
-                      if (P->jtot <= LDS_YS) hipLaunchKernelGGL((lds_fft::pres4_ysolve_kernel<TF, LDS_YS, 0>), yg, yb, yl, st, ya); \
-                      MHH_FOR_NY_T(M, TF) return MHH_OK; }()
-        if (int e = MHH_DISPATCH(g, CALL)) return e;
-#undef CALL
-#undef M
+        const lds_fft::Pres4LdsSolve<TF> ya{static_cast<C2<TF>*>(P->spec), cp<TF>(P->w3l), cp<TF>(P->m[6]), static_cast<const C2<TF>*>(P->ty), P->itot/2, P->jtot, ny, P->ktot};
+        const size_t yl = lds_bytes_y(P->jtot, P->esz);
+        lds_y_variant<TF>(P->jtot, [&](auto NY) { hipLaunchKernelGGL((lds_fft::pres4_ysolve_kernel<TF, lds_bt_y(NY), NY>), dim3(P->itot/2), dim3(P->jtot), yl, st, ya); });
     }
     else
     {
         MHH_REQUIRE(f && f->p && f->ut && f->vt && f->wt, "null field");
-#define M(TF, N) else if (nx == N) hipLaunchKernelGGL((lds_fft::pres4_ifftx_out_kernel<TF, (2 << N), N>), xgrid, dim3(P->itot), lds_bytes_x(P, 11), st, a);
-#define CALL(TF) [&]{ lds_fft::Pres4LdsOut<TF> a{make_grid<TF>(g), static_cast<const C2<TF>*>(P->spec), static_cast<const C2<TF>*>(P->tx), \
-                          mp<TF>(f->p), mp<TF>(f->ut), mp<TF>(f->vt), nx, kc}; \
-                      if (P->itot <= LDS_XS) hipLaunchKernelGGL((lds_fft::pres4_ifftx_out_kernel<TF, LDS_XS, 0>), xgrid, dim3(P->itot), lds_bytes_x(P, 11), st, a); \
-                      MHH_FOR_NX_T(M, TF) return MHH_OK; }()
-        if (int e = MHH_DISPATCH(g, CALL)) return e;
-#undef CALL
-#undef M
+        const lds_fft::Pres4LdsOut<TF> a{make_grid<TF>(g), static_cast<const C2<TF>*>(P->spec), static_cast<const C2<TF>*>(P->tx),
+                                         mp<TF>(f->p), mp<TF>(f->ut), mp<TF>(f->vt), nx, kc};
+        const size_t xl = lds_bytes_x(P->itot, P->esz, 4, 11);
+        lds_x_variant(P->itot, [&](auto NX) { hipLaunchKernelGGL((lds_fft::pres4_ifftx_out_kernel<TF, lds_bt_x(NX), NX>), xgrid, dim3(P->itot), xl, st, a); });
         MHH_LAUNCH_CHECK();
-        const char* wm = getenv("MHH_PRES4_WT");                             // "cell": the one-thread-per-cell form (A/B)
-        if (wm && !strcmp(wm, "cell"))
+        const GridDev<TF> gd = make_grid<TF>(g);
+        if (env_is("MHH_PRES4_WT", "cell"))                                    // the one-thread-per-cell form (A/B)
         {
-#define CALL(TF) [&]{ const GridDev<TF> gd = make_grid<TF>(g); Pres4WtOp<TF> op{gd, cp<TF>(f->p), mp<TF>(f->wt)}; return launch_interior(st, gd, g->kstart + 1, g->kend, op); }()
-            if (int e = MHH_DISPATCH(g, CALL)) return e;
-#undef CALL
+            Pres4WtOp<TF> op{gd, cp<TF>(f->p), mp<TF>(f->wt)};
+            if (int e = launch_interior(st, gd, g->kstart + 1, g->kend, op)) return e;
         }
         else if (g->kmax > 1)
         {
             const int wkc = 32;
             const dim3 wg((g->imax + 63)/64, (g->jmax + 3)/4, (g->kmax - 1 + wkc - 1)/wkc);
-#define CALL(TF) [&]{ hipLaunchKernelGGL(pres4_wt_march_kernel<TF>, wg, dim3(64, 4), 0, st, make_grid<TF>(g), cp<TF>(f->p), mp<TF>(f->wt), wkc); return MHH_OK; }()
-            if (int e = MHH_DISPATCH(g, CALL)) return e;
-#undef CALL
+            hipLaunchKernelGGL(pres4_wt_march_kernel<TF>, wg, dim3(64, 4), 0, st, gd, cp<TF>(f->p), mp<TF>(f->wt), wkc);
         }
     }
-    MHH_LAUNCH_CHECK();
     return MHH_OK;
 }
 // the three stages, also callable one by one (tests): 1 = input + x transform, 2 = y transforms + Thomas, 3 = x transform + p + output
@@ -1088,315 +1009,171 @@ MHH_API int mhh_pres_lds_stage(mhh_pres_plan* P, const mhh_grid* g, const mhh_fi
     MHH_REQUIRE(P->dtype == g->dtype && P->itot == g->itot && P->jtot == g->jtot && P->ktot == g->ktot && g->npy == 1, "plan/grid mismatch");
     MHH_REQUIRE(stage >= 1 && stage <= 3, "stage");
     hipStream_t st = as_stream(stream);
-    const int kc = lds_levels_per_block(P);
+    const int kc = lds_levels_per_block(P->ktot, P->jtot);
     const dim3 xgrid((unsigned)(P->jtot/8) * (unsigned)((P->ktot + kc-1)/kc));        // strips x chunks, decoded by lds_strip_of_block
-    const int nx = ilog2(P->itot/2), ny = ilog2(P->jtot);
-    if (P->order == 4) return pres4_lds_stage(P, g, f, dt, stage, xgrid, kc, st);
-    if (stage == 1)
-    {
-        MHH_REQUIRE(f && f->u && f->v && f->w && f->ut && f->vt && f->wt && f->rhoref && f->rhorefh, "null field");
-        MHH_REQUIRE(dt > 0., "dt");
-        if (int e = pres_input_halos(g, 2, f, stream)) return e;
-#define M(TF, N) else if (nx == N) hipLaunchKernelGGL((lds_fft::pres_in_fftx_kernel<TF, LDS_RG, (2 << N), N>), xgrid, dim3(P->itot), lds_bytes_x(P, 8), st, a);
-#define CALL(TF) [&]{ lds_fft::PresLdsIn<TF> a{make_grid<TF>(g), cp<TF>(f->u), cp<TF>(f->v), cp<TF>(f->w), cp<TF>(f->ut), cp<TF>(f->vt), cp<TF>(f->wt), \
-                          cp<TF>(f->rhoref), cp<TF>(f->rhorefh), TF(1.)/TF(dt), static_cast<C2<TF>*>(P->spec), static_cast<const C2<TF>*>(P->tx), nx, kc, 0, P->ktot, P->jtot, {}}; \
-                      if (P->itot <= LDS_XS) hipLaunchKernelGGL((lds_fft::pres_in_fftx_kernel<TF, LDS_RG, LDS_XS, 0>), xgrid, dim3(P->itot), lds_bytes_x(P, 8), st, a); \
-                      MHH_FOR_NX_T(M, TF) return MHH_OK; }()
-        if (int e = MHH_DISPATCH(g, CALL)) return e;
-#undef CALL
-#undef M
-    }
-    else if (stage == 2 && pres_y_twisted(P))
-    {
-        // two blocks per column, two launches: eliminate towards the split | solve where the halves meet and substitute outward
-#define M(TF, N) else if (ny == N) { if constexpr (lds_has_ny<TF, N>()) { hipLaunchKernelGGL((lds_fft::pres_ysolve_tw_kernel<TF, (1 << N), N, 1>), yg, yb, yl, st, ya); \
-                                                                          hipLaunchKernelGGL((lds_fft::pres_ysolve_tw_kernel<TF, (1 << N), N, 2>), yg, yb, yl, st, ya); } }
-#define CALL(TF) [&]{ const dim3 yg(P->itot), yb(P->jtot); const size_t yl = lds_bytes_y(P); \
-                      const lds_fft::PresLdsSolveTw<TF> ya{lds_solve_args<TF>(P), cp<TF>(P->a3l), static_cast<C2<TF>*>(P->itw), P->ksplit}; \
-                      if (P->jtot <= LDS_YS) { hipLaunchKernelGGL((lds_fft::pres_ysolve_tw_kernel<TF, LDS_YS, 0, 1>), yg, yb, yl, st, ya); \
-                                               hipLaunchKernelGGL((lds_fft::pres_ysolve_tw_kernel<TF, LDS_YS, 0, 2>), yg, yb, yl, st, ya); } \
-                      MHH_FOR_NY_T(M, TF) return MHH_OK; }()
-        if (int e = MHH_DISPATCH(g, CALL)) return e;
-#undef CALL
-#undef M
-    }
-    else if (stage == 2)
-    {
-#define M(TF, N) else if (ny == N) { if constexpr (lds_has_ny<TF, N>()) hipLaunchKernelGGL((lds_fft::pres_ysolve_kernel<TF, (1 << N), N>), yg, yb, yl, st, ya); }
-#define CALL(TF) [&]{ const dim3 yg(P->itot/2), yb(P->jtot); const size_t yl = lds_bytes_y(P); const auto ya = lds_solve_args<TF>(P); \
-                      if (P->jtot <= LDS_YS) hipLaunchKernelGGL((lds_fft::pres_ysolve_kernel<TF, LDS_YS, 0>), yg, yb, yl, st, ya); \
-                      MHH_FOR_NY_T(M, TF) return MHH_OK; }()
-        if (int e = MHH_DISPATCH(g, CALL)) return e;
-#undef CALL
-#undef M
-    }
-    else
-    {
-        MHH_REQUIRE(f && f->p && f->ut && f->vt && f->wt, "null field");
-#define M(TF, N) else if (nx == N) { if (P->rk_on) hipLaunchKernelGGL((lds_fft::pres_ifftx_out_kernel<TF, LDS_RG, (2 << N), N, false, true>), xgrid, dim3(P->itot), lds_bytes_x(P, 9), st, a); \
-                                    else          hipLaunchKernelGGL((lds_fft::pres_ifftx_out_kernel<TF, LDS_RG, (2 << N), N>), xgrid, dim3(P->itot), lds_bytes_x(P, 9), st, a); }
-#define CALL(TF) [&]{ lds_fft::PresLdsOut<TF> a{make_grid<TF>(g), static_cast<const C2<TF>*>(P->spec), static_cast<const C2<TF>*>(P->tx), \
-                          mp<TF>(f->p), mp<TF>(f->ut), mp<TF>(f->vt), mp<TF>(f->wt), nx, kc, 0, P->ktot, P->jtot, {}, \
-                          mp<TF>(P->rk_u), mp<TF>(P->rk_v), mp<TF>(P->rk_w), TF(P->rk_cA), TF(P->rk_cB), TF(P->rk_dt)}; \
-                      if (P->itot <= LDS_XS) { if (P->rk_on) hipLaunchKernelGGL((lds_fft::pres_ifftx_out_kernel<TF, LDS_RG, LDS_XS, 0, false, true>), xgrid, dim3(P->itot), lds_bytes_x(P, 9), st, a); \
-                                               else          hipLaunchKernelGGL((lds_fft::pres_ifftx_out_kernel<TF, LDS_RG, LDS_XS, 0>), xgrid, dim3(P->itot), lds_bytes_x(P, 9), st, a); } \
-                      MHH_FOR_NX_T(M, TF) return MHH_OK; }()
-        if (int e = MHH_DISPATCH(g, CALL)) return e;
-#undef CALL
-#undef M
-    }
+    const bool f64 = (P->dtype == MHH_F64);
+    int e;
+    if (P->order == 4) e = f64 ? pres4_lds_stage<double>(P, g, f, dt, stage, xgrid, kc, st) : pres4_lds_stage<float>(P, g, f, dt, stage, xgrid, kc, st);
+    else               e = f64 ? pres2_lds_stage<double>(P, g, f, dt, stage, xgrid, kc, st) : pres2_lds_stage<float>(P, g, f, dt, stage, xgrid, kc, st);
+    if (e) return e;
     MHH_LAUNCH_CHECK();
     return MHH_OK;
 }
 // ---- the x stages for a slab rank (k_slab.hip): the same kernels on the rank's own rows, reading / writing the all-to-all
 // buffers of the x <-> y transposes directly (pres_lds.h, LdsSlab). Internal to the library (pres_lds_slab.h).
-namespace mhh
-{
 template<class TF>
-static int lds_slab_kernels_ready(int itot, bool& usable)
+static int lds_slab_kernels_ready(const mhh_grid* g, bool& usable)
 {
-    const int nx = ilog2(itot/2);
-    const void* k[2] = {nullptr, nullptr};
-    if (itot <= LDS_XS) { k[0] = reinterpret_cast<const void*>(&lds_fft::pres_in_fftx_kernel<TF, LDS_RG, LDS_XS, 0, true>); k[1] = reinterpret_cast<const void*>(&lds_fft::pres_ifftx_out_kernel<TF, LDS_RG, LDS_XS, 0, true>); }
-#define M(N) if (nx == N) { k[0] = reinterpret_cast<const void*>(&lds_fft::pres_in_fftx_kernel<TF, LDS_RG, (2 << N), N, true>); k[1] = reinterpret_cast<const void*>(&lds_fft::pres_ifftx_out_kernel<TF, LDS_RG, (2 << N), N, true>); }
-    MHH_FOR_NX(M)
-#undef M
-    usable = true;
-    for (int n=0; n<2; ++n)
-    {
-        if (!k[n]) { usable = false; return MHH_OK; }
-        bool u = false;
-        if (int e = lds_kernel_ready(k[n], u)) return e;
-        usable = usable && u;
-    }
-    return MHH_OK;
+    const void* k[4] = {nullptr, nullptr, nullptr, nullptr};
+    lds_x_variant(g->itot, [&](auto NX) { k[0] = kfn(&lds_fft::pres_in_fftx_kernel<TF, LDS_RG, lds_bt_x(NX), NX, true>);
+                                           k[1] = kfn(&lds_fft::pres_ifftx_out_kernel<TF, LDS_RG, lds_bt_x(NX), NX, true>); });
+    lds_y_variant<TF>(g->jtot, [&](auto NY) { k[2] = kfn(&lds_fft::slab_yfft_kernel<TF, lds_bt_y(NY), NY, true>);
+                                              k[3] = kfn(&lds_fft::slab_yfft_kernel<TF, lds_bt_y(NY), NY, false>); });
+    return lds_kernels_ready({k[0], k[1], k[2], k[3]}, usable);
 }
-template<class TF>
-static int lds_slab_y_ready(int jtot, bool& usable)
+int mhh::lds_slab_usable(const mhh_grid* g)
 {
-    const int ny = ilog2(jtot);
-    const void* k[2] = {nullptr, nullptr};
-    if (jtot <= LDS_YS) { k[0] = reinterpret_cast<const void*>(&lds_fft::slab_yfft_kernel<TF, LDS_YS, 0, true>); k[1] = reinterpret_cast<const void*>(&lds_fft::slab_yfft_kernel<TF, LDS_YS, 0, false>); }
-#define M(N) if (ny == N) { if constexpr (lds_has_ny<TF, N>()) { k[0] = reinterpret_cast<const void*>(&lds_fft::slab_yfft_kernel<TF, (1 << N), N, true>); k[1] = reinterpret_cast<const void*>(&lds_fft::slab_yfft_kernel<TF, (1 << N), N, false>); } }
-    MHH_FOR_NY(M)
-#undef M
-    usable = true;
-    for (int n=0; n<2; ++n)
-    {
-        if (!k[n]) { usable = false; return MHH_OK; }
-        bool u = false;
-        if (int e = lds_kernel_ready(k[n], u)) return e;
-        usable = usable && u;
-    }
-    return MHH_OK;
-}
-static size_t lds_slab_bytes_x(int itot, size_t esz, int rows) { return ((size_t)rows*(itot/2 + 2) + itot) * 2*esz + (rows == 9 ? (size_t)8*itot*esz : 0); }
-// 1 if a rank of this grid can run the x stages in LDS: power-of-two itot with an instantiation, rows in whole strips of eight
-int lds_slab_usable(const mhh_grid* g)
-{
-    if (!(is_pow2(g->itot) && g->itot >= 16 && g->itot <= 1024 && g->jmax % 8 == 0 && g->jmax >= 8)) return 0;
-    if (lds_slab_bytes_x(g->itot, g->dtype == MHH_F64 ? 8 : 4, 9) > 160*1024 || g->igc > g->itot) return 0;
-    if ((long long)g->icells*g->jcells*g->kcells >= (1ll << 31)) return 0;
-    if (!(is_pow2(g->jtot) && g->jtot >= 8 && g->jtot <= 1024 && g->jtot % g->jmax == 0)) return 0;
-    if (((size_t)8*g->jtot + g->jtot) * 2*(g->dtype == MHH_F64 ? 8 : 4) > 160*1024) return 0;
-    bool usable = false, usable_y = false;
-    int e = (g->dtype == MHH_F64) ? lds_slab_kernels_ready<double>(g->itot, usable) : lds_slab_kernels_ready<float>(g->itot, usable);
-    if (e == MHH_OK) e = (g->dtype == MHH_F64) ? lds_slab_y_ready<double>(g->jtot, usable_y) : lds_slab_y_ready<float>(g->jtot, usable_y);
-    return (e == MHH_OK && usable && usable_y) ? 1 : 0;
-}
-// exp(-2 pi i m / itot), m < itot, on the device (the caller frees it)
-int lds_slab_twiddles(const mhh_grid* g, void** tx)
-{
-    const double pi = std::acos(-1.);
-    const int n = g->itot;
-    auto fill = [&](auto* t) { for (int m=0; m<n; ++m) { t[2*m] = std::cos(2.*pi*m/n); t[2*m+1] = -std::sin(2.*pi*m/n); }
-                               t[0] = 1; t[1] = 0; t[n] = -1; t[n+1] = 0; if (n >= 4) { t[n/2] = 0; t[n/2+1] = -1; t[3*n/2] = 0; t[3*n/2+1] = 1; } };
-    if (g->dtype == MHH_F64) { std::vector<double> t(2*(size_t)n); fill(t.data()); return upload(tx, t); }
-    std::vector<float> t(2*(size_t)n); fill(t.data()); return upload(tx, t);
-}
-// exp(-2 pi i m / jtot), m < jtot
-int lds_slab_twiddles_y(const mhh_grid* g, void** ty)
-{
-    const double pi = std::acos(-1.);
-    const int n = g->jtot;
-    auto fill = [&](auto* t) { for (int m=0; m<n; ++m) { t[2*m] = std::cos(2.*pi*m/n); t[2*m+1] = -std::sin(2.*pi*m/n); }
-                               t[0] = 1; t[1] = 0; t[n] = -1; t[n+1] = 0; if (n >= 4) { t[n/2] = 0; t[n/2+1] = -1; t[3*n/2] = 0; t[3*n/2+1] = 1; } };
-    if (g->dtype == MHH_F64) { std::vector<double> t(2*(size_t)n); fill(t.data()); return upload(ty, t); }
-    std::vector<float> t(2*(size_t)n); fill(t.data()); return upload(ty, t);
+    if (!lds_eligible(g, 2) || g->jmax % 8 != 0 || g->jmax < 8 || g->jtot % g->jmax != 0) return 0;
+    bool usable = false;
+    const int e = (g->dtype == MHH_F64) ? lds_slab_kernels_ready<double>(g, usable) : lds_slab_kernels_ready<float>(g, usable);
+    return (e == MHH_OK && usable) ? 1 : 0;
 }
 // the transforms along y of the levels [kbeg, kend): forward from the receive buffer into specy[k][kxl][ky], or back from specy into the send buffer
-int lds_slab_yfft(const mhh_grid* g, bool fwd, void* xbuf, void* specy, const void* ty, int nxb, int npy, int ks, int kbeg, int kend, hipStream_t st)
+int mhh::lds_slab_yfft(const mhh_grid* g, bool fwd, void* xbuf, void* specy, const void* ty, int nxb, int npy, int ks, int kbeg, int kend, hipStream_t st)
 {
     const int ny = ilog2(g->jtot);
     const dim3 grid((unsigned)nxb, (unsigned)((kend - kbeg + 7)/8)), block((unsigned)g->jtot);
-    const size_t lds = ((size_t)8*g->jtot + g->jtot) * 2*(g->dtype == MHH_F64 ? 8 : 4);
-#define M(TF, N) else if (ny == N) { if constexpr (lds_has_ny<TF, N>()) { \
-                     if (fwd) hipLaunchKernelGGL((lds_fft::slab_yfft_kernel<TF, (1 << N), N, true>), grid, block, lds, st, a); \
-                     else     hipLaunchKernelGGL((lds_fft::slab_yfft_kernel<TF, (1 << N), N, false>), grid, block, lds, st, a); } }
-#define CALL(TF) [&]{ lds_fft::SlabYfft<TF> a{static_cast<C2<TF>*>(xbuf), static_cast<C2<TF>*>(specy), static_cast<const C2<TF>*>(ty), g->jtot, g->jmax, ny, nxb, kbeg, kend, {nxb, npy, ks}}; \
-                      if (g->jtot <= LDS_YS) { if (fwd) hipLaunchKernelGGL((lds_fft::slab_yfft_kernel<TF, LDS_YS, 0, true>), grid, block, lds, st, a); \
-                                               else     hipLaunchKernelGGL((lds_fft::slab_yfft_kernel<TF, LDS_YS, 0, false>), grid, block, lds, st, a); } \
-                      MHH_FOR_NY_T(M, TF) return MHH_OK; }()
-    if (int e = MHH_DISPATCH(g, CALL)) return e;
+    const size_t lds = lds_bytes_y(g->jtot, g->dtype == MHH_F64 ? 8 : 4);
+#define CALL(TF) [&]{ const lds_fft::SlabYfft<TF> a{static_cast<C2<TF>*>(xbuf), static_cast<C2<TF>*>(specy), static_cast<const C2<TF>*>(ty), g->jtot, g->jmax, ny, nxb, kbeg, kend, {nxb, npy, ks}}; \
+                      lds_y_variant<TF>(g->jtot, [&](auto NY) { \
+                          if (fwd) hipLaunchKernelGGL((lds_fft::slab_yfft_kernel<TF, lds_bt_y(NY), NY, true>), grid, block, lds, st, a); \
+                          else     hipLaunchKernelGGL((lds_fft::slab_yfft_kernel<TF, lds_bt_y(NY), NY, false>), grid, block, lds, st, a); }); }()
+    MHH_DISPATCH(g, CALL);
 #undef CALL
-#undef M
     MHH_LAUNCH_CHECK();
     return MHH_OK;
 }
-static int lds_slab_kc(const mhh_grid* g, int nlev)
-{
-    const char* e = getenv("MHH_PRES_LDS_KC");
-    int kc = e ? atoi(e) : (int)(((long long)nlev * (g->jmax/8)) / 2048);
-    if (!e) kc = kc < 4 ? 4 : (kc > 32 ? 32 : kc);
-    return kc < 1 ? 1 : (kc > nlev ? nlev : kc);
-}
 // Pres_2::input + the transform along x of the levels [kbeg, kend) into the send buffer of the x -> y transpose
-int lds_slab_stage_in(const mhh_grid* g, const mhh_fields* f, double dt, void* xbuf, const void* tx, int nxb, int npy, int ks, int kbeg, int kend, hipStream_t st)
+int mhh::lds_slab_stage_in(const mhh_grid* g, const mhh_fields* f, double dt, void* xbuf, const void* tx, int nxb, int npy, int ks, int kbeg, int kend, hipStream_t st)
 {
     if (int e = pres_input_halos(g, 2, f, st)) return e;
-    const int nx = ilog2(g->itot/2), kc = lds_slab_kc(g, kend - kbeg);
+    const int nx = ilog2(g->itot/2), kc = lds_levels_per_block(kend - kbeg, g->jmax);
     const dim3 xgrid((unsigned)(g->jmax/8) * (unsigned)((kend - kbeg + kc-1)/kc));
-    const size_t lds = lds_slab_bytes_x(g->itot, g->dtype == MHH_F64 ? 8 : 4, 8);
-#define M(TF, N) else if (nx == N) hipLaunchKernelGGL((lds_fft::pres_in_fftx_kernel<TF, LDS_RG, (2 << N), N, true>), xgrid, dim3(g->itot), lds, st, a);
-#define CALL(TF) [&]{ lds_fft::PresLdsIn<TF> a{make_grid<TF>(g), cp<TF>(f->u), cp<TF>(f->v), cp<TF>(f->w), cp<TF>(f->ut), cp<TF>(f->vt), cp<TF>(f->wt), \
+    const size_t lds = lds_bytes_x(g->itot, g->dtype == MHH_F64 ? 8 : 4, 2, 8);
+#define CALL(TF) [&]{ const lds_fft::PresLdsIn<TF> a{make_grid<TF>(g), cp<TF>(f->u), cp<TF>(f->v), cp<TF>(f->w), cp<TF>(f->ut), cp<TF>(f->vt), cp<TF>(f->wt), \
                           cp<TF>(f->rhoref), cp<TF>(f->rhorefh), TF(1.)/TF(dt), static_cast<C2<TF>*>(xbuf), static_cast<const C2<TF>*>(tx), nx, kc, kbeg, kend, g->jmax, {nxb, npy, ks}}; \
-                      if (g->itot <= LDS_XS) hipLaunchKernelGGL((lds_fft::pres_in_fftx_kernel<TF, LDS_RG, LDS_XS, 0, true>), xgrid, dim3(g->itot), lds, st, a); \
-                      MHH_FOR_NX_T(M, TF) return MHH_OK; }()
-    if (int e = MHH_DISPATCH(g, CALL)) return e;
+                      lds_x_variant(g->itot, [&](auto NX) { \
+                          hipLaunchKernelGGL((lds_fft::pres_in_fftx_kernel<TF, LDS_RG, lds_bt_x(NX), NX, true>), xgrid, dim3(g->itot), lds, st, a); }); }()
+    MHH_DISPATCH(g, CALL);
 #undef CALL
-#undef M
     MHH_LAUNCH_CHECK();
     return MHH_OK;
 }
 // the transform back along x of the levels [kbeg, kend) from the receive buffer of the y -> x transpose + p + Pres_2::output
-int lds_slab_stage_out(const mhh_grid* g, const mhh_fields* f, const void* xbuf, const void* tx, int nxb, int npy, int ks, int kbeg, int kend, hipStream_t st)
+int mhh::lds_slab_stage_out(const mhh_grid* g, const mhh_fields* f, const void* xbuf, const void* tx, int nxb, int npy, int ks, int kbeg, int kend, hipStream_t st)
 {
-    const int nx = ilog2(g->itot/2), kc = lds_slab_kc(g, kend - kbeg);
+    const int nx = ilog2(g->itot/2), kc = lds_levels_per_block(kend - kbeg, g->jmax);
     const dim3 xgrid((unsigned)(g->jmax/8) * (unsigned)((kend - kbeg + kc-1)/kc));
-    const size_t lds = lds_slab_bytes_x(g->itot, g->dtype == MHH_F64 ? 8 : 4, 9);
-#define M(TF, N) else if (nx == N) hipLaunchKernelGGL((lds_fft::pres_ifftx_out_kernel<TF, LDS_RG, (2 << N), N, true>), xgrid, dim3(g->itot), lds, st, a);
-#define CALL(TF) [&]{ lds_fft::PresLdsOut<TF> a{make_grid<TF>(g), static_cast<const C2<TF>*>(xbuf), static_cast<const C2<TF>*>(tx), \
+    const size_t lds = lds_bytes_x(g->itot, g->dtype == MHH_F64 ? 8 : 4, 2, 9);
+#define CALL(TF) [&]{ const lds_fft::PresLdsOut<TF> a{make_grid<TF>(g), static_cast<const C2<TF>*>(xbuf), static_cast<const C2<TF>*>(tx), \
                           mp<TF>(f->p), mp<TF>(f->ut), mp<TF>(f->vt), mp<TF>(f->wt), nx, kc, kbeg, kend, g->jmax, {nxb, npy, ks}, nullptr, nullptr, nullptr, TF(0), TF(0), TF(0)}; \
-                      if (g->itot <= LDS_XS) hipLaunchKernelGGL((lds_fft::pres_ifftx_out_kernel<TF, LDS_RG, LDS_XS, 0, true>), xgrid, dim3(g->itot), lds, st, a); \
-                      MHH_FOR_NX_T(M, TF) return MHH_OK; }()
-    if (int e = MHH_DISPATCH(g, CALL)) return e;
+                      lds_x_variant(g->itot, [&](auto NX) { \
+                          hipLaunchKernelGGL((lds_fft::pres_ifftx_out_kernel<TF, LDS_RG, lds_bt_x(NX), NX, true>), xgrid, dim3(g->itot), lds, st, a); }); }()
+    MHH_DISPATCH(g, CALL);
 #undef CALL
-#undef M
     MHH_LAUNCH_CHECK();
     return MHH_OK;
 }
-} // namespace mhh
 
 // 1 if the plan can run the LDS-transform form (mhh_pres_exec takes it by itself on large grids, see there)
 MHH_API int mhh_pres_plan_has_lds_form(const mhh_pres_plan* P) { return (P && P->lds_ok) ? 1 : 0; }
 // the spectral array between the stages (tests): S[k][kx][j], complex
 MHH_API void* mhh_pres_plan_spectral(mhh_pres_plan* P) { return P ? P->spec : nullptr; }
 
-// the form mhh_pres_exec takes for this plan: 0 = staged (rocFFT), 1 = transforms in LDS
-MHH_API int mhh_pres_exec_form(const mhh_pres_plan* P)
+// The forms of Pres::exec: the three kernels with the transforms in LDS; the rocFFT transforms with unpack + output in one kernel;
+// the same with unpack and output as two kernels (MHH_PRES_UNPACK_OUT=0, A/B)
+enum PresRoute { PRES_LDS, PRES_UNPACK_OUT, PRES_STAGED };
+// the form mhh_pres_exec takes for this plan, from the switches as they are at the call
+static PresRoute pres_route(const mhh_pres_plan* P)
 {
-    if (!P || !P->lds_ok) return 0;
-    const char* le = getenv("MHH_PRES_LDS");
-    // measured on MI355X with every row length in its own instantiation (profiles/r3_pres_forms.md; ms staged / LDS form):
+    // The LDS form pays where the arrays are far larger than the caches and there is a block per CU for the y stage. Measured on
+    // MI355X with every row length in its own instantiation (profiles/r3_pres_forms.md; ms staged / LDS form):
     // 128^3 0.137 / 0.184, 256^3 0.742 / 0.688, 256x256x512 1.55 / 1.43, 512x256x256 1.38 / 1.16, 512x512x128 1.44 / 1.12,
     // 512^3 5.80 / 4.05, 1024x512x256 6.00 / 4.60; fp32 256^3 0.472 / 0.464, 512^3 3.68 / 2.42, 1024x1024x256 7.81 / 4.61:
-    // the LDS form from 2^24 cells on (below that the arrays sit in the Infinity Cache and the staged passes are cheap)
-    const bool lds_large = (long long)P->itot*P->jtot*P->ktot >= (1ll << 24);
-    return (le ? !strcmp(le, "1") : lds_large) ? 1 : 0;
-}
-MHH_API int mhh_pres_exec(mhh_pres_plan* P, const mhh_grid* g, const mhh_fields* f, double dt, void* stream)
-{
-    MHH_REQUIRE(P != nullptr, "plan");
-    // Opt-in (MHH_PRES_FUSED=1). Measured on MI355X: identical bits, but the transforms run the heavy producer through an
-    // indirect call per element and lose more than the two saved array passes give back (512^3: 15.7 ms vs 14.7 ms per step;
-    // 512x256x256 pres_4: 4.05 vs 3.42 ms), so the staged form stays the default.
-    // The LDS form pays where the arrays are far larger than the caches and there is a block per CU for the y stage (measured on
-    // MI355X: 512^3 fp64 5.8 -> 5.0 ms, 1024 x 1024 x 256 fp32 7.9 -> 5.0 ms; 256^3 0.78 -> 0.92 ms, so not there).
+    // the LDS form from 2^24 cells on (below that the arrays sit in the Infinity Cache and the staged passes are cheap).
     // MHH_PRES_LDS=0 / 1: never / wherever the plan has the form.
-    if (mhh_pres_exec_form(P) == 1)
+    const bool lds_large = (long long)P->itot*P->jtot*P->ktot >= (1ll << 24);
+    if (P->lds_ok && !env_is("MHH_PRES_LDS", "0") && (lds_large || env_is("MHH_PRES_LDS", "1"))) return PRES_LDS;
+    return env_is("MHH_PRES_UNPACK_OUT", "0") ? PRES_STAGED : PRES_UNPACK_OUT;
+}
+// the form mhh_pres_exec takes for this plan: 0 = staged (rocFFT), 1 = transforms in LDS
+MHH_API int mhh_pres_exec_form(const mhh_pres_plan* P) { return (P && pres_route(P) == PRES_LDS) ? 1 : 0; }
+
+// unpack (src/pres_2.cxx:333-362, src/pres_4.cxx:481-528) and output in one kernel, from the packed solution
+template<class TF>
+static void pres_unpack_output(const mhh_pres_plan* P, const mhh_grid* g, const mhh_fields* f, hipStream_t st)
+{
+    const GridDev<TF> gd = make_grid<TF>(g);
+    const dim3 ug((g->icells*g->jcells + 255)/256, 1, g->kmax + (P->order == 2 ? 1 : 4));    // + the ghost levels of p
+    auto launch = [&](auto POW2) {
+        if (P->order == 2)
+            hipLaunchKernelGGL((unpack_out2_kernel<POW2, TF>), ug, dim3(256), 0, st, mp<TF>(f->p), cp<TF>(P->packed), mp<TF>(f->ut), mp<TF>(f->vt), mp<TF>(f->wt), gd.dzhi,
+                               gd.dxi_t, gd.dyi_t, g->itot, g->jtot, g->kmax, g->igc, g->jgc, g->kgc, g->icells, g->jcells,
+                               (P->rk_on ? mp<TF>(P->rk_u) : nullptr), mp<TF>(P->rk_v), mp<TF>(P->rk_w), TF(P->rk_cA), TF(P->rk_cB), TF(P->rk_dt));
+        else
+            hipLaunchKernelGGL((unpack_out4_kernel<POW2, TF>), ug, dim3(256), 0, st, mp<TF>(f->p), cp<TF>(P->packed), mp<TF>(f->ut), mp<TF>(f->vt), mp<TF>(f->wt), gd.dzhi4,
+                               gd.dxi_d, gd.dyi_d, (int)gd.dim3, g->itot, g->jtot, g->kmax, g->igc, g->jgc, g->kgc, g->icells, g->jcells); };
+    if (is_pow2(g->itot) && is_pow2(g->jtot)) launch(std::true_type{});
+    else                                      launch(std::false_type{});
+}
+static int pres_exec(mhh_pres_plan* P, const mhh_grid* g, const mhh_fields* f, double dt, PresRoute route, void* stream)
+{
+    if (route == PRES_LDS)
     {
         for (int stage=1; stage<=3; ++stage) if (int e = mhh_pres_lds_stage(P, g, f, dt, stage, stream)) return e;
         return MHH_OK;
     }
-    const char* env = getenv("MHH_PRES_FUSED");
-    if (!P->cb_ready || !(env && !strcmp(env, "1")))
+    if (int e = mhh_pres_input(P, g, f, dt, nullptr, stream)) return e;
+    if (route == PRES_STAGED)
     {
-        if (int e = mhh_pres_input(P, g, f, dt, nullptr, stream)) return e;
-        const char* uo = getenv("MHH_PRES_UNPACK_OUT");                       // "0": unpack and output as two kernels (A/B)
-        if (P->order == 2 && !(uo && !strcmp(uo, "0")))
-        {
-            if (int e = check_grid(g)) return e;
-            MHH_REQUIRE(f && f->p && f->ut && f->vt && f->wt, "null field");
-            MHH_REQUIRE(P->dtype == g->dtype && P->itot == g->itot && P->jtot == g->jtot && P->ktot == g->ktot, "plan/grid mismatch");
-            hipStream_t st = as_stream(stream);
-            if (int e = pres_spectral(P, g, P->packed, st)) return e;
-            dim3 ug((g->icells*g->jcells + 255)/256, 1, g->kmax + 1);
-            const bool pow2 = is_pow2(g->itot) && is_pow2(g->jtot);
-#define RKARGS(TF) (P->rk_on ? mp<TF>(P->rk_u) : nullptr), mp<TF>(P->rk_v), mp<TF>(P->rk_w), TF(P->rk_cA), TF(P->rk_cB), TF(P->rk_dt)
-#define CALL(TF) [&]{ const GridDev<TF> gd = make_grid<TF>(g); \
-                if (pow2) hipLaunchKernelGGL((unpack_out2_kernel<true, TF>), ug, dim3(256), 0, st, mp<TF>(f->p), cp<TF>(P->packed), mp<TF>(f->ut), mp<TF>(f->vt), mp<TF>(f->wt), gd.dzhi, \
-                                   gd.dxi_t, gd.dyi_t, g->itot, g->jtot, g->kmax, g->igc, g->jgc, g->kgc, g->icells, g->jcells, RKARGS(TF)); \
-                else hipLaunchKernelGGL((unpack_out2_kernel<false, TF>), ug, dim3(256), 0, st, mp<TF>(f->p), cp<TF>(P->packed), mp<TF>(f->ut), mp<TF>(f->vt), mp<TF>(f->wt), gd.dzhi, \
-                                   gd.dxi_t, gd.dyi_t, g->itot, g->jtot, g->kmax, g->igc, g->jgc, g->kgc, g->icells, g->jcells, RKARGS(TF)); return MHH_OK; }()
-            if (int e = MHH_DISPATCH(g, CALL)) return e;
-#undef CALL
-            MHH_LAUNCH_CHECK();
-            return MHH_OK;
-        }
-        if (P->order == 4 && !(uo && !strcmp(uo, "0")))
-        {
-            if (int e = check_grid(g)) return e;
-            MHH_REQUIRE(f && f->p && f->ut && f->vt && f->wt, "null field");
-            MHH_REQUIRE(P->dtype == g->dtype && P->itot == g->itot && P->jtot == g->jtot && P->ktot == g->ktot, "plan/grid mismatch");
-            hipStream_t st = as_stream(stream);
-            if (int e = pres_spectral(P, g, P->packed, st)) return e;
-            dim3 ug((g->icells*g->jcells + 255)/256, 1, g->kmax + 4);
-            const bool pow2 = is_pow2(g->itot) && is_pow2(g->jtot);
-#define CALL(TF) [&]{ const GridDev<TF> gd = make_grid<TF>(g); \
-                if (pow2) hipLaunchKernelGGL((unpack_out4_kernel<true, TF>), ug, dim3(256), 0, st, mp<TF>(f->p), cp<TF>(P->packed), mp<TF>(f->ut), mp<TF>(f->vt), mp<TF>(f->wt), gd.dzhi4, \
-                                   gd.dxi_d, gd.dyi_d, (int)gd.dim3, g->itot, g->jtot, g->kmax, g->igc, g->jgc, g->kgc, g->icells, g->jcells); \
-                else hipLaunchKernelGGL((unpack_out4_kernel<false, TF>), ug, dim3(256), 0, st, mp<TF>(f->p), cp<TF>(P->packed), mp<TF>(f->ut), mp<TF>(f->vt), mp<TF>(f->wt), gd.dzhi4, \
-                                   gd.dxi_d, gd.dyi_d, (int)gd.dim3, g->itot, g->jtot, g->kmax, g->igc, g->jgc, g->kgc, g->icells, g->jcells); return MHH_OK; }()
-            if (int e = MHH_DISPATCH(g, CALL)) return e;
-#undef CALL
-            MHH_LAUNCH_CHECK();
-            return MHH_OK;
-        }
         if (int e = mhh_pres_solve(P, g, f, nullptr, stream)) return e;
         return mhh_pres_output(P, g, f, stream);
     }
     if (int e = check_grid(g)) return e;
-    MHH_REQUIRE(f && f->p && f->u && f->v && f->w && f->ut && f->vt && f->wt, "null field");
+    MHH_REQUIRE(f && f->p && f->ut && f->vt && f->wt, "null field");
     MHH_REQUIRE(P->dtype == g->dtype && P->itot == g->itot && P->jtot == g->jtot && P->ktot == g->ktot, "plan/grid mismatch");
-    MHH_REQUIRE(dt > 0., "dt");
-    MHH_REQUIRE(P->order == 4 || (f->rhoref && f->rhorefh), "rhoref");
-    MHH_REQUIRE((unsigned long long)g->itot*g->jtot*g->ktot < (1ull << 31), "fused form indexes the packed cells with 32 bits");
-    if (int e = pres_input_halos(g, P->order, f, stream)) return e;
-    if (int e = (g->dtype == MHH_F64) ? pres_exec_fused<double>(P, g, f, dt, as_stream(stream)) : pres_exec_fused<float>(P, g, f, dt, as_stream(stream))) return e;
-    return mhh_pres_output(P, g, f, stream);
+    hipStream_t st = as_stream(stream);
+    if (int e = pres_spectral(P, g, P->packed, st)) return e;
+    if (g->dtype == MHH_F64) pres_unpack_output<double>(P, g, f, st);
+    else                     pres_unpack_output<float>(P, g, f, st);
+    MHH_LAUNCH_CHECK();
+    return MHH_OK;
+}
+MHH_API int mhh_pres_exec(mhh_pres_plan* P, const mhh_grid* g, const mhh_fields* f, double dt, void* stream)
+{
+    MHH_REQUIRE(P != nullptr, "plan");
+    return pres_exec(P, g, f, dt, pres_route(P), stream);
 }
 
 // Pres::exec followed by the Runge-Kutta sub-step of u, v, w (timeloop.exec() in Model::exec, src/model.cxx:411,484;
 // src/timeloop.cxx:250-334): where the corrected tendencies are stored by a pres_2 kernel of this library (the LDS form's last stage,
-// the staged form's unpack + output kernel) the sub-step is applied there, in registers; otherwise -- pres_4, the two-kernel and
-// callback forms, the last sub-step of a step (the tendency reset covers the ghost cells) -- Pres::exec is followed by three
+// the staged form's unpack + output kernel) the sub-step is applied there, in registers; otherwise -- pres_4, the two-kernel form,
+// the last sub-step of a step (the tendency reset covers the ghost cells), MHH_PRES_RK_FUSED=0 -- Pres::exec is followed by three
 // mhh_rk_substep calls. Either way the bits of mhh_pres_exec + mhh_rk_substep x 3. Scalars keep their own mhh_rk_substep call.
 MHH_API int mhh_pres_exec_rk(mhh_pres_plan* P, const mhh_grid* g, const mhh_fields* f, double dt, int rkorder, int substep, double rkdt, void* stream)
 {
     MHH_REQUIRE(P != nullptr && f != nullptr && f->u && f->v && f->w && f->ut && f->vt && f->wt, "plan, fields");
     double cA = 0, cB = 0; bool reset = false;
     MHH_REQUIRE(rk_coefficients(rkorder, substep, cA, cB, reset), "rkorder 3 or 4, substep in range");
-    const char* uo = getenv("MHH_PRES_UNPACK_OUT"); const char* fe = getenv("MHH_PRES_FUSED"); const char* rke = getenv("MHH_PRES_RK_FUSED");
-    const bool one_kernel = mhh_pres_exec_form(P) == 1 || (P->order == 2 && !(uo && !strcmp(uo, "0")) && !(P->cb_ready && fe && !strcmp(fe, "1")));
-    const bool fuse = !reset && P->order == 2 && one_kernel && !(rke && !strcmp(rke, "0"));
-    if (fuse)
+    const PresRoute route = pres_route(P);
+    if (!reset && P->order == 2 && route != PRES_STAGED && !env_is("MHH_PRES_RK_FUSED", "0"))
     {
         P->rk_on = true; P->rk_cA = cA; P->rk_cB = cB; P->rk_dt = rkdt; P->rk_u = f->u; P->rk_v = f->v; P->rk_w = f->w;
-        const int e = mhh_pres_exec(P, g, f, dt, stream);
+        const int e = pres_exec(P, g, f, dt, route, stream);
         P->rk_on = false;
         return e;
     }
-    if (int e = mhh_pres_exec(P, g, f, dt, stream)) return e;
+    if (int e = pres_exec(P, g, f, dt, route, stream)) return e;
     if (int e = mhh_rk_substep(g, rkorder, substep, rkdt, f->u, f->ut, stream)) return e;
     if (int e = mhh_rk_substep(g, rkorder, substep, rkdt, f->v, f->vt, stream)) return e;
     return mhh_rk_substep(g, rkorder, substep, rkdt, f->w, f->wt, stream);

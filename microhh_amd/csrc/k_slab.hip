@@ -6,17 +6,11 @@
 // Reference semantics: Boundary_cyclic::exec's MPI path (src/boundary_cyclic.cxx:116-176) and the FFT/solve
 // sequence of src/fft.cxx:451-583 with npx = 1, where only Transpose::exec_xy / exec_yx move data
 // (src/transpose.cxx:170-219) and Pres_2::solve swaps the mode indices (src/pres_2.cxx:297-299).
-#include <vector>
-#include <rocfft/rocfft.h>
 #include "fft_lifetime.h"
-#include "k_common.h"
 #include "pres_lds_slab.h"
 #include "pres4_bands.h"
 
 using namespace mhh;
-
-#define MHH_FFT_TRY(expr) do { rocfft_status s_ = (expr); if (s_ != rocfft_status_success) { \
-    mhh::set_error("FFT error: %s returned %d (%s:%d)", #expr, (int)s_, __FILE__, __LINE__); return MHH_EFFT; } } while (0)
 
 // =======================================================================================================
 // North-south halo: buffers are [field][k][jg][i] with all icells (x ghosts included, so corners are right
@@ -97,8 +91,6 @@ MHH_API unsigned long long mhh_halo_buffer_elems(const mhh_grid* g, int nf)
 //   xbuf  [q][k][jl][kxl]        all-to-all buffer, q = destination / source rank, kx = q*nxb + kxl (zero padded)
 //   specy [k][kxl][j]            after the exchange, j over the full jtot, unit stride for the y transform
 // =======================================================================================================
-template<class TF> struct alignas(2*sizeof(TF)) C2 { TF x, y; };   // naturally aligned: one 16-byte access per fp64 number
-
 struct mhh_pres_slab_plan
 {
     int order = 2, dtype = 0, itot = 0, jtot = 0, ktot = 0, jmax = 0, npy = 1, rank = 0, nxh = 0, nxb = 0;
@@ -117,13 +109,6 @@ struct mhh_pres_slab_plan
     void* tx_lds = nullptr; void* ty_lds = nullptr;
 };
 
-template<class TF>
-static int up(void** dst, const std::vector<TF>& v)
-{
-    MHH_HIP_TRY(hipMalloc(dst, v.size()*sizeof(TF)));
-    MHH_HIP_TRY(hipMemcpy(*dst, v.data(), v.size()*sizeof(TF), hipMemcpyHostToDevice));
-    return MHH_OK;
-}
 template<class TF>
 static int slab_tables(mhh_pres_slab_plan* P, const mhh_grid* g, const void* hdz, const void* hdzhi, const void* hrho, const void* hrhoh)
 {
@@ -144,12 +129,12 @@ static int slab_tables(mhh_pres_slab_plan* P, const mhh_grid* g, const void* hdz
         c[k] = dz[k+kgc] * rhoh[k+kgc+1]*dzhi[k+kgc+1];
         dzk[k] = dz[k+kgc]; rk[k] = rho[k+kgc];
     }
-    if (int e = up(&P->bmati, bi)) return e;
-    if (int e = up(&P->bmatj, bj)) return e;
-    if (int e = up(&P->a, a)) return e;
-    if (int e = up(&P->c, c)) return e;
-    if (int e = up(&P->dz, dzk)) return e;
-    return up(&P->rhoref, rk);
+    if (int e = upload(&P->bmati, bi)) return e;
+    if (int e = upload(&P->bmatj, bj)) return e;
+    if (int e = upload(&P->a, a)) return e;
+    if (int e = upload(&P->c, c)) return e;
+    if (int e = upload(&P->dz, dzk)) return e;
+    return upload(&P->rhoref, rk);
 }
 // Pres_4::set_values, src/pres_4.cxx:179-252: the single-GPU plan's own host tables (pres4_bands.h)
 template<class TF>
@@ -158,9 +143,9 @@ static int slab_tables4(mhh_pres_slab_plan* P, const mhh_grid* g, const void* hd
     std::vector<TF> bi, bj, m[7];
     host_bmat<TF>(4, g, bi, bj);
     host_pres4_bands<TF>(g, cp<TF>(hdzi4), cp<TF>(hdzhi4), m);
-    if (int e = up(&P->bmati, bi)) return e;
-    if (int e = up(&P->bmatj, bj)) return e;
-    for (int n=0; n<7; ++n) if (int e = up(&P->m[n], m[n])) return e;
+    if (int e = upload(&P->bmati, bi)) return e;
+    if (int e = upload(&P->bmatj, bj)) return e;
+    for (int n=0; n<7; ++n) if (int e = upload(&P->m[n], m[n])) return e;
     return MHH_OK;
 }
 
@@ -239,7 +224,7 @@ MHH_API int mhh_pres_slab_plan_create_order(const mhh_grid* g, int order, const 
         }
     }
     if (!e) e = slab_factor(P);
-    if (!e && order == 2 && lds_slab_usable(g)) { e = lds_slab_twiddles(g, &P->tx_lds); if (!e) e = lds_slab_twiddles_y(g, &P->ty_lds); }      // the transforms in LDS
+    if (!e && order == 2 && lds_slab_usable(g)) { e = lds_twiddles(g->itot, g->dtype, &P->tx_lds); if (!e) e = lds_twiddles(g->jtot, g->dtype, &P->ty_lds); }      // the transforms in LDS
     if (e) { mhh_pres_slab_plan_destroy(P); return e; }
     *out = P;
     return MHH_OK;
@@ -929,8 +914,8 @@ MHH_API int mhh_pres_bwd_x_chunk(mhh_pres_slab_plan* P, const mhh_grid* g, void*
 // the transposes is unchanged. c = k-slice (0 with unsliced transposes): the kernels work the levels of that slice only.
 MHH_API int mhh_pres_slab_has_lds(const mhh_pres_slab_plan* P)
 {
-    const char* e = getenv("MHH_PRES_SLAB_LDS");          // "0": the staged x stages (A/B runs, tests of both forms)
-    return (P && P->order == 2 && P->tx_lds && !(e && !strcmp(e, "0"))) ? 1 : 0;
+    // MHH_PRES_SLAB_LDS=0: the staged x stages (A/B runs, tests of both forms)
+    return (P && P->order == 2 && P->tx_lds && !env_is("MHH_PRES_SLAB_LDS", "0")) ? 1 : 0;
 }
 MHH_API int mhh_pres_slab_lds_fwd(mhh_pres_slab_plan* P, const mhh_grid* g, const mhh_fields* f, double dt, void* sendbuf, int c, void* stream)
 {
