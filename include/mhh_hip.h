@@ -221,6 +221,15 @@ typedef struct mhh_diff_params
      * the 2-D surface inputs valid on those rows.                                                      */
     int    evisc_ghost_rows;
     const void* mlen2;       /* [kcells] optional device table from mhh_smag2_mlen2_host (uniform z0m), or NULL */
+    /* which thermodynamics th_for_N2 belongs to. 0 = Thermo_dry (the meaning above). 1 = Thermo_buoy (src/thermo_buoy.cxx):
+     * th_for_N2 names the buoyancy scalar b; the inline N2 of exec_viscosity is 0.5*(b[k+1]-b[k-1])*dzi[k] + bg_n2 (calc_N2,
+     * :49-61; thref and grav unused), and the folded buoyancy is b at the w level (calc_buoyancy_tend_2nd / _4th, :94-109,
+     * :167-184; threfh unused). With alpha != 0 or bg_n2 != 0 the slope / stratified form (:111-165, :186-250) applies: the
+     * fused passes then run mhh_thermo_buoy_tend first and fold nothing. Zero-initialised: Thermo_dry, as before.          */
+    int    buoyancy_kind;
+    double bg_n2;            /* [thermo] N2: background stratification (bs.n2)                       */
+    double alpha;            /* [thermo] alpha: slope angle in radians (bs.alpha)                    */
+    double utrans;           /* grid.utrans: Galilean transformation velocity                        */
 } mhh_diff_params;
 int mhh_diff_exec_viscosity(const mhh_grid* g, int scheme, const mhh_fields* f, const mhh_diff_params* p, void* stream);
 /* exec_viscosity over the rows [j0, j1) of [jstart-1, jend+1) only (the wall mirror and the east-west wrap still cover
@@ -245,6 +254,17 @@ int mhh_diff_exec(const mhh_grid* g, int scheme, const mhh_fields* f, const mhh_
 int mhh_thermo_dry_buoyancy_tend(const mhh_grid* g, int order, void* wt, const void* th, const void* threfh,
                                  double grav, void* stream);
 
+/* Thermo_buoy::exec (src/thermo_buoy.cxx:347-395) in ONE launch, all fields through `f`; b = f->s[b_index], its tendency
+ * f->st[b_index]. alpha == 0 and n2 == 0: the flat form, wt += interp(b) at the w level (k in (kstart, kend)); otherwise
+ * the slope / stratified form: ut += sin(alpha)*interp_x(b), wt += cos(alpha)*interp(b),
+ * bt -= n2*(sin(alpha)*(interp(u) + utrans) + cos(alpha)*interp(w)). order 2 | 4 (grid.swspatialorder) selects interp2 /
+ * interp4c; order 4 needs kgc >= 2 and, for the slope form, igc >= 2. sin and cos are taken on the host in the grid's dtype
+ * (std::sin / std::cos of TF(alpha)), as the reference does. swbaroclinic is not covered.                              */
+int mhh_thermo_buoy_tend(const mhh_grid* g, int order, const mhh_fields* f, int b_index, double alpha, double n2,
+                         double utrans, void* stream);
+/* Thermo_buoy::get_thermo_field("N2") (calc_N2, src/thermo_buoy.cxx:49-61): N2 = 0.5*(b[k+1]-b[k-1])*dzi[k] + bg_n2, interior */
+int mhh_thermo_buoy_N2(const mhh_grid* g, void* N2, const void* b, double bg_n2, void* stream);
+
 /* ---- Fused RHS: advec.exec + diff.exec in one pass over the tendencies ------------------
  * Same arithmetic, same order of accumulation into each tendency as calling
  * mhh_advec_exec then mhh_diff_exec (bit-identical results), one read of every input
@@ -252,10 +272,15 @@ int mhh_thermo_dry_buoyancy_tend(const mhh_grid* g, int order, void* wt, const v
  * pair of valid schemes runs as the two operator calls.                                   */
 int mhh_rhs_exec(const mhh_grid* g, int advec_scheme, int diff_scheme, const mhh_fields* f,
                  const mhh_diff_params* p, void* stream);
+/* p->buoyancy with p->buoyancy_kind == 1 (Thermo_buoy): the flat form is folded into the w equation of the (2,2) and (2i5,smag2)
+ * passes (b = scalar 0 in the marching one; another index, or a flux-limited b, runs mhh_thermo_buoy_tend first) and of the
+ * (4,4) pass (with p->buoyancy == 4, in both its forms); every other pair runs mhh_thermo_buoy_tend first. The slope / stratified
+ * form is never folded: mhh_thermo_buoy_tend, then the pass without buoyancy, issued only once the call's inputs have passed their
+ * checks. Same bits as mhh_thermo_buoy_tend followed by the unfused calls in every case.                              */
 
 /* the (advec_2i5, diff_smag2) pass over the rows [j0, j1) of the interior only; u, v, w and up to MHH_MAX_SCALARS
  * unlimited scalars (scalar 0 in the fused marching kernel, the others in its scalar pass over the same rows; buoyancy only
- * as the 2nd-order form folded with scalar 0); same bits as the whole-slab call on those rows */
+ * as the 2nd-order form folded with scalar 0: Thermo_dry, or Thermo_buoy's flat form); same bits as the whole-slab call on those rows */
 int mhh_rhs_exec_rows(const mhh_grid* g, int advec_scheme, int diff_scheme, const mhh_fields* f,
                       const mhh_diff_params* p, int j0, int j1, void* stream);
 /* the same over TWO disjoint, ordered row ranges in one launch (a slab's two edge strips once its north-south halos are in) */

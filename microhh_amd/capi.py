@@ -30,7 +30,8 @@ class MhhFields(C.Structure):
 class MhhDiffParams(C.Structure):
     _fields_ = [("cs", cd), ("tPr", cd), ("surface_model", ci), ("neutral", ci), ("N2", vp),
                 ("th_for_N2", ci), ("thref", vp), ("grav", cd), ("mlen0", vp),
-                ("buoyancy", ci), ("threfh", vp), ("evisc_ghost_rows", ci), ("mlen2", vp)]
+                ("buoyancy", ci), ("threfh", vp), ("evisc_ghost_rows", ci), ("mlen2", vp),
+                ("buoyancy_kind", ci), ("bg_n2", cd), ("alpha", cd), ("utrans", cd)]
 
 
 FP = C.POINTER(MhhFields)
@@ -62,6 +63,8 @@ SIGNATURES = {
     "mhh_stat_rhs44_march_launches": (C.c_ulonglong, []),
     "mhh_stat_scalar_march_launches": (C.c_ulonglong, []),
     "mhh_thermo_dry_buoyancy_tend": (ci, [GP, ci, vp, vp, vp, cd, vp]),
+    "mhh_thermo_buoy_tend": (ci, [GP, ci, FP, ci, cd, cd, cd, vp]),
+    "mhh_thermo_buoy_N2": (ci, [GP, vp, vp, cd, vp]),
     "mhh_advec_cfl": (ci, [GP, ci, vp, vp, vp, cd, vp, C.POINTER(cd), vp]),
     "mhh_diff_c": (ci, [GP, ci, vp, vp, cd, vp]),
     "mhh_diff_w": (ci, [GP, ci, vp, vp, cd, vp]),

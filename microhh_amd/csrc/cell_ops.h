@@ -299,6 +299,27 @@ MHH_HD TF buoyancy_tend(const TF* __restrict__ th, int c, int kk, int order, TF 
     return grav/threfh_k * (thh - threfh_k);
 }
 
+// Thermo_buoy (src/thermo_buoy.cxx), in the reference's expression order. Only the w terms depend on k near the walls: the
+// caller runs them for k in (kstart, kend), so b[k-2] at k = kstart+1 is b[kstart-1], the first ghost level. What needs kgc >= 2 at
+// 4th order is the bt term of the slope form, w[k+2] = w[kend+1] at k = kend-1; the entry points ask it of every 4th-order call,
+// as the dry buoyancy does.
+// b at the w level: calc_buoyancy_tend_2nd / _4th (:94-109, :167-184)
+template<class TF> MHH_HD TF buoy_w(const TF* __restrict__ b, int c, int kk, int order)
+{ return (order == 4) ? i4c(b[c-2*kk], b[c-kk], b[c], b[c+kk]) : i2(b[c-kk], b[c]); }
+// the same at 4th order from a register window b[k-2 .. k+1] (k_march4.hip)
+template<class TF> MHH_HD TF buoy_w4(const TF (&bw)[4]) { return i4c(bw[0], bw[1], bw[2], bw[3]); }
+// b at the u location (calc_buoyancy_tend_u_2nd / _4th, :111-126, :186-201): b[i-2] at istart needs igc >= 2 at 4th order
+template<class TF> MHH_HD TF buoy_u(const TF* __restrict__ b, int c, int order)
+{ return (order == 4) ? i4c(b[c-2], b[c-1], b[c], b[c+1]) : i2(b[c-1], b[c]); }
+// the stratification term of bt (calc_buoyancy_tend_b_2nd / _4th, :145-165, :220-250): bt -= n2 * buoy_bt(...)
+template<class TF> MHH_HD TF buoy_bt(const TF* __restrict__ u, const TF* __restrict__ w, int c, int kk, int order, TF sa, TF ca, TF utrans)
+{
+    if (order == 4) return sa * (i4c(u[c-1], u[c], u[c+1], u[c+2]) + utrans) + ca * i4c(w[c-kk], w[c], w[c+kk], w[c+2*kk]);
+    return sa * (i2(u[c], u[c+1]) + utrans) + ca * i2(w[c], w[c+kk]);
+}
+// calc_N2 (:49-61)
+template<class TF> MHH_HD TF buoy_N2(TF bm, TF bp, TF dzi, TF bg_n2) { return TF(0.5)*(bp - bm)*dzi + bg_n2; }
+
 // =======================================================================================================
 // Koren (1993) flux-limited scalar advection (include/advec_monotonic.h:10-180, selected per scalar by
 // advec.fluxlimit_list, src/advec_2i5.cxx:921,1030). face = 0: interior face, 1: first face above the bottom wall

@@ -125,6 +125,7 @@ template<class TF> struct MarchFields
     const TF* __restrict__ ufb; const TF* __restrict__ uft; const TF* __restrict__ vfb; const TF* __restrict__ vft;
     const TF* __restrict__ sfb; const TF* __restrict__ sft;
     const TF* __restrict__ threfh; TF grav;      // folded dry buoyancy of the scalar (threfh == nullptr: off)
+    int bflat;                                   // folded flat Thermo_buoy buoyancy of the scalar (it is b)
     int sm;
 #ifdef MHH_MARCH_STAMP      // probe builds: per-wave cycle sums of the phases of a level (scripts/experiments/march_stamps.py)
     unsigned long long* dbg;
@@ -604,7 +605,8 @@ rhs25_march_kernel(const MarchMetrics<typename lane_of<VT>::scalar> mm, const Gr
                     if (FAST || k > g.kstart)
                     {   // w
                         VT t = TPREF ? tcw : tld(pwt, bo0);
-                        if (HAS_S && f.threfh) { const TF th_k = uniform_load(f.threfh, k); t += f.grav/th_k * (i2(s0m, s0) - th_k); }   // src/thermo_dry.cxx:165-178
+                        if (HAS_S && f.bflat) t += i2(s0m, s0);                                                                    // src/thermo_buoy.cxx:94-109
+                        else if (HAS_S && f.threfh) { const TF th_k = uniform_load(f.threfh, k); t += f.grav/th_k * (i2(s0m, s0) - th_k); }   // src/thermo_dry.cxx:165-178
                         if constexpr (ADV)
                         {
                             t += advec25_hor_f0(wk, w0, TI, u1m + u_e, u0m + u0, vNm + v_n, v0m + v0, dxih, dyih);
@@ -1015,7 +1017,8 @@ int march_launch(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* 
     mf.sm = (p && ops != MARCH_ADVEC) ? p->surface_model : 0;
     MHH_REQUIRE(ops == MARCH_ADVEC || !has_s || known_divisor_ok(mm.tPr2), "tPr must be a positive normal number whose significand is not all ones");
     const bool buoy = ops == MARCH_BOTH && has_s && p->buoyancy == 2 && p->th_for_N2 == 0;
-    mf.threfh = buoy ? cp<TF>(p->threfh) : nullptr; mf.grav = buoy ? TF(p->grav) : TF(0);
+    const bool bflat = buoy && p->buoyancy_kind == 1;
+    mf.threfh = (buoy && !bflat) ? cp<TF>(p->threfh) : nullptr; mf.grav = (buoy && !bflat) ? TF(p->grav) : TF(0); mf.bflat = bflat;
     const int kc = march_chunk_levels<TF>(g, rows);
     MHH_REQUIRE(kc > 0, "a plane of this grid is too large for the marching kernel's 32-bit lane offsets");
     const MarchTiling t = make_march_tiling(g, NJ, kc, 64*CW, rows);

@@ -11,6 +11,9 @@
 // LDS budget: u and v keep exactly their four planes -- the w equation, the only reader of the oldest one, is computed
 // first, then a barrier, then the copy of plane k+2 is issued into that slot and lands while the u and v equations are
 // computed; w has a fifth slot for its copy. 13 planes of 70 x (NJ+6) doubles = 72.8 KB: two blocks per CU.
+//
+// BUOY: Thermo_buoy's flat 4th-order buoyancy (src/thermo_buoy.cxx:167-184) folded in as the first term of wt. b is read at no
+// horizontal offset, so it needs no LDS: a per-lane register window of the own column at k-2 .. k+1, one load per level.
 #include <cstdint>
 #include "k_common.h"
 #include "k_march_common.h"
@@ -29,6 +32,7 @@ template<class TF> struct March4Fields
     const TF* __restrict__ u; const TF* __restrict__ v; const TF* __restrict__ w;
     TF* __restrict__ ut; TF* __restrict__ vt; TF* __restrict__ wt;
     TF visc;
+    const TF* __restrict__ b;        // the buoyancy scalar of the BUOY instantiation
 };
 
 // field view of the marching kernel: horizontal offsets from the LDS plane of that level, the own column from registers
@@ -56,7 +60,7 @@ template<class TF> __device__ __forceinline__ void shift7(TF (&w)[7], TF nw)
 #endif
 
 // ADV / DIF: both operators (the fused pass) or one of them (Advec_4::exec / Diff_4::exec called separately: same body, same bits)
-template<class TF, int NJ, int PB, bool ADV = true, bool DIF = true>
+template<class TF, int NJ, int PB, bool ADV = true, bool DIF = true, bool BUOY = false>
 __global__ void __launch_bounds__(64*NJ, MHH_MARCH4_OCC) rhs44_march_kernel(const GridDev<TF> g, const March4Fields<TF> f, const MarchTiling mt)
 {
     constexpr int AL = (PB == 16) ? 16 / (int)sizeof(TF) : 1;
@@ -96,6 +100,12 @@ __global__ void __launch_bounds__(64*NJ, MHH_MARCH4_OCC) rhs44_march_kernel(cons
     TF uw[7], vw[7], ww[7];
 #pragma unroll
     for (int n=0; n<7; ++n) { uw[n] = colval(f.u, kb-3+n); vw[n] = colval(f.v, kb-3+n); ww[n] = colval(f.w, kb-3+n); }
+    TF bw[4] = {0, 0, 0, 0};                                          // BUOY: b at k-2 .. k+1 of the own column
+    if constexpr (BUOY)
+    {
+#pragma unroll
+        for (int n=0; n<4; ++n) bw[n] = colval(f.b, kb-2+n);
+    }
     // The tendencies are read one level ahead of their use (MHH_MARCH4_TPREF=0: where they are used); those of the first
     // level here, ahead of the prologue's wait, so that no load is pending when the loop is entered.
 #ifndef MHH_MARCH4_TPREF
@@ -136,6 +146,8 @@ __global__ void __launch_bounds__(64*NJ, MHH_MARCH4_OCC) rhs44_march_kernel(cons
         const TF tcu = tnu, tcv = tnv, tcw = tnw;
         if (TPREF && more && active) { const int cn = col + (k+1)*kk; tnu = stream_load(f.ut + cn); tnv = stream_load(f.vt + cn); tnw = stream_load(f.wt + cn); }
         const TF nu = more ? colval(f.u, k+4) : TF(0), nv = more ? colval(f.v, k+4) : TF(0), nw = more ? colval(f.w, k+4) : TF(0);
+        TF nb = TF(0);
+        if constexpr (BUOY) nb = more ? colval(f.b, k+2) : TF(0);
 
         const MarchView<TF, TI> Uv{{U[su(k-2)]+l, U[su(k-1)]+l, U[su(k)]+l, U[su(k+1)]+l, nullptr}, uw};
         const MarchView<TF, TI> Vv{{V[su(k-2)]+l, V[su(k-1)]+l, V[su(k)]+l, V[su(k+1)]+l, nullptr}, vw};
@@ -151,7 +163,9 @@ __global__ void __launch_bounds__(64*NJ, MHH_MARCH4_OCC) rhs44_march_kernel(cons
             const TF gw4[4] = {uniform_load(g.dzi4, k-2), uniform_load(g.dzi4, k-1), uniform_load(g.dzi4, k), uniform_load(g.dzi4, k+1)};
             if constexpr (ADV) advec4_mom_vc<2>(ad, Wv, Uv, Vv, Wv, botw, top, dxi, dyi, uniform_load(g.dzhi4, k), dim3, aw, fresh_w);
             if constexpr (DIF) diff4_vc(df, Wv, botw, top, f.visc, g.dxidxi_t, g.dyidyi_t, gw4, uniform_load(g.dzhi4, k), dim3, dw, fresh_w);
-            stream_store(f.wt + c, both(TPREF ? tcw : stream_load(f.wt + c), ad, df));
+            TF t = TPREF ? tcw : stream_load(f.wt + c);
+            if constexpr (BUOY) t += buoy_w4(bw);                    // wt += interp4c(b[k-2], b[k-1], b[k], b[k+1]) first
+            stream_store(f.wt + c, both(t, ad, df));
         }
         if (more)
         {
@@ -173,6 +187,7 @@ __global__ void __launch_bounds__(64*NJ, MHH_MARCH4_OCC) rhs44_march_kernel(cons
         wait_vmem();                  // unconditional: every path back to the loop head carries a vmcnt(0) the compiler can see
         __syncthreads();
         if (more) { shift7(uw, nu); shift7(vw, nv); shift7(ww, nw); }
+        if constexpr (BUOY) if (more) { bw[0] = bw[1]; bw[1] = bw[2]; bw[2] = bw[3]; bw[3] = nb; }
     }
     if (c_pending >= 0) { stream_store(f.ut + c_pending, ut_pending); stream_store(f.vt + c_pending, vt_pending); }
 }
@@ -181,16 +196,21 @@ __global__ void __launch_bounds__(64*NJ, MHH_MARCH4_OCC) rhs44_march_kernel(cons
 #define MHH_MARCH4_NJ 4
 #endif
 template<class TF>
-int march4_launch(const mhh_grid* g, const mhh_fields* f, int pb, MarchOps ops, hipStream_t st)
+int march4_launch(const mhh_grid* g, const mhh_fields* f, int pb, MarchOps ops, const void* bfold, hipStream_t st)
 {
     constexpr int NJ = MHH_MARCH4_NJ;
     March4Fields<TF> mf;
     mf.u = cp<TF>(f->u); mf.v = cp<TF>(f->v); mf.w = cp<TF>(f->w);
-    mf.ut = mp<TF>(f->ut); mf.vt = mp<TF>(f->vt); mf.wt = mp<TF>(f->wt); mf.visc = TF(f->visc);
+    mf.ut = mp<TF>(f->ut); mf.vt = mp<TF>(f->vt); mf.wt = mp<TF>(f->wt); mf.visc = TF(f->visc); mf.b = cp<TF>(bfold);
     const MarchTiling t = make_march_tiling(g, NJ, MHH_MARCH4_KC);
     const dim3 nb(march_blocks(t)), bs(64, NJ);
     const GridDev<TF> gd = make_grid<TF>(g);
-    march_variant(ops, pb, [&](auto PB, auto A, auto D) { hipLaunchKernelGGL((rhs44_march_kernel<TF, NJ, PB, A, D>), nb, bs, 0, st, gd, mf, t); });
+    if (bfold)              // the fused pass only (ops == MARCH_BOTH, checked by the caller)
+    {
+        if (pb == 16) hipLaunchKernelGGL((rhs44_march_kernel<TF, NJ, 16, true, true, true>), nb, bs, 0, st, gd, mf, t);
+        else          hipLaunchKernelGGL((rhs44_march_kernel<TF, NJ, 4, true, true, true>),  nb, bs, 0, st, gd, mf, t);
+    }
+    else march_variant(ops, pb, [&](auto PB, auto A, auto D) { hipLaunchKernelGGL((rhs44_march_kernel<TF, NJ, PB, A, D>), nb, bs, 0, st, gd, mf, t); });
     MHH_LAUNCH_CHECK();
     return MHH_OK;
 }
@@ -199,12 +219,14 @@ static unsigned long long g_rhs44_march_launches = 0;
 
 MHH_API unsigned long long mhh_stat_rhs44_march_launches(void) { return g_rhs44_march_launches; }
 
-// (advec_4, diff_4), Advec_4::exec or Diff_4::exec for u, v, w (scalars take the per-field kernels)
-int mhh::march44(const mhh_grid* g, const mhh_fields* f, MarchOps ops, void* stream)
+// (advec_4, diff_4), Advec_4::exec or Diff_4::exec for u, v, w (scalars take the per-field kernels); bfold: the buoyancy scalar b
+// whose flat Thermo_buoy term is folded into wt (MARCH_BOTH only), or null
+int mhh::march44(const mhh_grid* g, const mhh_fields* f, MarchOps ops, void* stream, const void* bfold)
 {
+    MHH_REQUIRE(!bfold || ops == MARCH_BOTH, "the buoyancy fold belongs to the fused pass");
     const int vec = (g->dtype == MHH_F64) ? 2 : 4;
     // 16-byte pieces need 16-byte aligned rows and tile origin (i0 - 3 = igc - 3 + 64*bx); other layouts copy in 4-byte pieces
     const int pb = (g->icells % vec == 0 && (g->igc - 3) % vec == 0 && al16(f->u) && al16(f->v) && al16(f->w)) ? 16 : 4;
     ++g_rhs44_march_launches;
-    return (g->dtype == MHH_F64) ? march4_launch<double>(g, f, pb, ops, as_stream(stream)) : march4_launch<float>(g, f, pb, ops, as_stream(stream));
+    return (g->dtype == MHH_F64) ? march4_launch<double>(g, f, pb, ops, bfold, as_stream(stream)) : march4_launch<float>(g, f, pb, ops, bfold, as_stream(stream));
 }

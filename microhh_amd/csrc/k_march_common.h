@@ -147,7 +147,7 @@ int march25(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, Ma
 // the same for the scalars idx[0 .. n) in the batched scalar pass (k_march.hip)
 int march25_scalars(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const int* idx, int n, MarchOps ops, const MarchRows& rows, void* stream);
 // advec_4 and / or diff_4 of u, v, w (k_march4.hip), where march44_takes(g)
-int march44(const mhh_grid* g, const mhh_fields* f, MarchOps ops, void* stream);
+int march44(const mhh_grid* g, const mhh_fields* f, MarchOps ops, void* stream, const void* bfold = nullptr);
 // Diff_smag2::exec_viscosity over the rows (k_visc.hip), where visc_march_takes(g)
 int visc_march(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const void* th, const MarchRows& rows, void* stream);
 // The advec_2i5 / diff_smag2 routing of every field (k_rhs.hip): u, v, w and scalar 0 to march25, further scalars to the

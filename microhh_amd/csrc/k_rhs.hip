@@ -114,6 +114,7 @@ struct ViscosityOp
     const TF* __restrict__ dudz; const TF* __restrict__ dvdz; const TF* __restrict__ dbdz; const TF* __restrict__ z0m;
     const TF* __restrict__ N2; const TF* __restrict__ th; const TF* __restrict__ thref; TF grav;
     const TF* __restrict__ mlen0; TF tPr; const TF* __restrict__ mlen2;
+    int bkind; TF bg_n2;           // th is Thermo_buoy's b (bkind 1)
     __device__ void operator()(int i, int j, int k, int c) const
     {
         const int ij = i + j*g.icells;
@@ -125,6 +126,7 @@ struct ViscosityOp
         {
             if (mo) n2 = dbdz[ij];
             else if (N2) n2 = N2[c];
+            else if (bkind) n2 = buoy_N2(th[c-g.ijcells], th[c+g.ijcells], g.dzi[k], bg_n2);
             else n2 = grav/thref[k]*TF(0.5)*(th[c+g.ijcells] - th[c-g.ijcells])*g.dzi[k];
         }
         const TF fac = mlen2 ? mlen2[k] : evisc_mlen2(sm, neutral, mlen0[k], sm ? g.z[k] : TF(0), sm ? z0m[ij] : TF(0));
@@ -149,7 +151,8 @@ template<class TF>
 static int viscosity_cells(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const void* th, const MarchRows& rows, bool marched, hipStream_t st)
 {
     ViscosityOp<TF> op{make_grid<TF>(g), p->surface_model, p->neutral, mp<TF>(f->evisc), cp<TF>(f->u), cp<TF>(f->v), cp<TF>(f->w),
-                       cp<TF>(f->dudz), cp<TF>(f->dvdz), cp<TF>(f->dbdz), cp<TF>(f->z0m), cp<TF>(p->N2), cp<TF>(th), cp<TF>(p->thref), TF(p->grav), cp<TF>(p->mlen0), TF(p->tPr), cp<TF>(p->mlen2)};
+                       cp<TF>(f->dudz), cp<TF>(f->dvdz), cp<TF>(f->dbdz), cp<TF>(f->z0m), cp<TF>(p->N2), cp<TF>(th), cp<TF>(p->thref), TF(p->grav), cp<TF>(p->mlen0), TF(p->tPr), cp<TF>(p->mlen2),
+                       p->buoyancy_kind, TF(p->bg_n2)};
     auto rows_of = [&](int j0, int j1) { return launch_cells(st, op, g->istart, g->iend, j0, j1, g->kstart, g->kend, g->icells, g->ijcells); };
     if (!marched)
     {
@@ -173,6 +176,7 @@ static int viscosity_cells(const mhh_grid* g, const mhh_fields* f, const mhh_dif
 static int viscosity_rows(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const MarchRows& rows, void* stream)
 {
     MHH_REQUIRE(f && p && f->evisc && f->u && f->v && f->w && p->mlen0, "null field");
+    MHH_REQUIRE(p->buoyancy_kind == 0 || p->buoyancy_kind == 1, "buoyancy_kind must be 0 (Thermo_dry) or 1 (Thermo_buoy)");
     MHH_REQUIRE(!p->surface_model || (f->dudz && f->dvdz && f->z0m), "surface model inputs");
     const void* th = nullptr;
     if (!p->neutral)
@@ -180,7 +184,7 @@ static int viscosity_rows(const mhh_grid* g, const mhh_fields* f, const mhh_diff
         MHH_REQUIRE(!p->surface_model || f->dbdz, "dbdz");
         if (!p->N2)
         {
-            MHH_REQUIRE(p->th_for_N2 >= 0 && p->th_for_N2 < f->nscalars && p->thref, "N2 or (th_for_N2, thref) required");
+            MHH_REQUIRE(p->th_for_N2 >= 0 && p->th_for_N2 < f->nscalars && (p->buoyancy_kind == 1 || p->thref), "N2 or (th_for_N2, thref) required");
             th = f->s[p->th_for_N2];
         }
     }
@@ -219,6 +223,16 @@ MHH_API int mhh_diff_exec_viscosity_rows2(const mhh_grid* g, int scheme, const m
     return viscosity_rows(g, f, p, MarchRows{j0, j1, j2, j3}, stream);
 }
 
+// The buoyancy tendency of p on its own (the forms that are not folded): Thermo_dry::exec or Thermo_buoy::exec
+static int buoyancy_alone(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, void* stream)
+{
+    if (p->buoyancy_kind == 1)
+        return mhh_thermo_buoy_tend(g, p->buoyancy, f, p->th_for_N2, p->alpha, p->bg_n2, p->utrans, stream);
+    return mhh_thermo_dry_buoyancy_tend(g, p->buoyancy, f->wt, f->s[p->th_for_N2], p->threfh, p->grav, stream);
+}
+// Thermo_buoy's slope / stratified form (src/thermo_buoy.cxx:318-319, :351-357): never folded
+static bool buoy_sloped(const mhh_diff_params* p) { return p->buoyancy_kind == 1 && (p->alpha != 0. || p->bg_n2 != 0.); }
+
 // advec_2i5 and / or diff_smag2 (ops) of every field over the rows (inputs validated by the caller; p null for MARCH_ADVEC):
 // u, v, w and scalar 0 in the fused marching kernel; further scalars in its scalar pass where `pass` (MHH_SCALAR_IMPL=cell: no),
 // flux-limited ones per field. Diffusion ignores the limiter. The row-wise callers have no flux-limited scalar and set `pass`:
@@ -233,7 +247,7 @@ int mhh::route25(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* 
     const mhh_diff_params* pm = p; mhh_diff_params pnb;
     if (ops == MARCH_BOTH && p->buoyancy && !(p->buoyancy == 2 && p->th_for_N2 == 0 && !f->s_fluxlimit[0]))
     {
-        if (int e = mhh_thermo_dry_buoyancy_tend(g, p->buoyancy, f->wt, f->s[p->th_for_N2], p->threfh, p->grav, stream)) return e;
+        if (int e = buoyancy_alone(g, f, p, stream)) return e;
         pnb = *p; pnb.buoyancy = 0; pm = &pnb;
     }
     if (int e = march25(g, &fm, pm, ops, rows, stream)) return e;
@@ -317,6 +331,9 @@ template<class TF> struct FieldsDev
     const TF* __restrict__ ufb; const TF* __restrict__ uft; const TF* __restrict__ vfb; const TF* __restrict__ vft;
     TF visc, tPr; int sm;
     const TF* __restrict__ bth; const TF* __restrict__ threfh; TF grav; int border;   // folded buoyancy (bth == nullptr: off)
+    int bkind;                                                                         // 0: Thermo_dry, 1: Thermo_buoy (flat form)
+    // the folded buoyancy term of w at level k (src/thermo_dry.cxx:165-197, src/thermo_buoy.cxx:94-109,167-184)
+    __device__ TF buoy(int c, int kk, int k) const { return bkind ? buoy_w(bth, c, kk, border) : buoyancy_tend(bth, c, kk, border, grav, threfh[k]); }
 };
 template<class TF>
 static FieldsDev<TF> make_fields(const mhh_fields* f, const mhh_diff_params* p)
@@ -336,7 +353,7 @@ static FieldsDev<TF> make_fields(const mhh_fields* f, const mhh_diff_params* p)
     d.visc = TF(f->visc); d.tPr = p ? TF(p->tPr) : TF(1); d.sm = p ? p->surface_model : 0;
     const bool buoy = p && p->buoyancy;
     d.bth = buoy ? cp<TF>(f->s[p->th_for_N2]) : nullptr; d.threfh = buoy ? cp<TF>(p->threfh) : nullptr;
-    d.grav = buoy ? TF(p->grav) : TF(0); d.border = buoy ? p->buoyancy : 0;
+    d.grav = buoy ? TF(p->grav) : TF(0); d.border = buoy ? p->buoyancy : 0; d.bkind = buoy ? p->buoyancy_kind : 0;
     return d;
 }
 
@@ -363,7 +380,7 @@ struct Rhs22Op
         if (k > g.kstart)
         {
             TF t = f.wt[c];
-            if (f.bth) t += buoyancy_tend(f.bth, c, kk, f.border, f.grav, f.threfh[k]);
+            if (f.bth) t += f.buoy(c, kk, k);
             t += advec2_mom(f.w, f.u, f.v, f.w, c, -kk, jj, kk, g.dxi_t, g.dyi_t, rk, f.rhoref[k-1], rhk, dzhi);
             f.wt[c] = diff2_apply(t, f.w, c, jj, kk, f.visc, g.dxidxi_2, g.dyidyi_2, dzi, g.dzi[k-1], dzhi);
         }
@@ -410,7 +427,7 @@ struct Rhs25SmagOp
             const int o = -kk;
             const TF rkm = f.rhoref[k-1];
             TF t = f.wt[c];
-            if (f.bth) t += buoyancy_tend(f.bth, c, kk, f.border, f.grav, f.threfh[k]);
+            if (f.bth) t += f.buoy(c, kk, k);
             t += advec25_hor(f.w, c, jj, i2(f.u[c+1+o], f.u[c+1]), i2(f.u[c+o], f.u[c]), i2(f.v[c+jj+o], f.v[c+jj]), i2(f.v[c+o], f.v[c]), g.dxi_t, g.dyi_t);
             t += advec25_ver(f.w, c, kk, order_face_w(k, g.kstart, g.kend), order_face_w(k-1, g.kstart, g.kend),
                              i2(f.w[c+kk+o], f.w[c+kk]), i2(f.w[c+o], f.w[c]), rk, rkm, rhk, dzhi);
@@ -458,7 +475,7 @@ struct Rhs44Op
             const TF gw4[4] = {g.dzi4[k-2], g.dzi4[k-1], g.dzi4[k], g.dzi4[k+1]};
             advec4_mom(ad, f.w, f.u, f.v, f.w, c, kk, true, jj, kk, botw, top, g.dxi_t, g.dyi_t, g.dzhi4[k], g.dim3);
             diff4_cell(df, f.w, c, jj, kk, botw, top, f.visc, g.dxidxi_t, g.dyidyi_t, gw4, g.dzhi4[k], g.dim3);
-            f.wt[c] = both(f.bth ? f.wt[c] + buoyancy_tend(f.bth, c, kk, f.border, f.grav, f.threfh[k]) : f.wt[c], ad, df);
+            f.wt[c] = both(f.bth ? f.wt[c] + f.buoy(c, kk, k) : f.wt[c], ad, df);
         }
         for (int n=0; n<f.ns; ++n)
         {
@@ -476,17 +493,29 @@ MHH_API int mhh_rhs_exec(const mhh_grid* g, int advec_scheme, int diff_scheme, c
     MHH_REQUIRE(f->nscalars >= 0 && f->nscalars <= MHH_MAX_SCALARS, "nscalars");
     for (int n=0; n<f->nscalars; ++n) MHH_REQUIRE(f->s[n] && f->st[n], "null scalar");
     hipStream_t st = as_stream(stream);
+    mhh_diff_params pnb;
     if (p && p->buoyancy)
     {
         MHH_REQUIRE(p->buoyancy == 2 || p->buoyancy == 4, "buoyancy order must be 2 or 4");
-        MHH_REQUIRE(p->th_for_N2 >= 0 && p->th_for_N2 < f->nscalars && p->threfh, "buoyancy needs th_for_N2 and threfh");
+        MHH_REQUIRE(p->buoyancy_kind == 0 || p->buoyancy_kind == 1, "buoyancy_kind must be 0 (Thermo_dry) or 1 (Thermo_buoy)");
+        MHH_REQUIRE(p->th_for_N2 >= 0 && p->th_for_N2 < f->nscalars && (p->buoyancy_kind == 1 || p->threfh), "buoyancy needs th_for_N2 (and threfh for Thermo_dry)");
         MHH_REQUIRE(g->kgc >= (p->buoyancy == 4 ? 2 : 1), "buoyancy: vertical ghost cells");
     }
+    // Thermo::exec precedes Advec::exec (src/model.cxx:366,388): Thermo_buoy's slope form first, on its own, then the pass without a
+    // fold. Each pair calls this after its own checks, so that a call it refuses has changed no tendency.
+    auto sloped_first = [&]() -> int
+    {
+        if (!(p && p->buoyancy && buoy_sloped(p))) return MHH_OK;
+        if (int e = buoyancy_alone(g, f, p, stream)) return e;
+        pnb = *p; pnb.buoyancy = 0; p = &pnb;
+        return MHH_OK;
+    };
     if (advec_scheme != MHH_ADVEC_2I5)
         for (int n=0; n<f->nscalars; ++n) MHH_REQUIRE(!f->s_fluxlimit[n], "fluxlimit_list is an advec_2i5 option (src/advec_2i5.cxx:39)");
     if (advec_scheme == MHH_ADVEC_2 && diff_scheme == MHH_DIFF_2)
     {
         MHH_REQUIRE(f->rhoref && f->rhorefh && g->igc >= 1 && g->jgc >= 1 && g->kgc >= 1, "advec_2+diff_2 inputs");
+        if (int e = sloped_first()) return e;
 #define CALL(TF) [&]{ Rhs22Op<TF> op{make_grid<TF>(g), make_fields<TF>(f, p)}; return launch_interior(st, op.g, g->kstart, g->kend, op); }()
         return MHH_DISPATCH(g, CALL);
 #undef CALL
@@ -500,6 +529,7 @@ MHH_API int mhh_rhs_exec(const mhh_grid* g, int advec_scheme, int diff_scheme, c
             MHH_REQUIRE(f->u_fluxbot && f->u_fluxtop && f->v_fluxbot && f->v_fluxtop, "surface fluxes");
             for (int n=0; n<f->nscalars; ++n) MHH_REQUIRE(f->s_fluxbot[n] && f->s_fluxtop[n], "scalar surface fluxes");
         }
+        if (int e = sloped_first()) return e;
         // default: the k-marching LDS kernel (k_march.hip) for u, v, w and scalar 0; further unlimited scalars take the scalar
         // pass of that kernel (MHH_SCALAR_IMPL=cell: the per-field kernels), flux-limited ones the per-field kernels.
         // MHH_RHS25_IMPL=cell selects the one-thread-per-cell fused kernel (A/B measurements); a call with a flux-limited scalar
@@ -515,12 +545,19 @@ MHH_API int mhh_rhs_exec(const mhh_grid* g, int advec_scheme, int diff_scheme, c
     if (advec_scheme == MHH_ADVEC_4 && diff_scheme == MHH_DIFF_4)
     {
         MHH_REQUIRE(g->igc >= 3 && g->jgc >= 3 && g->kgc >= 3, "4th order needs gc(3,3,3)");
-        // default: the k-marching LDS kernel (k_march4.hip) for u, v, w where the rows allow LDS-DMA; scalars and the folded
-        // buoyancy then take their own kernels (same order of accumulation). MHH_RHS44_IMPL=cell selects the cell kernel.
+        if (int e = sloped_first()) return e;
+        // default: the k-marching LDS kernel (k_march4.hip) for u, v, w where the rows allow LDS-DMA; scalars take their own
+        // kernels (same order of accumulation). Thermo_buoy's flat 4th-order buoyancy is folded into the w equation there (a
+        // register window of b); the dry buoyancy, or a 2nd-order one, takes its own kernel first. MHH_RHS44_IMPL=cell selects
+        // the cell kernel, which folds both.
         if (march44_takes(g))
         {
-            if (p && p->buoyancy) if (int e = mhh_thermo_dry_buoyancy_tend(g, p->buoyancy, f->wt, f->s[p->th_for_N2], p->threfh, p->grav, stream)) return e;
-            if (int e = march44(g, f, MARCH_BOTH, stream)) return e;
+            // the fold where every row of a block lies in the domain: 2.12 against 2.27 ms for the separate launch at 512 x 256 x 256
+            // fp64; with jmax < 4 (a 2-D run, jtot = 1) three of a block's four rows idle and the separate launch is the faster,
+            // 0.157 against 0.160 ms at 1024 x 1 x 384 (profiles/buoy_cost.jsonl)
+            const bool fold = p && p->buoyancy == 4 && p->buoyancy_kind == 1 && g->jmax >= 4;
+            if (p && p->buoyancy && !fold) if (int e = buoyancy_alone(g, f, p, stream)) return e;
+            if (int e = march44(g, f, MARCH_BOTH, stream, fold ? f->s[p->th_for_N2] : nullptr)) return e;
             for (int n=0; n<f->nscalars; ++n)
             {
                 if (int e = mhh_advec_s(g, MHH_ADVEC_4, f->st[n], f->s[n], f->u, f->v, f->w, f->rhoref, f->rhorefh, stream)) return e;
@@ -532,9 +569,11 @@ MHH_API int mhh_rhs_exec(const mhh_grid* g, int advec_scheme, int diff_scheme, c
         return MHH_DISPATCH(g, CALL);
 #undef CALL
     }
-    // any other pair of valid schemes: the two operator calls, in the reference's order (same bits as calling them directly)
+    // any other pair of valid schemes: the two operator calls, in the reference's order (same bits as calling them directly);
+    // the buoyancy first, as Model::exec has it (their checks are the operators' own)
+    if (int e = sloped_first()) return e;
     if (p && p->buoyancy)
-        if (int e = mhh_thermo_dry_buoyancy_tend(g, p->buoyancy, f->wt, f->s[p->th_for_N2], p->threfh, p->grav, stream)) return e;
+        if (int e = buoyancy_alone(g, f, p, stream)) return e;
     if (int e = mhh_advec_exec(g, advec_scheme, f, stream)) return e;
     return mhh_diff_exec(g, diff_scheme, f, p, stream);
 }
@@ -548,7 +587,9 @@ static int rhs_rows_checks(const mhh_grid* g, int advec_scheme, int diff_scheme,
     MHH_REQUIRE(f && p && f->u && f->v && f->w && f->ut && f->vt && f->wt && f->evisc && f->rhoref && f->rhorefh, "null field");
     MHH_REQUIRE(f->nscalars >= 0 && f->nscalars <= MHH_MAX_SCALARS, "nscalars");
     for (int n=0; n<f->nscalars; ++n) MHH_REQUIRE(f->s[n] && f->st[n] && !f->s_fluxlimit[n], "row-wise pass: at most one, unlimited scalar");
-    MHH_REQUIRE(!p->buoyancy || (p->buoyancy == 2 && p->th_for_N2 == 0 && f->nscalars >= 1 && p->threfh), "row-wise pass: buoyancy only as the in-kernel 2nd-order form of scalar 0");
+    MHH_REQUIRE(p->buoyancy_kind == 0 || p->buoyancy_kind == 1, "buoyancy_kind must be 0 (Thermo_dry) or 1 (Thermo_buoy)");
+    MHH_REQUIRE(!p->buoyancy || (p->buoyancy == 2 && p->th_for_N2 == 0 && f->nscalars >= 1 && (p->buoyancy_kind == 1 || p->threfh) && !buoy_sloped(p)),
+                "row-wise pass: buoyancy only as the in-kernel 2nd-order form of scalar 0 (Thermo_dry, or Thermo_buoy's flat form)");
     MHH_REQUIRE(g->igc >= 3 && g->jgc >= 3 && g->kgc >= 1 && g->ktot >= 6, "advec_2i5 needs gc(3,3,1), ktot>=6");
     if (p->surface_model)
     {

@@ -633,6 +633,68 @@ MHH_API int mhh_calc_N2(const mhh_grid* g, void* N2, const void* th, const void*
 #undef CALL
 }
 
+// Thermo_buoy::exec (src/thermo_buoy.cxx:347-395): the flat form (w only) or the slope / stratified form (u, w and b) in one
+// launch. The three loops of the reference write three different arrays and read only b, u and w, so one cell applies them all.
+template<class TF>
+struct BuoyTendOp
+{
+    GridDev<TF> g; int order; bool slope;
+    TF* __restrict__ ut; TF* __restrict__ wt; TF* __restrict__ bt;
+    const TF* __restrict__ b; const TF* __restrict__ u; const TF* __restrict__ w;
+    TF sa, ca, n2, utrans;
+    __device__ void operator()(int, int, int k, int c) const
+    {
+        const int kk = g.ijcells;
+        if (!slope) { wt[c] += buoy_w(b, c, kk, order); return; }          // launched over (kstart, kend) only
+        ut[c] += sa * buoy_u(b, c, order);
+        if (k > g.kstart) wt[c] += ca * buoy_w(b, c, kk, order);
+        bt[c] -= n2 * buoy_bt(u, w, c, kk, order, sa, ca, utrans);
+    }
+};
+template<class TF>
+static int buoy_tend(const mhh_grid* g, int order, const mhh_fields* f, int n, double alpha, double n2, double utrans, hipStream_t st)
+{
+    // bs.alpha and bs.n2 are TF in the reference, sin and cos taken on the host in TF (std::sin(float) in the -DUSESP build)
+    const TF a = TF(alpha), sa = std::sin(a), ca = std::cos(a);
+    const bool slope = (alpha != 0.) || (n2 != 0.);                       // bs.has_slope || bs.has_N2 (src/thermo_buoy.cxx:318-319)
+    BuoyTendOp<TF> op{make_grid<TF>(g), order, slope, mp<TF>(f->ut), mp<TF>(f->wt), mp<TF>(f->st[n]), cp<TF>(f->s[n]), cp<TF>(f->u), cp<TF>(f->w),
+                      sa, ca, TF(n2), TF(utrans)};
+    return launch_interior(st, op.g, slope ? g->kstart : g->kstart+1, g->kend, op);
+}
+MHH_API int mhh_thermo_buoy_tend(const mhh_grid* g, int order, const mhh_fields* f, int b_index, double alpha, double n2, double utrans, void* stream)
+{
+    if (int e = check_grid(g)) return e;
+    MHH_REQUIRE(order == 2 || order == 4, "order must be 2 or 4 (grid.swspatialorder)");
+    MHH_REQUIRE(f != nullptr && f->nscalars >= 0 && f->nscalars <= MHH_MAX_SCALARS, "fields");
+    MHH_REQUIRE(b_index >= 0 && b_index < f->nscalars, "b_index must name a scalar of f");
+    MHH_REQUIRE(f->wt && f->s[b_index], "null field");
+    const bool slope = (alpha != 0.) || (n2 != 0.);
+    MHH_REQUIRE(!slope || (f->ut && f->st[b_index] && f->u && f->w), "the slope / stratified form needs ut, bt, u and w");
+    MHH_REQUIRE(g->kgc >= (order == 4 ? 2 : 1), "vertical ghost cells: kgc >= 2 at 4th order");
+    MHH_REQUIRE(!slope || g->igc >= (order == 4 ? 2 : 1), "ghost cells in x: igc >= 2 for the 4th-order slope form");
+    hipStream_t st = as_stream(stream);
+#define CALL(TF) buoy_tend<TF>(g, order, f, b_index, alpha, n2, utrans, st)
+    return MHH_DISPATCH(g, CALL);
+#undef CALL
+}
+
+// Thermo_buoy calc_N2 (src/thermo_buoy.cxx:49-61)
+template<class TF>
+struct BuoyN2Op
+{
+    GridDev<TF> g; TF* __restrict__ N2; const TF* __restrict__ b; TF bg_n2;
+    __device__ void operator()(int, int, int k, int c) const { N2[c] = buoy_N2(b[c-g.ijcells], b[c+g.ijcells], g.dzi[k], bg_n2); }
+};
+MHH_API int mhh_thermo_buoy_N2(const mhh_grid* g, void* N2, const void* b, double bg_n2, void* stream)
+{
+    if (int e = check_grid(g)) return e;
+    MHH_REQUIRE(N2 && b, "null field");
+#define CALL(TF) [&]{ BuoyN2Op<TF> op{make_grid<TF>(g), mp<TF>(N2), cp<TF>(b), TF(bg_n2)}; \
+                      return launch_interior(as_stream(stream), op.g, g->kstart, g->kend, op); }()
+    return MHH_DISPATCH(g, CALL);
+#undef CALL
+}
+
 // =======================================================================================================
 // Timeloop rk3/rk4 substep (src/timeloop.cxx:250-334): a += cB*dt*at; at = cA_next*at (interior) or 0 (all cells)
 // =======================================================================================================

@@ -27,6 +27,7 @@ template<class TF> struct ViscFields
     const TF* __restrict__ N2; const TF* __restrict__ th; const TF* __restrict__ thref; const TF* __restrict__ mlen0; const TF* __restrict__ mlen2;
     TF grav, tPr; int sm, neutral, ex;
     TF rtPr;                       // RN(1 / tPr) from the host, or 0: the division by tPr as it stands (div_known, cell_ops.h)
+    int bkind; TF bg_n2;           // th is Thermo_buoy's b (bkind 1): N2 = calc_N2 of src/thermo_buoy.cxx:49-61, no thref
 };
 
 // acc + 0.125*q and 2*acc + c as ONE fma each: the products with powers of two are exact (q, acc far from the subnormal range or exactly
@@ -101,7 +102,7 @@ __global__ void __launch_bounds__(64*NJ, MHH_VISC_OCC) visc_march_kernel(const G
 #ifndef MHH_VISC_LANE_QUOT
 #define MHH_VISC_LANE_QUOT 1
 #endif
-    const bool lane_quot = MHH_VISC_LANE_QUOT && !f.neutral && !EXT_N2 && f.thref && (ke - kb) <= 64;
+    const bool lane_quot = MHH_VISC_LANE_QUOT && !f.neutral && !EXT_N2 && !f.bkind && f.thref && (ke - kb) <= 64;
     TF gq = TF(0);
     if (lane_quot) { const int kq = kb + tx; gq = f.grav / f.thref[kq < g.kcells ? kq : g.kcells-1] * TF(0.5); }   // grav/thref[k] * 0.5: the first product of N2 below
     TF bu0 = 0, bu1 = 0, bv0 = 0, bv1 = 0;                            // carried bottom-face terms: the squares (their 1/8 is applied where they are added)
@@ -166,6 +167,7 @@ __global__ void __launch_bounds__(64*NJ, MHH_VISC_OCC) visc_march_kernel(const G
             {
                 if (mo) n2 = dbdz_c;
                 else if (EXT_N2) n2 = f.N2[c];
+                else if (f.bkind) n2 = buoy_N2(thm, thp, uniform_load(g.dzi, k), f.bg_n2);
                 else
                 {
                     const TF gth = lane_quot ? value_of_lane(gq, k - kb, f.grav/f.thref[k]*TF(0.5)) : f.grav/uniform_load(f.thref, k)*TF(0.5);
@@ -204,6 +206,7 @@ int visc_launch(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p
     vf.dudz = cp<TF>(f->dudz); vf.dvdz = cp<TF>(f->dvdz); vf.dbdz = cp<TF>(f->dbdz); vf.z0m = cp<TF>(f->z0m);
     vf.N2 = cp<TF>(p->N2); vf.th = cp<TF>(th); vf.thref = cp<TF>(p->thref); vf.mlen0 = cp<TF>(p->mlen0); vf.mlen2 = cp<TF>(p->mlen2);
     vf.grav = TF(p->grav); vf.tPr = TF(p->tPr); vf.sm = p->surface_model; vf.neutral = p->neutral; vf.ex = ex;
+    vf.bkind = p->buoyancy_kind; vf.bg_n2 = TF(p->bg_n2);
 #ifndef MHH_VISC_DIVKNOWN
 #define MHH_VISC_DIVKNOWN 1
 #endif

@@ -98,13 +98,29 @@ struct Thermo
     TF* N2_g = nullptr;            // get_thermo_field("N2") result, or null to have it evaluated from scalar `th`
     std::string th = "th"; TF* thref_g = nullptr; TF* threfh_g = nullptr; TF grav = 9.81;
     int swspatialorder = 2;        // grid.swspatialorder: calc_buoyancy_tend_2nd / _4th (src/thermo_dry.cxx:557-562)
+    // swthermo == "buoy" (Thermo_buoy, src/thermo_buoy.cxx:303-325): the buoyancy scalar, [thermo] alpha and N2 (bs.alpha, bs.n2),
+    // grid.utrans. alpha == 0 and n2 == 0: the flat form (wt only), otherwise the slope / stratified form (ut, wt, bt)
+    std::string b = "b"; TF alpha = 0, n2 = 0, utrans = 0;
     std::string get_switch() const { return swthermo; }
-    // Thermo_dry::exec (src/thermo_dry.cxx:551-565): the buoyancy tendency of w; defined after Fields/Grid below
+    // Thermo_dry::exec (src/thermo_dry.cxx:551-565): the buoyancy tendency of w; Thermo_buoy::exec (src/thermo_buoy.cxx:347-395):
+    // that of w, or of u, w and b. Defined after Fields/Grid below
     template<class G, class F> void exec(G& grid, F& fields, void* stream = nullptr)
     {
-        if (swthermo != "dry") return;
         mhh_grid g = grid.abi();
-        mhh_check(mhh_thermo_dry_buoyancy_tend(&g, swspatialorder, fields.mt.at("w")->fld_g, fields.sp.at(th)->fld_g, threfh_g, grav, stream));
+        if (swthermo == "dry")
+            mhh_check(mhh_thermo_dry_buoyancy_tend(&g, swspatialorder, fields.mt.at("w")->fld_g, fields.sp.at(th)->fld_g, threfh_g, grav, stream));
+        else if (swthermo == "buoy")
+        {
+            mhh_fields f = abi_fields(fields);
+            mhh_check(mhh_thermo_buoy_tend(&g, swspatialorder, &f, scalar_index(fields, b), alpha, n2, utrans, stream));
+        }
+    }
+    // Thermo_buoy::get_thermo_field_g("N2") (src/thermo_buoy.cxx:402-415, calc_N2 :49-61) into a caller-owned 3-D device field
+    template<class G, class F> void get_thermo_field_N2(G& grid, F& fields, TF* N2_out, void* stream = nullptr)
+    {
+        if (swthermo != "buoy") throw std::runtime_error("get_thermo_field_N2: swthermo=buoy only");
+        mhh_grid g = grid.abi();
+        mhh_check(mhh_thermo_buoy_N2(&g, N2_out, fields.sp.at(b)->fld_g, n2, stream));
     }
 };
 struct Stats {};                   // calc_tend is a no-op off sampling steps (src/stats.cxx:1893-1896)
@@ -383,6 +399,11 @@ class Diff
                 p.buoyancy = fold_buoyancy->swspatialorder; p.th_for_N2 = scalar_index(fields, fold_buoyancy->th);
                 p.threfh = fold_buoyancy->threfh_g; p.grav = fold_buoyancy->grav;
             }
+            else if (fold_buoyancy && fold_buoyancy->get_switch() == "buoy")
+            {   // the flat form is folded into the pass; the slope / stratified form runs on its own first, inside mhh_rhs_exec
+                p.buoyancy = fold_buoyancy->swspatialorder; p.buoyancy_kind = 1; p.th_for_N2 = scalar_index(fields, fold_buoyancy->b);
+                p.bg_n2 = fold_buoyancy->n2; p.alpha = fold_buoyancy->alpha; p.utrans = fold_buoyancy->utrans;
+            }
             advec.mark_limited(f);
             mhh_check(mhh_rhs_exec(&g, a, scheme, &f, &p, stream));
         }
@@ -413,7 +434,12 @@ class Diff
             if (thermo && !p.neutral)
             {
                 p.N2 = thermo->N2_g;
-                if (!p.N2) { p.th_for_N2 = scalar_index(fields, thermo->th); p.thref = thermo->thref_g; p.grav = thermo->grav; }
+                if (p.N2) {}
+                else if (thermo->get_switch() == "buoy")      // N2 of b inside the kernel (Thermo_buoy calc_N2, src/thermo_buoy.cxx:49-61)
+                {
+                    p.th_for_N2 = scalar_index(fields, thermo->b); p.buoyancy_kind = 1; p.bg_n2 = thermo->n2;
+                }
+                else { p.th_for_N2 = scalar_index(fields, thermo->th); p.thref = thermo->thref_g; p.grav = thermo->grav; }
             }
             return p;
         }

@@ -27,6 +27,14 @@ CASES = {
     # gabls1 (cases/gabls1/gabls1.ini: cs = 0.1, 400 m domain at 32^2 columns, scaled with the column count)
     "gabls1": dict(advec=ADVEC_2I5, diff=DIFF_SMAG2, pres=2, order=2, gc=(3, 3, 1), size=(12800., 12800., 400.), nscalars=1, sm=1, visc=1e-5, cs=0.1),
     "moser600": dict(advec=ADVEC_4, diff=DIFF_4, pres=4, order=4, gc=(3, 3, 3), size=(2*math.pi, math.pi, 2.), nscalars=0, sm=0, visc=1e-5),
+    # Thermo_buoy cases (swthermo=buoy, src/thermo_buoy.cxx): scalar 0 is the buoyancy b, whose flat-form tendency of w is folded
+    # into the RHS pass and whose N2 feeds exec_viscosity inline. drycbl: cases/drycbl/drycbl.ini (its jtot = 1 is the usual shape
+    # of the family; 512^3 and 1024 x 1 x 384 = vanheerwaarden2016 are the sizes the tests run). sbl: cases/SBL_Smag/SBL1800.ini
+    # (tPr = 10, surface model) with the 2i5 advection of the second-order LES cases.
+    "drycbl": dict(advec=ADVEC_4, diff=DIFF_4, pres=4, order=4, gc=(3, 3, 3), size=(1., 1., 1.2908699973147109), nscalars=1, sm=0, visc=8e-5,
+                   thermo="buoy"),
+    "sbl": dict(advec=ADVEC_2I5, diff=DIFF_SMAG2, pres=2, order=2, gc=(3, 3, 1), size=(27.386127875258303, 27.386127875258303, 18.074844397670482),
+                nscalars=1, sm=1, visc=1.5e-5, tPr=10., thermo="buoy"),
 }
 
 FIELDS3 = ("u", "v", "w", "ut", "vt", "wt")
@@ -121,7 +129,8 @@ class HotPath:
             self.u, self.v, self.w = rnd(n3, -1, 1), rnd(n3, -1, 1), rnd(n3, -0.5, 0.5)
             self.ut, self.vt, self.wt = rnd(n3, 0, 1e-3), rnd(n3, 0, 1e-3), rnd(n3, 0, 1e-3)
             zc = torch.from_numpy(g.z.astype(np.float64)).to(self.device).to(td)
-            self.s = [(300. + 0.003*zc[:, None, None] + rnd(n3, -0.05, 0.05)).contiguous() for _ in range(nsc)]
+            s0 = 0. if cfg.get("thermo") == "buoy" else 300.          # a buoyancy b has no reference level
+            self.s = [(s0 + 0.003*zc[:, None, None] + rnd(n3, -0.05, 0.05)).contiguous() for _ in range(nsc)]
             self.st = [rnd(n3, 0, 1e-4) for _ in range(nsc)]
             self.surf = {k: rnd(n2, 0, 1e-2) for k in SURF}
             self.surf["dbdz"] = rnd(n2, 0, 1e-4)
@@ -155,8 +164,13 @@ class HotPath:
         self.work = torch.zeros(16, device=self.device, dtype=torch.float64)
         # Diff_smag2::prepare_device: per-level mixing-length table from the host libm
         self.params = p = capi.MhhDiffParams()
-        p.cs, p.tPr, p.surface_model, p.neutral, p.N2, p.th_for_N2, p.grav = cfg.get("cs", 0.23), 1./3., cfg["sm"], 0, None, 0, 9.81
+        p.cs, p.tPr, p.surface_model, p.neutral, p.N2, p.th_for_N2, p.grav = cfg.get("cs", 0.23), cfg.get("tPr", 1./3.), cfg["sm"], 0, None, 0, 9.81
         p.thref = self.thref.data_ptr()
+        # Thermo_buoy: scalar 0 is b. Its N2 is evaluated inside exec_viscosity, and Thermo_buoy::exec (flat form: no slope, no
+        # background N2) is folded into the RHS pass as the first term of wt (src/model.cxx:366,388)
+        self.buoyant = cfg.get("thermo") == "buoy" and nsc >= 1
+        if self.buoyant:
+            p.buoyancy, p.buoyancy_kind, p.bg_n2, p.alpha, p.utrans = cfg["order"], 1, 0., 0., 0.
         if cfg["diff"] == DIFF_SMAG2:
             ml = np.zeros(g.kcells, dtype=g.np_dtype)
             self._ok(self.lib.mhh_smag2_mlen0_host(g.host_struct(), p.cs, ml.ctypes.data))
@@ -396,6 +410,9 @@ class HotPath:
         self._ok(self.lib.mhh_rhs_exec(self.G, self.cfg["advec"], self.cfg["diff"], C.byref(self.fields), C.byref(self.params), self.stream))
 
     def rhs_unfused(self):
+        if self.buoyant:            # Thermo_buoy::exec on its own, then Advec::exec and Diff::exec
+            p = self.params
+            self._ok(self.lib.mhh_thermo_buoy_tend(self.G, p.buoyancy, C.byref(self.fields), p.th_for_N2, p.alpha, p.bg_n2, p.utrans, self.stream))
         self._ok(self.lib.mhh_advec_exec(self.G, self.cfg["advec"], C.byref(self.fields), self.stream))
         self._ok(self.lib.mhh_diff_exec(self.G, self.cfg["diff"], C.byref(self.fields), C.byref(self.params), self.stream))
 
