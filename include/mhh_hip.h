@@ -342,29 +342,24 @@ int mhh_halo_pack_rows  (const mhh_grid* g, void* const* fields, int nfields, in
                          void* send_south, void* send_north, void* stream);
 int mhh_halo_unpack_rows(const mhh_grid* g, void* const* fields, int nfields, int rows_south, int rows_north,
                          const void* recv_from_south, const void* recv_from_north, void* stream);
-/* pres_2 (and pres_4, below) split at the transposes. All-to-all buffers hold mhh_pres_slab_xbuf_elems() COMPLEX elements,
- * laid out [peer][k][jl][kxl] so that one equal-split all_to_all moves them.                               */
+/* pres_2 (and pres_4, below) split at the transposes, in nchunks slices of k (mhh_pres_slab_set_chunks, ktot % nchunks == 0; a new
+ * plan has ONE slice = all levels), so that the host can overlap the all-to-all of slice c with the transforms of slice c+1 (the
+ * reference's FFT::exec_forward transposes and transforms plane batches in turn as well, src/fft.cxx:451-583). The two all-to-all
+ * buffers hold mhh_pres_slab_xbuf_elems() COMPLEX elements each, laid out [slice][peer][k in slice][jl][kxl]: slice c is the
+ * equal-split all-to-all of elements [c*n, (c+1)*n), n = mhh_pres_slab_xbuf_elems() / nchunks. Call order per solve (order 2):
+ *   north-south halo of vt (rows_south = 1 is all the input reads);  mhh_pres_input_packed(g, 2) into mhh_pres_slab_packed;
+ *   for c: fwd_x_pack_chunk(c) -> all-to-all(c);  for c: fwd_y_chunk(c);  solve_y;
+ *   for c: bwd_y_chunk(c) -> all-to-all(c);       for c: bwd_x_chunk(c);
+ *   unpack_output_slab; halo of p (rows_north = 1); output_south_row     -- or: unpack_slab; halo of p; mhh_pres_output_order(g, 2).
+ * unpack_output_slab applies Pres_2::output (src/pres_2.cxx:365-387) in the unpack kernel for everything but vt on the
+ * southernmost row (its p[j-1] lives on the south neighbour): same bits as the second ending, one pass over p, ut, vt, wt less. */
 typedef struct mhh_pres_slab_plan mhh_pres_slab_plan;
 int  mhh_pres_slab_plan_create(const mhh_grid* g, const void* host_dz, const void* host_dzhi,
                                const void* host_rhoref, const void* host_rhorefh, mhh_pres_slab_plan** out);
 void mhh_pres_slab_plan_destroy(mhh_pres_slab_plan* plan);
 unsigned long long mhh_pres_slab_xbuf_elems(const mhh_pres_slab_plan* plan);
 void* mhh_pres_slab_packed(mhh_pres_slab_plan* plan);   /* plan-owned packed-divergence buffer (imax*jmax*kmax) */
-int mhh_pres_fwd_x_pack       (mhh_pres_slab_plan* plan, const mhh_grid* g, void* p_packed, void* sendbuf, void* stream);
-int mhh_pres_fwd_y_solve_bwd_y(mhh_pres_slab_plan* plan, const mhh_grid* g, void* recvbuf, void* sendbuf, void* stream);
-int mhh_pres_bwd_x_unpack     (mhh_pres_slab_plan* plan, const mhh_grid* g, void* recvbuf, const mhh_fields* f, void* stream);
-/* the same with Pres_2::output (src/pres_2.cxx:365-387) in the unpack kernel, for everything but vt on the southernmost row
- * (its p[j-1] lives on the south neighbour): exchange the one-row halo of p, then mhh_pres_output_south_row. Same bits as
- * mhh_pres_bwd_x_unpack + halo + mhh_pres_output_order, one pass over p, ut, vt, wt less. */
-int mhh_pres_bwd_x_unpack_output(mhh_pres_slab_plan* plan, const mhh_grid* g, void* recvbuf, const mhh_fields* f, void* stream);
-int mhh_pres_output_south_row (const mhh_grid* g, const mhh_fields* f, void* stream);
-/* The same solve in nchunks slices of k (ktot % nchunks == 0), so that the host can overlap the all-to-all of slice c with the
- * transforms of slice c+1 (the reference's FFT::exec_forward transposes and transforms plane batches in turn as well,
- * src/fft.cxx:451-583). The all-to-all buffers are then laid out [slice][peer][k in slice][jl][kxl]: slice c is the equal-split
- * all-to-all of elements [c*n, (c+1)*n), n = mhh_pres_slab_xbuf_elems() / nchunks. Call order per solve:
- *   for c: fwd_x_pack_chunk(c) -> all-to-all(c);  for c: fwd_y_chunk(c);  solve_y;
- *   for c: bwd_y_chunk(c) -> all-to-all(c);        for c: bwd_x_chunk(c);  unpack_output_slab; p halo; output_south_row.      */
-int mhh_pres_slab_set_chunks(mhh_pres_slab_plan* plan, int nchunks);          /* 1 = the unsliced calls above */
+int mhh_pres_slab_set_chunks(mhh_pres_slab_plan* plan, int nchunks);          /* rebuilds the plan's transforms for ktot / nchunks levels */
 int mhh_pres_slab_chunks(const mhh_pres_slab_plan* plan);
 int mhh_pres_fwd_x_pack_chunk(mhh_pres_slab_plan* plan, const mhh_grid* g, void* p_packed, void* sendbuf, int c, void* stream);
 int mhh_pres_fwd_y_chunk     (mhh_pres_slab_plan* plan, const mhh_grid* g, void* recvbuf, int c, void* stream);
@@ -372,6 +367,15 @@ int mhh_pres_solve_y         (mhh_pres_slab_plan* plan, const mhh_grid* g, void*
 int mhh_pres_bwd_y_chunk     (mhh_pres_slab_plan* plan, const mhh_grid* g, void* sendbuf, int c, void* stream);
 int mhh_pres_bwd_x_chunk     (mhh_pres_slab_plan* plan, const mhh_grid* g, void* recvbuf, int c, void* stream);
 int mhh_pres_unpack_output_slab(mhh_pres_slab_plan* plan, const mhh_grid* g, const mhh_fields* f, void* stream);
+int mhh_pres_output_south_row (const mhh_grid* g, const mhh_fields* f, void* stream);
+/* The same calls on slice 0 of a ONE-slice plan, joined per side of the transposes: fwd_x_pack = fwd_x_pack_chunk(0);
+ * fwd_y_solve_bwd_y = fwd_y_chunk(0), solve_y, bwd_y_chunk(0); bwd_x_unpack = bwd_x_chunk(0), unpack_slab; bwd_x_unpack_output =
+ * bwd_x_chunk(0), unpack_output_slab. On a plan with more than one slice they return MHH_EINVAL (the message names
+ * mhh_pres_slab_set_chunks(plan, 1)): its transforms and buffer layout are those of the slices. */
+int mhh_pres_fwd_x_pack       (mhh_pres_slab_plan* plan, const mhh_grid* g, void* p_packed, void* sendbuf, void* stream);
+int mhh_pres_fwd_y_solve_bwd_y(mhh_pres_slab_plan* plan, const mhh_grid* g, void* recvbuf, void* sendbuf, void* stream);
+int mhh_pres_bwd_x_unpack     (mhh_pres_slab_plan* plan, const mhh_grid* g, void* recvbuf, const mhh_fields* f, void* stream);
+int mhh_pres_bwd_x_unpack_output(mhh_pres_slab_plan* plan, const mhh_grid* g, void* recvbuf, const mhh_fields* f, void* stream);
 /* pres_4 on the slab (src/pres_4.cxx:64-140; the reference's MPI decomposition swaps the mode indices after the x/y transpose as
  * Pres_2 does, src/pres_4.cxx:327-470). mhh_pres_slab_plan_create_order is the slab counterpart of mhh_pres_plan_create
  * (Pres_4::set_values, src/pres_4.cxx:179-252, from the HOST metrics dzi4 / dzhi4; order 2 reads dz, dzhi, rhoref, rhorefh and gives
@@ -379,8 +383,7 @@ int mhh_pres_unpack_output_slab(mhh_pres_slab_plan* plan, const mhh_grid* g, con
  * keeps the LU factors of the 7-band system of every column of the rank (src/pres_4.cxx:358-470, 574-730): 7*(kmax+4)*nxb*jtot
  * values, nxb = ceil((itot/2+1)/npy). Call order per solve (order 4):
  *   north-south halo of vt, rows_south = 2, rows_north = 1 (the input reads vt[j-1..j+2], src/pres_4.cxx:312-315);
- *   mhh_pres_input_packed(g, 4) into mhh_pres_slab_packed;  fwd_x_pack -> all-to-all -> fwd_y_solve_bwd_y -> all-to-all -> bwd_x_unpack
- *   (or, k-sliced: the chunk calls above with solve_y, then mhh_pres_unpack_slab);
+ *   mhh_pres_input_packed(g, 4) into mhh_pres_slab_packed;  the chunk calls above with solve_y, then mhh_pres_unpack_slab;
  *   halo of p, rows_south = 1, rows_north = 2 (the output reads p[j-2..j+1], src/pres_4.cxx:555-569);  mhh_pres_output_order(g, 4).
  * The unpack writes p's interior rows, its x halo and the four mirrored vertical ghost levels (src/pres_4.cxx:481-528). The fused
  * Pres_2::output entry points (bwd_x_unpack_output, unpack_output_slab) and the LDS x stages (mhh_pres_slab_lds_*) refuse an order-4
@@ -389,15 +392,14 @@ int mhh_pres_slab_plan_create_order(const mhh_grid* g, int order /*2|4*/, const 
                                     const void* host_dzi4, const void* host_dzhi4, const void* host_rhoref, const void* host_rhorefh,
                                     mhh_pres_slab_plan** out);
 int mhh_pres_slab_order(const mhh_pres_slab_plan* plan);
-/* the unpack of mhh_pres_bwd_x_unpack alone (either order): the packed solution of the last bwd_x_chunk into p (src/pres_2.cxx:333-362,
- * src/pres_4.cxx:481-528) */
+/* the unpack (either order): the packed solution of the last bwd_x_chunk into p (src/pres_2.cxx:333-362, src/pres_4.cxx:481-528) */
 int mhh_pres_unpack_slab(mhh_pres_slab_plan* plan, const mhh_grid* g, const mhh_fields* f, void* stream);
 /* The x stages of the slab solve with the transforms in LDS (csrc/pres_lds.h; power-of-two itot, jmax a multiple of 8;
  * mhh_pres_slab_has_lds tells): Pres_2::input + the transform along x (src/pres_2.cxx:156-196, src/fft.cxx:451-497) of k-slice c
  * written straight into segment c of the send buffer of Transpose::exec_xy (src/transpose.cxx:170-193), and the transform back
  * along x + p with its x halo + Pres_2::output (src/fft.cxx:540-583, src/pres_2.cxx:333-387) read straight from segment c of the
- * receive buffer of Transpose::exec_yx. They replace mhh_pres_input_packed + fwd_x_pack[_chunk] and bwd_x[_chunk] +
- * unpack_output_slab; the y stage, the one-row halo of p and mhh_pres_output_south_row stay. c = 0 with unsliced transposes.
+ * receive buffer of Transpose::exec_yx. They replace mhh_pres_input_packed + fwd_x_pack_chunk and bwd_x_chunk +
+ * unpack_output_slab; the y stage, the one-row halo of p and mhh_pres_output_south_row stay.
  * Same tolerance as the staged form (different transforms, not the same bits). */
 int mhh_pres_slab_has_lds(const mhh_pres_slab_plan* plan);
 int mhh_pres_slab_lds_fwd(mhh_pres_slab_plan* plan, const mhh_grid* g, const mhh_fields* f, double dt, void* sendbuf, int c, void* stream);

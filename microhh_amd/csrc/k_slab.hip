@@ -6,6 +6,7 @@
 // Reference semantics: Boundary_cyclic::exec's MPI path (src/boundary_cyclic.cxx:116-176) and the FFT/solve
 // sequence of src/fft.cxx:451-583 with npx = 1, where only Transpose::exec_xy / exec_yx move data
 // (src/transpose.cxx:170-219) and Pres_2::solve swaps the mode indices (src/pres_2.cxx:297-299).
+#include <utility>
 #include "fft_lifetime.h"
 #include "pres_lds_slab.h"
 #include "pres4_bands.h"
@@ -98,11 +99,10 @@ struct mhh_pres_slab_plan
     void* bmati = nullptr; void* bmatj = nullptr; void* a = nullptr; void* c = nullptr; void* dz = nullptr; void* rhoref = nullptr;
     void* m[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};     // pres_4: the interior rows of the seven bands
     void* packed = nullptr; void* specx = nullptr; void* specy = nullptr; void* work = nullptr;
-    rocfft_plan fx = nullptr, bx = nullptr, fy = nullptr, by = nullptr;
-    // the same transforms over ONE k-slice of ktot / nchunks levels (mhh_pres_slab_set_chunks): slice c of the all-to-all can
-    // travel while slice c+1 is transformed
+    // the transforms over ONE k-slice of ktot / nchunks levels (mhh_pres_slab_set_chunks; one slice = all levels): slice c of the
+    // all-to-all can travel while slice c+1 is transformed
     int nchunks = 1;
-    rocfft_plan cfx = nullptr, cbx = nullptr, cfy = nullptr, cby = nullptr;
+    rocfft_plan fx = nullptr, bx = nullptr, fy = nullptr, by = nullptr;
     rocfft_execution_info info = nullptr;
     void* wb = nullptr; size_t wbs = 0, wb_cap = 0;
     // the x stages with the transforms in LDS (pres_lds.h, pres_lds_slab.h): twiddles exp(-2 pi i m / itot); null = not available
@@ -164,12 +164,30 @@ static int plan1d(rocfft_plan* plan, rocfft_transform_type type, rocfft_result_p
     return MHH_OK;
 }
 
+// the four transforms of the solve over one k-slice of ktot / nchunks levels, in place of the ones the plan has (which live until
+// the new ones exist: rocFFT shares the tables of equal lengths between live plans; a failure leaves the plan as it was). *wbs grows
+// to the largest work area they ask for
+static int slab_fft_plans(mhh_pres_slab_plan* P, int nchunks, size_t* wbs)
+{
+    const int kc = P->ktot / nchunks;
+    const rocfft_array_type R = rocfft_array_type_real, H = rocfft_array_type_hermitian_interleaved, Cx = rocfft_array_type_complex_interleaved;
+    const size_t bx = (size_t)P->jmax*kc, by = (size_t)P->nxb*kc;
+    rocfft_plan n[4] = {nullptr, nullptr, nullptr, nullptr};
+    int e = plan1d(&n[0], rocfft_transform_type_real_forward, rocfft_placement_notinplace, P->dtype, P->itot, bx, R, H, P->itot, P->nxh, wbs);
+    if (!e) e = plan1d(&n[1], rocfft_transform_type_real_inverse, rocfft_placement_notinplace, P->dtype, P->itot, bx, H, R, P->nxh, P->itot, wbs);
+    if (!e) e = plan1d(&n[2], rocfft_transform_type_complex_forward, rocfft_placement_inplace, P->dtype, P->jtot, by, Cx, Cx, P->jtot, P->jtot, wbs);
+    if (!e) e = plan1d(&n[3], rocfft_transform_type_complex_inverse, rocfft_placement_inplace, P->dtype, P->jtot, by, Cx, Cx, P->jtot, P->jtot, wbs);
+    if (!e) { std::swap(n[0], P->fx); std::swap(n[1], P->bx); std::swap(n[2], P->fy); std::swap(n[3], P->by); P->nchunks = nchunks; }
+    for (rocfft_plan p : n) if (p) rocfft_plan_destroy(p);
+    return e;
+}
+
 MHH_API void mhh_pres_slab_plan_destroy(mhh_pres_slab_plan* P)
 {
     if (P && P->tx_lds) { (void)hipFree(P->tx_lds); P->tx_lds = nullptr; }
     if (P && P->ty_lds) { (void)hipFree(P->ty_lds); P->ty_lds = nullptr; }
     if (!P) return;
-    for (rocfft_plan p : {P->fx, P->bx, P->fy, P->by, P->cfx, P->cbx, P->cfy, P->cby}) if (p) rocfft_plan_destroy(p);
+    for (rocfft_plan p : {P->fx, P->bx, P->fy, P->by}) if (p) rocfft_plan_destroy(p);
     if (P->info) rocfft_execution_info_destroy(P->info);
     for (void* b : {P->bmati, P->bmatj, P->a, P->c, P->dz, P->rhoref, P->packed, P->specx, P->specy, P->work, P->wb}) if (b) (void)hipFree(b);
     for (void* b : P->m) if (b) (void)hipFree(b);
@@ -210,12 +228,7 @@ MHH_API int mhh_pres_slab_plan_create_order(const mhh_grid* g, int order, const 
     if (!e)
     {
         fft_acquire();
-        const rocfft_array_type R = rocfft_array_type_real, H = rocfft_array_type_hermitian_interleaved, Cx = rocfft_array_type_complex_interleaved;
-        const size_t bx = (size_t)g->jmax*g->ktot, by = (size_t)P->nxb*g->ktot;
-        e = plan1d(&P->fx, rocfft_transform_type_real_forward, rocfft_placement_notinplace, g->dtype, g->itot, bx, R, H, g->itot, P->nxh, &P->wbs);
-        if (!e) e = plan1d(&P->bx, rocfft_transform_type_real_inverse, rocfft_placement_notinplace, g->dtype, g->itot, bx, H, R, P->nxh, g->itot, &P->wbs);
-        if (!e) e = plan1d(&P->fy, rocfft_transform_type_complex_forward, rocfft_placement_inplace, g->dtype, g->jtot, by, Cx, Cx, g->jtot, g->jtot, &P->wbs);
-        if (!e) e = plan1d(&P->by, rocfft_transform_type_complex_inverse, rocfft_placement_inplace, g->dtype, g->jtot, by, Cx, Cx, g->jtot, g->jtot, &P->wbs);
+        e = slab_fft_plans(P, 1, &P->wbs);
         if (!e && rocfft_execution_info_create(&P->info) != rocfft_status_success) { set_error("FFT error: execution_info_create"); e = MHH_EFFT; }
         if (!e && P->wbs)
         {
@@ -550,27 +563,36 @@ __global__ void __launch_bounds__(128) hdma_slab_kernel(TF* __restrict__ p, cons
 #undef A
 }
 
-static int slab_factor(mhh_pres_slab_plan* P)
+// the launches of the factor and sweep kernels of the plan's order on TF
+template<class TF>
+static void slab_factor_launch(mhh_pres_slab_plan* P)
 {
     dim3 gf((P->jtot + 63)/64, P->nxb);
     const size_t ny = (size_t)P->nxb*P->jtot*P->ktot;
     if (P->order == 4)
-    {
-#define M7(TF) cp<TF>(P->m[0]), cp<TF>(P->m[1]), cp<TF>(P->m[2]), cp<TF>(P->m[3]), cp<TF>(P->m[4]), cp<TF>(P->m[5]), cp<TF>(P->m[6])
-        if (P->dtype == MHH_F64)
-            hipLaunchKernelGGL(hdma_slab_factor_kernel<double>, gf, dim3(64), 0, 0, (double*)P->work, cp<double>(P->bmati), cp<double>(P->bmatj), M7(double),
-                               P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
-        else
-            hipLaunchKernelGGL(hdma_slab_factor_kernel<float>, gf, dim3(64), 0, 0, (float*)P->work, cp<float>(P->bmati), cp<float>(P->bmatj), M7(float),
-                               P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
-#undef M7
-    }
-    else if (P->dtype == MHH_F64)
-        hipLaunchKernelGGL(tdma_slab_factor_kernel<double>, gf, dim3(64), 0, 0, (double*)P->work, (double*)P->work + ny, cp<double>(P->bmati), cp<double>(P->bmatj),
-                           cp<double>(P->a), cp<double>(P->c), cp<double>(P->dz), cp<double>(P->rhoref), P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
+        hipLaunchKernelGGL(hdma_slab_factor_kernel<TF>, gf, dim3(64), 0, 0, mp<TF>(P->work), cp<TF>(P->bmati), cp<TF>(P->bmatj),
+                           cp<TF>(P->m[0]), cp<TF>(P->m[1]), cp<TF>(P->m[2]), cp<TF>(P->m[3]), cp<TF>(P->m[4]), cp<TF>(P->m[5]), cp<TF>(P->m[6]),
+                           P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
     else
-        hipLaunchKernelGGL(tdma_slab_factor_kernel<float>, gf, dim3(64), 0, 0, (float*)P->work, (float*)P->work + ny, cp<float>(P->bmati), cp<float>(P->bmatj),
-                           cp<float>(P->a), cp<float>(P->c), cp<float>(P->dz), cp<float>(P->rhoref), P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
+        hipLaunchKernelGGL(tdma_slab_factor_kernel<TF>, gf, dim3(64), 0, 0, mp<TF>(P->work), mp<TF>(P->work) + ny, cp<TF>(P->bmati), cp<TF>(P->bmatj),
+                           cp<TF>(P->a), cp<TF>(P->c), cp<TF>(P->dz), cp<TF>(P->rhoref), P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
+}
+template<class TF>
+static void slab_solve_launch(mhh_pres_slab_plan* P, hipStream_t st)
+{
+    const size_t ny = (size_t)P->nxb*P->jtot*P->ktot;
+    dim3 gs((2*P->jtot + 127)/128, P->nxb);
+    if (P->order == 4)
+        hipLaunchKernelGGL(hdma_slab_kernel<TF>, gs, dim3(128), 0, st, mp<TF>(P->specy), cp<TF>(P->work), P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
+    else
+        hipLaunchKernelGGL(tdma_slab_kernel<TF>, gs, dim3(128), 0, st, mp<TF>(P->specy), cp<TF>(P->work), cp<TF>(P->work) + ny,
+                           cp<TF>(P->a), cp<TF>(P->dz), P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
+}
+static int slab_factor(mhh_pres_slab_plan* P)
+{
+#define CALL(TF) slab_factor_launch<TF>(P)
+    MHH_DISPATCH(P, CALL);
+#undef CALL
     hipError_t h = hipGetLastError(); if (h == hipSuccess) h = hipStreamSynchronize(0);
     if (h != hipSuccess) { set_error("%s: %s", P->order == 4 ? "hdma_slab_factor" : "tdma_slab_factor", hipGetErrorString(h)); return MHH_EHIP; }
     return MHH_OK;
@@ -578,19 +600,9 @@ static int slab_factor(mhh_pres_slab_plan* P)
 // the k-sweeps of every column of the rank's slab on specy: Thomas (pres_2) or the factored 7-band substitution (pres_4)
 static int slab_column_solve(mhh_pres_slab_plan* P, hipStream_t st)
 {
-    const size_t ny = (size_t)P->nxb*P->jtot*P->ktot;
-    dim3 gs((2*P->jtot + 127)/128, P->nxb);
-    if (P->order == 4)
-    {
-        if (P->dtype == MHH_F64) hipLaunchKernelGGL(hdma_slab_kernel<double>, gs, dim3(128), 0, st, (double*)P->specy, cp<double>(P->work), P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
-        else                     hipLaunchKernelGGL(hdma_slab_kernel<float>,  gs, dim3(128), 0, st, (float*)P->specy,  cp<float>(P->work),  P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
-    }
-    else if (P->dtype == MHH_F64)
-        hipLaunchKernelGGL(tdma_slab_kernel<double>, gs, dim3(128), 0, st, (double*)P->specy, cp<double>(P->work), cp<double>(P->work) + ny,
-                           cp<double>(P->a), cp<double>(P->dz), P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
-    else
-        hipLaunchKernelGGL(tdma_slab_kernel<float>, gs, dim3(128), 0, st, (float*)P->specy, cp<float>(P->work), cp<float>(P->work) + ny,
-                           cp<float>(P->a), cp<float>(P->dz), P->nxh, P->nxb, P->rank*P->nxb, P->jtot, P->ktot);
+#define CALL(TF) slab_solve_launch<TF>(P, st)
+    MHH_DISPATCH(P, CALL);
+#undef CALL
     MHH_LAUNCH_CHECK();
     return MHH_OK;
 }
@@ -671,145 +683,18 @@ static int slab_match(const mhh_pres_slab_plan* P, const mhh_grid* g)
     return MHH_OK;
 }
 
-// stage 1: x transform of the packed divergence + pack for the forward all-to-all
-MHH_API int mhh_pres_fwd_x_pack(mhh_pres_slab_plan* P, const mhh_grid* g, void* p_packed, void* sendbuf, void* stream)
-{
-    if (int e = slab_match(P, g)) return e;
-    MHH_REQUIRE(sendbuf != nullptr, "sendbuf");
-    if (!p_packed) p_packed = P->packed;
-    hipStream_t st = as_stream(stream);
-    MHH_FFT_TRY(rocfft_execution_info_set_stream(P->info, st));
-    void* in[1] = {p_packed}; void* out[1] = {P->specx};
-    MHH_FFT_TRY(rocfft_execute(P->fx, in, out, P->info));
-    dim3 grid((P->npy*P->nxb + 255)/256, P->jmax, P->ktot);
-    if (g->dtype == MHH_F64) hipLaunchKernelGGL((xbuf_x_kernel<double, true>), grid, dim3(256), 0, st, (C2<double>*)P->specx, (C2<double>*)sendbuf, P->nxh, P->nxb, P->jmax, P->ktot, P->npy);
-    else                     hipLaunchKernelGGL((xbuf_x_kernel<float, true>), grid, dim3(256), 0, st, (C2<float>*)P->specx, (C2<float>*)sendbuf, P->nxh, P->nxb, P->jmax, P->ktot, P->npy);
-    MHH_LAUNCH_CHECK();
-    return MHH_OK;
-}
-// stage 2: after the forward all-to-all: y transform, tridiagonal (pres_2) or 7-band (pres_4) solves, inverse y transform, pack for the way back
-MHH_API int mhh_pres_fwd_y_solve_bwd_y(mhh_pres_slab_plan* P, const mhh_grid* g, void* recvbuf, void* sendbuf, void* stream)
-{
-    if (int e = slab_match(P, g)) return e;
-    MHH_REQUIRE(recvbuf && sendbuf, "buffers");
-    hipStream_t st = as_stream(stream);
-    MHH_FFT_TRY(rocfft_execution_info_set_stream(P->info, st));
-    dim3 gy((unsigned)(((P->nxb + 31)/32) * ((P->jmax + 63)/64) * P->npy), P->ktot);
-    void* io[1] = {P->specy};
-    if (g->dtype == MHH_F64)
-    {
-        hipLaunchKernelGGL((xbuf_y_kernel<double, true>), gy, dim3(256), 0, st, (C2<double>*)P->specy, (C2<double>*)recvbuf, P->nxb, P->jmax, P->jtot, P->ktot);
-        MHH_LAUNCH_CHECK();
-        MHH_FFT_TRY(rocfft_execute(P->fy, io, nullptr, P->info));
-        if (int e = slab_column_solve(P, st)) return e;
-        MHH_FFT_TRY(rocfft_execute(P->by, io, nullptr, P->info));
-        hipLaunchKernelGGL((xbuf_y_kernel<double, false>), gy, dim3(256), 0, st, (C2<double>*)P->specy, (C2<double>*)sendbuf, P->nxb, P->jmax, P->jtot, P->ktot);
-    }
-    else
-    {
-        hipLaunchKernelGGL((xbuf_y_kernel<float, true>), gy, dim3(256), 0, st, (C2<float>*)P->specy, (C2<float>*)recvbuf, P->nxb, P->jmax, P->jtot, P->ktot);
-        MHH_LAUNCH_CHECK();
-        MHH_FFT_TRY(rocfft_execute(P->fy, io, nullptr, P->info));
-        if (int e = slab_column_solve(P, st)) return e;
-        MHH_FFT_TRY(rocfft_execute(P->by, io, nullptr, P->info));
-        hipLaunchKernelGGL((xbuf_y_kernel<float, false>), gy, dim3(256), 0, st, (C2<float>*)P->specy, (C2<float>*)sendbuf, P->nxb, P->jmax, P->jtot, P->ktot);
-    }
-    MHH_LAUNCH_CHECK();
-    return MHH_OK;
-}
-// the unpack of the packed solution into p (unpack_slab_kernel) on `st`
-static int slab_unpack(mhh_pres_slab_plan* P, const mhh_grid* g, const mhh_fields* f, hipStream_t st)
-{
-    dim3 ug((g->icells + 255)/256, g->jmax, g->kmax + (P->order == 2 ? 1 : 4));
-    if (g->dtype == MHH_F64)
-        hipLaunchKernelGGL(unpack_slab_kernel<double>, ug, dim3(256), 0, st, mp<double>(f->p), cp<double>(P->packed), P->order, g->itot, g->jtot, g->jmax, g->kmax, g->igc, g->jgc, g->kgc, g->icells, g->jcells);
-    else
-        hipLaunchKernelGGL(unpack_slab_kernel<float>, ug, dim3(256), 0, st, mp<float>(f->p), cp<float>(P->packed), P->order, g->itot, g->jtot, g->jmax, g->kmax, g->igc, g->jgc, g->kgc, g->icells, g->jcells);
-    MHH_LAUNCH_CHECK();
-    return MHH_OK;
-}
-// stage 3: after the backward all-to-all: inverse x transform, normalise, write p (interior rows, x halo, vertical ghost levels)
-MHH_API int mhh_pres_bwd_x_unpack(mhh_pres_slab_plan* P, const mhh_grid* g, void* recvbuf, const mhh_fields* f, void* stream)
-{
-    if (int e = slab_match(P, g)) return e;
-    MHH_REQUIRE(recvbuf && f && f->p, "buffers");
-    hipStream_t st = as_stream(stream);
-    MHH_FFT_TRY(rocfft_execution_info_set_stream(P->info, st));
-    dim3 grid((P->npy*P->nxb + 255)/256, P->jmax, P->ktot);
-    void* in[1] = {P->specx}; void* out[1] = {P->packed};
-    if (g->dtype == MHH_F64) hipLaunchKernelGGL((xbuf_x_kernel<double, false>), grid, dim3(256), 0, st, (C2<double>*)P->specx, (C2<double>*)recvbuf, P->nxh, P->nxb, P->jmax, P->ktot, P->npy);
-    else                     hipLaunchKernelGGL((xbuf_x_kernel<float, false>), grid, dim3(256), 0, st, (C2<float>*)P->specx, (C2<float>*)recvbuf, P->nxh, P->nxb, P->jmax, P->ktot, P->npy);
-    MHH_LAUNCH_CHECK();
-    MHH_FFT_TRY(rocfft_execute(P->bx, in, out, P->info));
-    return slab_unpack(P, g, f, st);
-}
-// the unpack alone, after the last mhh_pres_bwd_x_chunk of a k-sliced solve
-MHH_API int mhh_pres_unpack_slab(mhh_pres_slab_plan* P, const mhh_grid* g, const mhh_fields* f, void* stream)
-{
-    if (int e = slab_match(P, g)) return e;
-    MHH_REQUIRE(f && f->p, "buffers");
-    return slab_unpack(P, g, f, as_stream(stream));
-}
-// stage 3, fused form: inverse x transform, then unpack + Pres_2::output in one kernel for everything but vt on the southernmost
-// row; the caller exchanges the one-row halo of p and finishes with mhh_pres_output_south_row.
-MHH_API int mhh_pres_bwd_x_unpack_output(mhh_pres_slab_plan* P, const mhh_grid* g, void* recvbuf, const mhh_fields* f, void* stream)
-{
-    if (int e = slab_match(P, g)) return e;
-    MHH_REQUIRE(P->order == 2, "Pres_2::output only: a pres_4 plan takes mhh_pres_bwd_x_unpack, the halo of p and mhh_pres_output_order(g, 4)");
-    MHH_REQUIRE(recvbuf && f && f->p && f->ut && f->vt && f->wt, "buffers");
-    hipStream_t st = as_stream(stream);
-    MHH_FFT_TRY(rocfft_execution_info_set_stream(P->info, st));
-    dim3 grid((P->npy*P->nxb + 255)/256, P->jmax, P->ktot);
-    dim3 ug((g->icells + 255)/256, g->jmax, g->kmax + 1);
-    void* in[1] = {P->specx}; void* out[1] = {P->packed};
-    const bool pow2 = is_pow2(g->itot) && is_pow2(g->jtot);
-#define CALL(TF) [&]{ const GridDev<TF> gd = make_grid<TF>(g); \
-        hipLaunchKernelGGL((xbuf_x_kernel<TF, false>), grid, dim3(256), 0, st, (C2<TF>*)P->specx, (C2<TF>*)recvbuf, P->nxh, P->nxb, P->jmax, P->ktot, P->npy); \
-        if (hipGetLastError() != hipSuccess) return (int)MHH_EHIP; \
-        if (rocfft_execute(P->bx, in, out, P->info) != rocfft_status_success) return (int)MHH_EFFT; \
-        if (pow2) hipLaunchKernelGGL((unpack_out_slab_kernel<true, TF>), ug, dim3(256), 0, st, mp<TF>(f->p), cp<TF>(P->packed), mp<TF>(f->ut), mp<TF>(f->vt), mp<TF>(f->wt), gd.dzhi, \
-                           gd.dxi_t, gd.dyi_t, g->itot, g->jtot, g->jmax, g->kmax, g->igc, g->jgc, g->kgc, g->icells, g->jcells); \
-        else hipLaunchKernelGGL((unpack_out_slab_kernel<false, TF>), ug, dim3(256), 0, st, mp<TF>(f->p), cp<TF>(P->packed), mp<TF>(f->ut), mp<TF>(f->vt), mp<TF>(f->wt), gd.dzhi, \
-                           gd.dxi_t, gd.dyi_t, g->itot, g->jtot, g->jmax, g->kmax, g->igc, g->jgc, g->kgc, g->icells, g->jcells); return (int)MHH_OK; }()
-    if (int e = MHH_DISPATCH(g, CALL)) { set_error("pres_bwd_x_unpack_output: launch / FFT error"); return e; }
-#undef CALL
-    MHH_LAUNCH_CHECK();
-    return MHH_OK;
-}
-MHH_API int mhh_pres_output_south_row(const mhh_grid* g, const mhh_fields* f, void* stream)
-{
-    if (int e = check_grid(g)) return e;
-    MHH_REQUIRE(f && f->p && f->vt && g->jgc >= 1, "null field");
-    dim3 grid((g->imax + 255)/256, g->kmax);
-#define CALL(TF) [&]{ const GridDev<TF> gd = make_grid<TF>(g); \
-        hipLaunchKernelGGL(pres_out_south_row_kernel<TF>, grid, dim3(256), 0, as_stream(stream), mp<TF>(f->vt), cp<TF>(f->p), gd.dyi_t, g->istart, g->iend, g->jstart, g->kstart, g->icells, g->ijcells); return (int)MHH_OK; }()
-    if (int e = MHH_DISPATCH(g, CALL)) return e;
-#undef CALL
-    MHH_LAUNCH_CHECK();
-    return MHH_OK;
-}
-
-
 // =======================================================================================================
-// The same solve in k-slices (src/fft.cxx:451-583 transforms the planes of a field one k-slice at a time too): the buffers of
-// the all-to-alls are laid out [slice][peer][k in slice][jl][kxl], so that slice c is ONE equal-split all-to-all of its own,
-// which the host issues on a second stream while slice c+1 is being transformed (microhh_amd/model.py: HotPath.pres). Every
-// plane goes through the same transform kernels as in the unsliced call; the Thomas sweeps need all slices.
+// The solve works in nchunks k-slices (src/fft.cxx:451-583 transforms the planes of a field one k-slice at a time too; one slice =
+// all levels): the buffers of the all-to-alls are laid out [slice][peer][k in slice][jl][kxl], so that slice c is ONE equal-split
+// all-to-all of its own, which the host issues on a second stream while slice c+1 is being transformed (microhh_amd/model.py:
+// HotPath.pres). Every plane goes through the same transform kernels whatever the slice count; the column solves need all slices.
 // =======================================================================================================
 MHH_API int mhh_pres_slab_set_chunks(mhh_pres_slab_plan* P, int nchunks)
 {
     MHH_REQUIRE(P && nchunks >= 1 && P->ktot % nchunks == 0, "the number of k-slices must divide ktot");
-    for (rocfft_plan* p : {&P->cfx, &P->cbx, &P->cfy, &P->cby}) if (*p) { rocfft_plan_destroy(*p); *p = nullptr; }
-    P->nchunks = nchunks;
-    if (nchunks == 1) return MHH_OK;
-    const int kc = P->ktot / nchunks;
-    const rocfft_array_type R = rocfft_array_type_real, H = rocfft_array_type_hermitian_interleaved, Cx = rocfft_array_type_complex_interleaved;
-    const size_t bx = (size_t)P->jmax*kc, by = (size_t)P->nxb*kc;
+    if (nchunks == P->nchunks) return MHH_OK;
     size_t wbs = P->wbs;
-    int e = plan1d(&P->cfx, rocfft_transform_type_real_forward, rocfft_placement_notinplace, P->dtype, P->itot, bx, R, H, P->itot, P->nxh, &wbs);
-    if (!e) e = plan1d(&P->cbx, rocfft_transform_type_real_inverse, rocfft_placement_notinplace, P->dtype, P->itot, bx, H, R, P->nxh, P->itot, &wbs);
-    if (!e) e = plan1d(&P->cfy, rocfft_transform_type_complex_forward, rocfft_placement_inplace, P->dtype, P->jtot, by, Cx, Cx, P->jtot, P->jtot, &wbs);
-    if (!e) e = plan1d(&P->cby, rocfft_transform_type_complex_inverse, rocfft_placement_inplace, P->dtype, P->jtot, by, Cx, Cx, P->jtot, P->jtot, &wbs);
+    int e = slab_fft_plans(P, nchunks, &wbs);
     if (!e && wbs > P->wb_cap)
     {
         MHH_HIP_TRY(hipStreamSynchronize(0));          // (the work buffer may still be in use by a solve in flight on the default stream)
@@ -833,42 +718,118 @@ inline Slice slice_of(const mhh_pres_slab_plan* P, int c)
 inline int chunk_ok(const mhh_pres_slab_plan* P, const mhh_grid* g, int c)
 {
     if (int e = slab_match(P, g)) return e;
-    MHH_REQUIRE(P->nchunks > 1 && c >= 0 && c < P->nchunks, "k-slice index (call mhh_pres_slab_set_chunks first)");
+    MHH_REQUIRE(c >= 0 && c < P->nchunks, "k-slice index (mhh_pres_slab_set_chunks sets their number)");
     return MHH_OK;
 }
+// the calls without a slice index work all levels at once: slice 0 of a plan that has one slice
+const char* const ONE_SLICE = "this plan works in k-slices: call mhh_pres_slab_set_chunks(plan, 1) first, or the per-slice entry points";
+
+// one transform of slice-sized batch on `st`
+inline int slab_fft(mhh_pres_slab_plan* P, rocfft_plan plan, void* in, void* out, hipStream_t st)
+{
+    MHH_FFT_TRY(rocfft_execution_info_set_stream(P->info, st));
+    void* i[1] = {in}; void* o[1] = {out};
+    MHH_FFT_TRY(rocfft_execute(plan, i, out ? o : nullptr, P->info));
+    return MHH_OK;
 }
-// slice c: x transform of the packed divergence + pack into segment c of sendbuf
+// specx of the slice <-> its segment of an all-to-all buffer; the same for specy
+template<class TF, bool FWD>
+int xbuf_x(mhh_pres_slab_plan* P, const Slice& sl, void* xbuf, hipStream_t st)
+{
+    hipLaunchKernelGGL((xbuf_x_kernel<TF, FWD>), dim3((P->npy*P->nxb + 255)/256, P->jmax, sl.kc), dim3(256), 0, st,
+                       (C2<TF>*)P->specx + sl.sx, (C2<TF>*)xbuf + sl.xseg, P->nxh, P->nxb, P->jmax, sl.kc, P->npy);
+    MHH_LAUNCH_CHECK();
+    return MHH_OK;
+}
+template<class TF, bool FWD>
+int xbuf_y(mhh_pres_slab_plan* P, const Slice& sl, void* xbuf, hipStream_t st)
+{
+    hipLaunchKernelGGL((xbuf_y_kernel<TF, FWD>), dim3((unsigned)(((P->nxb + 31)/32) * ((P->jmax + 63)/64) * P->npy), sl.kc), dim3(256), 0, st,
+                       (C2<TF>*)P->specy + sl.sy, (C2<TF>*)xbuf + sl.xseg, P->nxb, P->jmax, P->jtot, sl.kc);
+    MHH_LAUNCH_CHECK();
+    return MHH_OK;
+}
+
+// ---- the stages of the solve on one slice ----
+// x transform of the packed divergence + pack into the slice's segment of sendbuf
+int stage_fwd_x(mhh_pres_slab_plan* P, const Slice& sl, void* p_packed, void* sendbuf, hipStream_t st)
+{
+    if (!p_packed) p_packed = P->packed;
+    if (int e = slab_fft(P, P->fx, static_cast<char*>(p_packed) + sl.pk*P->esz, static_cast<char*>(P->specx) + sl.sx*2*P->esz, st)) return e;
+#define CALL(TF) xbuf_x<TF, true>(P, sl, sendbuf, st)
+    return MHH_DISPATCH(P, CALL);
+#undef CALL
+}
+// after the slice's forward all-to-all: reorder into [k][kxl][j] and forward y transform
+int stage_fwd_y(mhh_pres_slab_plan* P, const Slice& sl, void* recvbuf, hipStream_t st)
+{
+#define CALL(TF) xbuf_y<TF, true>(P, sl, recvbuf, st)
+    if (int e = MHH_DISPATCH(P, CALL)) return e;
+#undef CALL
+    return slab_fft(P, P->fy, static_cast<char*>(P->specy) + sl.sy*2*P->esz, nullptr, st);
+}
+// (all slices in: slab_column_solve)  inverse y transform + reorder into the slice's segment of sendbuf
+int stage_bwd_y(mhh_pres_slab_plan* P, const Slice& sl, void* sendbuf, hipStream_t st)
+{
+    if (int e = slab_fft(P, P->by, static_cast<char*>(P->specy) + sl.sy*2*P->esz, nullptr, st)) return e;
+#define CALL(TF) xbuf_y<TF, false>(P, sl, sendbuf, st)
+    return MHH_DISPATCH(P, CALL);
+#undef CALL
+}
+// after the slice's backward all-to-all: back into [k][jl][kx] and inverse x transform into the packed solution
+int stage_bwd_x(mhh_pres_slab_plan* P, const Slice& sl, void* recvbuf, hipStream_t st)
+{
+#define CALL(TF) xbuf_x<TF, false>(P, sl, recvbuf, st)
+    if (int e = MHH_DISPATCH(P, CALL)) return e;
+#undef CALL
+    return slab_fft(P, P->bx, static_cast<char*>(P->specx) + sl.sx*2*P->esz, static_cast<char*>(P->packed) + sl.pk*P->esz, st);
+}
+// all slices back: the packed solution into p (unpack_slab_kernel) ...
+template<class TF>
+int unpack(mhh_pres_slab_plan* P, const mhh_grid* g, const mhh_fields* f, hipStream_t st)
+{
+    hipLaunchKernelGGL(unpack_slab_kernel<TF>, dim3((g->icells + 255)/256, g->jmax, g->kmax + (P->order == 2 ? 1 : 4)), dim3(256), 0, st, mp<TF>(f->p), cp<TF>(P->packed),
+                       P->order, g->itot, g->jtot, g->jmax, g->kmax, g->igc, g->jgc, g->kgc, g->icells, g->jcells);
+    MHH_LAUNCH_CHECK();
+    return MHH_OK;
+}
+int stage_unpack(mhh_pres_slab_plan* P, const mhh_grid* g, const mhh_fields* f, hipStream_t st)
+{
+#define CALL(TF) unpack<TF>(P, g, f, st)
+    return MHH_DISPATCH(g, CALL);
+#undef CALL
+}
+// ... or into p with Pres_2::output applied in the same kernel (unpack_out_slab_kernel)
+template<bool POW2, class TF>
+int unpack_output(mhh_pres_slab_plan* P, const mhh_grid* g, const mhh_fields* f, hipStream_t st)
+{
+    const GridDev<TF> gd = make_grid<TF>(g);
+    hipLaunchKernelGGL((unpack_out_slab_kernel<POW2, TF>), dim3((g->icells + 255)/256, g->jmax, g->kmax + 1), dim3(256), 0, st, mp<TF>(f->p), cp<TF>(P->packed),
+                       mp<TF>(f->ut), mp<TF>(f->vt), mp<TF>(f->wt), gd.dzhi, gd.dxi_t, gd.dyi_t, g->itot, g->jtot, g->jmax, g->kmax, g->igc, g->jgc, g->kgc, g->icells, g->jcells);
+    MHH_LAUNCH_CHECK();
+    return MHH_OK;
+}
+int stage_unpack_output(mhh_pres_slab_plan* P, const mhh_grid* g, const mhh_fields* f, hipStream_t st)
+{
+    const bool pow2 = is_pow2(g->itot) && is_pow2(g->jtot);
+#define CALL(TF) (pow2 ? unpack_output<true, TF>(P, g, f, st) : unpack_output<false, TF>(P, g, f, st))
+    return MHH_DISPATCH(g, CALL);
+#undef CALL
+}
+}
+
+// ---- per slice c ----
 MHH_API int mhh_pres_fwd_x_pack_chunk(mhh_pres_slab_plan* P, const mhh_grid* g, void* p_packed, void* sendbuf, int c, void* stream)
 {
     if (int e = chunk_ok(P, g, c)) return e;
     MHH_REQUIRE(sendbuf != nullptr, "sendbuf");
-    if (!p_packed) p_packed = P->packed;
-    const Slice sl = slice_of(P, c);
-    hipStream_t st = as_stream(stream);
-    MHH_FFT_TRY(rocfft_execution_info_set_stream(P->info, st));
-    void* in[1] = {static_cast<char*>(p_packed) + sl.pk*P->esz}; void* out[1] = {static_cast<char*>(P->specx) + sl.sx*2*P->esz};
-    MHH_FFT_TRY(rocfft_execute(P->cfx, in, out, P->info));
-    dim3 grid((P->npy*P->nxb + 255)/256, P->jmax, sl.kc);
-    if (g->dtype == MHH_F64) hipLaunchKernelGGL((xbuf_x_kernel<double, true>), grid, dim3(256), 0, st, (C2<double>*)P->specx + sl.sx, (C2<double>*)sendbuf + sl.xseg, P->nxh, P->nxb, P->jmax, sl.kc, P->npy);
-    else                     hipLaunchKernelGGL((xbuf_x_kernel<float, true>), grid, dim3(256), 0, st, (C2<float>*)P->specx + sl.sx, (C2<float>*)sendbuf + sl.xseg, P->nxh, P->nxb, P->jmax, sl.kc, P->npy);
-    MHH_LAUNCH_CHECK();
-    return MHH_OK;
+    return stage_fwd_x(P, slice_of(P, c), p_packed, sendbuf, as_stream(stream));
 }
-// slice c, after its forward all-to-all: reorder into [k][kxl][j] and forward y transform
 MHH_API int mhh_pres_fwd_y_chunk(mhh_pres_slab_plan* P, const mhh_grid* g, void* recvbuf, int c, void* stream)
 {
     if (int e = chunk_ok(P, g, c)) return e;
     MHH_REQUIRE(recvbuf != nullptr, "recvbuf");
-    const Slice sl = slice_of(P, c);
-    hipStream_t st = as_stream(stream);
-    MHH_FFT_TRY(rocfft_execution_info_set_stream(P->info, st));
-    dim3 gy((unsigned)(((P->nxb + 31)/32) * ((P->jmax + 63)/64) * P->npy), sl.kc);
-    void* io[1] = {static_cast<char*>(P->specy) + sl.sy*2*P->esz};
-    if (g->dtype == MHH_F64) hipLaunchKernelGGL((xbuf_y_kernel<double, true>), gy, dim3(256), 0, st, (C2<double>*)P->specy + sl.sy, (C2<double>*)recvbuf + sl.xseg, P->nxb, P->jmax, P->jtot, sl.kc);
-    else                     hipLaunchKernelGGL((xbuf_y_kernel<float, true>), gy, dim3(256), 0, st, (C2<float>*)P->specy + sl.sy, (C2<float>*)recvbuf + sl.xseg, P->nxb, P->jmax, P->jtot, sl.kc);
-    MHH_LAUNCH_CHECK();
-    MHH_FFT_TRY(rocfft_execute(P->cfy, io, nullptr, P->info));
-    return MHH_OK;
+    return stage_fwd_y(P, slice_of(P, c), recvbuf, as_stream(stream));
 }
 // all slices in: the tridiagonal (pres_2) or 7-band (pres_4) solves over k
 MHH_API int mhh_pres_solve_y(mhh_pres_slab_plan* P, const mhh_grid* g, void* stream)
@@ -876,38 +837,87 @@ MHH_API int mhh_pres_solve_y(mhh_pres_slab_plan* P, const mhh_grid* g, void* str
     if (int e = slab_match(P, g)) return e;
     return slab_column_solve(P, as_stream(stream));
 }
-// slice c: inverse y transform + reorder into segment c of sendbuf
 MHH_API int mhh_pres_bwd_y_chunk(mhh_pres_slab_plan* P, const mhh_grid* g, void* sendbuf, int c, void* stream)
 {
     if (int e = chunk_ok(P, g, c)) return e;
     MHH_REQUIRE(sendbuf != nullptr, "sendbuf");
-    const Slice sl = slice_of(P, c);
-    hipStream_t st = as_stream(stream);
-    MHH_FFT_TRY(rocfft_execution_info_set_stream(P->info, st));
-    dim3 gy((unsigned)(((P->nxb + 31)/32) * ((P->jmax + 63)/64) * P->npy), sl.kc);
-    void* io[1] = {static_cast<char*>(P->specy) + sl.sy*2*P->esz};
-    MHH_FFT_TRY(rocfft_execute(P->cby, io, nullptr, P->info));
-    if (g->dtype == MHH_F64) hipLaunchKernelGGL((xbuf_y_kernel<double, false>), gy, dim3(256), 0, st, (C2<double>*)P->specy + sl.sy, (C2<double>*)sendbuf + sl.xseg, P->nxb, P->jmax, P->jtot, sl.kc);
-    else                     hipLaunchKernelGGL((xbuf_y_kernel<float, false>), gy, dim3(256), 0, st, (C2<float>*)P->specy + sl.sy, (C2<float>*)sendbuf + sl.xseg, P->nxb, P->jmax, P->jtot, sl.kc);
-    MHH_LAUNCH_CHECK();
-    return MHH_OK;
+    return stage_bwd_y(P, slice_of(P, c), sendbuf, as_stream(stream));
 }
-// slice c, after its backward all-to-all: back into [k][jl][kx] and inverse x transform into the packed solution
 MHH_API int mhh_pres_bwd_x_chunk(mhh_pres_slab_plan* P, const mhh_grid* g, void* recvbuf, int c, void* stream)
 {
     if (int e = chunk_ok(P, g, c)) return e;
     MHH_REQUIRE(recvbuf != nullptr, "recvbuf");
-    const Slice sl = slice_of(P, c);
+    return stage_bwd_x(P, slice_of(P, c), recvbuf, as_stream(stream));
+}
+// all slices back
+MHH_API int mhh_pres_unpack_slab(mhh_pres_slab_plan* P, const mhh_grid* g, const mhh_fields* f, void* stream)
+{
+    if (int e = slab_match(P, g)) return e;
+    MHH_REQUIRE(f && f->p, "buffers");
+    return stage_unpack(P, g, f, as_stream(stream));
+}
+// the caller then exchanges the one-row halo of p and finishes vt on the southernmost row with mhh_pres_output_south_row
+MHH_API int mhh_pres_unpack_output_slab(mhh_pres_slab_plan* P, const mhh_grid* g, const mhh_fields* f, void* stream)
+{
+    if (int e = slab_match(P, g)) return e;
+    MHH_REQUIRE(P->order == 2, "Pres_2::output only: a pres_4 plan takes mhh_pres_unpack_slab, the halo of p and mhh_pres_output_order(g, 4)");
+    MHH_REQUIRE(f && f->p && f->ut && f->vt && f->wt, "buffers");
+    return stage_unpack_output(P, g, f, as_stream(stream));
+}
+
+// ---- all levels at once: the stages above on slice 0 of a one-slice plan ----
+// stage 1: x transform of the packed divergence + pack for the forward all-to-all
+MHH_API int mhh_pres_fwd_x_pack(mhh_pres_slab_plan* P, const mhh_grid* g, void* p_packed, void* sendbuf, void* stream)
+{
+    if (int e = slab_match(P, g)) return e;
+    MHH_REQUIRE(sendbuf != nullptr, "sendbuf");
+    MHH_REQUIRE(P->nchunks == 1, ONE_SLICE);
+    return stage_fwd_x(P, slice_of(P, 0), p_packed, sendbuf, as_stream(stream));
+}
+// stage 2: after the forward all-to-all: y transform, tridiagonal (pres_2) or 7-band (pres_4) solves, inverse y transform, pack for the way back
+MHH_API int mhh_pres_fwd_y_solve_bwd_y(mhh_pres_slab_plan* P, const mhh_grid* g, void* recvbuf, void* sendbuf, void* stream)
+{
+    if (int e = slab_match(P, g)) return e;
+    MHH_REQUIRE(recvbuf && sendbuf, "buffers");
+    MHH_REQUIRE(P->nchunks == 1, ONE_SLICE);
     hipStream_t st = as_stream(stream);
-    MHH_FFT_TRY(rocfft_execution_info_set_stream(P->info, st));
-    dim3 grid((P->npy*P->nxb + 255)/256, P->jmax, sl.kc);
-    if (g->dtype == MHH_F64) hipLaunchKernelGGL((xbuf_x_kernel<double, false>), grid, dim3(256), 0, st, (C2<double>*)P->specx + sl.sx, (C2<double>*)recvbuf + sl.xseg, P->nxh, P->nxb, P->jmax, sl.kc, P->npy);
-    else                     hipLaunchKernelGGL((xbuf_x_kernel<float, false>), grid, dim3(256), 0, st, (C2<float>*)P->specx + sl.sx, (C2<float>*)recvbuf + sl.xseg, P->nxh, P->nxb, P->jmax, sl.kc, P->npy);
+    if (int e = stage_fwd_y(P, slice_of(P, 0), recvbuf, st)) return e;
+    if (int e = slab_column_solve(P, st)) return e;
+    return stage_bwd_y(P, slice_of(P, 0), sendbuf, st);
+}
+// stage 3: after the backward all-to-all: inverse x transform, normalise, write p (interior rows, x halo, vertical ghost levels)
+MHH_API int mhh_pres_bwd_x_unpack(mhh_pres_slab_plan* P, const mhh_grid* g, void* recvbuf, const mhh_fields* f, void* stream)
+{
+    if (int e = slab_match(P, g)) return e;
+    MHH_REQUIRE(recvbuf && f && f->p, "buffers");
+    MHH_REQUIRE(P->nchunks == 1, ONE_SLICE);
+    if (int e = stage_bwd_x(P, slice_of(P, 0), recvbuf, as_stream(stream))) return e;
+    return stage_unpack(P, g, f, as_stream(stream));
+}
+// stage 3, fused form: inverse x transform, then unpack + Pres_2::output in one kernel for everything but vt on the southernmost
+// row; the caller exchanges the one-row halo of p and finishes with mhh_pres_output_south_row.
+MHH_API int mhh_pres_bwd_x_unpack_output(mhh_pres_slab_plan* P, const mhh_grid* g, void* recvbuf, const mhh_fields* f, void* stream)
+{
+    if (int e = slab_match(P, g)) return e;
+    MHH_REQUIRE(P->order == 2, "Pres_2::output only: a pres_4 plan takes mhh_pres_bwd_x_unpack, the halo of p and mhh_pres_output_order(g, 4)");
+    MHH_REQUIRE(recvbuf && f && f->p && f->ut && f->vt && f->wt, "buffers");
+    MHH_REQUIRE(P->nchunks == 1, ONE_SLICE);
+    if (int e = stage_bwd_x(P, slice_of(P, 0), recvbuf, as_stream(stream))) return e;
+    return stage_unpack_output(P, g, f, as_stream(stream));
+}
+MHH_API int mhh_pres_output_south_row(const mhh_grid* g, const mhh_fields* f, void* stream)
+{
+    if (int e = check_grid(g)) return e;
+    MHH_REQUIRE(f && f->p && f->vt && g->jgc >= 1, "null field");
+    dim3 grid((g->imax + 255)/256, g->kmax);
+#define CALL(TF) [&]{ const GridDev<TF> gd = make_grid<TF>(g); \
+        hipLaunchKernelGGL(pres_out_south_row_kernel<TF>, grid, dim3(256), 0, as_stream(stream), mp<TF>(f->vt), cp<TF>(f->p), gd.dyi_t, g->istart, g->iend, g->jstart, g->kstart, g->icells, g->ijcells); return (int)MHH_OK; }()
+    if (int e = MHH_DISPATCH(g, CALL)) return e;
+#undef CALL
     MHH_LAUNCH_CHECK();
-    void* in[1] = {static_cast<char*>(P->specx) + sl.sx*2*P->esz}; void* out[1] = {static_cast<char*>(P->packed) + sl.pk*P->esz};
-    MHH_FFT_TRY(rocfft_execute(P->cbx, in, out, P->info));
     return MHH_OK;
 }
+
 // ---- the x stages with the transforms in LDS (pres_lds.h): input + x transform WRITING the send buffer of the x -> y transpose,
 // x transform + p + output READING the receive buffer of the y -> x transpose -- two kernels and four array passes per rank where
 // the staged form has input | x r2c | pack and unpack | x c2r | unpack + output (six kernels, eleven passes). The y stage between
@@ -955,23 +965,4 @@ MHH_API int mhh_pres_slab_lds_bwd_y(mhh_pres_slab_plan* P, const mhh_grid* g, vo
     MHH_REQUIRE(P->ty_lds != nullptr && sendbuf && c >= 0 && c < P->nchunks, "LDS form, buffer, k-slice");
     const int ks = P->ktot / P->nchunks;
     return lds_slab_yfft(g, false, sendbuf, P->specy, P->ty_lds, P->nxb, P->npy, ks, c*ks, (c+1)*ks, as_stream(stream));
-}
-// all slices back: unpack + Pres_2::output in one kernel (the tail of mhh_pres_bwd_x_unpack_output)
-MHH_API int mhh_pres_unpack_output_slab(mhh_pres_slab_plan* P, const mhh_grid* g, const mhh_fields* f, void* stream)
-{
-    if (int e = slab_match(P, g)) return e;
-    MHH_REQUIRE(P->order == 2, "Pres_2::output only: a pres_4 plan takes mhh_pres_unpack_slab, the halo of p and mhh_pres_output_order(g, 4)");
-    MHH_REQUIRE(f && f->p && f->ut && f->vt && f->wt, "buffers");
-    hipStream_t st = as_stream(stream);
-    dim3 ug((g->icells + 255)/256, g->jmax, g->kmax + 1);
-    const bool pow2 = is_pow2(g->itot) && is_pow2(g->jtot);
-#define CALL(TF) [&]{ const GridDev<TF> gd = make_grid<TF>(g); \
-        if (pow2) hipLaunchKernelGGL((unpack_out_slab_kernel<true, TF>), ug, dim3(256), 0, st, mp<TF>(f->p), cp<TF>(P->packed), mp<TF>(f->ut), mp<TF>(f->vt), mp<TF>(f->wt), gd.dzhi, \
-                           gd.dxi_t, gd.dyi_t, g->itot, g->jtot, g->jmax, g->kmax, g->igc, g->jgc, g->kgc, g->icells, g->jcells); \
-        else hipLaunchKernelGGL((unpack_out_slab_kernel<false, TF>), ug, dim3(256), 0, st, mp<TF>(f->p), cp<TF>(P->packed), mp<TF>(f->ut), mp<TF>(f->vt), mp<TF>(f->wt), gd.dzhi, \
-                           gd.dxi_t, gd.dyi_t, g->itot, g->jtot, g->jmax, g->kmax, g->igc, g->jgc, g->kgc, g->icells, g->jcells); return (int)MHH_OK; }()
-    if (int e = MHH_DISPATCH(g, CALL)) return e;
-#undef CALL
-    MHH_LAUNCH_CHECK();
-    return MHH_OK;
 }

@@ -171,17 +171,10 @@ class Pres_slab
             while (n > 1 && gd.ktot % n) --n;
             mhh_check(mhh_pres_slab_set_chunks(plan, n));
             nchunks = n;
-            if (n > 1 && !comm_stream)
-            {
-                hip_check(hipStreamCreateWithFlags(&comm_stream, hipStreamNonBlocking), "hipStreamCreate");
-                events.resize(4*(size_t)n);
-                for (auto& e : events) hip_check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
-            }
-            else if (n > 1 && events.size() < 4*(size_t)n)
-            {
-                const size_t old = events.size(); events.resize(4*(size_t)n);
-                for (size_t m = old; m < events.size(); ++m) hip_check(hipEventCreateWithFlags(&events[m], hipEventDisableTiming), "hipEventCreate");
-            }
+            if (n > 1 && !comm_stream) hip_check(hipStreamCreateWithFlags(&comm_stream, hipStreamNonBlocking), "hipStreamCreate");
+            const size_t old = events.size();
+            if (n > 1 && old < 4*(size_t)n) events.resize(4*(size_t)n);
+            for (size_t m = old; m < events.size(); ++m) hip_check(hipEventCreateWithFlags(&events[m], hipEventDisableTiming), "hipEventCreate");
         }
         int chunks() const { return nchunks; }
         void clear_device()
@@ -194,75 +187,68 @@ class Pres_slab
             if (comm_stream) { (void)hipStreamDestroy(comm_stream); comm_stream = nullptr; }
             nchunks = 1;
         }
+        // Pres_2::exec / Pres_4::exec (src/pres_2.cxx:66-94, src/pres_4.cxx:64-140): the x stages around the two transposes, per k-slice;
+        // the column solves over all levels between them; p's y halo by exchange before (what is left of) the output
         void exec(double dt, Stats&)
         {
             if (!plan) throw std::runtime_error("Pres_slab::exec before prepare_device");
-            if (order == 4) { exec4(dt); return; }
             mhh_grid g = grid.abi();
             mhh_fields f = abi_fields(fields);
             void* st = master.stream;
-            halo.exec_g({fields.mt.at("v")->fld_g}, 1, 0);                 // pres_2 input reads vt[j+1] only (src/pres_2.cxx:181,193)
-            // x stages with the transforms in LDS where the plan has them: input + x transform write the send buffer, x transform +
-            // p + output read the receive buffer (mhh_pres_slab_lds_fwd / _bwd); otherwise the staged kernels around a packed array
+            // the rows of vt the input reads beyond the slab: vt[j+1] (src/pres_2.cxx:181,193), vt[j-1..j+2] (src/pres_4.cxx:312-315)
+            if (order == 2) halo.exec_g({fields.mt.at("v")->fld_g}, 1, 0);
+            else            halo.exec_g({fields.mt.at("v")->fld_g}, 2, 1);
+            // x stages with the transforms in LDS where the plan has them (pres_2): input + x transform write the send buffer, x
+            // transform + p + output read the receive buffer (mhh_pres_slab_lds_fwd / _bwd); otherwise the staged kernels around a packed array
             const bool lds = mhh_pres_slab_has_lds(plan) == 1;
             void* packed = mhh_pres_slab_packed(plan);
-            if (!lds) mhh_check(mhh_pres_input_packed(&g, 2, &f, dt, packed, st));
-            if (nchunks == 1)
+            if (!lds) mhh_check(mhh_pres_input_packed(&g, order, &f, dt, packed, st));
+            const int n = nchunks;
+            const size_t seg = nbytes / n;                                 // slice c = bytes [c*seg, (c+1)*seg) of both buffers: an equal-split all-to-all of its own
+            // the all-to-all of slice c: with one slice on the caller's stream, otherwise on the exchange stream between the events
+            // ready (events[way*n + c]) and done (events[(way+1)*n + c]); way 0 = Transpose::exec_xy, 2 = exec_yx
+            auto exchange = [&](int c, int way)
             {
-                if (lds) mhh_check(mhh_pres_slab_lds_fwd(plan, &g, &f, dt, xsend, 0, st));
-                else     mhh_check(mhh_pres_fwd_x_pack(plan, &g, packed, xsend, st));
-                transpose.exec(xsend, xrecv, nbytes / master.npy);            // Transpose::exec_xy
-                if (lds)
-                {
-                    mhh_check(mhh_pres_slab_lds_fwd_y(plan, &g, xrecv, 0, st));
-                    mhh_check(mhh_pres_solve_y(plan, &g, st));
-                    mhh_check(mhh_pres_slab_lds_bwd_y(plan, &g, xsend, 0, st));
-                }
-                else mhh_check(mhh_pres_fwd_y_solve_bwd_y(plan, &g, xrecv, xsend, st));
-                transpose.exec(xsend, xrecv, nbytes / master.npy);            // Transpose::exec_yx
-                if (lds) mhh_check(mhh_pres_slab_lds_bwd(plan, &g, xrecv, &f, 0, st));
-                else     mhh_check(mhh_pres_bwd_x_unpack_output(plan, &g, xrecv, &f, st));
+                if (n == 1) { transpose.exec(xsend, xrecv, seg / master.npy); return; }
+                hip_check(hipEventRecord(events[way*n + c], master.stream), "hipEventRecord");
+                hip_check(hipStreamWaitEvent(comm_stream, events[way*n + c], 0), "hipStreamWaitEvent");
+                transpose.exec(static_cast<char*>(xsend) + c*seg, static_cast<char*>(xrecv) + c*seg, seg / master.npy, comm_stream);
+                hip_check(hipEventRecord(events[(way+1)*n + c], comm_stream), "hipEventRecord");
+            };
+            auto arrived = [&](int c, int way) { if (n > 1) hip_check(hipStreamWaitEvent(master.stream, events[(way+1)*n + c], 0), "hipStreamWaitEvent"); };
+            for (int c = 0; c < n; ++c)
+            {
+                mhh_check(lds ? mhh_pres_slab_lds_fwd(plan, &g, &f, dt, xsend, c, st) : mhh_pres_fwd_x_pack_chunk(plan, &g, packed, xsend, c, st));
+                exchange(c, 0);
+            }
+            for (int c = 0; c < n; ++c)
+            {
+                arrived(c, 0);
+                mhh_check(lds ? mhh_pres_slab_lds_fwd_y(plan, &g, xrecv, c, st) : mhh_pres_fwd_y_chunk(plan, &g, xrecv, c, st));
+            }
+            mhh_check(mhh_pres_solve_y(plan, &g, st));
+            for (int c = 0; c < n; ++c)
+            {
+                mhh_check(lds ? mhh_pres_slab_lds_bwd_y(plan, &g, xsend, c, st) : mhh_pres_bwd_y_chunk(plan, &g, xsend, c, st));
+                exchange(c, 2);
+            }
+            for (int c = 0; c < n; ++c)
+            {
+                arrived(c, 2);
+                mhh_check(lds ? mhh_pres_slab_lds_bwd(plan, &g, xrecv, &f, c, st) : mhh_pres_bwd_x_chunk(plan, &g, xrecv, c, st));
+            }
+            if (order == 2)
+            {
+                if (!lds) mhh_check(mhh_pres_unpack_output_slab(plan, &g, &f, st));
+                halo.exec_g({fields.sd.at("p")->fld_g}, 0, 1);             // output of the southernmost row reads p[j-1] (:383-385)
+                mhh_check(mhh_pres_output_south_row(&g, &f, st));
             }
             else
             {
-                const size_t seg = nbytes / nchunks;                       // slice c = bytes [c*seg, (c+1)*seg) of both buffers: an equal-split all-to-all of its own
-                auto exchange = [&](int c, hipEvent_t ready, hipEvent_t done)
-                {
-                    hip_check(hipEventRecord(ready, master.stream), "hipEventRecord");
-                    hip_check(hipStreamWaitEvent(comm_stream, ready, 0), "hipStreamWaitEvent");
-                    transpose.exec(static_cast<char*>(xsend) + c*seg, static_cast<char*>(xrecv) + c*seg, seg / master.npy, comm_stream);
-                    hip_check(hipEventRecord(done, comm_stream), "hipEventRecord");
-                };
-                const int n = nchunks;
-                for (int c = 0; c < n; ++c)
-                {
-                    if (lds) mhh_check(mhh_pres_slab_lds_fwd(plan, &g, &f, dt, xsend, c, st));
-                    else     mhh_check(mhh_pres_fwd_x_pack_chunk(plan, &g, packed, xsend, c, st));
-                    exchange(c, events[c], events[n + c]);
-                }
-                for (int c = 0; c < n; ++c)
-                {
-                    hip_check(hipStreamWaitEvent(master.stream, events[n + c], 0), "hipStreamWaitEvent");
-                    if (lds) mhh_check(mhh_pres_slab_lds_fwd_y(plan, &g, xrecv, c, st));
-                    else     mhh_check(mhh_pres_fwd_y_chunk(plan, &g, xrecv, c, st));
-                }
-                mhh_check(mhh_pres_solve_y(plan, &g, st));
-                for (int c = 0; c < n; ++c)
-                {
-                    if (lds) mhh_check(mhh_pres_slab_lds_bwd_y(plan, &g, xsend, c, st));
-                    else     mhh_check(mhh_pres_bwd_y_chunk(plan, &g, xsend, c, st));
-                    exchange(c, events[2*n + c], events[3*n + c]);
-                }
-                for (int c = 0; c < n; ++c)
-                {
-                    hip_check(hipStreamWaitEvent(master.stream, events[3*n + c], 0), "hipStreamWaitEvent");
-                    if (lds) mhh_check(mhh_pres_slab_lds_bwd(plan, &g, xrecv, &f, c, st));
-                    else     mhh_check(mhh_pres_bwd_x_chunk(plan, &g, xrecv, c, st));
-                }
-                if (!lds) mhh_check(mhh_pres_unpack_output_slab(plan, &g, &f, st));
+                mhh_check(mhh_pres_unpack_slab(plan, &g, &f, st));
+                halo.exec_g({fields.sd.at("p")->fld_g}, 1, 2);             // the output reads p[j-2..j+1] (src/pres_4.cxx:555-569)
+                mhh_check(mhh_pres_output_order(&g, 4, &f, st));
             }
-            halo.exec_g({fields.sd.at("p")->fld_g}, 0, 1);                 // output of the southernmost row reads p[j-1] (:383-385)
-            mhh_check(mhh_pres_output_south_row(&g, &f, st));
         }
         TF check_divergence()
         {
@@ -273,61 +259,6 @@ class Pres_slab
             return static_cast<TF>(master.max(div));
         }
     private:
-        // Pres_4::exec (src/pres_4.cxx:64-140): the staged x stages (input | x transform + pack, x transform + unpack) around the
-        // transposes, the 7-band solve between them; p's y halo by exchange before Pres_4::output
-        void exec4(double dt)
-        {
-            mhh_grid g = grid.abi();
-            mhh_fields f = abi_fields(fields);
-            void* st = master.stream;
-            halo.exec_g({fields.mt.at("v")->fld_g}, 2, 1);                 // the input reads vt[j-1..j+2] (src/pres_4.cxx:312-315)
-            void* packed = mhh_pres_slab_packed(plan);
-            mhh_check(mhh_pres_input_packed(&g, 4, &f, dt, packed, st));
-            if (nchunks == 1)
-            {
-                mhh_check(mhh_pres_fwd_x_pack(plan, &g, packed, xsend, st));
-                transpose.exec(xsend, xrecv, nbytes / master.npy);            // Transpose::exec_xy
-                mhh_check(mhh_pres_fwd_y_solve_bwd_y(plan, &g, xrecv, xsend, st));
-                transpose.exec(xsend, xrecv, nbytes / master.npy);            // Transpose::exec_yx
-                mhh_check(mhh_pres_bwd_x_unpack(plan, &g, xrecv, &f, st));
-            }
-            else
-            {
-                const size_t seg = nbytes / nchunks;
-                auto exchange = [&](int c, hipEvent_t ready, hipEvent_t done)
-                {
-                    hip_check(hipEventRecord(ready, master.stream), "hipEventRecord");
-                    hip_check(hipStreamWaitEvent(comm_stream, ready, 0), "hipStreamWaitEvent");
-                    transpose.exec(static_cast<char*>(xsend) + c*seg, static_cast<char*>(xrecv) + c*seg, seg / master.npy, comm_stream);
-                    hip_check(hipEventRecord(done, comm_stream), "hipEventRecord");
-                };
-                const int n = nchunks;
-                for (int c = 0; c < n; ++c)
-                {
-                    mhh_check(mhh_pres_fwd_x_pack_chunk(plan, &g, packed, xsend, c, st));
-                    exchange(c, events[c], events[n + c]);
-                }
-                for (int c = 0; c < n; ++c)
-                {
-                    hip_check(hipStreamWaitEvent(master.stream, events[n + c], 0), "hipStreamWaitEvent");
-                    mhh_check(mhh_pres_fwd_y_chunk(plan, &g, xrecv, c, st));
-                }
-                mhh_check(mhh_pres_solve_y(plan, &g, st));
-                for (int c = 0; c < n; ++c)
-                {
-                    mhh_check(mhh_pres_bwd_y_chunk(plan, &g, xsend, c, st));
-                    exchange(c, events[2*n + c], events[3*n + c]);
-                }
-                for (int c = 0; c < n; ++c)
-                {
-                    hip_check(hipStreamWaitEvent(master.stream, events[3*n + c], 0), "hipStreamWaitEvent");
-                    mhh_check(mhh_pres_bwd_x_chunk(plan, &g, xrecv, c, st));
-                }
-                mhh_check(mhh_pres_unpack_slab(plan, &g, &f, st));
-            }
-            halo.exec_g({fields.sd.at("p")->fld_g}, 1, 2);                 // the output reads p[j-2..j+1] (src/pres_4.cxx:555-569)
-            mhh_check(mhh_pres_output_order(&g, 4, &f, st));
-        }
         Master_rccl& master; Grid<TF>& grid; Fields<TF>& fields;
         Boundary_cyclic_slab<TF> halo; Transpose transpose; int order;
         mhh_pres_slab_plan* plan = nullptr; void* work = nullptr;

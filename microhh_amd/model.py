@@ -416,79 +416,93 @@ class HotPath:
         self._ok(self.lib.mhh_advec_exec(self.G, self.cfg["advec"], C.byref(self.fields), self.stream))
         self._ok(self.lib.mhh_diff_exec(self.G, self.cfg["diff"], C.byref(self.fields), C.byref(self.params), self.stream))
 
-    def pres(self):
-        if not self.slab:
-            self._ok(self.lib.mhh_pres_exec(self.plan, self.G, C.byref(self.fields), self.dt, self.stream))
-            return
-        if self.cfg["pres"] == 4:
-            self._pres4_slab()
-            return
-        lib, st = self.lib, self.stream
-        if self.slim: self.halo([self.vt], rows_south=1, rows_north=0)      # only vt[j+1] at the north edge is read (pres_2.cxx:181,193)
-        else:         self.halo([self.vt])
-        F = C.byref(self.fields)
-        # x stages with the transforms in LDS where the plan has them (needs the slim halos: p's y halo is the one row): input + x
-        # transform write the send buffer, x transform + p + output read the receive buffer -- no packed array, no pack / unpack
-        lds_x = self.slim and lib.mhh_pres_slab_has_lds(self.plan) == 1
-        packed = lib.mhh_pres_slab_packed(self.plan)
-        if not lds_x:
-            self._ok(lib.mhh_pres_input_packed(self.G, 2, F, self.dt, packed, st))
-        if self.pres_chunks > 1:
-            self._pres_sliced(packed, lds_x)
-            return
-        if lds_x:
-            self._ok(lib.mhh_pres_slab_lds_fwd(self.plan, self.G, F, self.dt, self.xsend.data_ptr(), 0, st))
-        else:
-            self._ok(lib.mhh_pres_fwd_x_pack(self.plan, self.G, packed, self.xsend.data_ptr(), st))
-        self._transpose()                                                    # Transpose::exec_xy
-        if lds_x:       # the y transforms read / write the transposes' buffers directly, around the Thomas sweeps
-            self._ok(lib.mhh_pres_slab_lds_fwd_y(self.plan, self.G, self.xrecv.data_ptr(), 0, self.stream))
-            self._ok(lib.mhh_pres_solve_y(self.plan, self.G, self.stream))
-            self._ok(lib.mhh_pres_slab_lds_bwd_y(self.plan, self.G, self.xsend.data_ptr(), 0, self.stream))
-        else:
-            self._ok(lib.mhh_pres_fwd_y_solve_bwd_y(self.plan, self.G, self.xrecv.data_ptr(), self.xsend.data_ptr(), self.stream))
-        self._transpose()                                                    # Transpose::exec_yx
-        if lds_x:
-            self._ok(lib.mhh_pres_slab_lds_bwd(self.plan, self.G, self.xrecv.data_ptr(), F, 0, self.stream))
-            self.halo([self.p], rows_south=0, rows_north=1)
-            self._ok(lib.mhh_pres_output_south_row(self.G, F, self.stream))
-            return
-        if self.slim:
-            # unpack + Pres_2::output in one kernel for everything but vt on the southernmost row, whose p[j-1] arrives with the
-            # one-row halo of p (pres_2.cxx:383-385)
-            self._ok(lib.mhh_pres_bwd_x_unpack_output(self.plan, self.G, self.xrecv.data_ptr(), C.byref(self.fields), self.stream))
-            self.halo([self.p], rows_south=0, rows_north=1)
-            self._ok(lib.mhh_pres_output_south_row(self.G, C.byref(self.fields), self.stream))
-        else:
-            self._ok(lib.mhh_pres_bwd_x_unpack(self.plan, self.G, self.xrecv.data_ptr(), C.byref(self.fields), self.stream))
-            self.halo([self.p])
-            self._ok(lib.mhh_pres_output_order(self.G, 2, C.byref(self.fields), self.stream))
-
     # the rows of vt the pressure input reads beyond the slab (rows_south, rows_north): pres_2 vt[j+1] (src/pres_2.cxx:181,193),
     # pres_4 vt[j-1..j+2] (src/pres_4.cxx:312-315)
     @property
     def _pres_vt_rows(self):
         return (2, 1) if self.cfg["pres"] == 4 else (1, 0)
 
-    def _pres4_slab(self):
-        """Pres_4::exec on a slab (src/pres_4.cxx:64-140): the staged x stages around the two transposes, whole or in k-slices, the
-        7-band solve on the rank's spectral columns; the unpack writes p's four mirrored ghost levels and its x halo, the exchange
-        its y halo (the output reads p[j-2..j+1], src/pres_4.cxx:555-569)."""
-        lib, st, F = self.lib, self.stream, C.byref(self.fields)
-        rs, rn = self._pres_vt_rows
-        self.halo([self.vt], rows_south=rs, rows_north=rn)
-        packed = lib.mhh_pres_slab_packed(self.plan)
-        self._ok(lib.mhh_pres_input_packed(self.G, 4, F, self.dt, packed, st))
-        if self.pres_chunks > 1:
-            self._pres_sliced(packed)
+    def pres(self):
+        """Pres_2::exec / Pres_4::exec (src/pres_2.cxx:66-94, src/pres_4.cxx:64-140). On a slab, in pres_chunks k-slices: per slice x
+        transform + pack, its all-to-all (with more than one slice: on the exchange stream while the next slice is transformed), y
+        transform as each slice arrives; the column solves over all levels; the same on the way back. Same kernels per plane
+        whatever the slice count (tests/test_slab_gloo.py, tests/test_slab4_gloo.py compare one slice with several)."""
+        if not self.slab:
+            self._ok(self.lib.mhh_pres_exec(self.plan, self.G, C.byref(self.fields), self.dt, self.stream))
+            return
+        lib, torch, n, order = self.lib, self.torch, self.pres_chunks, self.cfg["pres"]
+        P, G, F = self.plan, self.G, C.byref(self.fields)
+        if self.slim or order == 4: self.halo([self.vt], *self._pres_vt_rows)
+        else:                       self.halo([self.vt])
+        # x stages with the transforms in LDS where the plan has them (pres_2; needs the slim halos: p's y halo is the one row): input
+        # + x transform write the send buffer, x transform + p + output read the receive buffer -- no packed array, no pack / unpack;
+        # the y transforms read / write the transposes' buffers directly
+        lds_x = self.slim and lib.mhh_pres_slab_has_lds(P) == 1
+        packed = lib.mhh_pres_slab_packed(P)
+        xs, xr = self.xsend.data_ptr(), self.xrecv.data_ptr()
+        if lds_x:
+            x_in = lambda c: lib.mhh_pres_slab_lds_fwd(P, G, F, self.dt, xs, c, self.stream)      # noqa: E731
+            y_in = lambda c: lib.mhh_pres_slab_lds_fwd_y(P, G, xr, c, self.stream)                # noqa: E731
+            y_out = lambda c: lib.mhh_pres_slab_lds_bwd_y(P, G, xs, c, self.stream)               # noqa: E731
+            x_out = lambda c: lib.mhh_pres_slab_lds_bwd(P, G, xr, F, c, self.stream)              # noqa: E731
         else:
-            self._ok(lib.mhh_pres_fwd_x_pack(self.plan, self.G, packed, self.xsend.data_ptr(), st))
-            self._transpose()                                                # Transpose::exec_xy
-            self._ok(lib.mhh_pres_fwd_y_solve_bwd_y(self.plan, self.G, self.xrecv.data_ptr(), self.xsend.data_ptr(), st))
-            self._transpose()                                                # Transpose::exec_yx
-            self._ok(lib.mhh_pres_bwd_x_unpack(self.plan, self.G, self.xrecv.data_ptr(), F, st))
-        self.halo([self.p], rows_south=1, rows_north=2)
-        self._ok(lib.mhh_pres_output_order(self.G, 4, F, self.stream))
+            self._ok(lib.mhh_pres_input_packed(G, order, F, self.dt, packed, self.stream))
+            x_in = lambda c: lib.mhh_pres_fwd_x_pack_chunk(P, G, packed, xs, c, self.stream)      # noqa: E731
+            y_in = lambda c: lib.mhh_pres_fwd_y_chunk(P, G, xr, c, self.stream)                   # noqa: E731
+            y_out = lambda c: lib.mhh_pres_bwd_y_chunk(P, G, xs, c, self.stream)                  # noqa: E731
+            x_out = lambda c: lib.mhh_pres_bwd_x_chunk(P, G, xr, c, self.stream)                  # noqa: E731
+        # one slice: the transposes run on the caller's stream
+        two_streams = n > 1 and self.on_gpu and not self._host_staged and (self.npy > 1 or self._force_comm)
+        if two_streams:
+            main = torch.cuda.current_stream(self.device)
+            if self._comm_stream is None:
+                self._comm_stream = torch.cuda.Stream(self.device)
+                self._ev = [torch.cuda.Event(), torch.cuda.Event()]
+            if not hasattr(self, "_sl_ev"):
+                self._sl_ev = [[torch.cuda.Event() for _ in range(n)] for _ in range(4)]
+        seg = self.xsend.numel() // n
+
+        def exchange(c, way):
+            """all-to-all of slice c (way 0: Transpose::exec_xy, 2: exec_yx): on the exchange stream once `ready` (recorded on the
+            main stream) has passed"""
+            a, b = self.xsend[c*seg:(c+1)*seg], self.xrecv[c*seg:(c+1)*seg]
+            if not two_streams:
+                self._transpose(a, b)
+                return
+            ready, done = self._sl_ev[way][c], self._sl_ev[way+1][c]
+            ready.record(main)
+            self._comm_stream.wait_event(ready)
+            with torch.cuda.stream(self._comm_stream):
+                self._transpose(a, b)
+                done.record(self._comm_stream)
+
+        def arrived(c, way):
+            if two_streams:
+                main.wait_event(self._sl_ev[way+1][c])
+
+        for c in range(n):
+            self._ok(x_in(c)); exchange(c, 0)
+        for c in range(n):
+            arrived(c, 0); self._ok(y_in(c))
+        self._ok(lib.mhh_pres_solve_y(P, G, self.stream))
+        for c in range(n):
+            self._ok(y_out(c)); exchange(c, 2)
+        for c in range(n):
+            arrived(c, 2); self._ok(x_out(c))
+        if order == 2 and self.slim:
+            # unpack + Pres_2::output in one kernel (the LDS x stage has done both) for everything but vt on the southernmost row,
+            # whose p[j-1] arrives with the one-row halo of p (pres_2.cxx:383-385)
+            if not lds_x:
+                self._ok(lib.mhh_pres_unpack_output_slab(P, G, F, self.stream))
+            self.halo([self.p], rows_south=0, rows_north=1)
+            self._ok(lib.mhh_pres_output_south_row(G, F, self.stream))
+        else:
+            # the unpack writes p's mirrored ghost levels and its x halo, the exchange its y halo (pres_4: the output reads
+            # p[j-2..j+1], src/pres_4.cxx:555-569)
+            self._ok(lib.mhh_pres_unpack_slab(P, G, F, self.stream))
+            if order == 4: self.halo([self.p], rows_south=1, rows_north=2)
+            else:          self.halo([self.p])
+            self._ok(lib.mhh_pres_output_order(G, order, F, self.stream))
 
     def pres_rk(self, rkorder, substep, dt):
         """pres->exec(self.dt) followed by timeloop.exec() for u, v, w (src/model.cxx:411,484) with the sub-step applied in the
@@ -500,68 +514,8 @@ class HotPath:
         for a, at in ((self.u, self.ut), (self.v, self.vt), (self.w, self.wt)):
             self._ok(self.lib.mhh_rk_substep(self.G, rkorder, substep, dt, a.data_ptr(), at.data_ptr(), self.stream))
 
-    def _pres_sliced(self, packed, lds_x=False):
-        """Pres::exec after the input stage, in k-slices: per slice x transform + pack, all-to-all on the exchange stream while
-        the next slice is transformed, y transform as each slice arrives; Thomas sweeps over all levels; the same on the way back.
-        Same kernels per plane as the unsliced path (tests/test_slab_gloo.py compares the two)."""
-        lib, torch, n = self.lib, self.torch, self.pres_chunks
-        seg = self.xsend.numel() // n
-        F = C.byref(self.fields)
-        two_streams = self.on_gpu and not self._host_staged and (self.npy > 1 or self._force_comm)
-        if two_streams:
-            main = torch.cuda.current_stream(self.device)
-            if self._comm_stream is None:
-                self._comm_stream = torch.cuda.Stream(self.device)
-                self._ev = [torch.cuda.Event(), torch.cuda.Event()]
-            if not hasattr(self, "_sl_ev"):
-                self._sl_ev = [[torch.cuda.Event() for _ in range(n)] for _ in range(4)]
-
-        def exchange(c, ready, done):
-            """all-to-all of slice c: on the exchange stream once `ready` (recorded on the main stream) has passed"""
-            a, b = self.xsend[c*seg:(c+1)*seg], self.xrecv[c*seg:(c+1)*seg]
-            if not two_streams:
-                self._transpose(a, b)
-                return
-            ready.record(main)
-            self._comm_stream.wait_event(ready)
-            with torch.cuda.stream(self._comm_stream):
-                self._transpose(a, b)
-                done.record(self._comm_stream)
-
-        for c in range(n):
-            if lds_x: self._ok(lib.mhh_pres_slab_lds_fwd(self.plan, self.G, F, self.dt, self.xsend.data_ptr(), c, self.stream))
-            else:     self._ok(lib.mhh_pres_fwd_x_pack_chunk(self.plan, self.G, packed, self.xsend.data_ptr(), c, self.stream))
-            exchange(c, *( (self._sl_ev[0][c], self._sl_ev[1][c]) if two_streams else (None, None) ))
-        for c in range(n):
-            if two_streams:
-                main.wait_event(self._sl_ev[1][c])
-            if lds_x: self._ok(lib.mhh_pres_slab_lds_fwd_y(self.plan, self.G, self.xrecv.data_ptr(), c, self.stream))
-            else:     self._ok(lib.mhh_pres_fwd_y_chunk(self.plan, self.G, self.xrecv.data_ptr(), c, self.stream))
-        self._ok(lib.mhh_pres_solve_y(self.plan, self.G, self.stream))
-        for c in range(n):
-            if lds_x: self._ok(lib.mhh_pres_slab_lds_bwd_y(self.plan, self.G, self.xsend.data_ptr(), c, self.stream))
-            else:     self._ok(lib.mhh_pres_bwd_y_chunk(self.plan, self.G, self.xsend.data_ptr(), c, self.stream))
-            exchange(c, *( (self._sl_ev[2][c], self._sl_ev[3][c]) if two_streams else (None, None) ))
-        for c in range(n):
-            if two_streams:
-                main.wait_event(self._sl_ev[3][c])
-            if lds_x: self._ok(lib.mhh_pres_slab_lds_bwd(self.plan, self.G, self.xrecv.data_ptr(), F, c, self.stream))
-            else:     self._ok(lib.mhh_pres_bwd_x_chunk(self.plan, self.G, self.xrecv.data_ptr(), c, self.stream))
-        if self.cfg["pres"] == 4:
-            self._ok(lib.mhh_pres_unpack_slab(self.plan, self.G, F, self.stream))    # the caller (_pres4_slab) exchanges p and applies the output
-            return
-        if not lds_x:
-            self._ok(lib.mhh_pres_unpack_output_slab(self.plan, self.G, F, self.stream))
-        self.halo([self.p], rows_south=0, rows_north=1)
-        self._ok(lib.mhh_pres_output_south_row(self.G, F, self.stream))
-
-    def _transpose(self, send=None, recv=None):
-        """x<->y transpose of the spectral pressure: one equal-split all-to-all (RCCL over xGMI)."""
-        if send is not None:
-            return self._transpose_buffers(send, recv)
-        return self._transpose_buffers(self.xsend, self.xrecv)
-
-    def _transpose_buffers(self, xsend, xrecv):
+    def _transpose(self, xsend, xrecv):
+        """x<->y transpose of the spectral pressure (or of one k-slice of it): one equal-split all-to-all (RCCL over xGMI)."""
         if self.npy == 1 and not self._force_comm:
             xrecv.copy_(xsend)
             return

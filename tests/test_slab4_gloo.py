@@ -179,3 +179,56 @@ def test_pres4_slab_abi():
         hp.close()
     for n in ("ut", "vt", "wt", "p"):
         assert np.array_equal(out[0][n], out[1][n]), n
+
+
+@pytest.mark.parametrize("case,grid", [("drycblles", (16, 32, 10)), (CASE, GRID)], ids=["order2-staged", "order4"])
+def test_pres_slab_calls_without_slice_index(case, grid, monkeypatch):
+    """The entry points without a slice index are the per-slice ones on slice 0 of a one-slice plan: HotPath.pres (per-slice calls) and
+    the same solve through mhh_pres_fwd_x_pack / fwd_y_solve_bwd_y / bwd_x_unpack[_output] give the same bits. On a plan with two
+    slices they are refused, and the message names mhh_pres_slab_set_chunks."""
+    monkeypatch.setenv("MHH_PRES_SLAB_LDS", "0")
+    lib = B.get("emul").lib
+    gi = synthetic_global(case, *grid)
+    out = []
+    for whole in (False, True):
+        hp = HotPath(case, *grid, device="cpu", lib=lib, global_init=gi, force_slab=True, pres_chunks=1)
+        P, G, F, st = hp.plan, hp.G, C.byref(hp.fields), hp.stream
+        order = lib.mhh_pres_slab_order(P)
+        assert lib.mhh_pres_slab_chunks(P) == 1 and lib.mhh_pres_slab_has_lds(P) == 0
+        _rhs(hp)
+        if not whole:
+            hp.pres()
+        else:
+            hp.halo([hp.vt], *hp._pres_vt_rows)
+            packed = lib.mhh_pres_slab_packed(P)
+            hp._ok(lib.mhh_pres_input_packed(G, order, F, hp.dt, packed, st))
+            hp._ok(lib.mhh_pres_fwd_x_pack(P, G, packed, hp.xsend.data_ptr(), st))
+            hp.xrecv.copy_(hp.xsend)
+            hp._ok(lib.mhh_pres_fwd_y_solve_bwd_y(P, G, hp.xrecv.data_ptr(), hp.xsend.data_ptr(), st))
+            hp.xrecv.copy_(hp.xsend)
+            if order == 2:
+                hp._ok(lib.mhh_pres_bwd_x_unpack_output(P, G, hp.xrecv.data_ptr(), F, st))
+                hp.halo([hp.p], rows_south=0, rows_north=1)
+                hp._ok(lib.mhh_pres_output_south_row(G, F, st))
+            else:
+                hp._ok(lib.mhh_pres_bwd_x_unpack(P, G, hp.xrecv.data_ptr(), F, st))
+                hp.halo([hp.p], rows_south=1, rows_north=2)
+                hp._ok(lib.mhh_pres_output_order(G, 4, F, st))
+        out.append({n: getattr(hp, n).numpy().copy() for n in ("ut", "vt", "wt", "p")})
+        if whole:
+            hp._ok(lib.mhh_pres_slab_set_chunks(P, 2))
+            xs, xr = hp.xsend.data_ptr(), hp.xrecv.data_ptr()
+            for name, call in (("mhh_pres_fwd_x_pack", lambda: lib.mhh_pres_fwd_x_pack(P, G, None, xs, st)),
+                               ("mhh_pres_fwd_y_solve_bwd_y", lambda: lib.mhh_pres_fwd_y_solve_bwd_y(P, G, xr, xs, st)),
+                               ("mhh_pres_bwd_x_unpack", lambda: lib.mhh_pres_bwd_x_unpack(P, G, xr, F, st))) + \
+                              ((("mhh_pres_bwd_x_unpack_output", lambda: lib.mhh_pres_bwd_x_unpack_output(P, G, xr, F, st)),) if order == 2 else ()):
+                assert call() != 0, name
+                assert b"set_chunks" in lib.mhh_last_error(), (name, lib.mhh_last_error())
+            # refused before anything ran: the fields are as they were; and one slice again gives the calls back
+            for n in ("ut", "vt", "wt", "p"):
+                assert np.array_equal(getattr(hp, n).numpy(), out[-1][n]), n
+            hp._ok(lib.mhh_pres_slab_set_chunks(P, 1))
+            hp._ok(lib.mhh_pres_fwd_x_pack(P, G, None, xs, st))
+        hp.close()
+    for n in ("ut", "vt", "wt", "p"):
+        assert np.array_equal(out[0][n], out[1][n]), n
