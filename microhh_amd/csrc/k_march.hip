@@ -253,8 +253,12 @@ rhs25_march_kernel(const MarchMetrics<typename lane_of<VT>::scalar> mm, const Gr
     constexpr int NP = PPR*TJ, NPE = PPRE*TJE;
     constexpr int NLD = (NP + NT - 1) / NT, NLDE = (NPE + NT - 1) / NT;
     // Every lane's piece lies inside the array: tiles that stick out over the east / north edge of the array (ragged grids)
-    // copy the array's last pieces / rows instead -- those LDS cells are read by inactive threads only -- so no lane mask is
-    // needed but for the one wave per sweep that straddles the end of the tile.
+    // copy the array's last pieces / rows instead, so no lane mask is needed but for the one wave per sweep that straddles the
+    // end of the tile. INVARIANT: no active lane reads a clamped piece. A clamped piece puts other cells' values into its LDS
+    // cells; that is harmless only where those cells lie east of iend-1 + reach (3 here, 1 for evisc). It holds for 4-byte
+    // pieces (a piece never straddles the end of a row) and for 16-byte pieces whose first one starts on a piece of the row;
+    // a tile origin off a piece makes the row's last piece straddle, and the clamp then shifts cells an active lane may read.
+    // march_launch enforces it (pieces16_clear_of_row_end, k_march_common.h) and otherwise takes the 4-byte form.
     unsigned off[NLD], offe[NLDE > 0 ? NLDE : 1];                     // byte offsets from the start of a plane
 #pragma unroll
     for (int n=0; n<NLD; ++n)
@@ -1030,9 +1034,21 @@ int march_launch(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* 
 #endif
     constexpr int VEC = 16 / (int)sizeof(TF);
     const bool aligned = (g->icells % VEC == 0) && al16(f->u) && al16(f->v) && al16(f->w) && (ops == MARCH_ADVEC || al16(f->evisc)) && (!has_s || al16(f->s[0]));
-    const int pb = march_piece_bytes(aligned);
+    int pb = march_piece_bytes(aligned);
     // tile origin on a 16-byte piece where three cells west of the first cell is not one (istart = 16: rows of whole cache lines)
     const bool hx4 = ops == MARCH_BOTH && has_s && pb == 16 && (g->istart - 3) % VEC != 0 && (g->istart - 4) % VEC == 0 && g->istart >= 4 && !env_is("MHH_MARCH_HX", "3");
+    // 16-byte pieces only with the tile's origin on a piece. HX = 4 exists for the fused pass with a scalar; every other
+    // operator mode (one operator at a time, no scalar) with istart - 3 off a piece copies in 4-byte pieces. (fp32, igc = 4,
+    // icells % 4 == 0 ran 16-byte pieces from origin 1: the kernel's east-edge clamp moved the last piece of a row one cell west
+    // and the columns iend-2, iend-1 read their neighbours' values: tests/test_layout_matrix.py.)
+    const int hx = hx4 ? 4 : 3;
+    if (pb == 16 && (g->istart - hx) % VEC != 0) pb = 4;
+    // What the kernel's east-edge clamp relies on: no active lane reads a clamped piece. The u, v, w, s tile (reach 3):
+    // origin on a piece. The evisc tile (reach 1) starts VEC cells west of the block, on a piece only where istart is: there
+    // the straddling piece lies east of iend (igc >= 3: pieces16_clear_of_row_end).
+    MHH_REQUIRE(pb == 4 || ((g->istart - hx) % VEC == 0 && pieces16_clear_of_row_end(g, hx, 3, VEC)), "marching kernel: 16-byte pieces need the tile origin on a piece");
+    MHH_REQUIRE(pb == 4 || ops == MARCH_ADVEC || pieces16_clear_of_row_end(g, VEC, 1, VEC), "marching kernel: an active lane would read a clamped evisc piece");
+    note_march_form(MARCH_K_RHS25, pb, hx, ops == MARCH_ADVEC ? 0 : (pb == 16 ? VEC : 1), CW);
     if (hx4) hipLaunchKernelGGL((rhs25_march_kernel<VT, NJ, true, 16, true, true, 4>), dim3(nblocks), dim3(64, NJ), 0, st, mm, gd, mf, t);
     else march_variant(ops, pb, [&](auto PB, auto A, auto D) {
         if (has_s) hipLaunchKernelGGL((rhs25_march_kernel<VT, NJ, true, PB, A, D>),  dim3(nblocks), dim3(64, NJ), 0, st, mm, gd, mf, t);
@@ -1072,6 +1088,8 @@ int scalar_march_launch(const mhh_grid* g, const mhh_fields* f, const mhh_diff_p
     const int pb = march_piece_bytes(aligned);
     sf.hx = (pb == 16) ? 3 + (g->istart - 3) % VEC : 3;
     sf.ex = (pb == 16) ? 1 + (g->istart - 1) % VEC : 1;
+    MHH_REQUIRE(pb == 4 || (g->istart >= sf.hx && (g->istart - sf.hx) % VEC == 0 && (ops == MARCH_ADVEC || (g->istart - sf.ex) % VEC == 0)), "scalar pass: 16-byte pieces need the tile origins on a piece");
+    note_march_form(MARCH_K_SCALARS, pb, sf.hx, ops == MARCH_ADVEC ? 0 : sf.ex, 1);
     march_variant(ops, pb, [&](auto PB, auto A, auto D) {
         hipLaunchKernelGGL((rhs25_scalar_march_kernel<TF, NJ, NB, PB, A, D>), dim3(nblocks), dim3(64, NJ), 0, st, mm, gd, sf, t); });
     MHH_LAUNCH_CHECK();
@@ -1118,3 +1136,17 @@ int mhh::march25_scalars(const mhh_grid* g, const mhh_fields* f, const mhh_diff_
     return scalar_march_batches<float>(g, f, p, idx, n, ops, rows, as_stream(stream));
 }
 MHH_API unsigned long long mhh_stat_scalar_march_launches(void) { return g_scalar_march_launches; }
+
+// diagnostics: the copy form of the last launch of each marching kernel (k_march_common.h)
+static int g_march_form[mhh::MARCH_K_COUNT][4];
+void mhh::note_march_form(MarchKernelId kernel, int pb, int hx, int ex, int cw)
+{
+    g_march_form[kernel][0] = pb; g_march_form[kernel][1] = hx; g_march_form[kernel][2] = ex; g_march_form[kernel][3] = cw;
+}
+MHH_API int mhh_stat_march_form(int kernel, int* piece_bytes, int* hx, int* ex, int* cells_per_lane)
+{
+    MHH_REQUIRE(kernel >= 0 && kernel < mhh::MARCH_K_COUNT, "kernel: 0 rhs25, 1 scalar pass, 2 rhs44, 3 visc");
+    MHH_REQUIRE(piece_bytes && hx && ex && cells_per_lane, "null result pointer");
+    *piece_bytes = g_march_form[kernel][0]; *hx = g_march_form[kernel][1]; *ex = g_march_form[kernel][2]; *cells_per_lane = g_march_form[kernel][3];
+    return MHH_OK;
+}

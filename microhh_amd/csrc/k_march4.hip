@@ -228,5 +228,6 @@ int mhh::march44(const mhh_grid* g, const mhh_fields* f, MarchOps ops, void* str
     // 16-byte pieces need 16-byte aligned rows and tile origin (i0 - 3 = igc - 3 + 64*bx); other layouts copy in 4-byte pieces
     const int pb = (g->icells % vec == 0 && (g->igc - 3) % vec == 0 && al16(f->u) && al16(f->v) && al16(f->w)) ? 16 : 4;
     ++g_rhs44_march_launches;
+    note_march_form(MARCH_K_RHS44, pb, 3, 0, 1);
     return (g->dtype == MHH_F64) ? march4_launch<double>(g, f, pb, ops, bfold, as_stream(stream)) : march4_launch<float>(g, f, pb, ops, bfold, as_stream(stream));
 }

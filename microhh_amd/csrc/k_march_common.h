@@ -80,6 +80,23 @@ inline int march_kc(const mhh_grid* g, const MarchRows& rows, int kc, const char
     return kc;
 }
 inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
+// The east-edge rule of a tile copied in 16-byte pieces (vec cells each) whose origin lies `off` cells west of istart (the
+// tiles of a row are whole pieces apart, rows are whole pieces: icells % vec == 0). A piece that would run past the end of
+// the row is moved west onto the row's last piece (the fused 2i5 kernel's clamp) or left out (TileCopy): the LDS cells it
+// covers do not hold their own values. With the origin on a piece no piece straddles the end of a row, and the pieces past
+// it are read by inactive lanes only (igc >= reach). With the origin r cells past a piece the straddling piece starts at
+// icells - vec + r, and the last cell an active lane reads, iend - 1 + reach, must lie west of it.
+inline bool pieces16_clear_of_row_end(const mhh_grid* g, int off, int reach, int vec)
+{
+    if (g->icells % vec != 0) return false;
+    const int r = (((g->istart - off) % vec) + vec) % vec;     // (off > istart: the first piece of a row starts in the row before it)
+    return r == 0 ? (g->igc >= reach) : (g->iend - 1 + reach < g->icells - vec + r);
+}
+// Diagnostics (mhh_stat_march_form): the copy form of the last launch of each marching kernel. pb = bytes per LDS-DMA piece;
+// hx = cells the tile of the fields starts west of the block's first cell; ex = the same for the evisc tile (0: the kernel has
+// none); cw = cells per lane
+enum MarchKernelId { MARCH_K_RHS25 = 0, MARCH_K_SCALARS = 1, MARCH_K_RHS44 = 2, MARCH_K_VISC = 3, MARCH_K_COUNT = 4 };
+void note_march_form(MarchKernelId kernel, int pb, int hx, int ex, int cw);
 // Calls fn(PB, ADV, DIF) with the run-time operators and piece size (4 or 16 bytes) as std::integral_constants: the template
 // arguments of a marching kernel
 template<class Fn> void march_variant(MarchOps ops, int pb, Fn&& fn)

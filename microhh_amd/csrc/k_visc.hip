@@ -284,5 +284,6 @@ int mhh::visc_march(const mhh_grid* g, const mhh_fields* f, const mhh_diff_param
     const int pb = ex ? 16 : 4;
     if (!ex) ex = 1;
     ++g_visc_march_launches;
+    note_march_form(MARCH_K_VISC, pb, ex, 0, 1);
     return (g->dtype == MHH_F64) ? visc_launch<double>(g, f, p, th, ex, pb, rows, as_stream(stream)) : visc_launch<float>(g, f, p, th, ex, pb, rows, as_stream(stream));
 }

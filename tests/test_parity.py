@@ -217,7 +217,7 @@ def test_smag2_kernels(be, sm, dtype):
 
 
 def _oracle_rhs(c, adv, dif, sm, tPr=1./3., visc=1e-5, svisc=1e-5, limited=(), buoy=None):
-    """Advec::exec followed by Diff::exec on the oracle; returns the tendencies."""
+    """Advec::exec followed by Diff::exec on the oracle; returns the tendencies. dif None: Advec::exec alone."""
     O = cm.oracle(); g = c.grid; Gh = g.host_struct()
     ut, vt, wt, st = c.ut.copy(), c.vt.copy(), c.wt.copy(), [x.copy() for x in c.st]
     a = (ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.rhoref), ptr(c.rhorefh))
@@ -230,6 +230,8 @@ def _oracle_rhs(c, adv, dif, sm, tPr=1./3., visc=1e-5, svisc=1e-5, limited=(), b
             O.orc_advec_s_lim(Gh, ptr(st[n]), ptr(c.s[n]), *a)
         else:
             O.orc_advec_s(Gh, adv, ptr(st[n]), ptr(c.s[n]), *a)
+    if dif is None:
+        return ut, vt, wt, st
     if dif in (cm.DIFF_2, cm.DIFF_4):
         o = 2 if dif == cm.DIFF_2 else 4
         O.orc_diff_c(Gh, o, ptr(ut), ptr(c.u), dbl(visc)); O.orc_diff_c(Gh, o, ptr(vt), ptr(c.v), dbl(visc)); O.orc_diff_w(Gh, o, ptr(wt), ptr(c.w), dbl(visc))
