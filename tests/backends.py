@@ -6,11 +6,13 @@
               arrays own the memory. It exists to debug kernel logic without a GPU and is never used by
               the package itself.
 """
+import contextlib
 import ctypes as C
 import os
 import subprocess
 
 import numpy as np
+import pytest
 
 import common as cm
 from microhh_amd import capi
@@ -101,8 +103,26 @@ def get(name):
     return _cache[name]
 
 
+@pytest.fixture(params=cm.BACKENDS)
+def be(request):
+    """The backend of a test that runs on both; modules take it with ``from backends import be  # noqa: F401``."""
+    return get(request.param)
+
+
 def ok(be, rc):
     capi.check(rc, be.lib)
+
+
+@contextlib.contextmanager
+def pres_plan(be, g, c, order):
+    """The single-rank pressure plan of grid g with the base state of case c, destroyed on the way out."""
+    plan = capi.PLAN()
+    ok(be, be.lib.mhh_pres_plan_create(g.host_struct(), order, cm.ptr(g.dz), cm.ptr(g.dzhi), cm.ptr(g.dzi4), cm.ptr(g.dzhi4),
+                                       cm.ptr(c.rhoref), cm.ptr(c.rhorefh), C.byref(plan)))
+    try:
+        yield plan
+    finally:
+        be.lib.mhh_pres_plan_destroy(plan)
 
 
 class DevCase:

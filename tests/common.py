@@ -3,22 +3,65 @@
 Oracle (oracle/liborc.so) and the in-place reference build (oracle/_ref/libmhhref.so) are TEST
 infrastructure; they are loaded here and nowhere under microhh_amd/.
 """
+import contextlib
 import ctypes as C
 import os
 import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from microhh_amd import capi  # noqa: E402
 from microhh_amd.grid import (Grid, MhhGrid, EDGE_EW, EDGE_NS, EDGE_BOTH,  # noqa: E402,F401
                               ADVEC_2, ADVEC_2I5, ADVEC_2I4, ADVEC_2I62, ADVEC_2I53, ADVEC_4M, ADVEC_4, DIFF_2, DIFF_4, DIFF_SMAG2, moser_z, uniform_z)
 
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 _libs = {}
+
+BACKENDS = [pytest.param("emul"), pytest.param("hip", marks=pytest.mark.gpu)]      # tests/backends.py
+DTYPES = [np.float64, np.float32]
+
+# Every environment variable the library reads (microhh_amd/csrc: per call; microhh_amd/model.py: per HotPath).
+# tests/test_switches.py compares this tuple with the sources.
+KNOWN_SWITCHES = (
+    "MHH_ADVEC25_IMPL", "MHH_DIFF22_IMPL", "MHH_RHS25_IMPL", "MHH_RHS44_IMPL", "MHH_VISC_IMPL", "MHH_SCALAR_IMPL", "MHH_SCALAR_BATCH",
+    "MHH_MARCH_DMA", "MHH_MARCH_HX", "MHH_MARCH_F32X2", "MHH_MARCH_KC_RT", "MHH_VISC_KC_RT",
+    "MHH_PRES_LDS", "MHH_PRES_LDS_KC", "MHH_PRES_PITCH", "MHH_PRES_Y_TWISTED", "MHH_PRES_UNPACK_OUT", "MHH_PRES_RK_FUSED", "MHH_PRES4_WT",
+    "MHH_PRES_SLAB_LDS", "MHH_OVERLAP", "MHH_FORCE_COMM", "MHH_PRES_CHUNKS",
+)
+
+
+def known_switches(names):
+    """names, after checking that each is one the library reads: a misspelt switch would leave an A/B test comparing a form
+    with itself."""
+    unknown = sorted(set(names) - set(KNOWN_SWITCHES))
+    if unknown:
+        raise KeyError("not a switch the library reads (tests/common.py, KNOWN_SWITCHES): " + ", ".join(unknown))
+    return names
+
+
+@contextlib.contextmanager
+def switches(**kw):
+    """Environment switches for the duration of a block (the library reads them per call): NAME=value sets str(value), NAME=None
+    takes the variable away. On the way out, through an exception as well, each is what it was before: its old value, or absent."""
+    old = {k: os.environ.get(k) for k in known_switches(kw)}
+
+    def put(values):
+        for k, v in values.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = str(v)
+    put(kw)
+    try:
+        yield
+    finally:
+        put(old)
 
 
 def build_oracle():
@@ -157,3 +200,64 @@ def limiter_inputs(c, dtype):
     s = (np.round(c.s[0] * 6) / 6).astype(dtype)
     s.flat[::7] = c.s[0].flat[::7]
     return u, v, w, np.ascontiguousarray(s)
+
+
+def same(a, b):
+    return np.array_equal(a, b)
+
+
+def same_bits(a, b):
+    """same, for the modules whose reference is numpy itself: shape, dtype and every byte (-0. is not 0.)."""
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+def diff_params(sm, **kw):
+    """mhh_diff_params as the tests start from it (cs 0.23, tPr 1/3, the given surface model), further members by name."""
+    p = capi.MhhDiffParams(); p.cs = 0.23; p.tPr = 1./3.; p.surface_model = sm
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def tendencies(be, d):
+    """ut, vt, wt and the list of every st of a backends.DevCase as host arrays: what oracle_rhs returns."""
+    return be.host(d.ut), be.host(d.vt), be.host(d.wt), [be.host(x) for x in d.st]
+
+
+def flat(tend):
+    """[ut, vt, wt, st0, st1, ...] of what tendencies and oracle_rhs return."""
+    return list(tend[:3]) + list(tend[3])
+
+
+def oracle_rhs(c, adv, dif, sm, tPr=1./3., visc=1e-5, svisc=1e-5, limited=(), buoy=None):
+    """Advec::exec followed by Diff::exec on the oracle; returns the tendencies (ut, vt, wt, [st]). dif None: Advec::exec alone.
+    svisc: one diffusivity or one per scalar; limited: the scalars of advec.fluxlimit_list; buoy = (order, scalar, threfh, grav):
+    Thermo_dry's buoyancy first."""
+    O = oracle(); g = c.grid; Gh = g.host_struct()
+    ut, vt, wt, st = c.ut.copy(), c.vt.copy(), c.wt.copy(), [x.copy() for x in c.st]
+    sv = list(svisc) if isinstance(svisc, (list, tuple)) else [svisc] * len(st)
+    a = (ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.rhoref), ptr(c.rhorefh))
+    if buoy is not None:          # Thermo_dry::exec runs before Advec::exec (src/model.cxx:365,388)
+        order, n, threfh, grav = buoy
+        O.orc_buoyancy_tend(Gh, order, ptr(wt), ptr(c.s[n]), ptr(threfh), dbl(grav))
+    O.orc_advec_u(Gh, adv, ptr(ut), *a); O.orc_advec_v(Gh, adv, ptr(vt), *a); O.orc_advec_w(Gh, adv, ptr(wt), *a)
+    for n in range(len(st)):
+        if n in limited:
+            O.orc_advec_s_lim(Gh, ptr(st[n]), ptr(c.s[n]), *a)
+        else:
+            O.orc_advec_s(Gh, adv, ptr(st[n]), ptr(c.s[n]), *a)
+    if dif is None:
+        return ut, vt, wt, st
+    if dif in (DIFF_2, DIFF_4):
+        o = 2 if dif == DIFF_2 else 4
+        O.orc_diff_c(Gh, o, ptr(ut), ptr(c.u), dbl(visc)); O.orc_diff_c(Gh, o, ptr(vt), ptr(c.v), dbl(visc)); O.orc_diff_w(Gh, o, ptr(wt), ptr(c.w), dbl(visc))
+        for n in range(len(st)):
+            O.orc_diff_c(Gh, o, ptr(st[n]), ptr(c.s[n]), dbl(sv[n]))
+    else:
+        O.orc_smag2_diff_u(Gh, sm, ptr(ut), ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.evisc), ptr(c.u_fluxbot), ptr(c.u_fluxtop), ptr(c.rhoref), ptr(c.rhorefh), dbl(visc))
+        O.orc_smag2_diff_v(Gh, sm, ptr(vt), ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.evisc), ptr(c.v_fluxbot), ptr(c.v_fluxtop), ptr(c.rhoref), ptr(c.rhorefh), dbl(visc))
+        O.orc_smag2_diff_w(Gh, ptr(wt), ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.evisc), ptr(c.rhoref), ptr(c.rhorefh), dbl(visc))
+        for n in range(len(st)):
+            O.orc_smag2_diff_c(Gh, sm, ptr(st[n]), ptr(c.s[n]), ptr(c.evisc), ptr(c.s_fluxbot), ptr(c.s_fluxtop), ptr(c.rhoref), ptr(c.rhorefh), dbl(tPr), dbl(sv[n]))
+    return ut, vt, wt, st

@@ -50,15 +50,8 @@ def test_bench_json_line(world):
 def test_bench_overlapped_path_two_ranks():
     d = _run(2, extra=[])                                 # default with more than one rank: the halo exchange overlaps the interior rows
     assert d["config"]["halo_overlap"] is True and d["value"] > 0 and d["self_check"]["ratio"] < 1e-9
-    env_was = os.environ.get("MHH_OVERLAP")
-    os.environ["MHH_OVERLAP"] = "0"
-    try:
+    with cm.switches(MHH_OVERLAP="0"):
         d = _run(2)
-    finally:
-        if env_was is None:
-            os.environ.pop("MHH_OVERLAP", None)
-        else:
-            os.environ["MHH_OVERLAP"] = env_was
     assert d["config"]["halo_overlap"] is False and d["value"] > 0
 
 

@@ -2,10 +2,10 @@
 two independent kernel forms agree bit for bit (k-marching LDS kernels vs one-thread-per-cell kernels, fused vs
 per-operator launches), the pressure step is a projection (divergence after it is rounding-level and a second solve
 finds nothing left), the cyclic fill is idempotent, the slab code path reproduces the single-rank bits."""
-import os
-
 import numpy as np
 import pytest
+
+import common as cm
 
 pytestmark = pytest.mark.gpu
 
@@ -24,14 +24,9 @@ def _tend(hp):
 def _run_rhs(hp, fn, env=None):
     import torch
     keep = [t.clone() for t in _tend(hp)]
-    for k, v in (env or {}).items():
-        os.environ[k] = v
-    try:
+    with cm.switches(**(env or {})):
         fn()
         hp.sync()
-    finally:
-        for k in (env or {}):
-            os.environ.pop(k, None)
     out = [t.clone() for t in _tend(hp)]
     for t, k in zip(_tend(hp), keep):
         t.copy_(k)
@@ -50,11 +45,8 @@ def test_kernel_forms_agree_at_full_size(case, shape):
     # exec_viscosity: marching form vs cell form
     if case in ("drycblles", "gabls1"):
         hp.exec_viscosity(); hp.sync(); ev_march = hp.evisc.clone()
-        os.environ["MHH_VISC_IMPL"] = "cell"
-        try:
+        with cm.switches(MHH_VISC_IMPL="cell"):
             hp.exec_viscosity(); hp.sync()
-        finally:
-            del os.environ["MHH_VISC_IMPL"]
         assert torch.equal(ev_march, hp.evisc)
         assert float(hp.evisc[hp.grid.kstart:hp.grid.kend].min()) > 0.
         del ev_march
@@ -114,12 +106,8 @@ def test_pressure_lds_transform_form_matches_staged_form_at_full_size(case, shap
         for t, k in zip((hp.ut, hp.vt, hp.wt), keep):
             t.copy_(k)
         hp.p.zero_()
-        if form == "staged":
-            os.environ["MHH_PRES_LDS"] = "0"
-        try:
+        with cm.switches(MHH_PRES_LDS="0" if form == "staged" else None):
             hp.pres(); hp.sync()
-        finally:
-            os.environ.pop("MHH_PRES_LDS", None)
         out[form] = [t.clone() for t in (hp.p, hp.ut, hp.vt, hp.wt)]
     del keep
     assert not torch.equal(out["staged"][0], out["default"][0])          # two different sets of transforms

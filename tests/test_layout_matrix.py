@@ -3,7 +3,7 @@
 The marching kernels (k_march.hip: the fused advec_2i5 + diff_smag2 kernel and its scalar pass; k_march4.hip; k_visc.hip) pick
 their copy form on the host: 16-byte or 4-byte LDS-DMA pieces and the cells the tile starts west of the block, from
 ``icells % VEC`` (VEC = cells per 16 bytes), the alignment of the field pointers, ``istart``, the operators of the call and whether
-scalar 0 rides along. This module walks that decision space on both backends of tests/test_parity.py (``emul``, and ``hip``
+scalar 0 rides along. This module walks that decision space on both backends of tests/backends.py (``emul``, and ``hip``
 marked gpu) and compares every tendency with the oracle with ``np.array_equal``; a failure names the first and the last differing
 index, their number and the distance in ulp.
 
@@ -39,7 +39,6 @@ cell east, the piece that straddles the end of a row lies east of iend for every
 (pieces16_clear_of_row_end, k_march_common.h); the test repeats the inequality.
 """
 import ctypes as C
-import os
 import zlib
 
 import numpy as np
@@ -47,9 +46,8 @@ import pytest
 
 import backends as B
 import common as cm
-from common import ptr, dbl
-from microhh_amd import capi
-from test_parity import BACKENDS, DTYPES, _oracle_rhs
+from backends import be  # noqa: F401
+from common import DTYPES, ptr, dbl
 
 RHS25, SCALARS, RHS44, VISC = 0, 1, 2, 3
 ITOTS = (16, 64, 128, 66, 70, 130, 67)
@@ -59,11 +57,6 @@ IGCS_4 = (3, 4, 5, 7)
 # (fused, scalars): 23 = two or three scalars, alternating
 MODES = [(fused, nsc) for fused in (True, False) for nsc in (0, 1, 23)]
 THERMO_GRAV = 9.81
-
-
-@pytest.fixture(params=BACKENDS)
-def be(request):
-    return B.get(request.param)
 
 
 def _vec(dtype):
@@ -89,10 +82,6 @@ def _compare(fails, key, got, want):
     for n, (a, b) in enumerate(zip(got[3], want[3])):
         if not np.array_equal(a, b):
             fails.append("%s st%d: %s" % (key, n, _report(a, b)))
-
-
-def _tend(be, d):
-    return (be.host(d.ut), be.host(d.vt), be.host(d.wt), [be.host(x) for x in d.st])
 
 
 def _draw(key):
@@ -132,7 +121,7 @@ class Seen:
 
 
 def _params(sm, buoy=None, dth=None, be=None):
-    p = capi.MhhDiffParams(); p.cs = 0.23; p.tPr = 1./3.; p.surface_model = sm
+    p = cm.diff_params(sm)
     if buoy:
         p.buoyancy = 2; p.th_for_N2 = 0; p.threfh = be.ptr(dth).value; p.grav = THERMO_GRAV
     return p
@@ -155,10 +144,7 @@ def _run_rhs(be, seen, fails, key, c, adv, dif, sm, fused, limited=(), buoy=Fals
     p = _params(sm, buoy, dth, be)
     kern = RHS44 if order == 4 else RHS25
     launches = be.lib.mhh_stat_scalar_march_launches
-    old = os.environ.pop("MHH_SCALAR_BATCH", None)
-    if batch1:
-        os.environ["MHH_SCALAR_BATCH"] = "1"
-    try:
+    with cm.switches(MHH_SCALAR_BATCH="1" if batch1 else None):
         if fused:
             n0 = launches()
             B.ok(be, be.lib.mhh_rhs_exec(d.G, adv, dif, C.byref(f), C.byref(p), be.stream))
@@ -166,7 +152,7 @@ def _run_rhs(be, seen, fails, key, c, adv, dif, sm, fused, limited=(), buoy=Fals
             seen.form(be, g, kern, ("both", has_s) if order == 2 else "both", key)
             if launches() > n0:
                 seen.form(be, g, SCALARS, "both", key)
-            _compare(fails, key + " fused", _tend(be, d), _oracle_rhs(c, adv, dif, sm, limited=limited, buoy=ob))
+            _compare(fails, key + " fused", cm.tendencies(be, d), cm.oracle_rhs(c, adv, dif, sm, limited=limited, buoy=ob))
         else:
             n0 = launches()
             B.ok(be, be.lib.mhh_advec_exec(d.G, adv, C.byref(f), be.stream))
@@ -174,17 +160,13 @@ def _run_rhs(be, seen, fails, key, c, adv, dif, sm, fused, limited=(), buoy=Fals
             seen.form(be, g, kern, ("advec", has_s) if order == 2 else "advec", key)
             if launches() > n0:
                 seen.form(be, g, SCALARS, "advec", key)
-            _compare(fails, key + " advec alone", _tend(be, d), _oracle_rhs(c, adv, None, sm, limited=limited))
+            _compare(fails, key + " advec alone", cm.tendencies(be, d), cm.oracle_rhs(c, adv, None, sm, limited=limited))
             n0 = launches()
             B.ok(be, be.lib.mhh_diff_exec(d.G, dif, C.byref(f), C.byref(p), be.stream))
             seen.form(be, g, kern, ("diff", nsc >= 1) if order == 2 else "diff", key)
             if launches() > n0:
                 seen.form(be, g, SCALARS, "diff", key)
-            _compare(fails, key + " advec + diff", _tend(be, d), _oracle_rhs(c, adv, dif, sm, limited=limited))
-    finally:
-        os.environ.pop("MHH_SCALAR_BATCH", None)
-        if old is not None:
-            os.environ["MHH_SCALAR_BATCH"] = old
+            _compare(fails, key + " advec + diff", cm.tendencies(be, d), cm.oracle_rhs(c, adv, dif, sm, limited=limited))
 
 
 def _run_visc(be, seen, fails, key, g, sm, fields=None):
@@ -407,16 +389,10 @@ def test_mid_size_grids_with_many_strips_and_k_chunks(shape, dtype):
     two-call sequence and the fused pass without a scalar -- the operator modes that have no shifted-origin instantiation."""
     be = B.get("hip")
     fails, seen = [], Seen()
-    old = os.environ.get("MHH_MARCH_KC_RT")
-    os.environ["MHH_MARCH_KC_RT"] = "16"
-    try:
+    with cm.switches(MHH_MARCH_KC_RT="16"):
         for igc in (4, 16):
             g = cm.grid_2nd(*shape, gc=(igc, 3, 1), dtype=dtype)
             key = "%s %s igc %d:" % (np.dtype(dtype).name, shape, igc)
             _run_rhs(be, seen, fails, key, cm.Case(g, nscalars=0, rho="one"), cm.ADVEC_2I5, cm.DIFF_SMAG2, 1, True)
             _run_rhs(be, seen, fails, key, cm.Case(g, nscalars=1, rho="one"), cm.ADVEC_2I5, cm.DIFF_SMAG2, 1, False)
-    finally:
-        os.environ.pop("MHH_MARCH_KC_RT", None)
-        if old is not None:
-            os.environ["MHH_MARCH_KC_RT"] = old
     _assert_clean(fails, seen)

@@ -19,16 +19,9 @@ import pytest
 
 import backends as B
 import common as cm
-from common import ptr, dbl
+from backends import be  # noqa: F401
+from common import DTYPES, ptr, dbl, same
 from microhh_amd import capi
-
-BACKENDS = [pytest.param("emul"), pytest.param("hip", marks=pytest.mark.gpu)]
-DTYPES = [np.float64, np.float32]
-
-
-@pytest.fixture(params=BACKENDS)
-def be(request):
-    return B.get(request.param)
 
 
 def grids2(dtype, small=False):
@@ -40,10 +33,6 @@ def grids2(dtype, small=False):
 def grids4(dtype, small=False):
     gs = [cm.grid_4th(16, 12, 12, dtype=dtype), cm.grid_4th(66, 5, 8, dtype=dtype), cm.grid_4th(12, 1, 8, dtype=dtype)]
     return gs[:1] if small else gs
-
-
-def same(a, b):
-    return np.array_equal(a, b)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -216,36 +205,6 @@ def test_smag2_kernels(be, sm, dtype):
         assert same(be.host(n2), w_)
 
 
-def _oracle_rhs(c, adv, dif, sm, tPr=1./3., visc=1e-5, svisc=1e-5, limited=(), buoy=None):
-    """Advec::exec followed by Diff::exec on the oracle; returns the tendencies. dif None: Advec::exec alone."""
-    O = cm.oracle(); g = c.grid; Gh = g.host_struct()
-    ut, vt, wt, st = c.ut.copy(), c.vt.copy(), c.wt.copy(), [x.copy() for x in c.st]
-    a = (ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.rhoref), ptr(c.rhorefh))
-    if buoy is not None:          # Thermo_dry::exec runs before Advec::exec (src/model.cxx:365,388)
-        order, n, threfh, grav = buoy
-        O.orc_buoyancy_tend(Gh, order, ptr(wt), ptr(c.s[n]), ptr(threfh), dbl(grav))
-    O.orc_advec_u(Gh, adv, ptr(ut), *a); O.orc_advec_v(Gh, adv, ptr(vt), *a); O.orc_advec_w(Gh, adv, ptr(wt), *a)
-    for n in range(len(st)):
-        if n in limited:
-            O.orc_advec_s_lim(Gh, ptr(st[n]), ptr(c.s[n]), *a)
-        else:
-            O.orc_advec_s(Gh, adv, ptr(st[n]), ptr(c.s[n]), *a)
-    if dif is None:
-        return ut, vt, wt, st
-    if dif in (cm.DIFF_2, cm.DIFF_4):
-        o = 2 if dif == cm.DIFF_2 else 4
-        O.orc_diff_c(Gh, o, ptr(ut), ptr(c.u), dbl(visc)); O.orc_diff_c(Gh, o, ptr(vt), ptr(c.v), dbl(visc)); O.orc_diff_w(Gh, o, ptr(wt), ptr(c.w), dbl(visc))
-        for n in range(len(st)):
-            O.orc_diff_c(Gh, o, ptr(st[n]), ptr(c.s[n]), dbl(svisc))
-    else:
-        O.orc_smag2_diff_u(Gh, sm, ptr(ut), ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.evisc), ptr(c.u_fluxbot), ptr(c.u_fluxtop), ptr(c.rhoref), ptr(c.rhorefh), dbl(visc))
-        O.orc_smag2_diff_v(Gh, sm, ptr(vt), ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.evisc), ptr(c.v_fluxbot), ptr(c.v_fluxtop), ptr(c.rhoref), ptr(c.rhorefh), dbl(visc))
-        O.orc_smag2_diff_w(Gh, ptr(wt), ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.evisc), ptr(c.rhoref), ptr(c.rhorefh), dbl(visc))
-        for n in range(len(st)):
-            O.orc_smag2_diff_c(Gh, sm, ptr(st[n]), ptr(c.s[n]), ptr(c.evisc), ptr(c.s_fluxbot), ptr(c.s_fluxtop), ptr(c.rhoref), ptr(c.rhorefh), dbl(tPr), dbl(svisc))
-    return ut, vt, wt, st
-
-
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("adv,dif,sm", [(cm.ADVEC_2, cm.DIFF_2, 0), (cm.ADVEC_2I5, cm.DIFF_SMAG2, 0), (cm.ADVEC_2I5, cm.DIFF_SMAG2, 1), (cm.ADVEC_4, cm.DIFF_4, 0)])
 def test_operator_exec_and_fused_rhs_bitexact(be, adv, dif, sm, dtype):
@@ -255,13 +214,13 @@ def test_operator_exec_and_fused_rhs_bitexact(be, adv, dif, sm, dtype):
             continue
         for nsc, rho in ((1, "random"), (2, "random"), (1, "one")):      # rho == 1 takes the kernels' division-free path
             c = cm.Case(g, nscalars=nsc, rho=rho)
-            want = _oracle_rhs(c, adv, dif, sm)
-            p = capi.MhhDiffParams(); p.cs = 0.23; p.tPr = 1./3.; p.surface_model = sm
+            want = cm.oracle_rhs(c, adv, dif, sm)
+            p = cm.diff_params(sm)
             # unfused
             d = B.DevCase(be, c); f = d.fields()
             B.ok(be, be.lib.mhh_advec_exec(d.G, adv, C.byref(f), be.stream))
             B.ok(be, be.lib.mhh_diff_exec(d.G, dif, C.byref(f), C.byref(p), be.stream))
-            got = (be.host(d.ut), be.host(d.vt), be.host(d.wt), [be.host(x) for x in d.st])
+            got = cm.tendencies(be, d)
             for a, b, nm in zip(got[:3], want[:3], "uvw"):
                 assert same(a, b), ("unfused", nm, adv, dif, g.shape3, cm.ulp_diff(a, b))
             for a, b in zip(got[3], want[3]):
@@ -269,7 +228,7 @@ def test_operator_exec_and_fused_rhs_bitexact(be, adv, dif, sm, dtype):
             # fused
             d = B.DevCase(be, c); f = d.fields()
             B.ok(be, be.lib.mhh_rhs_exec(d.G, adv, dif, C.byref(f), C.byref(p), be.stream))
-            got = (be.host(d.ut), be.host(d.vt), be.host(d.wt), [be.host(x) for x in d.st])
+            got = cm.tendencies(be, d)
             for a, b, nm in zip(got[:3], want[:3], "uvw"):
                 assert same(a, b), ("fused", nm, adv, dif, g.shape3, cm.ulp_diff(a, b))
             for a, b in zip(got[3], want[3]):
@@ -286,11 +245,11 @@ def test_fused_rhs_and_viscosity_with_sixteen_ghost_cells_in_x(be, dtype):
     for g in (cm.grid_2nd(70, 9, 10, gc=(16, 3, 1), dtype=dtype), cm.grid_2nd(128, 6, 8, gc=(16, 3, 1), dtype=dtype), cm.grid_2nd(16, 5, 8, gc=(4, 3, 1), dtype=dtype)):
         for rho in ("one", "random"):
             c = cm.Case(g, nscalars=1, rho=rho, periodic=True)
-            want = _oracle_rhs(c, adv, dif, sm)
-            p = capi.MhhDiffParams(); p.cs = 0.23; p.tPr = 1./3.; p.surface_model = sm
+            want = cm.oracle_rhs(c, adv, dif, sm)
+            p = cm.diff_params(sm)
             d = B.DevCase(be, c); f = d.fields()
             B.ok(be, be.lib.mhh_rhs_exec(d.G, adv, dif, C.byref(f), C.byref(p), be.stream))
-            got = (be.host(d.ut), be.host(d.vt), be.host(d.wt), [be.host(x) for x in d.st])
+            got = cm.tendencies(be, d)
             for a, b, nm in zip(got[:3], want[:3], "uvw"):
                 assert same(a, b), ("fused", nm, g.shape3, rho, cm.ulp_diff(a, b))
             assert same(got[3][0], want[3][0]), ("fused s", g.shape3, rho)
@@ -303,7 +262,7 @@ def test_fused_rhs_and_viscosity_with_sixteen_ghost_cells_in_x(be, dtype):
         O.orc_smag2_evisc(Gh, sm, ptr(want), ptr(n2), ptr(c.dbdz), ptr(c.z0m), dbl(0.23), dbl(1./3.))
         O.orc_boundary_cyclic(Gh, ptr(want), cm.EDGE_BOTH)
         d = B.DevCase(be, c); f = d.fields()
-        p = capi.MhhDiffParams(); p.cs = 0.23; p.tPr = 1./3.; p.surface_model = sm; p.grav = 9.81
+        p = cm.diff_params(sm, grav=9.81)
         dth = be.arr(thref); p.thref = be.ptr(dth).value
         ml = B.mlen0(be, g, 0.23); p.mlen0 = be.ptr(ml).value
         B.ok(be, be.lib.mhh_diff_exec_viscosity(d.G, dif, C.byref(f), C.byref(p), be.stream))
@@ -319,8 +278,8 @@ def test_fused_rhs_with_fluxlimit_list(be, limited, dtype):
     for g in grids2(dtype)[:2]:
         c = cm.Case(g, nscalars=2)
         c.u, c.v, c.w, c.s[0] = cm.limiter_inputs(c, dtype)
-        want = _oracle_rhs(c, adv, dif, sm, limited=limited)
-        p = capi.MhhDiffParams(); p.cs = 0.23; p.tPr = 1./3.; p.surface_model = sm
+        want = cm.oracle_rhs(c, adv, dif, sm, limited=limited)
+        p = cm.diff_params(sm)
         for fused in (False, True):
             d = B.DevCase(be, c); f = d.fields()
             for n in limited:
@@ -330,7 +289,7 @@ def test_fused_rhs_with_fluxlimit_list(be, limited, dtype):
             else:
                 B.ok(be, be.lib.mhh_advec_exec(d.G, adv, C.byref(f), be.stream))
                 B.ok(be, be.lib.mhh_diff_exec(d.G, dif, C.byref(f), C.byref(p), be.stream))
-            got = (be.host(d.ut), be.host(d.vt), be.host(d.wt), [be.host(x) for x in d.st])
+            got = cm.tendencies(be, d)
             for a, b, nm in zip(got[:3], want[:3], "uvw"):
                 assert same(a, b), (fused, nm, g.shape3, cm.ulp_diff(a, b))
             for n, (a, b) in enumerate(zip(got[3], want[3])):
@@ -354,12 +313,12 @@ def test_dry_buoyancy_standalone_and_folded(be, adv, dif, order, dtype):
         B.ok(be, be.lib.mhh_thermo_dry_buoyancy_tend(d.G, order, be.ptr(t), be.ptr(d.s[0]), be.ptr(dth), grav, be.stream))
         assert same(be.host(t), want) and not np.array_equal(want, c.wt)
         for nth in (0, 1):          # scalar 0 rides inside the march kernel, scalar 1 takes the separate kernel first
-            want = _oracle_rhs(c, adv, dif, 1 if dif == cm.DIFF_SMAG2 else 0, buoy=(order, nth, threfh, grav))
+            want = cm.oracle_rhs(c, adv, dif, 1 if dif == cm.DIFF_SMAG2 else 0, buoy=(order, nth, threfh, grav))
             d = B.DevCase(be, c); f = d.fields()
-            p = capi.MhhDiffParams(); p.cs = 0.23; p.tPr = 1./3.; p.surface_model = 1 if dif == cm.DIFF_SMAG2 else 0
+            p = cm.diff_params(1 if dif == cm.DIFF_SMAG2 else 0)
             p.buoyancy = order; p.th_for_N2 = nth; p.threfh = be.ptr(dth).value; p.grav = grav
             B.ok(be, be.lib.mhh_rhs_exec(d.G, adv, dif, C.byref(f), C.byref(p), be.stream))
-            got = (be.host(d.ut), be.host(d.vt), be.host(d.wt), [be.host(x) for x in d.st])
+            got = cm.tendencies(be, d)
             for a, b, nm in zip(got[:3], want[:3], "uvw"):
                 assert same(a, b), ("folded buoyancy", nm, adv, nth, g.shape3, cm.ulp_diff(a, b))
             for a, b in zip(got[3], want[3]):
@@ -385,7 +344,7 @@ def test_exec_viscosity(be, sm, neutral, dtype):
             n2 = np.zeros(g.shape3, dtype=dtype); O.orc_calc_N2(Gh, ptr(n2), ptr(c.s[0]), ptr(thref), dbl(grav))
             O.orc_smag2_evisc(Gh, sm, ptr(want), ptr(n2), ptr(c.dbdz), ptr(c.z0m), dbl(cs), dbl(tPr))
         d = B.DevCase(be, c); f = d.fields()
-        p = capi.MhhDiffParams(); p.cs = cs; p.tPr = tPr; p.surface_model = sm; p.neutral = neutral
+        p = cm.diff_params(sm, neutral=neutral)
         p.N2 = None; p.th_for_N2 = 0; dthref = be.arr(thref); p.thref = be.ptr(dthref).value; p.grav = grav
         ml = B.mlen0(be, g, cs); p.mlen0 = be.ptr(ml).value
         B.ok(be, be.lib.mhh_diff_exec_viscosity(d.G, cm.DIFF_SMAG2, C.byref(f), C.byref(p), be.stream))
@@ -403,19 +362,17 @@ def test_unpack_normalisation_is_two_divisions_bit_for_bit(be, dtype):
     very same packed solution, read back through mhh_pres_solve's in-place buffer."""
     for shape in ((16, 8, 6), (16, 12, 6), (8, 1, 6)):
         g = cm.grid_2nd(*shape, gc=(2, 2, 1), dtype=dtype)
-        c = cm.Case(g, rho="random", periodic=True); Gh = g.host_struct()
+        c = cm.Case(g, rho="random", periodic=True)
         d = B.DevCase(be, c); f = d.fields()
-        plan = capi.PLAN()
-        B.ok(be, be.lib.mhh_pres_plan_create(Gh, 2, ptr(g.dz), ptr(g.dzhi), ptr(g.dzi4), ptr(g.dzhi4), ptr(c.rhoref), ptr(c.rhorefh), C.byref(plan)))
         rng = np.random.default_rng(5)
         pk0 = (rng.standard_normal((g.ktot, g.jtot, g.itot)) * 10.0**rng.integers(-30, 30, (g.ktot, g.jtot, g.itot))).astype(dtype)
         pk = be.arr(pk0)
-        B.ok(be, be.lib.mhh_pres_solve(plan, d.G, C.byref(f), be.ptr(pk), be.stream))
-        sol = be.host(pk)                                   # the un-normalised solution the unpack read
+        with B.pres_plan(be, g, c, 2) as plan:
+            B.ok(be, be.lib.mhh_pres_solve(plan, d.G, C.byref(f), be.ptr(pk), be.stream))
+            sol = be.host(pk)                               # the un-normalised solution the unpack read
         want = (sol / dtype(g.jtot) / dtype(g.itot)).astype(dtype)
         got = be.host(d.p)[g.kstart:g.kend, g.jstart:g.jend, g.istart:g.iend]
         assert same(got, want), (shape, cm.ulp_diff(got, want))
-        be.lib.mhh_pres_plan_destroy(plan)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -426,20 +383,13 @@ def test_pres4_exec_unpack_and_output_in_one_kernel_equals_two(be, dtype):
         c = cm.Case(g, rho="one", periodic=True)
         for m in (1, 2):
             c.w[g.kstart-m] = -c.w[g.kstart+m]; c.w[g.kend+m] = -c.w[g.kend-m]
-        Gh = g.host_struct(); dt = 0.7
+        dt = 0.7
         out = {}
         for form in ("one", "two"):
             d = B.DevCase(be, c); f = d.fields()
-            plan = capi.PLAN()
-            B.ok(be, be.lib.mhh_pres_plan_create(Gh, 4, ptr(g.dz), ptr(g.dzhi), ptr(g.dzi4), ptr(g.dzhi4), ptr(c.rhoref), ptr(c.rhorefh), C.byref(plan)))
-            if form == "two":
-                os.environ["MHH_PRES_UNPACK_OUT"] = "0"
-            try:
+            with B.pres_plan(be, g, c, 4) as plan, cm.switches(MHH_PRES_UNPACK_OUT="0" if form == "two" else None):
                 B.ok(be, be.lib.mhh_pres_exec(plan, d.G, C.byref(f), dt, be.stream))
-            finally:
-                os.environ.pop("MHH_PRES_UNPACK_OUT", None)
             out[form] = [be.host(x) for x in (d.p, d.ut, d.vt, d.wt)]
-            be.lib.mhh_pres_plan_destroy(plan)
         for x, y, nm in zip(out["one"], out["two"], ("p", "ut", "vt", "wt")):
             assert same(x, y), (g.shape3, nm, cm.ulp_diff(x, y))
         assert not np.array_equal(out["one"][1], c.ut)
@@ -454,21 +404,14 @@ def test_pres2_exec_unpack_and_output_in_one_kernel_equals_two(be, dtype):
           cm.grid_2nd(8, 1, 6, gc=(1, 1, 1), dtype=dtype)]
     for g in gl:
         c = cm.Case(g, rho="random", periodic=True)
-        Gh = g.host_struct(); dt = 0.7
+        dt = 0.7
         out = {}
         for form in ("one", "two"):
             d = B.DevCase(be, c); f = d.fields()
-            plan = capi.PLAN()
-            B.ok(be, be.lib.mhh_pres_plan_create(Gh, 2, ptr(g.dz), ptr(g.dzhi), ptr(g.dzi4), ptr(g.dzhi4), ptr(c.rhoref), ptr(c.rhorefh), C.byref(plan)))
-            if form == "two":
-                os.environ["MHH_PRES_UNPACK_OUT"] = "0"
-            os.environ["MHH_PRES_LDS"] = "0"                     # both are forms of the rocFFT path
-            try:
+            # MHH_PRES_LDS=0: both are forms of the rocFFT path
+            with B.pres_plan(be, g, c, 2) as plan, cm.switches(MHH_PRES_UNPACK_OUT="0" if form == "two" else None, MHH_PRES_LDS="0"):
                 B.ok(be, be.lib.mhh_pres_exec(plan, d.G, C.byref(f), dt, be.stream))
-            finally:
-                os.environ.pop("MHH_PRES_UNPACK_OUT", None); os.environ.pop("MHH_PRES_LDS", None)
             out[form] = [be.host(x) for x in (d.p, d.ut, d.vt, d.wt)]
-            be.lib.mhh_pres_plan_destroy(plan)
         for x, y, nm in zip(out["one"], out["two"], ("p", "ut", "vt", "wt")):
             assert same(x, y), (g.shape3, nm, cm.ulp_diff(x, y))
         assert not np.array_equal(out["one"][1], c.ut)
@@ -488,17 +431,13 @@ def test_pres2_lds_transform_form(be, dtype):
         g = cm.grid_2nd(*shape, gc=gc, dtype=dtype)
         c = cm.Case(g, rho="random", periodic=True); Gh = g.host_struct(); dt = 0.7
         d = B.DevCase(be, c); f = d.fields()
-        plan = capi.PLAN()
-        B.ok(be, be.lib.mhh_pres_plan_create(Gh, 2, ptr(g.dz), ptr(g.dzhi), ptr(g.dzi4), ptr(g.dzhi4), ptr(c.rhoref), ptr(c.rhorefh), C.byref(plan)))
-        if kc: os.environ["MHH_PRES_LDS_KC"] = kc
-        try:
+        with B.pres_plan(be, g, c, 2) as plan, cm.switches(MHH_PRES_LDS_KC=kc):
             assert be.lib.mhh_pres_plan_has_lds_form(plan) == 1
             assert be.lib.mhh_pres_exec_form(plan) == 0                  # small grid: mhh_pres_exec stays with the staged form ...
-            os.environ["MHH_PRES_LDS"] = "1"
-            assert be.lib.mhh_pres_exec_form(plan) == 1                  # ... unless told otherwise
-            os.environ["MHH_PRES_LDS"] = "0"
-            assert be.lib.mhh_pres_exec_form(plan) == 0
-            os.environ.pop("MHH_PRES_LDS")
+            with cm.switches(MHH_PRES_LDS="1"):
+                assert be.lib.mhh_pres_exec_form(plan) == 1              # ... unless told otherwise
+            with cm.switches(MHH_PRES_LDS="0"):
+                assert be.lib.mhh_pres_exec_form(plan) == 0
             pk_want = np.zeros((g.ktot, g.jtot, g.itot), dtype=dtype)
             ut, vt, wt = c.ut.copy(), c.vt.copy(), c.wt.copy()
             O.orc_pres_input(Gh, 2, ptr(pk_want), ptr(c.u), ptr(c.v), ptr(c.w), ptr(ut), ptr(vt), ptr(wt), ptr(c.rhoref), ptr(c.rhorefh), dbl(dt))
@@ -523,26 +462,18 @@ def test_pres2_lds_transform_form(be, dtype):
                 assert np.abs(be.host(got_t) - want_t).max() <= tol*max(np.abs(want_t).max(), pscale/float(min(g.dx, g.dy))), (shape, nm)
             # mhh_pres_exec in this form (by itself only on large grids): same bits as the three stages
             d2 = B.DevCase(be, c); f2 = d2.fields()
-            os.environ["MHH_PRES_LDS"] = "1"
-            try:
+            with cm.switches(MHH_PRES_LDS="1"):
                 B.ok(be, be.lib.mhh_pres_exec(plan, d2.G, C.byref(f2), dt, be.stream))
-            finally:
-                os.environ.pop("MHH_PRES_LDS", None)
             for x, y in ((d.p, d2.p), (d.ut, d2.ut), (d.vt, d2.vt), (d.wt, d2.wt)):
                 assert same(be.host(x), be.host(y))
             # and it is a projection: nothing left for a second solve
             pk = be.zeros((g.ktot, g.jtot, g.itot), dtype)
             B.ok(be, be.lib.mhh_pres_input(plan, d2.G, C.byref(f2), dt, be.ptr(pk), be.stream))
             assert np.abs(be.host(pk)).max() <= (1e-9 if dtype == np.float64 else 2e-2) * np.abs(pk_want).max()
-        finally:
-            os.environ.pop("MHH_PRES_LDS_KC", None)
-            be.lib.mhh_pres_plan_destroy(plan)
     # grids the form does not cover keep the staged one
     g = cm.grid_2nd(12, 10, 8, gc=(3, 3, 1), dtype=dtype); c = cm.Case(g, rho="random", periodic=True)
-    plan = capi.PLAN()
-    B.ok(be, be.lib.mhh_pres_plan_create(g.host_struct(), 2, ptr(g.dz), ptr(g.dzhi), ptr(g.dzi4), ptr(g.dzhi4), ptr(c.rhoref), ptr(c.rhorefh), C.byref(plan)))
-    assert be.lib.mhh_pres_plan_has_lds_form(plan) == 0
-    be.lib.mhh_pres_plan_destroy(plan)
+    with B.pres_plan(be, g, c, 2) as plan:
+        assert be.lib.mhh_pres_plan_has_lds_form(plan) == 0
 
 
 def _lds4_form_against_oracle(be, shape, dtype, tol, kc=None, stages=False):
@@ -556,17 +487,11 @@ def _lds4_form_against_oracle(be, shape, dtype, tol, kc=None, stages=False):
         c.w[g.kstart-m] = -c.w[g.kstart+m]; c.w[g.kend+m] = -c.w[g.kend-m]
     Gh = g.host_struct(); dt = 0.7
     d = B.DevCase(be, c); f = d.fields()
-    plan = capi.PLAN()
-    B.ok(be, be.lib.mhh_pres_plan_create(Gh, 4, ptr(g.dz), ptr(g.dzhi), ptr(g.dzi4), ptr(g.dzhi4), ptr(c.rhoref), ptr(c.rhorefh), C.byref(plan)))
-    if kc: os.environ["MHH_PRES_LDS_KC"] = kc
-    try:
+    with B.pres_plan(be, g, c, 4) as plan, cm.switches(MHH_PRES_LDS_KC=kc):
         assert be.lib.mhh_pres_plan_has_lds_form(plan) == 1, shape
-        os.environ["MHH_PRES_LDS"] = "1"
-        try:
+        with cm.switches(MHH_PRES_LDS="1"):
             assert be.lib.mhh_pres_exec_form(plan) == 1
             B.ok(be, be.lib.mhh_pres_exec(plan, d.G, C.byref(f), dt, be.stream))
-        finally:
-            os.environ.pop("MHH_PRES_LDS", None)
         pk = np.zeros((g.ktot, g.jtot, g.itot), dtype=dtype); p_want = np.zeros(g.shape3, dtype=dtype)
         ut, vt, wt = c.ut.copy(), c.vt.copy(), c.wt.copy()
         O.orc_pres_input(Gh, 4, ptr(pk), ptr(c.u), ptr(c.v), ptr(c.w), ptr(ut), ptr(vt), ptr(wt), ptr(c.rhoref), ptr(c.rhorefh), dbl(dt))
@@ -598,9 +523,6 @@ def _lds4_form_against_oracle(be, shape, dtype, tol, kc=None, stages=False):
             pk2 = be.zeros((g.ktot, g.jtot, g.itot), dtype)
             B.ok(be, be.lib.mhh_pres_input(plan, d2.G, C.byref(f2), dt, be.ptr(pk2), be.stream))
             assert np.abs(be.host(pk2)).max() <= (1e-9 if dtype == np.float64 else 2e-2) * np.abs(pk_in).max()
-    finally:
-        os.environ.pop("MHH_PRES_LDS_KC", None)
-        be.lib.mhh_pres_plan_destroy(plan)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -612,10 +534,8 @@ def test_pres4_lds_transform_form(be, dtype):
         _lds4_form_against_oracle(be, shape, dtype, tol, kc=kc, stages=True)
     # grids the form does not cover keep the staged one
     g = cm.grid_4th(12, 10, 8, dtype=dtype); c = cm.Case(g, rho="one", periodic=True)
-    plan = capi.PLAN()
-    B.ok(be, be.lib.mhh_pres_plan_create(g.host_struct(), 4, ptr(g.dz), ptr(g.dzhi), ptr(g.dzi4), ptr(g.dzhi4), ptr(c.rhoref), ptr(c.rhorefh), C.byref(plan)))
-    assert be.lib.mhh_pres_plan_has_lds_form(plan) == 0
-    be.lib.mhh_pres_plan_destroy(plan)
+    with B.pres_plan(be, g, c, 4) as plan:
+        assert be.lib.mhh_pres_plan_has_lds_form(plan) == 0
 
 
 @pytest.mark.gpu
@@ -634,15 +554,10 @@ def _lds_form_against_oracle(be, shape, gc, dtype, tol):
     g = cm.grid_2nd(*shape, gc=gc, dtype=dtype)
     c = cm.Case(g, rho="random", periodic=True); Gh = g.host_struct(); dt = 0.7
     d = B.DevCase(be, c); f = d.fields()
-    plan = capi.PLAN()
-    B.ok(be, be.lib.mhh_pres_plan_create(Gh, 2, ptr(g.dz), ptr(g.dzhi), ptr(g.dzi4), ptr(g.dzhi4), ptr(c.rhoref), ptr(c.rhorefh), C.byref(plan)))
-    try:
+    with B.pres_plan(be, g, c, 2) as plan:
         assert be.lib.mhh_pres_plan_has_lds_form(plan) == 1, shape
-        os.environ["MHH_PRES_LDS"] = "1"
-        try:
+        with cm.switches(MHH_PRES_LDS="1"):
             B.ok(be, be.lib.mhh_pres_exec(plan, d.G, C.byref(f), dt, be.stream))
-        finally:
-            os.environ.pop("MHH_PRES_LDS", None)
         pk = np.zeros((g.ktot, g.jtot, g.itot), dtype=dtype); p_want = np.zeros(g.shape3, dtype=dtype)
         ut, vt, wt = c.ut.copy(), c.vt.copy(), c.wt.copy()
         O.orc_pres_input(Gh, 2, ptr(pk), ptr(c.u), ptr(c.v), ptr(c.w), ptr(ut), ptr(vt), ptr(wt), ptr(c.rhoref), ptr(c.rhorefh), dbl(dt))
@@ -654,8 +569,6 @@ def _lds_form_against_oracle(be, shape, gc, dtype, tol):
         assert err <= tol, (shape, err)
         for got_t, want_t, nm in ((d.ut, ut, "ut"), (d.vt, vt, "vt"), (d.wt, wt, "wt")):
             assert np.abs(be.host(got_t) - want_t).max() <= tol*max(np.abs(want_t).max(), pscale/float(min(g.dx, g.dy))), (shape, nm)
-    finally:
-        be.lib.mhh_pres_plan_destroy(plan)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -664,28 +577,18 @@ def test_pres2_lds_y_stage_with_two_blocks_per_column(be, dtype):
     the upper ones top-down by a second, a 2 x 2 system where they meet) against the oracle, like the one-block form: upper halves of
     one level, of whole and of partial rounds of eight; and against the one-block form within the same tolerance."""
     tol = 1e-11 if dtype == np.float64 else 2e-4
-    os.environ["MHH_PRES_Y_TWISTED"] = "1"
-    try:
+    with cm.switches(MHH_PRES_Y_TWISTED="1"):
         for shape in ((16, 64, 17), (32, 16, 24), (16, 8, 37), (64, 32, 40), (128, 32, 16)):
             _lds_form_against_oracle(be, shape, (3, 3, 1), dtype, tol)
-    finally:
-        os.environ.pop("MHH_PRES_Y_TWISTED", None)
     # the switch does something: the two forms differ in rounding (and only in rounding)
     g = cm.grid_2nd(32, 16, 24, gc=(3, 3, 1), dtype=dtype); c = cm.Case(g, rho="random", periodic=True)
-    plan = capi.PLAN()
-    B.ok(be, be.lib.mhh_pres_plan_create(g.host_struct(), 2, ptr(g.dz), ptr(g.dzhi), ptr(g.dzi4), ptr(g.dzhi4), ptr(c.rhoref), ptr(c.rhorefh), C.byref(plan)))
     out = {}
-    try:
+    with B.pres_plan(be, g, c, 2) as plan:
         for tw in ("0", "1"):
             d = B.DevCase(be, c); f = d.fields()
-            os.environ["MHH_PRES_LDS"] = "1"; os.environ["MHH_PRES_Y_TWISTED"] = tw
-            try:
+            with cm.switches(MHH_PRES_LDS="1", MHH_PRES_Y_TWISTED=tw):
                 B.ok(be, be.lib.mhh_pres_exec(plan, d.G, C.byref(f), 0.7, be.stream))
-            finally:
-                os.environ.pop("MHH_PRES_LDS", None); os.environ.pop("MHH_PRES_Y_TWISTED", None)
             out[tw] = be.host(d.p)
-    finally:
-        be.lib.mhh_pres_plan_destroy(plan)
     assert not np.array_equal(out["0"], out["1"])
     assert np.abs(out["0"] - out["1"]).max() <= tol * np.abs(out["0"]).max()
 
@@ -705,10 +608,8 @@ def test_pres2_lds_form_at_every_instantiated_row_length(dtype):
         _lds_form_against_oracle(be, shape, (3, 3, 1), dtype, tol)
     if dtype == np.float64:     # fp64 rows of 1024 along y have no instantiation (scratch): the plan says so and mhh_pres_exec takes the staged form
         g = cm.grid_2nd(128, 1024, 3, gc=(3, 3, 1), dtype=dtype); c = cm.Case(g, rho="random", periodic=True)
-        plan = capi.PLAN()
-        B.ok(be, be.lib.mhh_pres_plan_create(g.host_struct(), 2, ptr(g.dz), ptr(g.dzhi), ptr(g.dzi4), ptr(g.dzhi4), ptr(c.rhoref), ptr(c.rhorefh), C.byref(plan)))
-        assert be.lib.mhh_pres_plan_has_lds_form(plan) == 0 and be.lib.mhh_pres_exec_form(plan) == 0
-        be.lib.mhh_pres_plan_destroy(plan)
+        with B.pres_plan(be, g, c, 2) as plan:
+            assert be.lib.mhh_pres_plan_has_lds_form(plan) == 0 and be.lib.mhh_pres_exec_form(plan) == 0
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -719,14 +620,8 @@ def test_pres2_lds_plans_of_different_sizes_do_not_disturb_each_other(be, dtype)
     O = cm.oracle()
     gl, gs = cm.grid_2nd(64, 32, 6, gc=(3, 3, 1), dtype=dtype), cm.grid_2nd(16, 8, 6, gc=(3, 3, 1), dtype=dtype)
     cl, cs = cm.Case(gl, rho="random", periodic=True), cm.Case(gs, rho="random", periodic=True)
-    plans = []
-    for g, c in ((gl, cl), (gs, cs)):
-        plan = capi.PLAN()
-        B.ok(be, be.lib.mhh_pres_plan_create(g.host_struct(), 2, ptr(g.dz), ptr(g.dzhi), ptr(g.dzi4), ptr(g.dzhi4), ptr(c.rhoref), ptr(c.rhorefh), C.byref(plan)))
-        plans.append(plan)
-    os.environ["MHH_PRES_LDS"] = "1"
-    try:
-        for g, c, plan in ((gl, cl, plans[0]), (gs, cs, plans[1]), (gl, cl, plans[0])):
+    with B.pres_plan(be, gl, cl, 2) as pl, B.pres_plan(be, gs, cs, 2) as ps, cm.switches(MHH_PRES_LDS="1"):
+        for g, c, plan in ((gl, cl, pl), (gs, cs, ps), (gl, cl, pl)):
             d = B.DevCase(be, c); f = d.fields(); dt = 0.7
             B.ok(be, be.lib.mhh_pres_exec(plan, d.G, C.byref(f), dt, be.stream))
             Gh = g.host_struct()
@@ -736,36 +631,17 @@ def test_pres2_lds_plans_of_different_sizes_do_not_disturb_each_other(be, dtype)
             O.orc_pres_solve(Gh, 2, ptr(p_want), ptr(pk), ptr(c.rhoref), ptr(c.rhorefh))
             sl = (slice(g.kstart-1, g.kend), slice(None), slice(None))
             assert np.abs(be.host(d.p)[sl] - p_want[sl]).max() <= tol*np.abs(p_want).max(), g.shape3
-    finally:
-        os.environ.pop("MHH_PRES_LDS", None)
-        for plan in plans:
-            be.lib.mhh_pres_plan_destroy(plan)
 
 
 @pytest.mark.parametrize("adv,dif", [(cm.ADVEC_2I4, cm.DIFF_2), (cm.ADVEC_2I62, cm.DIFF_SMAG2), (cm.ADVEC_2I53, cm.DIFF_SMAG2), (cm.ADVEC_4M, cm.DIFF_4)])
 def test_rhs_exec_other_scheme_pairs_run_as_two_calls(be, adv, dif):
     """mhh_rhs_exec accepts every pair of valid schemes: pairs without a fused kernel run Advec::exec then Diff::exec."""
-    O = cm.oracle()
     g = cm.grid_4th(16, 12, 12) if adv == cm.ADVEC_4M else cm.grid_2nd(16, 12, 10, gc=(3, 3, 2))
-    c = cm.Case(g, nscalars=1); Gh = g.host_struct()
+    c = cm.Case(g, nscalars=1)
     sm = 1 if dif == cm.DIFF_SMAG2 else 0
-    ut, vt, wt, st = c.ut.copy(), c.vt.copy(), c.wt.copy(), c.st[0].copy()
-    a = (ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.rhoref), ptr(c.rhorefh))
-    O.orc_advec_u(Gh, adv, ptr(ut), *a); O.orc_advec_v(Gh, adv, ptr(vt), *a); O.orc_advec_w(Gh, adv, ptr(wt), *a); O.orc_advec_s(Gh, adv, ptr(st), ptr(c.s[0]), *a)
-    cpy = cm.Case(g, nscalars=1)
-    cpy.ut, cpy.vt, cpy.wt, cpy.st = ut, vt, wt, [st]
-    want = None
-    if dif == cm.DIFF_SMAG2:
-        O.orc_smag2_diff_u(Gh, sm, ptr(ut), ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.evisc), ptr(c.u_fluxbot), ptr(c.u_fluxtop), ptr(c.rhoref), ptr(c.rhorefh), dbl(1e-5))
-        O.orc_smag2_diff_v(Gh, sm, ptr(vt), ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.evisc), ptr(c.v_fluxbot), ptr(c.v_fluxtop), ptr(c.rhoref), ptr(c.rhorefh), dbl(1e-5))
-        O.orc_smag2_diff_w(Gh, ptr(wt), ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.evisc), ptr(c.rhoref), ptr(c.rhorefh), dbl(1e-5))
-        O.orc_smag2_diff_c(Gh, sm, ptr(st), ptr(c.s[0]), ptr(c.evisc), ptr(c.s_fluxbot), ptr(c.s_fluxtop), ptr(c.rhoref), ptr(c.rhorefh), dbl(1./3.), dbl(1e-5))
-    else:
-        o = 2 if dif == cm.DIFF_2 else 4
-        O.orc_diff_c(Gh, o, ptr(ut), ptr(c.u), dbl(1e-5)); O.orc_diff_c(Gh, o, ptr(vt), ptr(c.v), dbl(1e-5)); O.orc_diff_w(Gh, o, ptr(wt), ptr(c.w), dbl(1e-5))
-        O.orc_diff_c(Gh, o, ptr(st), ptr(c.s[0]), dbl(1e-5))
+    ut, vt, wt, (st,) = cm.oracle_rhs(c, adv, dif, sm)
     d = B.DevCase(be, c); f = d.fields()
-    p = capi.MhhDiffParams(); p.cs = 0.23; p.tPr = 1./3.; p.surface_model = sm
+    p = cm.diff_params(sm)
     B.ok(be, be.lib.mhh_rhs_exec(d.G, adv, dif, C.byref(f), C.byref(p), be.stream))
     for got, w_, nm in ((d.ut, ut, "ut"), (d.vt, vt, "vt"), (d.wt, wt, "wt"), (d.st[0], st, "st")):
         assert same(be.host(got), w_), (adv, dif, nm)
@@ -783,8 +659,8 @@ def test_fused_rhs_on_minimal_and_ragged_grids(be, dtype):
         for shape in shapes:
             g = cm.grid_4th(*shape, dtype=dtype) if adv == cm.ADVEC_4 else cm.grid_2nd(*shape, gc=((3, 3, 1) if adv == cm.ADVEC_2I5 else (1, 1, 1)), dtype=dtype)
             c = cm.Case(g, nscalars=1)
-            want = _oracle_rhs(c, adv, dif, sm)
-            p = capi.MhhDiffParams(); p.cs = 0.23; p.tPr = 1./3.; p.surface_model = sm
+            want = cm.oracle_rhs(c, adv, dif, sm)
+            p = cm.diff_params(sm)
             d = B.DevCase(be, c); f = d.fields()
             B.ok(be, be.lib.mhh_rhs_exec(d.G, adv, dif, C.byref(f), C.byref(p), be.stream))
             got = (be.host(d.ut), be.host(d.vt), be.host(d.wt), be.host(d.st[0]))
@@ -800,20 +676,16 @@ def test_advec25_and_diff_smag2_alone_marching_form_equals_per_field_kernels(be,
     for shape, sm, lim in [((70, 10, 12), 1, (0, 0)), ((17, 9, 8), 0, (0, 1)), ((8, 6, 6), 1, (1, 0)), ((130, 3, 6), 1, (0, 0)), ((128, 5, 7), 1, (0, 0))]:
         g = cm.grid_2nd(*shape, gc=(3, 3, 2), dtype=dtype)
         c = cm.Case(g, nscalars=2)
-        p = capi.MhhDiffParams(); p.cs = 0.23; p.tPr = 1./3.; p.surface_model = sm
+        p = cm.diff_params(sm)
         out = {}
         for impl in ("march", "cell"):
             d = B.DevCase(be, c); f = d.fields()
             f.s_fluxlimit[0], f.s_fluxlimit[1] = lim
-            if impl == "cell":
-                os.environ["MHH_ADVEC25_IMPL"] = "cell"; os.environ["MHH_DIFF22_IMPL"] = "cell"
-            try:
+            with cm.switches(**({"MHH_ADVEC25_IMPL": "cell", "MHH_DIFF22_IMPL": "cell"} if impl == "cell" else {})):
                 B.ok(be, be.lib.mhh_advec_exec(d.G, cm.ADVEC_2I5, C.byref(f), be.stream))
                 adv = [be.host(x) for x in (d.ut, d.vt, d.wt, d.st[0], d.st[1])]
                 B.ok(be, be.lib.mhh_diff_exec(d.G, cm.DIFF_SMAG2, C.byref(f), C.byref(p), be.stream))
                 dif = [be.host(x) for x in (d.ut, d.vt, d.wt, d.st[0], d.st[1])]
-            finally:
-                os.environ.pop("MHH_ADVEC25_IMPL", None); os.environ.pop("MHH_DIFF22_IMPL", None)
             out[impl] = (adv, dif)
         for stage, nm in ((0, "advec"), (1, "diff")):
             for a, b, fld in zip(out["march"][stage], out["cell"][stage], ("ut", "vt", "wt", "st0", "st1")):
@@ -831,17 +703,13 @@ def test_advec4_and_diff4_alone_marching_form_equals_per_field_kernels(be, dtype
         out = {}
         for impl in ("march", "cell"):
             d = B.DevCase(be, c); f = d.fields()
-            if impl == "cell":
-                os.environ["MHH_RHS44_IMPL"] = "cell"
-            try:
+            with cm.switches(**({"MHH_RHS44_IMPL": "cell"} if impl == "cell" else {})):
                 n0 = be.lib.mhh_stat_rhs44_march_launches()
                 B.ok(be, be.lib.mhh_advec_exec(d.G, cm.ADVEC_4, C.byref(f), be.stream))
                 adv = [be.host(x) for x in (d.ut, d.vt, d.wt, d.st[0])]
                 B.ok(be, be.lib.mhh_diff_exec(d.G, cm.DIFF_4, C.byref(f), None, be.stream))
                 dif = [be.host(x) for x in (d.ut, d.vt, d.wt, d.st[0])]
                 assert be.lib.mhh_stat_rhs44_march_launches() - n0 == (2 if impl == "march" else 0)
-            finally:
-                os.environ.pop("MHH_RHS44_IMPL", None)
             out[impl] = (adv, dif)
         for stage, nm in ((0, "advec"), (1, "diff")):
             for a, b, fld in zip(out["march"][stage], out["cell"][stage], ("ut", "vt", "wt", "st")):
@@ -868,23 +736,17 @@ def test_rhs25_march_copy_forms_agree(be, dtype):
     for shape in [(70, 10, 12), (17, 9, 8)]:
         g = cm.grid_2nd(*shape, gc=(3, 3, 1), dtype=dtype)
         c = cm.Case(g, nscalars=1)
-        p = capi.MhhDiffParams(); p.cs = 0.23; p.tPr = 1./3.; p.surface_model = 1
+        p = cm.diff_params(1)
         out = {}
         for form in ("default", "4", "cell"):
             d = B.DevCase(be, c); f = d.fields()
-            key, val = ("MHH_RHS25_IMPL", "cell") if form == "cell" else ("MHH_MARCH_DMA", form)
-            if form != "default":
-                os.environ[key] = val
-            if form == "cell":
-                os.environ["MHH_ADVEC25_IMPL"] = "cell"; os.environ["MHH_DIFF22_IMPL"] = "cell"
-            try:
+            env = {"default": {}, "4": {"MHH_MARCH_DMA": "4"}, "cell": {"MHH_RHS25_IMPL": "cell", "MHH_ADVEC25_IMPL": "cell", "MHH_DIFF22_IMPL": "cell"}}[form]
+            with cm.switches(**env):
                 if form == "cell":
                     B.ok(be, be.lib.mhh_advec_exec(d.G, adv, C.byref(f), be.stream))
                     B.ok(be, be.lib.mhh_diff_exec(d.G, dif, C.byref(f), C.byref(p), be.stream))
                 else:
                     B.ok(be, be.lib.mhh_rhs_exec(d.G, adv, dif, C.byref(f), C.byref(p), be.stream))
-            finally:
-                os.environ.pop(key, None); os.environ.pop("MHH_ADVEC25_IMPL", None); os.environ.pop("MHH_DIFF22_IMPL", None)
             out[form] = [be.host(x) for x in (d.ut, d.vt, d.wt, d.st[0])]
         for form in ("4", "cell"):
             for a, b, nm in zip(out["default"], out[form], ("ut", "vt", "wt", "st")):
@@ -898,26 +760,14 @@ def test_rhs25_march_tall_columns(be, dtype, rho):
     levels each), Boussinesq (rho == 1: rotated windows) and anelastic (shifted windows) base states, with and without a
     scalar, ragged in i and j: the fused pass equals the oracle's operator-by-operator result bit for bit."""
     adv, dif = cm.ADVEC_2I5, cm.DIFF_SMAG2
-    O = cm.oracle()
     for shape, ns in [((20, 6, 150), 1), ((66, 5, 31), 0), ((12, 9, 133), 1), ((128, 6, 40), 1)]:
         g = cm.grid_2nd(*shape, gc=(3, 3, 1), dtype=dtype)
         c = cm.Case(g, nscalars=ns, rho=rho)
-        p = capi.MhhDiffParams(); p.cs = 0.23; p.tPr = 1./3.; p.surface_model = 1
+        p = cm.diff_params(1)
         d = B.DevCase(be, c); f = d.fields()
         B.ok(be, be.lib.mhh_rhs_exec(d.G, adv, dif, C.byref(f), C.byref(p), be.stream))
-        got = [be.host(x) for x in (d.ut, d.vt, d.wt)] + [be.host(x) for x in d.st]
-        Gh = g.host_struct()
-        ut, vt, wt = c.ut.copy(), c.vt.copy(), c.wt.copy(); st = [x.copy() for x in c.st]
-        a = (ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.rhoref), ptr(c.rhorefh))
-        O.orc_advec_u(Gh, 25, ptr(ut), *a); O.orc_advec_v(Gh, 25, ptr(vt), *a); O.orc_advec_w(Gh, 25, ptr(wt), *a)
-        for n in range(ns):
-            O.orc_advec_s(Gh, 25, ptr(st[n]), ptr(c.s[n]), *a)
-        v5 = dbl(1e-5)
-        O.orc_smag2_diff_u(Gh, 1, ptr(ut), ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.evisc), ptr(c.u_fluxbot), ptr(c.u_fluxtop), ptr(c.rhoref), ptr(c.rhorefh), v5)
-        O.orc_smag2_diff_v(Gh, 1, ptr(vt), ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.evisc), ptr(c.v_fluxbot), ptr(c.v_fluxtop), ptr(c.rhoref), ptr(c.rhorefh), v5)
-        O.orc_smag2_diff_w(Gh, ptr(wt), ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.evisc), ptr(c.rhoref), ptr(c.rhorefh), v5)
-        for n in range(ns):
-            O.orc_smag2_diff_c(Gh, 1, ptr(st[n]), ptr(c.s[n]), ptr(c.evisc), ptr(c.s_fluxbot), ptr(c.s_fluxtop), ptr(c.rhoref), ptr(c.rhorefh), dbl(1./3.), v5)
+        got = cm.flat(cm.tendencies(be, d))
+        ut, vt, wt, st = cm.oracle_rhs(c, adv, dif, 1)
         for a_, b_, nm in zip(got, [ut, vt, wt] + st, ("ut", "vt", "wt", "st")):
             assert same(a_, b_), (shape, rho, nm, cm.ulp_diff(a_, b_))
 
@@ -935,13 +785,10 @@ def test_rhs44_marching_form_equals_cell_form(be, dtype):
         for impl in ("march", "cell"):
             d = B.DevCase(be, c); f = d.fields(); dth = be.arr(threfh)
             p = capi.MhhDiffParams(); p.buoyancy = 4; p.th_for_N2 = 0; p.threfh = be.ptr(dth).value; p.grav = 9.81
-            os.environ["MHH_RHS44_IMPL"] = impl
-            try:
+            with cm.switches(MHH_RHS44_IMPL=impl):
                 n0 = be.lib.mhh_stat_rhs44_march_launches()
                 B.ok(be, be.lib.mhh_rhs_exec(d.G, cm.ADVEC_4, cm.DIFF_4, C.byref(f), C.byref(p), be.stream))
                 ran = be.lib.mhh_stat_rhs44_march_launches() - n0
-            finally:
-                del os.environ["MHH_RHS44_IMPL"]
             out[impl] = [be.host(x) for x in (d.ut, d.vt, d.wt, d.st[0])]
             assert ran == (1 if impl == "march" else 0), (impl, shape, ran)
         for a, b, nm in zip(out["march"], out["cell"], ("ut", "vt", "wt", "st")):
@@ -961,16 +808,13 @@ def test_exec_viscosity_marching_form_equals_cell_form(be, sm, neutral, dtype):
         out = {}
         for impl in ("march", "cell"):
             d = B.DevCase(be, c); f = d.fields()
-            p = capi.MhhDiffParams(); p.cs = 0.23; p.tPr = 1./3.; p.surface_model = sm; p.neutral = neutral
+            p = cm.diff_params(sm, neutral=neutral)
             p.N2 = None; p.th_for_N2 = 0; dthref = be.arr(thref); p.thref = be.ptr(dthref).value; p.grav = 9.81
             ml = B.mlen0(be, g, 0.23); p.mlen0 = be.ptr(ml).value
-            os.environ["MHH_VISC_IMPL"] = impl
-            try:
+            with cm.switches(MHH_VISC_IMPL=impl):
                 n0 = be.lib.mhh_stat_visc_march_launches()
                 B.ok(be, be.lib.mhh_diff_exec_viscosity(d.G, cm.DIFF_SMAG2, C.byref(f), C.byref(p), be.stream))
                 ran = be.lib.mhh_stat_visc_march_launches() - n0
-            finally:
-                del os.environ["MHH_VISC_IMPL"]
             out[impl] = be.host(d.evisc)
             assert ran == (1 if impl == "march" else 0), (impl, shape, ran)     # 16-byte or 4-byte copies, never the cell form
         assert same(out["march"], out["cell"]), (shape, cm.ulp_diff(out["march"], out["cell"]))
@@ -1003,7 +847,7 @@ def test_exec_viscosity_with_the_mixing_length_table_equals_per_cell_evaluation(
         for impl in ("march", "cell"):
             for table in (False, True):
                 d = B.DevCase(be, c); f = d.fields()
-                p = capi.MhhDiffParams(); p.cs = 0.23; p.tPr = 1./3.; p.surface_model = sm; p.neutral = neutral
+                p = cm.diff_params(sm, neutral=neutral)
                 p.N2 = None; p.th_for_N2 = 0; dthref = be.arr(thref); p.thref = be.ptr(dthref).value; p.grav = 9.81
                 ml_h = np.zeros(g.kcells, dtype=dtype)
                 B.ok(be, be.lib.mhh_smag2_mlen0_host(g.host_struct(), 0.23, ptr(ml_h)))
@@ -1013,11 +857,8 @@ def test_exec_viscosity_with_the_mixing_length_table_equals_per_cell_evaluation(
                     B.ok(be, be.lib.mhh_smag2_mlen2_host(g.host_struct(), sm, neutral, ptr(ml_h), float(c.z0m.flat[0]), ptr(m2_h)))
                     assert (m2_h[g.kstart:g.kend] > 0).all()
                     m2 = be.arr(m2_h); p.mlen2 = be.ptr(m2).value
-                os.environ["MHH_VISC_IMPL"] = impl
-                try:
+                with cm.switches(MHH_VISC_IMPL=impl):
                     B.ok(be, be.lib.mhh_diff_exec_viscosity(d.G, cm.DIFF_SMAG2, C.byref(f), C.byref(p), be.stream))
-                finally:
-                    del os.environ["MHH_VISC_IMPL"]
                 out[impl, table] = be.host(d.evisc)
         for impl in ("march", "cell"):
             assert same(out[impl, True], out[impl, False]), (impl, shape, cm.ulp_diff(out[impl, True], out[impl, False]))
@@ -1039,9 +880,7 @@ def test_pres(be, order, dtype):
                 c.w[g.kstart-m] = -c.w[g.kstart+m]; c.w[g.kend+m] = -c.w[g.kend-m]
         Gh = g.host_struct(); dt = 0.7
         d = B.DevCase(be, c); f = d.fields()
-        plan = capi.PLAN()
-        B.ok(be, be.lib.mhh_pres_plan_create(Gh, order, ptr(g.dz), ptr(g.dzhi), ptr(g.dzi4), ptr(g.dzhi4), ptr(c.rhoref), ptr(c.rhorefh), C.byref(plan)))
-        try:
+        with B.pres_plan(be, g, c, order) as plan:
             # stage 1: input -- bit-exact incl. the ghost-cell side effects on ut, vt (and wt for pres_4)
             pk_want = np.zeros((g.ktot, g.jtot, g.itot), dtype=dtype)
             ut, vt, wt = c.ut.copy(), c.vt.copy(), c.wt.copy()
@@ -1074,8 +913,6 @@ def test_pres(be, order, dtype):
             out = C.c_double(0)
             B.ok(be, be.lib.mhh_pres_check_divergence(d.G, order, C.byref(f), be.ptr(d.work), C.byref(out), be.stream))
             assert out.value == O.orc_pres_divergence(Gh, order, ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.rhoref), ptr(c.rhorefh))
-        finally:
-            be.lib.mhh_pres_plan_destroy(plan)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -1102,11 +939,8 @@ def test_pres_exec_with_the_rk_substep_in_its_last_kernel(be, form, dtype):
     if form == "staged":
         cases += [(2, cm.grid_2nd(12, 10, 8, gc=(3, 3, 1), dtype=dtype), "random"), (4, cm.grid_4th(16, 12, 12, dtype=dtype), "one")]
     for order, g, rho in cases:
-        c = cm.Case(g, rho=rho, periodic=True); Gh = g.host_struct(); dt, sub_dt = 0.31, 0.1
-        plan = capi.PLAN()
-        B.ok(be, be.lib.mhh_pres_plan_create(Gh, order, ptr(g.dz), ptr(g.dzhi), ptr(g.dzi4), ptr(g.dzhi4), ptr(c.rhoref), ptr(c.rhorefh), C.byref(plan)))
-        os.environ["MHH_PRES_LDS"] = "1" if form == "lds" else "0"
-        try:
+        c = cm.Case(g, rho=rho, periodic=True); dt, sub_dt = 0.31, 0.1
+        with B.pres_plan(be, g, c, order) as plan, cm.switches(MHH_PRES_LDS="1" if form == "lds" else "0"):
             for rko, nsub in ((3, 3), (4, 5)):
                 for sub in range(nsub):
                     d1 = B.DevCase(be, c); f1 = d1.fields()
@@ -1118,9 +952,6 @@ def test_pres_exec_with_the_rk_substep_in_its_last_kernel(be, form, dtype):
                     for nm in ("u", "v", "w", "ut", "vt", "wt", "p"):
                         assert same(be.host(getattr(d1, nm)), be.host(getattr(d2, nm))), (form, order, g.shape3, rko, sub, nm)
                     assert not same(be.host(d2.u), c.u)
-        finally:
-            os.environ.pop("MHH_PRES_LDS", None)
-            be.lib.mhh_pres_plan_destroy(plan)
 
 
 def test_errors_are_reported(be):

@@ -4,72 +4,21 @@ row-wise forms. Every tendency must carry the oracle's bits, the per-field cell 
 
 Runs on the ``emul`` backend (the same kernel sources on the CPU) and on the ``hip`` backend (marked gpu)."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import backends as B
 import common as cm
-from common import ptr, dbl
-from microhh_amd import capi
+from backends import be  # noqa: F401
+from common import DTYPES
 
-BACKENDS = [pytest.param("emul"), pytest.param("hip", marks=pytest.mark.gpu)]
-DTYPES = [np.float64, np.float32]
 ADV, DIF = cm.ADVEC_2I5, cm.DIFF_SMAG2
-
-
-@pytest.fixture(params=BACKENDS)
-def be(request):
-    return B.get(request.param)
-
-
-class _env:
-    """Environment switches for the duration of a block (the library reads them per call)."""
-
-    def __init__(self, **kw):
-        self.kw = kw
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kw}
-        os.environ.update({k: str(v) for k, v in self.kw.items()})
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-        return False
 
 
 def _svisc(n):
     """A different diffusivity per scalar: a batch that mixed up its scalars' coefficients would show."""
     return [1e-5 * (1 + 0.25*m) for m in range(n)]
-
-
-def _oracle_rhs(c, sm, svisc, limited=(), tPr=1./3., visc=1e-5):
-    """Advec::exec followed by Diff::exec on the oracle; returns the tendencies."""
-    O = cm.oracle(); g = c.grid; Gh = g.host_struct()
-    ut, vt, wt, st = c.ut.copy(), c.vt.copy(), c.wt.copy(), [x.copy() for x in c.st]
-    a = (ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.rhoref), ptr(c.rhorefh))
-    O.orc_advec_u(Gh, ADV, ptr(ut), *a); O.orc_advec_v(Gh, ADV, ptr(vt), *a); O.orc_advec_w(Gh, ADV, ptr(wt), *a)
-    for n in range(len(st)):
-        if n in limited:
-            O.orc_advec_s_lim(Gh, ptr(st[n]), ptr(c.s[n]), *a)
-        else:
-            O.orc_advec_s(Gh, ADV, ptr(st[n]), ptr(c.s[n]), *a)
-    O.orc_smag2_diff_u(Gh, sm, ptr(ut), ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.evisc), ptr(c.u_fluxbot), ptr(c.u_fluxtop), ptr(c.rhoref), ptr(c.rhorefh), dbl(visc))
-    O.orc_smag2_diff_v(Gh, sm, ptr(vt), ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.evisc), ptr(c.v_fluxbot), ptr(c.v_fluxtop), ptr(c.rhoref), ptr(c.rhorefh), dbl(visc))
-    O.orc_smag2_diff_w(Gh, ptr(wt), ptr(c.u), ptr(c.v), ptr(c.w), ptr(c.evisc), ptr(c.rhoref), ptr(c.rhorefh), dbl(visc))
-    for n in range(len(st)):
-        O.orc_smag2_diff_c(Gh, sm, ptr(st[n]), ptr(c.s[n]), ptr(c.evisc), ptr(c.s_fluxbot), ptr(c.s_fluxtop), ptr(c.rhoref), ptr(c.rhorefh), dbl(tPr), dbl(svisc[n]))
-    return [ut, vt, wt] + st
-
-
-def _params(sm):
-    p = capi.MhhDiffParams(); p.cs = 0.23; p.tPr = 1./3.; p.surface_model = sm
-    return p
 
 
 def _dev(be, c, svisc, limited=()):
@@ -82,19 +31,19 @@ def _dev(be, c, svisc, limited=()):
 
 
 def _got(be, d):
-    return [be.host(x) for x in (d.ut, d.vt, d.wt)] + [be.host(x) for x in d.st]
+    return cm.flat(cm.tendencies(be, d))
 
 
 def _fused(be, c, sm, svisc, limited=()):
     d, f = _dev(be, c, svisc, limited)
-    B.ok(be, be.lib.mhh_rhs_exec(d.G, ADV, DIF, C.byref(f), C.byref(_params(sm)), be.stream))
+    B.ok(be, be.lib.mhh_rhs_exec(d.G, ADV, DIF, C.byref(f), C.byref(cm.diff_params(sm)), be.stream))
     return _got(be, d)
 
 
 def _unfused(be, c, sm, svisc, limited=()):
     d, f = _dev(be, c, svisc, limited)
     B.ok(be, be.lib.mhh_advec_exec(d.G, ADV, C.byref(f), be.stream))
-    B.ok(be, be.lib.mhh_diff_exec(d.G, DIF, C.byref(f), C.byref(_params(sm)), be.stream))
+    B.ok(be, be.lib.mhh_diff_exec(d.G, DIF, C.byref(f), C.byref(cm.diff_params(sm)), be.stream))
     return _got(be, d)
 
 
@@ -126,12 +75,12 @@ def test_scalar_pass_bitexact_against_oracle(be, dtype, nsc):
         g = cm.grid_2nd(*shape, gc=gc, dtype=dtype)
         for rho, sm, limited in (("random", 1, ()), ("one", 0, ()), ("random", 0, (1,)), ("one", 1, (nsc - 1,))):
             c = cm.Case(g, nscalars=nsc, rho=rho, periodic=gc[0] > 3)
-            want = _oracle_rhs(c, sm, svisc, limited)
+            want = cm.flat(cm.oracle_rhs(c, ADV, DIF, sm, svisc=svisc, limited=limited))
             # the pass must have run: the fused call launches it for the unlimited scalars >= 1, the unfused pair at least for
             # the diffusion of scalars >= 1 (which has no limiter)
             fused_runs = any(n not in limited for n in range(1, nsc))
             launches = be.lib.mhh_stat_scalar_march_launches
-            with _env(**env):
+            with cm.switches(**env):
                 n0 = launches()
                 _check(_fused(be, c, sm, svisc, limited), want, ("fused", shape, gc, rho, sm, limited))
                 n1 = launches()
@@ -149,11 +98,11 @@ def test_scalar_pass_equals_cell_kernels_and_one_per_launch(be, dtype):
     svisc = _svisc(4)
     out = {}
     for form, env in (("pass", {}), ("single", {"MHH_SCALAR_BATCH": "1"}), ("cell", {"MHH_SCALAR_IMPL": "cell"})):
-        with _env(**env):
+        with cm.switches(**env):
             d, f = _dev(be, c, svisc)
             B.ok(be, be.lib.mhh_advec_exec(d.G, ADV, C.byref(f), be.stream))
             adv = _got(be, d)
-            B.ok(be, be.lib.mhh_diff_exec(d.G, DIF, C.byref(f), C.byref(_params(1)), be.stream))
+            B.ok(be, be.lib.mhh_diff_exec(d.G, DIF, C.byref(f), C.byref(cm.diff_params(1)), be.stream))
             out[form] = (adv, _got(be, d), _fused(be, c, 1, svisc))
     for form in ("single", "cell"):
         for stage in range(3):
@@ -167,7 +116,7 @@ def test_scalar_pass_launch_counter(be):
     lib = be.lib
     for nsc, env, rises in ((2, {}, True), (3, {}, True), (1, {}, False), (3, {"MHH_SCALAR_IMPL": "cell"}, False)):
         c = cm.Case(g, nscalars=nsc)
-        with _env(**env):
+        with cm.switches(**env):
             n0 = lib.mhh_stat_scalar_march_launches()
             _fused(be, c, 1, _svisc(nsc))
             n1 = lib.mhh_stat_scalar_march_launches()
@@ -184,7 +133,7 @@ def test_row_wise_forms_with_three_scalars(be, dtype):
         svisc = _svisc(3)
         want = _fused(be, c, sm, svisc)
         d, f = _dev(be, c, svisc)
-        P = _params(sm)
+        P = cm.diff_params(sm)
         ja, jb = g.jstart + 4, g.jend - 4
         B.ok(be, be.lib.mhh_rhs_exec_rows(d.G, ADV, DIF, C.byref(f), C.byref(P), ja, jb, be.stream))
         B.ok(be, be.lib.mhh_rhs_exec_rows2(d.G, ADV, DIF, C.byref(f), C.byref(P), g.jstart, ja, jb, g.jend, be.stream))
@@ -199,7 +148,7 @@ def _rhs_once(hp, fn, env):
     import torch
     tend = [hp.ut, hp.vt, hp.wt] + list(hp.st)
     keep = [t.clone() for t in tend]
-    with _env(**env):
+    with cm.switches(**env):
         fn(); hp.sync()
     out = [t.clone() for t in tend]
     for t, k in zip(tend, keep):

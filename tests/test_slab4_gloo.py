@@ -4,21 +4,16 @@ the same global synthetic fields: RHS tendencies bit-exact, pressure-corrected t
 instead of 2-D, the 7-band solve multiplies by reciprocal pivots). nxh = 9 modes do not divide by 2 or 4 ranks: the padded x-mode
 blocks are part of every run. One rank of the slab path is also checked against the oracle's Pres_4 input -> solve -> output."""
 import ctypes as C
-import os
-import sys
-import tempfile
 
 import numpy as np
 import pytest
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import backends as B  # noqa: E402
-import common as cm  # noqa: E402
-from common import ptr, dbl  # noqa: E402
-from microhh_amd import capi  # noqa: E402
-from microhh_amd.model import HotPath, synthetic_global  # noqa: E402
+import backends as B
+import common as cm
+from common import ptr, dbl
+from microhh_amd import capi
+from microhh_amd.model import HotPath, synthetic_global
+from ranks import run_ranks
 
 CASE = "moser600"
 GRID = (16, 32, 12)        # world 4: jmax = 8; nxh = 9
@@ -55,28 +50,18 @@ def _single(dtype=np.float64, **kw):
     return out
 
 
-def _worker(rank, world, port, tmp, chunks, dtype):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        lib = B.get("emul").lib
-        hp = HotPath(CASE, *GRID, device="cpu", lib=lib, dtype=dtype, npy=world, rank=rank, global_init=synthetic_global(CASE, *GRID, dtype=dtype),
-                     pres_chunks=chunks)
-        assert hp.pres_chunks == chunks and lib.mhh_pres_slab_order(hp.plan) == 4
-        out = {}
-        _run(hp, out)
-        np.savez(os.path.join(tmp, "rank%d.npz" % rank), **out)
-        hp.close()
-    finally:
-        dist.destroy_process_group()
+def _worker(rank, world, out, chunks, dtype):
+    lib = B.get("emul").lib
+    hp = HotPath(CASE, *GRID, device="cpu", lib=lib, dtype=dtype, npy=world, rank=rank, global_init=synthetic_global(CASE, *GRID, dtype=dtype),
+                 pres_chunks=chunks)
+    assert hp.pres_chunks == chunks and lib.mhh_pres_slab_order(hp.plan) == 4
+    _run(hp, out)
+    hp.close()
 
 
 def _ranks(world, chunks, dtype=np.float64):
-    with tempfile.TemporaryDirectory() as tmp:
-        port = 30100 + 3*world + chunks + (50 if dtype == np.float32 else 0) + os.getpid() % 1000
-        mp.spawn(_worker, args=(world, port, tmp, chunks, dtype), nprocs=world, join=True)
-        parts = [np.load(os.path.join(tmp, "rank%d.npz" % r)) for r in range(world)]
-        return {k: (np.concatenate([p[k] for p in parts], axis=1) if parts[0][k].ndim == 3 else [float(p[k]) for p in parts]) for k in parts[0].files}
+    parts = run_ranks(_worker, world, backend="gloo", tag="slab4-gloo", args=(chunks, dtype))
+    return {k: (np.concatenate([p[k] for p in parts], axis=1) if parts[0][k].ndim == 3 else [float(p[k]) for p in parts]) for k in parts[0]}
 
 
 def _close(got, ref, keys, tol):
@@ -182,53 +167,53 @@ def test_pres4_slab_abi():
 
 
 @pytest.mark.parametrize("case,grid", [("drycblles", (16, 32, 10)), (CASE, GRID)], ids=["order2-staged", "order4"])
-def test_pres_slab_calls_without_slice_index(case, grid, monkeypatch):
+def test_pres_slab_calls_without_slice_index(case, grid):
     """The entry points without a slice index are the per-slice ones on slice 0 of a one-slice plan: HotPath.pres (per-slice calls) and
     the same solve through mhh_pres_fwd_x_pack / fwd_y_solve_bwd_y / bwd_x_unpack[_output] give the same bits. On a plan with two
     slices they are refused, and the message names mhh_pres_slab_set_chunks."""
-    monkeypatch.setenv("MHH_PRES_SLAB_LDS", "0")
     lib = B.get("emul").lib
     gi = synthetic_global(case, *grid)
     out = []
-    for whole in (False, True):
-        hp = HotPath(case, *grid, device="cpu", lib=lib, global_init=gi, force_slab=True, pres_chunks=1)
-        P, G, F, st = hp.plan, hp.G, C.byref(hp.fields), hp.stream
-        order = lib.mhh_pres_slab_order(P)
-        assert lib.mhh_pres_slab_chunks(P) == 1 and lib.mhh_pres_slab_has_lds(P) == 0
-        _rhs(hp)
-        if not whole:
-            hp.pres()
-        else:
-            hp.halo([hp.vt], *hp._pres_vt_rows)
-            packed = lib.mhh_pres_slab_packed(P)
-            hp._ok(lib.mhh_pres_input_packed(G, order, F, hp.dt, packed, st))
-            hp._ok(lib.mhh_pres_fwd_x_pack(P, G, packed, hp.xsend.data_ptr(), st))
-            hp.xrecv.copy_(hp.xsend)
-            hp._ok(lib.mhh_pres_fwd_y_solve_bwd_y(P, G, hp.xrecv.data_ptr(), hp.xsend.data_ptr(), st))
-            hp.xrecv.copy_(hp.xsend)
-            if order == 2:
-                hp._ok(lib.mhh_pres_bwd_x_unpack_output(P, G, hp.xrecv.data_ptr(), F, st))
-                hp.halo([hp.p], rows_south=0, rows_north=1)
-                hp._ok(lib.mhh_pres_output_south_row(G, F, st))
+    with cm.switches(MHH_PRES_SLAB_LDS="0"):
+        for whole in (False, True):
+            hp = HotPath(case, *grid, device="cpu", lib=lib, global_init=gi, force_slab=True, pres_chunks=1)
+            P, G, F, st = hp.plan, hp.G, C.byref(hp.fields), hp.stream
+            order = lib.mhh_pres_slab_order(P)
+            assert lib.mhh_pres_slab_chunks(P) == 1 and lib.mhh_pres_slab_has_lds(P) == 0
+            _rhs(hp)
+            if not whole:
+                hp.pres()
             else:
-                hp._ok(lib.mhh_pres_bwd_x_unpack(P, G, hp.xrecv.data_ptr(), F, st))
-                hp.halo([hp.p], rows_south=1, rows_north=2)
-                hp._ok(lib.mhh_pres_output_order(G, 4, F, st))
-        out.append({n: getattr(hp, n).numpy().copy() for n in ("ut", "vt", "wt", "p")})
-        if whole:
-            hp._ok(lib.mhh_pres_slab_set_chunks(P, 2))
-            xs, xr = hp.xsend.data_ptr(), hp.xrecv.data_ptr()
-            for name, call in (("mhh_pres_fwd_x_pack", lambda: lib.mhh_pres_fwd_x_pack(P, G, None, xs, st)),
-                               ("mhh_pres_fwd_y_solve_bwd_y", lambda: lib.mhh_pres_fwd_y_solve_bwd_y(P, G, xr, xs, st)),
-                               ("mhh_pres_bwd_x_unpack", lambda: lib.mhh_pres_bwd_x_unpack(P, G, xr, F, st))) + \
-                              ((("mhh_pres_bwd_x_unpack_output", lambda: lib.mhh_pres_bwd_x_unpack_output(P, G, xr, F, st)),) if order == 2 else ()):
-                assert call() != 0, name
-                assert b"set_chunks" in lib.mhh_last_error(), (name, lib.mhh_last_error())
-            # refused before anything ran: the fields are as they were; and one slice again gives the calls back
-            for n in ("ut", "vt", "wt", "p"):
-                assert np.array_equal(getattr(hp, n).numpy(), out[-1][n]), n
-            hp._ok(lib.mhh_pres_slab_set_chunks(P, 1))
-            hp._ok(lib.mhh_pres_fwd_x_pack(P, G, None, xs, st))
-        hp.close()
+                hp.halo([hp.vt], *hp._pres_vt_rows)
+                packed = lib.mhh_pres_slab_packed(P)
+                hp._ok(lib.mhh_pres_input_packed(G, order, F, hp.dt, packed, st))
+                hp._ok(lib.mhh_pres_fwd_x_pack(P, G, packed, hp.xsend.data_ptr(), st))
+                hp.xrecv.copy_(hp.xsend)
+                hp._ok(lib.mhh_pres_fwd_y_solve_bwd_y(P, G, hp.xrecv.data_ptr(), hp.xsend.data_ptr(), st))
+                hp.xrecv.copy_(hp.xsend)
+                if order == 2:
+                    hp._ok(lib.mhh_pres_bwd_x_unpack_output(P, G, hp.xrecv.data_ptr(), F, st))
+                    hp.halo([hp.p], rows_south=0, rows_north=1)
+                    hp._ok(lib.mhh_pres_output_south_row(G, F, st))
+                else:
+                    hp._ok(lib.mhh_pres_bwd_x_unpack(P, G, hp.xrecv.data_ptr(), F, st))
+                    hp.halo([hp.p], rows_south=1, rows_north=2)
+                    hp._ok(lib.mhh_pres_output_order(G, 4, F, st))
+            out.append({n: getattr(hp, n).numpy().copy() for n in ("ut", "vt", "wt", "p")})
+            if whole:
+                hp._ok(lib.mhh_pres_slab_set_chunks(P, 2))
+                xs, xr = hp.xsend.data_ptr(), hp.xrecv.data_ptr()
+                for name, call in (("mhh_pres_fwd_x_pack", lambda: lib.mhh_pres_fwd_x_pack(P, G, None, xs, st)),
+                                   ("mhh_pres_fwd_y_solve_bwd_y", lambda: lib.mhh_pres_fwd_y_solve_bwd_y(P, G, xr, xs, st)),
+                                   ("mhh_pres_bwd_x_unpack", lambda: lib.mhh_pres_bwd_x_unpack(P, G, xr, F, st))) + \
+                                  ((("mhh_pres_bwd_x_unpack_output", lambda: lib.mhh_pres_bwd_x_unpack_output(P, G, xr, F, st)),) if order == 2 else ()):
+                    assert call() != 0, name
+                    assert b"set_chunks" in lib.mhh_last_error(), (name, lib.mhh_last_error())
+                # refused before anything ran: the fields are as they were; and one slice again gives the calls back
+                for n in ("ut", "vt", "wt", "p"):
+                    assert np.array_equal(getattr(hp, n).numpy(), out[-1][n]), n
+                hp._ok(lib.mhh_pres_slab_set_chunks(P, 1))
+                hp._ok(lib.mhh_pres_fwd_x_pack(P, G, None, xs, st))
+            hp.close()
     for n in ("ut", "vt", "wt", "p"):
         assert np.array_equal(out[0][n], out[1][n]), n

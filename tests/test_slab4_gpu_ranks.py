@@ -5,13 +5,12 @@ Every run is compared with the single-GPU path on the same fields: RHS tendencie
 to 1e-10 (fp64) / 2e-4 (fp32)."""
 import os
 import subprocess
-import sys
 import tempfile
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from ranks import run_ranks
 
 pytestmark = pytest.mark.gpu
 CASE = "moser600"
@@ -59,32 +58,20 @@ def _compare(got, ref, tol, exact_div=True):
             assert abs(float(div) - float(ref["div"])) <= 1e-12 * abs(float(ref["div"])) + 1e-18
 
 
-def _worker(rank, world, port, tmp, chunks, dtype):
+def _worker(rank, world, out, chunks, dtype):
     import torch
-    import torch.distributed as dist
     from microhh_amd.model import HotPath, synthetic_global
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        torch.cuda.set_device(0)
-        hp = HotPath(CASE, *GRID, device="cuda:0", dtype=dtype, npy=world, rank=rank, global_init=synthetic_global(CASE, *GRID, dtype=dtype), pres_chunks=chunks)
-        assert hp._host_staged and hp.pres_chunks == chunks and hp.lib.mhh_pres_slab_order(hp.plan) == 4
-        out = {}
-        _run(hp, out)
-        np.savez(os.path.join(tmp, "rank%d.npz" % rank), **out)
-        hp.close()
-    finally:
-        dist.destroy_process_group()
+    torch.cuda.set_device(0)
+    hp = HotPath(CASE, *GRID, device="cuda:0", dtype=dtype, npy=world, rank=rank, global_init=synthetic_global(CASE, *GRID, dtype=dtype), pres_chunks=chunks)
+    assert hp._host_staged and hp.pres_chunks == chunks and hp.lib.mhh_pres_slab_order(hp.plan) == 4
+    _run(hp, out)
+    hp.close()
 
 
 def _ranks(world, chunks, dtype=np.float64):
-    import torch.multiprocessing as mp
-    with tempfile.TemporaryDirectory() as tmp:
-        port = 30300 + 3*world + chunks + (50 if dtype == np.float32 else 0) + os.getpid() % 1000
-        mp.spawn(_worker, args=(world, port, tmp, chunks, dtype), nprocs=world, join=True)       # at most 4 ranks + this process on the GPU
-        parts = [np.load(os.path.join(tmp, "rank%d.npz" % r)) for r in range(world)]
-        return {k: (np.concatenate([p[k] for p in parts], axis=1) if parts[0][k].ndim == 3 else np.array([float(p[k]) for p in parts]))
-                for k in parts[0].files}
+    parts = run_ranks(_worker, world, backend="gloo", tag="slab4-gpu", args=(chunks, dtype))       # at most 4 ranks + this process on the GPU
+    return {k: (np.concatenate([p[k] for p in parts], axis=1) if parts[0][k].ndim == 3 else np.array([float(p[k]) for p in parts]))
+            for k in parts[0]}
 
 
 @pytest.mark.parametrize("world,chunks", [(2, 1), (4, 1), (4, 4)], ids=["2", "4", "4-sliced"])
@@ -96,23 +83,12 @@ def test_pres4_slab_ranks_on_one_gpu_fp32():
     _compare(_ranks(2, 1, np.float32), _single(np.float32), 2e-4)
 
 
-def _rccl_worker(rank, port, tmp, chunks):
-    import torch
-    import torch.distributed as dist
+def _rccl_worker(rank, world, out, chunks):
     from microhh_amd.model import HotPath, synthetic_global
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
-    os.environ["MHH_FORCE_COMM"] = "1"
-    torch.cuda.set_device(0)
-    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-    try:
-        hp = HotPath(CASE, *GRID, device="cuda:0", npy=1, rank=0, force_slab=True, global_init=synthetic_global(CASE, *GRID), pres_chunks=chunks)
-        assert hp.pres_chunks == chunks and hp._force_comm and not hp._host_staged
-        out = {}
-        _run(hp, out)
-        np.savez(os.path.join(tmp, "rank0.npz"), **out)
-        hp.close()
-    finally:
-        dist.destroy_process_group()
+    hp = HotPath(CASE, *GRID, device="cuda:0", npy=1, rank=0, force_slab=True, global_init=synthetic_global(CASE, *GRID), pres_chunks=chunks)
+    assert hp.pres_chunks == chunks and hp._force_comm and not hp._host_staged
+    _run(hp, out)
+    hp.close()
 
 
 @pytest.mark.parametrize("chunks", [1, 4], ids=["whole-transposes", "sliced-transposes"])
@@ -120,14 +96,11 @@ def test_pres4_slab_through_real_rccl_on_one_rank(chunks):
     """The slab code path with its exchanges through RCCL (nccl backend, one-rank communicator, MHH_FORCE_COMM=1): the halos of vt
     (2 rows south, 1 north) and p (1 south, 2 north) as batch_isend_irecv to self, the transposes as all_to_all_single -- whole or in
     four k-slices on the exchange stream. Same bits as the plain slab run on one rank, which matches the single-rank run."""
-    import torch.multiprocessing as mp
     plain = _single(force_slab=True, pres_chunks=chunks)
     _compare(plain, _single(), 1e-10)
-    with tempfile.TemporaryDirectory() as tmp:
-        mp.spawn(_rccl_worker, args=(30500 + chunks + os.getpid() % 1000, tmp, chunks), nprocs=1, join=True)
-        got = np.load(os.path.join(tmp, "rank0.npz"))
-        for key in plain:
-            assert np.array_equal(got[key], plain[key]), key
+    got, = run_ranks(_rccl_worker, 1, backend="nccl", tag="slab4-gpu-rccl", env={"MHH_FORCE_COMM": "1"}, args=(chunks,))
+    for key in plain:
+        assert np.array_equal(got[key], plain[key]), key
 
 
 def test_pres4_slab_full_size_matches_single_gpu():

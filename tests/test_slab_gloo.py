@@ -4,18 +4,14 @@ stand-in (tests/emul). Each run is compared with the single-rank run on the same
 RHS tendencies and evisc bit-exact (same stencils, same halos), pressure-corrected tendencies to 1e-10
 (the transform is split x / y instead of 2-D)."""
 import os
-import sys
 import tempfile
 
 import numpy as np
 import pytest
-import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import backends as B  # noqa: E402
-from microhh_amd.model import HotPath, synthetic_global  # noqa: E402
+import backends as B
+from microhh_amd.model import HotPath, synthetic_global
+from ranks import run_ranks
 
 GRID = (16, 32, 10)        # jmax = 16 / 8 rows per rank: whole strips of eight, so the slim-halo runs take the LDS x stages of the pressure solve
 
@@ -45,22 +41,14 @@ def _run(hp, out, overlapped=False):
     out["cfl"] = np.array(hp.cfl(0.5))
 
 
-def _worker(rank, world, port, tmp, slim, lds_x=True):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
-    os.environ["MHH_PRES_SLAB_LDS"] = "1" if lds_x else "0"
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        lib = B.get("emul").lib
-        hp = HotPath("drycblles", *GRID, device="cpu", lib=lib, npy=world, rank=rank, global_init=synthetic_global("drycblles", *GRID),
-                     slim_halos=slim, overlap=(slim and world == 2))
-        assert hp.evisc_local_ghosts == slim
-        assert lib.mhh_pres_slab_has_lds(hp.plan) == (1 if lds_x else 0)
-        out = {}
-        _run(hp, out, overlapped=(slim and world == 2))
-        np.savez(os.path.join(tmp, "rank%d.npz" % rank), **out)
-        hp.close()
-    finally:
-        dist.destroy_process_group()
+def _worker(rank, world, out, slim, lds_x):
+    lib = B.get("emul").lib
+    hp = HotPath("drycblles", *GRID, device="cpu", lib=lib, npy=world, rank=rank, global_init=synthetic_global("drycblles", *GRID),
+                 slim_halos=slim, overlap=(slim and world == 2))
+    assert hp.evisc_local_ghosts == slim
+    assert lib.mhh_pres_slab_has_lds(hp.plan) == (1 if lds_x else 0)
+    _run(hp, out, overlapped=(slim and world == 2))
+    hp.close()
 
 
 @pytest.mark.parametrize("world,slim,lds_x", [(2, True, True), (4, True, True), (2, False, True), (2, True, False)], ids=["2-slim", "4-slim", "2-full-halos", "2-slim-staged-x"])
@@ -74,35 +62,28 @@ def test_slab_matches_single_rank(world, slim, lds_x):
     hp = HotPath("drycblles", *GRID, device="cpu", lib=lib, global_init=synthetic_global("drycblles", *GRID))
     _run(hp, ref)
     hp.close()
-    with tempfile.TemporaryDirectory() as tmp:
-        mp.spawn(_worker, args=(world, 29500 + world + 7*int(slim) + 13*int(lds_x) + os.getpid() % 1000, tmp, slim, lds_x), nprocs=world, join=True)
-        parts = [np.load(os.path.join(tmp, "rank%d.npz" % r)) for r in range(world)]
-        for key in ("evisc", "rhs_ut", "rhs_vt", "rhs_wt", "rhs_st"):
-            got = np.concatenate([p[key] for p in parts], axis=1)
-            assert np.array_equal(got, ref[key]), key
-        for key in ("ut", "vt", "wt", "p"):
-            got = np.concatenate([p[key] for p in parts], axis=1)
-            scale = np.abs(ref[key]).max()
-            assert np.abs(got - ref[key]).max() <= 1e-10 * scale, (key, np.abs(got - ref[key]).max() / scale)
-        for p in parts:
-            assert float(p["cfl"]) == float(ref["cfl"])
-            assert abs(float(p["div"]) - float(ref["div"])) <= 1e-12 * abs(float(ref["div"]))
+    parts = run_ranks(_worker, world, backend="gloo", tag="slab-gloo", env={"MHH_PRES_SLAB_LDS": "1" if lds_x else "0"}, args=(slim, lds_x))
+    for key in ("evisc", "rhs_ut", "rhs_vt", "rhs_wt", "rhs_st"):
+        got = np.concatenate([p[key] for p in parts], axis=1)
+        assert np.array_equal(got, ref[key]), key
+    for key in ("ut", "vt", "wt", "p"):
+        got = np.concatenate([p[key] for p in parts], axis=1)
+        scale = np.abs(ref[key]).max()
+        assert np.abs(got - ref[key]).max() <= 1e-10 * scale, (key, np.abs(got - ref[key]).max() / scale)
+    for p in parts:
+        assert float(p["cfl"]) == float(ref["cfl"])
+        assert abs(float(p["div"]) - float(ref["div"])) <= 1e-12 * abs(float(ref["div"]))
 
 
-def _save_worker(rank, world, port, tmp):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        import time
-        lib = B.get("emul").lib
-        hp = HotPath("drycblles", *GRID, device="cpu", lib=lib, npy=world, rank=rank, global_init=synthetic_global("drycblles", *GRID))
-        if rank == 0:
-            time.sleep(0.5)              # rank 0 (which creates the files) arrives LAST: the others must wait for it
-        hp.save(tmp, iteration=3)
-        hp.save(tmp, iteration=3)        # again over existing files of the right size: nobody's rows may be wiped
-        hp.close()
-    finally:
-        dist.destroy_process_group()
+def _save_worker(rank, world, out, tmp):
+    import time
+    lib = B.get("emul").lib
+    hp = HotPath("drycblles", *GRID, device="cpu", lib=lib, npy=world, rank=rank, global_init=synthetic_global("drycblles", *GRID))
+    if rank == 0:
+        time.sleep(0.5)              # rank 0 (which creates the files) arrives LAST: the others must wait for it
+    hp.save(tmp, iteration=3)
+    hp.save(tmp, iteration=3)        # again over existing files of the right size: nobody's rows may be wiped
+    hp.close()
 
 
 def test_slab_ranks_save_restart_files_concurrently():
@@ -115,7 +96,7 @@ def test_slab_ranks_save_restart_files_concurrently():
         hp.save(one, iteration=3); names = [n for n, _ in hp._restart_fields()]; hp.close()
         with open(os.path.join(two, "u.0000003"), "wb") as f:
             f.write(b"stale")
-        mp.spawn(_save_worker, args=(2, 29700 + os.getpid() % 1000, two), nprocs=2, join=True)
+        run_ranks(_save_worker, 2, backend="gloo", tag="slab-save", args=(two,))
         for n in names + ["grid"]:
             fn = "%s.%07d" % (n, 0 if n == "grid" else 3)
             assert open(os.path.join(one, fn), "rb").read() == open(os.path.join(two, fn), "rb").read(), fn

@@ -4,15 +4,11 @@ the same global fields: RHS tendencies (every st included) and evisc bit-exact, 
 
 * emulated: world 2 over gloo, kernels = the library's own sources on the CPU (tests/emul);
 * on the GPU (marked gpu): 2 rank processes sharing the one card, messages over gloo through host copies."""
-import os
-import sys
-import tempfile
-
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import backends as B  # noqa: E402
+import backends as B
+from ranks import run_ranks
 
 GRID = (16, 32, 10)
 GRID_GPU = (128, 64, 32)
@@ -51,26 +47,17 @@ def _compare(parts, ref, nsc):
         assert np.abs(got - ref[key]).max() <= 1e-10 * scale, (key, np.abs(got - ref[key]).max() / scale)
 
 
-def _emul_worker(rank, world, port, tmp, nsc):
-    import torch.distributed as dist
+def _emul_worker(rank, world, out, nsc):
     from microhh_amd.model import HotPath, synthetic_global
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        lib = B.get("emul").lib
-        hp = HotPath("drycblles", *GRID, device="cpu", lib=lib, npy=world, rank=rank, nscalars=nsc,
-                     global_init=synthetic_global("drycblles", *GRID, nscalars=nsc), overlap=True)
-        assert len(hp.s) == nsc and hp.can_overlap
-        out = {}
-        _run(hp, out, overlapped=True)
-        np.savez(os.path.join(tmp, "rank%d.npz" % rank), **out)
-        hp.close()
-    finally:
-        dist.destroy_process_group()
+    lib = B.get("emul").lib
+    hp = HotPath("drycblles", *GRID, device="cpu", lib=lib, npy=world, rank=rank, nscalars=nsc,
+                 global_init=synthetic_global("drycblles", *GRID, nscalars=nsc), overlap=True)
+    assert len(hp.s) == nsc and hp.can_overlap
+    _run(hp, out, overlapped=True)
+    hp.close()
 
 
 def test_overlapped_slab_with_three_scalars_matches_single_rank_emulated():
-    import torch.multiprocessing as mp
     from microhh_amd.model import HotPath, synthetic_global
     nsc, world = 3, 2
     lib = B.get("emul").lib
@@ -79,9 +66,7 @@ def test_overlapped_slab_with_three_scalars_matches_single_rank_emulated():
     assert len(hp.s) == nsc
     _run(hp, ref)
     hp.close()
-    with tempfile.TemporaryDirectory() as tmp:
-        mp.spawn(_emul_worker, args=(world, 29300 + os.getpid() % 1000, tmp, nsc), nprocs=world, join=True)
-        _compare([np.load(os.path.join(tmp, "rank%d.npz" % r)) for r in range(world)], ref, nsc)
+    _compare(run_ranks(_emul_worker, world, backend="gloo", tag="slab-scalars-emul", args=(nsc,)), ref, nsc)
 
 
 def test_hotpath_scalar_count():
@@ -101,34 +86,23 @@ def test_hotpath_scalar_count():
         HotPath("drycblles", *GRID, device="cpu", lib=lib, nscalars=9)
 
 
-def _gpu_worker(rank, world, port, tmp, nsc):
+def _gpu_worker(rank, world, out, nsc):
     import torch
-    import torch.distributed as dist
     from microhh_amd.model import HotPath, synthetic_global
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        torch.cuda.set_device(0)
-        hp = HotPath("drycblles", *GRID_GPU, device="cuda:0", npy=world, rank=rank, nscalars=nsc,
-                     global_init=synthetic_global("drycblles", *GRID_GPU, nscalars=nsc), overlap=True)
-        assert hp._host_staged and hp.can_overlap
-        out = {}
-        _run(hp, out, overlapped=True)
-        np.savez(os.path.join(tmp, "rank%d.npz" % rank), **out)
-        hp.close()
-    finally:
-        dist.destroy_process_group()
+    torch.cuda.set_device(0)
+    hp = HotPath("drycblles", *GRID_GPU, device="cuda:0", npy=world, rank=rank, nscalars=nsc,
+                 global_init=synthetic_global("drycblles", *GRID_GPU, nscalars=nsc), overlap=True)
+    assert hp._host_staged and hp.can_overlap
+    _run(hp, out, overlapped=True)
+    hp.close()
 
 
 @pytest.mark.gpu
 def test_overlapped_slab_with_two_scalars_on_one_gpu_matches_single_rank():
-    import torch.multiprocessing as mp
     from microhh_amd.model import HotPath, synthetic_global
     nsc, world = 2, 2
     ref = {}
     hp = HotPath("drycblles", *GRID_GPU, device="cuda:0", nscalars=nsc, global_init=synthetic_global("drycblles", *GRID_GPU, nscalars=nsc))
     _run(hp, ref)
     hp.close()
-    with tempfile.TemporaryDirectory() as tmp:
-        mp.spawn(_gpu_worker, args=(world, 29800 + os.getpid() % 1000, tmp, nsc), nprocs=world, join=True)
-        _compare([np.load(os.path.join(tmp, "rank%d.npz" % r)) for r in range(world)], ref, nsc)
+    _compare(run_ranks(_gpu_worker, world, backend="gloo", tag="slab-scalars-gpu", args=(nsc,)), ref, nsc)

@@ -11,10 +11,8 @@ import pytest
 
 import backends as B
 import common as cm
-from common import ptr
+from common import BACKENDS, ptr
 from microhh_amd.model import HotPath, CASES, SURF
-
-BACKENDS = [pytest.param("emul"), pytest.param("hip", marks=pytest.mark.gpu)]
 
 
 @pytest.mark.parametrize("name", BACKENDS)

@@ -9,17 +9,16 @@ the C library in the grid's dtype, as std::sin / std::cos of a TF do in the refe
 Runs on the ``emul`` backend (the same kernel sources on the CPU) and on the ``hip`` backend (marked gpu)."""
 import ctypes as C
 import ctypes.util
-import os
 
 import numpy as np
 import pytest
 
 import backends as B
 import common as cm
+from backends import be  # noqa: F401
+from common import DTYPES, same_bits as same
 from microhh_amd import capi
 
-BACKENDS = [pytest.param("emul"), pytest.param("hip", marks=pytest.mark.gpu)]
-DTYPES = [np.float64, np.float32]
 SHAPES = [(70, 9, 10), (17, 9, 8), (20, 1, 12)]          # ragged 3-D sizes and jtot = 1
 # (alpha, N2, utrans): flat form, stratified (N2 != 0, alpha = 0), sloped (the prandtlslope set-up)
 FORMS = {"flat": (0., 0., 0.), "stratified": (0., 0.7, 0.), "sloped": (0.5235, 1., 0.13)}
@@ -28,33 +27,6 @@ _libm = C.CDLL(ctypes.util.find_library("m"))
 for _n, _t in (("sin", C.c_double), ("cos", C.c_double), ("sinf", C.c_float), ("cosf", C.c_float)):
     getattr(_libm, _n).restype = _t
     getattr(_libm, _n).argtypes = [_t]
-
-
-@pytest.fixture(params=BACKENDS)
-def be(request):
-    return B.get(request.param)
-
-
-class _env:
-    def __init__(self, **kw):
-        self.kw = kw
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kw}
-        os.environ.update({k: str(v) for k, v in self.kw.items()})
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-        return False
-
-
-def same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 def sincos(alpha, T):
@@ -188,7 +160,7 @@ def test_refusals(be):
     # buoyancy_kind is 0 or 1; the row-wise pass folds the flat form only
     g2 = cm.grid_2nd(16, 12, 10, gc=(3, 3, 1))
     d2 = B.DevCase(be, case(g2)); f2 = d2.fields()
-    p = capi.MhhDiffParams(); p.cs = 0.23; p.tPr = 1./3.; p.surface_model = 1; p.mlen0 = be.ptr(B.mlen0(be, g2, 0.23)).value
+    p = cm.diff_params(1, mlen0=be.ptr(B.mlen0(be, g2, 0.23)).value)
     p.buoyancy = 2; p.buoyancy_kind = 2; p.th_for_N2 = 0
     refused(be.lib.mhh_rhs_exec(d2.G, cm.ADVEC_2I5, cm.DIFF_SMAG2, C.byref(f2), C.byref(p), be.stream), "buoyancy_kind")
     p.buoyancy_kind = 1; p.alpha = 0.5235
@@ -199,7 +171,7 @@ def test_refusals(be):
 
 # ---- N2 of b inside exec_viscosity ---------------------------------------------------------------------------------------
 def _visc_params(be, g, sm, keep):
-    p = capi.MhhDiffParams(); p.cs = 0.23; p.tPr = 1./3.; p.surface_model = sm; p.neutral = 0
+    p = cm.diff_params(sm, neutral=0)
     ml = B.mlen0(be, g, 0.23); keep.append(ml); p.mlen0 = be.ptr(ml).value
     return p
 
@@ -226,7 +198,7 @@ def test_exec_viscosity_inline_N2_of_b_equals_N2_through_a_pointer(be, dtype, sm
                 B.ok(be, be.lib.mhh_thermo_buoy_N2(d.G, be.ptr(n2), be.ptr(d.s[1]), p.bg_n2, be.stream))
                 B.ok(be, be.lib.mhh_boundary_cyclic(d.G, be.ptr(n2), cm.EDGE_BOTH, be.stream))   # the ghost rows of the row forms
                 p.N2 = be.ptr(n2).value; p.th_for_N2 = -1
-            with _env(MHH_VISC_IMPL="cell" if route == "cell" else "march"):
+            with cm.switches(MHH_VISC_IMPL="cell" if route == "cell" else "march"):
                 if route == "rows":
                     p.evisc_ghost_rows = 1
                     B.ok(be, be.lib.mhh_diff_exec_viscosity_rows(d.G, cm.DIFF_SMAG2, C.byref(f), C.byref(p), g.jstart + 1, g.jend - 1, be.stream))
@@ -272,7 +244,7 @@ def test_folded_buoyancy_equals_standalone_then_unfused(be, dtype, adv, dif, ord
                 p = _visc_params(be, g, sm, keep) if sm else capi.MhhDiffParams()
                 if not sm:
                     p.cs = 0.23; p.tPr = 1./3.
-                with _env(**env):
+                with cm.switches(**env):
                     if how == "folded":
                         p.buoyancy = order; p.buoyancy_kind = 1; p.th_for_N2 = nb; p.alpha, p.bg_n2, p.utrans = alpha, n2, utrans
                         B.ok(be, be.lib.mhh_rhs_exec(d.G, adv, dif, C.byref(f), C.byref(p), be.stream))
