@@ -7,10 +7,12 @@ that this package accelerates, expressed as calls into the C ABI.
     pres->exec(dt)                        -> mhh_pres_exec, or its slab form around 2 all-to-alls (:411)
 
 One process per GPU. With ``npy`` > 1 the grid is slab-decomposed in y (npx = 1): halos travel as ring
-send/recv and the pressure solver's x<->y transposes as all_to_all, both through torch.distributed
-(backend "nccl" = RCCL over xGMI). PyTorch provides device memory, streams and the process group only;
-every kernel is the hand-written HIP behind the C ABI. Case recipes follow SURVEY.md §8(d).
+send/recv and the pressure solver's x<->y transposes as all_to_all (backend "nccl" = RCCL over xGMI).
+The exchanges live in master.py: its ``Master`` decides once how messages travel (local copy, direct,
+host-staged), HotPath packs, calls it and unpacks. PyTorch provides device memory, streams and the process
+group only; every kernel is the hand-written HIP behind the C ABI. Case recipes follow SURVEY.md §8(d).
 """
+import contextlib
 import ctypes as C
 import math
 import os
@@ -18,6 +20,7 @@ import os
 import numpy as np
 
 from . import capi
+from .master import Master
 from .grid import Grid, ADVEC_2, ADVEC_2I5, ADVEC_4, DIFF_2, DIFF_4, DIFF_SMAG2, EDGE_BOTH, EDGE_EW, moser_z
 
 CASES = {
@@ -92,7 +95,6 @@ class HotPath:
         elif overlap is None:
             overlap = npy > 1
         self.overlap = bool(overlap)
-        self._comm_stream = None
         self.device = torch.device(device)
         self.on_gpu = self.device.type == "cuda"
         if self.on_gpu:
@@ -100,18 +102,11 @@ class HotPath:
             # this HotPath's device the current one (cuda:N without a prior torch.cuda.set_device(N) would otherwise put the
             # plan on device 0 and the fields on device N)
             torch.cuda.set_device(self.device)
-        # Rehearsal of the N > 1 path on a box with fewer GPUs than ranks: several ranks share one card and talk over
-        # gloo, which has no device-side send/recv or all-to-all, so the MESSAGES (never the compute) pass through host
-        # copies. With the nccl backend (= RCCL, the product path) the device buffers go to the collective as they are.
-        self._host_staged = False
-        # MHH_FORCE_COMM=1 (tests): with one rank, still send the halos / transposes / maxima through torch.distributed (to
+        # MHH_FORCE_COMM=1 (tests): with one rank, still send the halos / transposes / maxima through the process group (to
         # self) instead of the local-copy shortcuts -- exercises the real RCCL calls on a one-GPU box
-        self._force_comm = os.environ.get("MHH_FORCE_COMM", "0") == "1"
+        self.master = Master(npy, rank, group, self.device, os.environ.get("MHH_FORCE_COMM", "0") == "1")
         # bench.py: device-event pairs around every exchange (tag, start, end) while comm_timing is a list
         self.comm_timing = None
-        if self.on_gpu and (npy > 1 or self._force_comm):
-            import torch.distributed as dist
-            self._host_staged = dist.is_initialized() and dist.get_backend(group) == "gloo"
         z = moser_z(ktot, cfg["size"][2]) if case == "moser600" else None
         # igc: ghost cells in x beyond what the schemes need -- what the reference's grid produces when an operator calls
         # Grid::set_minimum_ghost_cells (src/grid.cxx:435-439; src/advec_2i5.cxx:42-45 uses it). igc = 16 with itot = 512 makes
@@ -225,6 +220,9 @@ class HotPath:
         if self.on_gpu:
             self.torch.cuda.synchronize(self.device)
 
+    _host_staged = property(lambda self: self.master.mode == "host_staged")
+    _force_comm = property(lambda self: self.master.force_comm)
+
     @property
     def stream(self):
         if not self.on_gpu:
@@ -267,91 +265,38 @@ class HotPath:
         g, nf = self.grid, len(tensors)
         rs = g.jgc if rows_south is None else rows_south
         rn = g.jgc if rows_north is None else rows_north
-        key = (nf, rs, rn)
-        if key not in self._halo:
-            per_row = nf * g.kcells * g.icells
-            # one send and one receive buffer, [northbound | southbound]: what I send north arrives as my north neighbour's
-            # "from south" part, so with two ranks (north == south) the whole buffer is ONE message pair
-            nn, ns = rn * per_row, rs * per_row
-            send = self.torch.zeros(max(1, nn + ns), device=self.device, dtype=self.td)
-            recv = self.torch.zeros(max(1, nn + ns), device=self.device, dtype=self.td)
-            self._halo[key] = [send[nn:nn+ns], send[:nn], recv[:nn], recv[nn:nn+ns], send, recv]   # send south, send north, recv from south, recv from north
-        s_south, s_north, r_south, r_north, send, recv = self._halo[key]
-        isz = send.element_size()                                   # (an empty view has a null data_ptr: offsets by hand)
-        off_s = s_north.numel() * isz
+        nn, ns = rn * nf * g.kcells * g.icells, rs * nf * g.kcells * g.icells
+        if (nf, rs, rn) not in self._halo:                   # one send and one receive buffer, [northbound | southbound]
+            self._halo[nf, rs, rn] = [self.torch.zeros(max(1, nn + ns), device=self.device, dtype=self.td) for _ in range(2)]
+        send, recv = self._halo[nf, rs, rn]
+        off_s = nn * send.element_size()                     # (an empty view has a null data_ptr: offsets by hand)
         self._ok(self.lib.mhh_halo_pack_rows(self.G, arr, nf, rs, rn, send.data_ptr() + off_s, send.data_ptr(), self.stream))
-        self._ring(rs, rn, s_south, s_north, r_south, r_north, send, recv)
+        with self._timed("halo"):
+            self.master.ring(send, recv, nn, ns)
         self._ok(self.lib.mhh_halo_unpack_rows(self.G, arr, nf, rs, rn, recv.data_ptr(), recv.data_ptr() + off_s, self.stream))
 
-    def _timed(self, tag):
-        """Context manager: records a pair of events on the current stream around an exchange when comm_timing is on."""
-        hp = self
-
-        class _T:
-            def __enter__(self_):
-                self_.on = hp.comm_timing is not None and hp.on_gpu
-                if self_.on:
-                    self_.a = hp.torch.cuda.Event(enable_timing=True); self_.b = hp.torch.cuda.Event(enable_timing=True)
-                    self_.a.record()
-
-            def __exit__(self_, *exc):
-                if self_.on:
-                    self_.b.record(); hp.comm_timing.append((tag, self_.a, self_.b))
-                return False
-        return _T()
-
-    def _ring(self, rs, rn, s_south, s_north, r_south, r_north, send, recv):
-        """The message part of _exchange_ns: my northbound rows to the north neighbour, southbound rows to the south one."""
-        with self._timed("halo"):
-            self._ring_impl(rs, rn, s_south, s_north, r_south, r_north, send, recv)
-
-    def _ring_impl(self, rs, rn, s_south, s_north, r_south, r_north, send, recv):
-        import torch.distributed as dist
-        if self.npy == 1 and not self._force_comm:          # both neighbours are this rank: the exchange is a local swap
-            r_south.copy_(s_north); r_north.copy_(s_south)
-        else:
-            south, north = (self.rank - 1) % self.npy, (self.rank + 1) % self.npy
-            ranks = dist.get_process_group_ranks(self.group) if self.group is not None else list(range(self.npy))
-            hs, hr = (send.cpu(), self.torch.empty_like(recv, device="cpu")) if self._host_staged else (send, recv)
-            nn, ns = (s_north.numel() if rn else 0), (s_south.numel() if rs else 0)
-            if north == south:                                   # two ranks: both halves travel to the same peer
-                ops = [dist.P2POp(dist.isend, hs, ranks[north], self.group), dist.P2POp(dist.irecv, hr, ranks[north], self.group)]
-            else:
-                ops = []
-                if rn: ops.append(dist.P2POp(dist.isend, hs[:nn], ranks[north], self.group))
-                if rs: ops.append(dist.P2POp(dist.isend, hs[nn:nn+ns], ranks[south], self.group))
-                if rn: ops.append(dist.P2POp(dist.irecv, hr[:nn], ranks[south], self.group))
-                if rs: ops.append(dist.P2POp(dist.irecv, hr[nn:nn+ns], ranks[north], self.group))
-            for w in dist.batch_isend_irecv(ops):
-                w.wait()
-            if self._host_staged:
-                recv.copy_(hr)
+    @contextlib.contextmanager
+    def _timed(self, tag, on=True):
+        """Records a pair of events on the current stream around an exchange when comm_timing is on."""
+        on = on and self.comm_timing is not None and self.on_gpu
+        if on:
+            a, b = self.torch.cuda.Event(enable_timing=True), self.torch.cuda.Event(enable_timing=True)
+            a.record()
+        yield
+        if on:
+            b.record(); self.comm_timing.append((tag, a, b))
 
     def _halo2d(self, t):
         """One-time periodic ghost cells of a 2-D surface array (Boundary_cyclic::exec_2d, src/boundary_cyclic.cxx:445-500)."""
         g = self.grid
-        if self.npy == 1 and not self._force_comm:
+        if self.master.mode == "local":
             self._ok(self.lib.mhh_boundary_cyclic_2d(self.G, t.data_ptr(), self.stream))
             return
-        import torch.distributed as dist
         t[:, :g.igc] = t[:, g.iend-g.igc:g.iend].clone(); t[:, g.iend:] = t[:, g.istart:g.istart+g.igc].clone()
-        s_north, s_south = t[g.jend-g.jgc:g.jend].contiguous(), t[g.jstart:g.jstart+g.jgc].contiguous()
-        if self._host_staged:
-            s_north, s_south = s_north.cpu(), s_south.cpu()
-        r_south, r_north = self.torch.empty_like(s_north), self.torch.empty_like(s_south)
-        south, north = (self.rank - 1) % self.npy, (self.rank + 1) % self.npy
-        ranks = dist.get_process_group_ranks(self.group) if self.group is not None else list(range(self.npy))
-        if north == south:                                       # two ranks: one message pair, [northbound | southbound]
-            both, got = self.torch.cat([s_north, s_south]), self.torch.cat([r_south, r_north])
-            for w in dist.batch_isend_irecv([dist.P2POp(dist.isend, both, ranks[north], self.group), dist.P2POp(dist.irecv, got, ranks[north], self.group)]):
-                w.wait()
-            r_south, r_north = got[:g.jgc], got[g.jgc:]
-        else:
-            ops = [dist.P2POp(dist.isend, s_north, ranks[north], self.group), dist.P2POp(dist.isend, s_south, ranks[south], self.group),
-                   dist.P2POp(dist.irecv, r_south, ranks[south], self.group), dist.P2POp(dist.irecv, r_north, ranks[north], self.group)]
-            for w in dist.batch_isend_irecv(ops):
-                w.wait()
-        t[:g.jgc] = r_south.to(t.device); t[g.jend:] = r_north.to(t.device)
+        send = self.torch.cat([t[g.jend-g.jgc:g.jend], t[g.jstart:g.jstart+g.jgc]]).reshape(-1)      # [northbound | southbound]
+        recv = self.torch.empty_like(send)
+        self.master.ring(send, recv, send.numel() // 2, send.numel() // 2)
+        t[:g.jgc], t[g.jend:] = recv.view(2, g.jgc, -1)
 
     def cyclic_prognostic(self):
         self.halo(self._prog)
@@ -374,14 +319,12 @@ class HotPath:
         self._ok(lib.mhh_boundary_cyclic_n(self.G, self._ptrs(self._prog), len(self._prog), EDGE_EW, self.stream))
         if self.on_gpu:
             main = torch.cuda.current_stream(self.device)
-            if self._comm_stream is None:
-                self._comm_stream = torch.cuda.Stream(self.device)
-                self._ev = [torch.cuda.Event(), torch.cuda.Event()]
-            self._ev[0].record(main)
-            self._comm_stream.wait_event(self._ev[0])
-            with torch.cuda.stream(self._comm_stream):
+            comm, cev = self.master.side_stream()
+            cev[0].record(main)
+            comm.wait_event(cev[0])
+            with torch.cuda.stream(comm):
                 self._exchange_ns(self._prog)
-                self._ev[1].record(self._comm_stream)
+                cev[1].record(comm)
         else:
             self._exchange_ns(self._prog)
         ja, jb = g.jstart + 4, g.jend - 4
@@ -395,7 +338,7 @@ class HotPath:
             ev[1].record()
         self.rhs_rows_timed = jb - ja
         if self.on_gpu:
-            torch.cuda.current_stream(self.device).wait_event(self._ev[1])
+            torch.cuda.current_stream(self.device).wait_event(cev[1])
         # both edge strips in one launch each
         self._ok(lib.mhh_diff_exec_viscosity_rows2(self.G, dif, F, P, g.jstart - 1, g.jstart + 1, g.jend - 1, g.jend + 1, self.stream))
         self._ok(lib.mhh_rhs_exec_rows2(self.G, adv, dif, F, P, g.jstart, ja, jb, g.jend, self.stream))
@@ -452,14 +395,10 @@ class HotPath:
             y_out = lambda c: lib.mhh_pres_bwd_y_chunk(P, G, xs, c, self.stream)                  # noqa: E731
             x_out = lambda c: lib.mhh_pres_bwd_x_chunk(P, G, xr, c, self.stream)                  # noqa: E731
         # one slice: the transposes run on the caller's stream
-        two_streams = n > 1 and self.on_gpu and not self._host_staged and (self.npy > 1 or self._force_comm)
+        two_streams = n > 1 and self.on_gpu and self.master.mode == "direct"
         if two_streams:
             main = torch.cuda.current_stream(self.device)
-            if self._comm_stream is None:
-                self._comm_stream = torch.cuda.Stream(self.device)
-                self._ev = [torch.cuda.Event(), torch.cuda.Event()]
-            if not hasattr(self, "_sl_ev"):
-                self._sl_ev = [[torch.cuda.Event() for _ in range(n)] for _ in range(4)]
+            comm, sl_ev = self.master.side_stream()[0], self.master.slice_events(n)
         seg = self.xsend.numel() // n
 
         def exchange(c, way):
@@ -469,16 +408,16 @@ class HotPath:
             if not two_streams:
                 self._transpose(a, b)
                 return
-            ready, done = self._sl_ev[way][c], self._sl_ev[way+1][c]
+            ready, done = sl_ev[way][c], sl_ev[way+1][c]
             ready.record(main)
-            self._comm_stream.wait_event(ready)
-            with torch.cuda.stream(self._comm_stream):
+            comm.wait_event(ready)
+            with torch.cuda.stream(comm):
                 self._transpose(a, b)
-                done.record(self._comm_stream)
+                done.record(comm)
 
         def arrived(c, way):
             if two_streams:
-                main.wait_event(self._sl_ev[way+1][c])
+                main.wait_event(sl_ev[way+1][c])
 
         for c in range(n):
             self._ok(x_in(c)); exchange(c, 0)
@@ -515,18 +454,9 @@ class HotPath:
             self._ok(self.lib.mhh_rk_substep(self.G, rkorder, substep, dt, a.data_ptr(), at.data_ptr(), self.stream))
 
     def _transpose(self, xsend, xrecv):
-        """x<->y transpose of the spectral pressure (or of one k-slice of it): one equal-split all-to-all (RCCL over xGMI)."""
-        if self.npy == 1 and not self._force_comm:
-            xrecv.copy_(xsend)
-            return
-        import torch.distributed as dist
-        if self._host_staged:
-            hs = xsend.cpu(); hr = self.torch.empty_like(hs)
-            dist.all_to_all_single(hr, hs, group=self.group)
-            xrecv.copy_(hr)
-            return
-        with self._timed("transpose"):
-            dist.all_to_all_single(xrecv, xsend, group=self.group)
+        """x<->y transpose of the spectral pressure (or of one k-slice of it): Master.all_to_all, timed where it is direct."""
+        with self._timed("transpose", self.master.mode == "direct"):
+            self.master.all_to_all(xsend, xrecv)
 
     def step(self):
         """One full RHS + pressure evaluation (the BASELINE metric's unit of work)."""
@@ -551,19 +481,11 @@ class HotPath:
             self.step()
         return graph
 
-    # -- reductions (local max, then MAX over ranks: Master::max, src/master_parallel.cxx:233-266) --------------
-    def _allmax(self, v):
-        if self.npy == 1 and not self._force_comm:
-            return v
-        import torch.distributed as dist
-        t = self.torch.tensor([v], device=("cpu" if self._host_staged else self.device), dtype=self.torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
-        return float(t.item())
-
+    # -- reductions (local max, then Master.max over ranks) ------------------------------------------------------
     def divergence(self):
         out = C.c_double(0)
         self._ok(self.lib.mhh_pres_check_divergence(self.G, self.cfg["pres"], C.byref(self.fields), self.work.data_ptr(), C.byref(out), self.stream))
-        return self._allmax(out.value)
+        return self.master.max(out.value)
 
     def projected_divergence(self):
         """(max |Pres::input| of the fields as they stand, max |Pres::input| of u, v, w alone), each without its horizontal mean per
@@ -587,14 +509,9 @@ class HotPath:
             # src/pres_2.cxx:311-316, src/pres_4.cxx:421-446) and pres_4 does not enforce its equation on the top levels -- with
             # synthetic fields, whose w has a horizontal mean, that mode is left with a remainder that says nothing about the solve
             r = buf.view(g.kmax, g.jmax, g.imax)
-            lev = r.sum(dim=(1, 2), dtype=torch.float64)
-            if self.npy > 1 or self._force_comm:
-                import torch.distributed as dist
-                t = lev.cpu() if self._host_staged else lev
-                dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
-                lev = t.to(self.device)
+            lev = self.master.sum_(r.sum(dim=(1, 2), dtype=torch.float64))
             mean = (lev / float(g.itot * g.jtot)).to(self.td)
-            return self._allmax(float((r - mean[:, None, None]).abs().max().item()))
+            return self.master.max(float((r - mean[:, None, None]).abs().max().item()))
         d1 = residual(self.fields, True)
         zero = torch.zeros_like(self.ut)
         f0 = self._fields()
@@ -605,7 +522,7 @@ class HotPath:
     def cfl(self, dt):
         out = C.c_double(0)
         self._ok(self.lib.mhh_advec_cfl(self.G, self.cfg["advec"], self.u.data_ptr(), self.v.data_ptr(), self.w.data_ptr(), dt, self.work.data_ptr(), C.byref(out), self.stream))
-        return self._allmax(out.value)
+        return self.master.max(out.value)
 
     # -- restart files in the reference's layout (microhh_amd/fieldio.py; src/field3d_io.cxx:54-230) ------------------
     def _restart_fields(self):
@@ -624,16 +541,10 @@ class HotPath:
             if self.npy > 1:
                 for fn, _ in names:
                     fieldio.prepare_global_file(fn, self.grid, self.npy)
-        self._barrier()
+        self.master.barrier()
         for fn, t in names:
             fieldio.save_field3d(fn, t.detach().cpu().numpy(), self.grid, rank=self.rank, npy=self.npy)
-        self._barrier()
-
-    def _barrier(self):
-        if self.npy > 1:
-            import torch.distributed as dist
-            if dist.is_initialized():
-                dist.barrier(self.group)
+        self.master.barrier()
 
     def load(self, path, iteration=0):
         """Read the prognostic fields' interiors back (ghost cells are refreshed by the next cyclic_prognostic())."""

@@ -8,6 +8,7 @@ import ctypes as C, os, sys, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from microhh_amd import capi
+from microhh_amd import model
 from microhh_amd.model import HotPath
 
 npy = int(sys.argv[1]) if len(sys.argv) > 1 else 8
@@ -17,13 +18,15 @@ shape = (n, n // 2, n // 2) if case == "moser600" else (n, n, n)
 lib = capi.lib()
 hp = HotPath("drycblles", n, n, n, npy=npy, rank=0, group=None, global_init=None) if False else None
 # build the rank-0 object without a process group: construct with npy ranks but never call the exchanges
-class NoComm(HotPath):
-    def _ring(self, *a):
+class NoCommMaster(model.Master):
+    def ring(self, *a):
         pass
+    def all_to_all(self, *a):
+        pass
+class NoComm(HotPath):
     def _halo2d(self, t):
         pass
-    def _transpose(self, *a):
-        pass
+model.Master = NoCommMaster
 hp = NoComm(case, *shape, npy=npy, rank=0)
 def timeit(fn, reps=10):
     for _ in range(3): fn()

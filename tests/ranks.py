@@ -14,10 +14,10 @@ import common as cm
 
 TESTS = os.path.dirname(os.path.abspath(__file__))
 
-# One base per tag, 29300 ... 30500 as the modules had them; a case of a tag moves up by less than 100 with its world size
+# One base per tag, 29300 ... 30700 as the modules had them; a case of a tag moves up by less than 100 with its world size
 # and arguments, the process by its pid: two suites on one host, and two cases in a row, keep apart.
 PORT_BASE = {"slab-scalars-emul": 29300, "slab-gloo": 29500, "slab-save": 29600, "slab-gpu": 29700, "slab-scalars-gpu": 29800,
-             "slab-gpu-rccl": 29900, "slab4-gloo": 30100, "slab4-gpu": 30300, "slab4-gpu-rccl": 30500}
+             "slab-gpu-rccl": 29900, "slab4-gloo": 30100, "slab4-gpu": 30300, "slab4-gpu-rccl": 30500, "master": 30700}
 
 
 def port(tag, world, args):
