@@ -244,8 +244,11 @@ unsigned long long mhh_stat_rhs44_march_launches(void);   /* same for the k-marc
 /* same for the scalar pass of the k-marching (advec_2i5, diff_smag2) kernel: one per launch, a launch takes a batch of scalars
  * 1, 2, ... (mhh_rhs_exec, mhh_rhs_exec_rows(2), mhh_advec_exec, mhh_diff_exec; MHH_SCALAR_IMPL=cell: the per-field kernels) */
 unsigned long long mhh_stat_scalar_march_launches(void);
+/* same for the scalar pass of the k-marching (advec_4, diff_4) kernel: one per launch, a launch takes a batch of scalars 0, 1, ...
+ * (mhh_rhs_exec, mhh_advec_exec, mhh_diff_exec where the 4th-order marching kernel takes u, v, w, under MHH_SCALAR_IMPL=march; the default is the per-field kernels) */
+unsigned long long mhh_stat_scalar4_march_launches(void);
 /* diagnostic: the copy form the LAST launch of a k-marching kernel took (kernel: 0 = the fused 2i5 + smag2 kernel, 1 = its scalar
- * pass, 2 = the advec_4 + diff_4 kernel, 3 = exec_viscosity). *piece_bytes: 16 or 4 bytes per LDS-DMA piece (0: never launched);
+ * pass, 2 = the advec_4 + diff_4 kernel, 3 = exec_viscosity, 4 = the scalar pass of the advec_4 + diff_4 kernel). *piece_bytes: 16 or 4 bytes per LDS-DMA piece (0: never launched);
  * *hx: cells the tile of the fields starts west of a block's first cell; *ex: the same for the evisc tile (0: the launch copies
  * none); *cells_per_lane: 2 for the packed fp32 form. 16-byte pieces are taken only with istart - hx on a piece of the row. */
 int mhh_stat_march_form(int kernel, int* piece_bytes, int* hx, int* ex, int* cells_per_lane);

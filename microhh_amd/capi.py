@@ -62,6 +62,7 @@ SIGNATURES = {
     "mhh_rhs_exec_rows2": (ci, [GP, ci, ci, FP, DP, ci, ci, ci, ci, vp]),
     "mhh_stat_rhs44_march_launches": (C.c_ulonglong, []),
     "mhh_stat_scalar_march_launches": (C.c_ulonglong, []),
+    "mhh_stat_scalar4_march_launches": (C.c_ulonglong, []),
     "mhh_stat_march_form": (ci, [ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),
     "mhh_thermo_dry_buoyancy_tend": (ci, [GP, ci, vp, vp, vp, cd, vp]),
     "mhh_thermo_buoy_tend": (ci, [GP, ci, FP, ci, cd, cd, cd, vp]),

@@ -491,27 +491,53 @@ MHH_HD void advec4_mom(TF d[3], const TF* __restrict__ f, const TF* __restrict__
     else if (sd == 1)  advec4_mom_v<0>(d, fv, uv, vv, wv, bot, top, dxi, dyi, dz, dim3);
     else               advec4_mom_v<1>(d, fv, uv, vv, wv, bot, top, dxi, dyi, dz, dim3);
 }
+// Scalar advection (src/advec_4.cxx:360-486): the velocities are taken at their faces, no interpolation. Written against views as
+// advec4_mom_v: u is read at<-1..2,0,0>, v at<0,-1..2,0>, w at<0,0,-1..2>, s at +-3 along each axis.
+template<int M, class TF, class SV, class UV>
+MHH_HD TF advec4_s_px(const SV& s, const UV& u)
+{ return u.template at<M-1,0,0>() * ci4<TF>(s.template at<M-3,0,0>(), s.template at<M-2,0,0>(), s.template at<M-1,0,0>(), s.template at<M,0,0>()); }
+template<int M, class TF, class SV, class VV>
+MHH_HD TF advec4_s_py(const SV& s, const VV& v)
+{ return v.template at<0,M-1,0>() * ci4<TF>(s.template at<0,M-3,0>(), s.template at<0,M-2,0>(), s.template at<0,M-1,0>(), s.template at<0,M,0>()); }
+template<int M, class TF, class SV, class WV>
+MHH_HD TF advec4_s_pz(const SV& s, const WV& w, bool bot, bool top)
+{
+    TF fi;
+    if (M == 0 && bot)      fi = bi4<TF>(s.template at<0,0,-2>(), s.template at<0,0,-1>(), s.template at<0,0,0>(), s.template at<0,0,1>());
+    else if (M == 3 && top) fi = ti4<TF>(s.template at<0,0,-1>(), s.template at<0,0,0>(), s.template at<0,0,1>(), s.template at<0,0,2>());
+    else                    fi = ci4<TF>(s.template at<0,0,M-3>(), s.template at<0,0,M-2>(), s.template at<0,0,M-1>(), s.template at<0,0,M>());
+    return w.template at<0,0,M-1>() * fi;
+}
+// The vertical face products w * ci4(s ...) are carried from level to level (see advec4_mom_vc): product M of level k+1 is
+// product M+1 of level k, same operands in the same order; `fresh` forms all four. This is the one statement of the arithmetic:
+// advec4_s_v is the form that carries nothing
+template<class TF, class SV, class UV, class VV, class WV>
+MHH_HD void advec4_s_vc(TF d[3], const SV& s, const UV& u, const VV& v, const WV& w, bool bot, bool top, TF dxi, TF dyi, TF dz, bool dim3, TF (&c)[3], bool fresh)
+{
+    const TF cg0 = TF(1./24.), cg1 = TF(-27./24.), cg2 = TF(27./24.), cg3 = TF(-1./24.);
+    d[0] = ( cg0*advec4_s_px<0,TF>(s, u) + cg1*advec4_s_px<1,TF>(s, u) + cg2*advec4_s_px<2,TF>(s, u) + cg3*advec4_s_px<3,TF>(s, u) ) * dxi;
+    d[1] = TF(0);
+    if (dim3)
+        d[1] = ( cg0*advec4_s_py<0,TF>(s, v) + cg1*advec4_s_py<1,TF>(s, v) + cg2*advec4_s_py<2,TF>(s, v) + cg3*advec4_s_py<3,TF>(s, v) ) * dyi;
+    TF p0, p1, p2;
+    if (fresh) { p0 = advec4_s_pz<0,TF>(s, w, bot, top); p1 = advec4_s_pz<1,TF>(s, w, bot, top); p2 = advec4_s_pz<2,TF>(s, w, bot, top); }
+    else       { p0 = c[0]; p1 = c[1]; p2 = c[2]; }
+    const TF p3 = advec4_s_pz<3,TF>(s, w, bot, top);
+    d[2] = ( cg0*p0 + cg1*p1 + cg2*p2 + cg3*p3 ) * dz;
+    c[0] = p1; c[1] = p2; c[2] = p3;
+}
+template<class TF, class SV, class UV, class VV, class WV>
+MHH_HD void advec4_s_v(TF d[3], const SV& s, const UV& u, const VV& v, const WV& w, bool bot, bool top, TF dxi, TF dyi, TF dz, bool dim3)
+{
+    TF carried[3];
+    advec4_s_vc(d, s, u, v, w, bot, top, dxi, dyi, dz, dim3, carried, true);
+}
 template<class TF>
 MHH_HD void advec4_s(TF d[3], const TF* __restrict__ s, const TF* __restrict__ u, const TF* __restrict__ v, const TF* __restrict__ w,
                      int c, int jj, int kk, bool bot, bool top, TF dxi, TF dyi, TF dz, bool dim3)
 {
-    const TF cg0 = TF(1./24.), cg1 = TF(-27./24.), cg2 = TF(27./24.), cg3 = TF(-1./24.);
-    d[0] = ( cg0*(u[c-1] * ci4(s[c-3], s[c-2], s[c-1], s[c  ]))
-           + cg1*(u[c  ] * ci4(s[c-2], s[c-1], s[c  ], s[c+1]))
-           + cg2*(u[c+1] * ci4(s[c-1], s[c  ], s[c+1], s[c+2]))
-           + cg3*(u[c+2] * ci4(s[c  ], s[c+1], s[c+2], s[c+3])) ) * dxi;
-    d[1] = TF(0);
-    if (dim3)
-        d[1] = ( cg0*(v[c-jj  ] * ci4(s[c-3*jj], s[c-2*jj], s[c-jj], s[c]))
-               + cg1*(v[c     ] * ci4(s[c-2*jj], s[c-jj], s[c], s[c+jj]))
-               + cg2*(v[c+jj  ] * ci4(s[c-jj], s[c], s[c+jj], s[c+2*jj]))
-               + cg3*(v[c+2*jj] * ci4(s[c], s[c+jj], s[c+2*jj], s[c+3*jj])) ) * dyi;
-    const TF f0 = bot ? bi4(s[c-2*kk], s[c-kk], s[c], s[c+kk]) : ci4(s[c-3*kk], s[c-2*kk], s[c-kk], s[c]);
-    const TF f3 = top ? ti4(s[c-kk], s[c], s[c+kk], s[c+2*kk]) : ci4(s[c], s[c+kk], s[c+2*kk], s[c+3*kk]);
-    d[2] = ( cg0*(w[c-kk  ] * f0)
-           + cg1*(w[c     ] * ci4(s[c-2*kk], s[c-kk], s[c], s[c+kk]))
-           + cg2*(w[c+kk  ] * ci4(s[c-kk], s[c], s[c+kk], s[c+2*kk]))
-           + cg3*(w[c+2*kk] * f3) ) * dz;
+    const GlobalView<TF> sv{s, c, jj, kk}, uv{u, c, jj, kk}, vv{v, c, jj, kk}, wv{w, c, jj, kk};
+    advec4_s_v(d, sv, uv, vv, wv, bot, top, dxi, dyi, dz, dim3);
 }
 
 // calc_cfl integrand (advec_2.cxx:51-78, advec_2i5.cxx:60-148, advec_4.cxx:51-86)

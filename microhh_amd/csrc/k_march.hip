@@ -1145,7 +1145,7 @@ void mhh::note_march_form(MarchKernelId kernel, int pb, int hx, int ex, int cw)
 }
 MHH_API int mhh_stat_march_form(int kernel, int* piece_bytes, int* hx, int* ex, int* cells_per_lane)
 {
-    MHH_REQUIRE(kernel >= 0 && kernel < mhh::MARCH_K_COUNT, "kernel: 0 rhs25, 1 scalar pass, 2 rhs44, 3 visc");
+    MHH_REQUIRE(kernel >= 0 && kernel < mhh::MARCH_K_COUNT, "kernel: 0 rhs25, 1 scalar pass, 2 rhs44, 3 visc, 4 scalar pass of rhs44");
     MHH_REQUIRE(piece_bytes && hx && ex && cells_per_lane, "null result pointer");
     *piece_bytes = g_march_form[kernel][0]; *hx = g_march_form[kernel][1]; *ex = g_march_form[kernel][2]; *cells_per_lane = g_march_form[kernel][3];
     return MHH_OK;

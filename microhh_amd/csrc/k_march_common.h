@@ -95,7 +95,7 @@ inline bool pieces16_clear_of_row_end(const mhh_grid* g, int off, int reach, int
 // Diagnostics (mhh_stat_march_form): the copy form of the last launch of each marching kernel. pb = bytes per LDS-DMA piece;
 // hx = cells the tile of the fields starts west of the block's first cell; ex = the same for the evisc tile (0: the kernel has
 // none); cw = cells per lane
-enum MarchKernelId { MARCH_K_RHS25 = 0, MARCH_K_SCALARS = 1, MARCH_K_RHS44 = 2, MARCH_K_VISC = 3, MARCH_K_COUNT = 4 };
+enum MarchKernelId { MARCH_K_RHS25 = 0, MARCH_K_SCALARS = 1, MARCH_K_RHS44 = 2, MARCH_K_VISC = 3, MARCH_K_SCALARS4 = 4, MARCH_K_COUNT = 5 };
 void note_march_form(MarchKernelId kernel, int pb, int hx, int ex, int cw);
 // Calls fn(PB, ADV, DIF) with the run-time operators and piece size (4 or 16 bytes) as std::integral_constants: the template
 // arguments of a marching kernel
@@ -165,6 +165,15 @@ int march25(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, Ma
 int march25_scalars(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const int* idx, int n, MarchOps ops, const MarchRows& rows, void* stream);
 // advec_4 and / or diff_4 of u, v, w (k_march4.hip), where march44_takes(g)
 int march44(const mhh_grid* g, const mhh_fields* f, MarchOps ops, void* stream, const void* bfold = nullptr);
+// the same for the scalars idx[0 .. n) in the batched 4th-order scalar pass (k_march4.hip), where march44_takes(g)
+int march44_scalars(const mhh_grid* g, const mhh_fields* f, const int* idx, int n, MarchOps ops, void* stream);
+// every scalar of f through that pass (inputs validated by the caller)
+inline int march44_all_scalars(const mhh_grid* g, const mhh_fields* f, MarchOps ops, void* stream)
+{
+    int idx[MHH_MAX_SCALARS];
+    for (int n=0; n<f->nscalars; ++n) idx[n] = n;
+    return march44_scalars(g, f, idx, f->nscalars, ops, stream);
+}
 // Diff_smag2::exec_viscosity over the rows (k_visc.hip), where visc_march_takes(g)
 int visc_march(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, const void* th, const MarchRows& rows, void* stream);
 // The advec_2i5 / diff_smag2 routing of every field (k_rhs.hip): u, v, w and scalar 0 to march25, further scalars to the
@@ -172,8 +181,13 @@ int visc_march(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p,
 int route25(const mhh_grid* g, const mhh_fields* f, const mhh_diff_params* p, MarchOps ops, const MarchRows& rows, bool pass, void* stream);
 
 // Does the marching form take the call? The A/B switches (read per call) and the ghost cells the kernels read; otherwise the
-// caller takes the one-thread-per-cell kernels. Scalars 1, 2, ...: the scalar pass unless MHH_SCALAR_IMPL=cell.
+// caller takes the one-thread-per-cell kernels. The scalars that the fused kernel does not carry (advec_2i5 / diff_smag2: scalars
+// 1, 2, ...) take the scalar pass unless MHH_SCALAR_IMPL=cell; every scalar of advec_4 / diff_4 takes the per-field kernels unless
+// MHH_SCALAR_IMPL=march, which selects the 4th-order scalar pass where march44_takes.
 inline bool march44_takes(const mhh_grid* g) { return !env_is("MHH_RHS44_IMPL", "cell") && g->igc >= 3 && g->jgc >= 3 && g->kgc >= 3; }
 inline bool visc_march_takes(const mhh_grid* g) { return !env_is("MHH_VISC_IMPL", "cell") && g->igc >= 1 && g->jgc >= 1 && g->kgc >= 1; }
 inline bool scalar_march_on() { return !env_is("MHH_SCALAR_IMPL", "cell"); }
+// The 4th-order scalar pass is opt-in, MHH_SCALAR_IMPL=march: it has the per-field kernels' bits, but no timing on the device shows
+// it the faster form yet (profiles/scalar4_pass.md says which runs decide that), so the per-field kernels stay the default there.
+inline bool scalar4_march_on() { return env_is("MHH_SCALAR_IMPL", "march"); }
 }

@@ -284,6 +284,12 @@ MHH_API int mhh_diff_exec(const mhh_grid* g, int scheme, const mhh_fields* f, co
             uvw_done = march44_takes(g);
             if (uvw_done) if (int e = march44(g, f, MARCH_DIFF, stream)) return e;
         }
+        if (uvw_done && f->nscalars == 0) return MHH_OK;
+        if (uvw_done && scalar4_march_on())     // MHH_SCALAR_IMPL=march: every scalar in the scalar pass of that kernel (default: per field)
+        {
+            for (int n=0; n<f->nscalars; ++n) MHH_REQUIRE(f->s[n] && f->st[n], "null field");
+            return march44_all_scalars(g, f, MARCH_DIFF, stream);
+        }
         if (!uvw_done)
         {
             if (int e = mhh_diff_c(g, o, f->ut, f->u, f->visc, stream)) return e;
@@ -546,10 +552,10 @@ MHH_API int mhh_rhs_exec(const mhh_grid* g, int advec_scheme, int diff_scheme, c
     {
         MHH_REQUIRE(g->igc >= 3 && g->jgc >= 3 && g->kgc >= 3, "4th order needs gc(3,3,3)");
         if (int e = sloped_first()) return e;
-        // default: the k-marching LDS kernel (k_march4.hip) for u, v, w where the rows allow LDS-DMA; scalars take their own
-        // kernels (same order of accumulation). Thermo_buoy's flat 4th-order buoyancy is folded into the w equation there (a
-        // register window of b); the dry buoyancy, or a 2nd-order one, takes its own kernel first. MHH_RHS44_IMPL=cell selects
-        // the cell kernel, which folds both.
+        // default: the k-marching LDS kernel (k_march4.hip) for u, v, w, then every scalar in its own two kernels
+        // (MHH_SCALAR_IMPL=march: the scalar pass of that file; same order of accumulation, same bits). Thermo_buoy's flat 4th-order buoyancy is
+        // folded into the w equation of the first kernel (a register window of b); the dry buoyancy, or a 2nd-order one, takes
+        // its own kernel first. MHH_RHS44_IMPL=cell selects the cell kernel, which folds both.
         if (march44_takes(g))
         {
             // the fold where every row of a block lies in the domain: 2.12 against 2.27 ms for the separate launch at 512 x 256 x 256
@@ -558,6 +564,8 @@ MHH_API int mhh_rhs_exec(const mhh_grid* g, int advec_scheme, int diff_scheme, c
             const bool fold = p && p->buoyancy == 4 && p->buoyancy_kind == 1 && g->jmax >= 4;
             if (p && p->buoyancy && !fold) if (int e = buoyancy_alone(g, f, p, stream)) return e;
             if (int e = march44(g, f, MARCH_BOTH, stream, fold ? f->s[p->th_for_N2] : nullptr)) return e;
+            if (f->nscalars == 0) return MHH_OK;
+            if (scalar4_march_on()) return march44_all_scalars(g, f, MARCH_BOTH, stream);
             for (int n=0; n<f->nscalars; ++n)
             {
                 if (int e = mhh_advec_s(g, MHH_ADVEC_4, f->st[n], f->s[n], f->u, f->v, f->w, f->rhoref, f->rhorefh, stream)) return e;

@@ -292,12 +292,22 @@ MHH_API int mhh_advec_exec(const mhh_grid* g, int scheme, const mhh_fields* f, v
         return route25(g, f, nullptr, MARCH_ADVEC, MarchRows{}, scalar_march_on(), stream);
     }
     bool uvw_done = false;
-    if (scheme == MHH_ADVEC_4)           // u, v, w in one pass of the 4th-order marching kernel (advective terms only); scalars per field
+    if (scheme == MHH_ADVEC_4)           // u, v, w in one pass of the 4th-order marching kernel (advective terms only); MHH_SCALAR_IMPL=march: the scalars in its scalar pass
     {
         if (int e = check_advec(g, scheme)) return e;
         MHH_REQUIRE(f->u && f->v && f->w && f->ut && f->vt && f->wt, "null field");
         uvw_done = march44_takes(g);
         if (uvw_done) if (int e = march44(g, f, MARCH_ADVEC, stream)) return e;
+        if (uvw_done && f->nscalars == 0) return MHH_OK;
+        if (uvw_done && scalar4_march_on())     // MHH_SCALAR_IMPL=march: every scalar in the scalar pass of that kernel (default: per field)
+        {
+            for (int n=0; n<f->nscalars; ++n)
+            {
+                MHH_REQUIRE(!f->s_fluxlimit[n], "fluxlimit_list is an option of advec_2i5 / advec_2i62 (src/advec_2i5.cxx:39, src/advec_2i62.cxx:39)");
+                MHH_REQUIRE(f->s[n] && f->st[n], "null field");
+            }
+            return march44_all_scalars(g, f, MARCH_ADVEC, stream);
+        }
     }
     if (!uvw_done)
     {
