@@ -419,6 +419,83 @@ int mhh_pres_slab_lds_bwd(mhh_pres_slab_plan* plan, const mhh_grid* g, const voi
 int mhh_pres_slab_lds_fwd_y(mhh_pres_slab_plan* plan, const mhh_grid* g, void* recvbuf, int c, void* stream);
 int mhh_pres_slab_lds_bwd_y(mhh_pres_slab_plan* plan, const mhh_grid* g, void* sendbuf, int c, void* stream);
 
+/* ---- Field3d_operators: horizontal means, deterministic ---------------------------------------------------------
+ * Two kernels per call and no floating-point atomics: a 64 x 4 block sums one level's cells of a chunk of
+ * mhh_field_mean_chunk_rows() rows in a fixed order into ONE double partial of scratch[field][k][chunk]; a second kernel
+ * adds the partials in index order. Two calls on the same input give the same bits. `scratch` is the caller's: device
+ * memory of mhh_field_mean_scratch_elems(g, nfields) DOUBLES. Up to 3 + MHH_MAX_SCALARS fields per call.               */
+#define MHH_MAX_MEAN_FIELDS (3 + MHH_MAX_SCALARS)
+unsigned long long mhh_field_mean_scratch_elems(const mhh_grid* g, int nfields);
+int mhh_field_mean_chunk_rows(void);
+/* Field3d_operators::calc_mean_profile (src/field3d_operators.cxx:45-66): for every level k in [0, kcells) the interior (i, j)
+ * cells summed in double, profs[n][k] = TF(sum / (itot*jtot)). The divisor is the GLOBAL itot*jtot: a slab rank produces its
+ * share and the caller sums the shares over the ranks (the reference's master.sum after the division).                    */
+int mhh_field_mean_profile(const mhh_grid* g, const void* const* fields, int nfields, void* const* profs /* TF [kcells] each */,
+                           void* scratch, void* stream);
+/* The sum of Field3d_operators::calc_mean (src/field3d_operators.cxx:132-155): fld[ijk]*dz[k] formed in TF, accumulated in
+ * double over the interior; sums[n] (DEVICE doubles) receives this rank's sum. The quotient by itot*jtot*zsize (formed in
+ * TF, :152) is taken where the sum is consumed (mhh_force_params::uflux_sums), so that a slab rank can all-reduce first.  */
+int mhh_field_mean_sum(const mhh_grid* g, const void* const* fields, int nfields, void* sums /* double [nfields] */,
+                       void* scratch, void* stream);
+
+/* ---- Buffer: the sponge layer (src/buffer.cxx:37-58,163-206) -----------------------------------------------------
+ * at[ijk] -= sigmaz[k]*(a[ijk] - abuf[k]) for u, v, every scalar (k in [bufferkstart, kend), table sigma) and w
+ * (k in [bufferkstarth, kend), half-level table sigmah). One launch over the buffer levels only. A zero-initialised
+ * struct (swbuffer = 0) is a no-op.                                                                                 */
+typedef struct mhh_buffer_params
+{
+    int swbuffer;
+    int bufferkstart, bufferkstarth;         /* Buffer::create (src/buffer.cxx:107-126)                            */
+    const void* sigma;                       /* [kcells] device tables from mhh_buffer_sigma_host                  */
+    const void* sigmah;
+    /* [kcells] device profiles per field: the fixed bufferprofs, or the mean profiles (swupdate); NULL = field left alone */
+    const void* abuf_u; const void* abuf_v; const void* abuf_w;
+    const void* abuf_s[MHH_MAX_SCALARS];
+} mhh_buffer_params;
+/* sigmaz[k] = sigma*pow((z[k]-zstart)/(zsize-zstart), beta) in the grid's dtype with the HOST C library's pow (powf in fp32,
+ * as the reference calls std::pow of TF, src/buffer.cxx:48); z = zh with half_level. `g_host` carries HOST metric pointers.
+ * Levels outside [kstart, kend) or below zstart get 0 (the kernels never read them).                                   */
+int mhh_buffer_sigma_host(const mhh_grid* g_host, double zstart, double sigma, double beta, int half_level, void* out_host);
+int mhh_buffer_exec(const mhh_grid* g, const mhh_fields* f, const mhh_buffer_params* b, void* stream);
+
+/* ---- Force (src/force.cxx:46-311,581-729) ------------------------------------------------------------------------
+ * One launch; per field the terms apply to each cell in the reference's order -- pressure force, swls, swwls, nudging --
+ * so a tendency has the bits of the separate reference loops run in sequence. Profiles are [kcells] DEVICE arrays of the
+ * grid's dtype. A zero-initialised struct is a no-op. rescale_nudgeprof (scalednudgelist) edits a host profile: the
+ * caller's, before the upload. w has no ls_ / nudge_ slot: the large-scale source and the nudging act on u, v and the
+ * scalars only (the reference takes any prognostic name in lslist / nudgelist; w reaches this pass through the sponge
+ * and through swwls = local with swwls_mom).                                                                         */
+#define MHH_LSPRES_NONE  0
+#define MHH_LSPRES_DPDX  1   /* add_pressure_force :47-60, ut += -dpdx                                              */
+#define MHH_LSPRES_UFLUX 2   /* enforce_fixed_flux :63-74                                                           */
+#define MHH_LSPRES_GEO   3   /* calc_coriolis_2nd / _4th :77-151                                                    */
+#define MHH_WLS_NONE  0
+#define MHH_WLS_MEAN  1      /* advec_wls_2nd_mean :203-235 (Large_scale_subsidence_type::Mean_field)               */
+#define MHH_WLS_LOCAL 2      /* advec_wls_2nd_local / _local_w :237-305 (Local_field)                               */
+typedef struct mhh_force_params
+{
+    int swlspres;
+    int order;                               /* geo: 2 | 4 (grid.swspatialorder); 4 needs igc >= 2 and jgc >= 2     */
+    double dpdx;
+    double uflux, dt;                        /* uflux: dt is narrowed to the grid's dtype first, as the reference's const TF dt */
+    const void* uflux_sums;                  /* DEVICE double[2]: GLOBAL sums of u*dz and ut*dz (mhh_field_mean_sum)  */
+    double fc, utrans, vtrans;               /* geo: fc, grid.utrans, grid.vtrans                                   */
+    const void* ug; const void* vg;
+    int swls;                                /* calc_large_scale_source :153-169: at += ls[k] where ls_* != NULL     */
+    const void* ls_u; const void* ls_v; const void* ls_s[MHH_MAX_SCALARS];
+    int swwls, swwls_mom;                    /* every scalar; with swwls_mom also u, v (and w in the local form)     */
+    const void* wls;
+    /* horizontal mean profiles (mhh_field_mean_profile, summed over the ranks): read by swwls = mean and by the nudging */
+    const void* mean_u; const void* mean_v; const void* mean_s[MHH_MAX_SCALARS];
+    int swnudge;                             /* calc_nudging_tendency :171-191 where nudge_* != NULL                 */
+    const void* nudge_factor;
+    const void* nudge_u; const void* nudge_v; const void* nudge_s[MHH_MAX_SCALARS];
+} mhh_force_params;
+int mhh_force_exec(const mhh_grid* g, const mhh_fields* f, const mhh_force_params* p, void* stream);
+/* buffer->exec then force->exec (src/model.cxx:395,404) as ONE read-modify-write of every tendency: the same kernel with
+ * both term groups compiled in; the bits of mhh_buffer_exec followed by mhh_force_exec.                                */
+int mhh_buffer_force_exec(const mhh_grid* g, const mhh_fields* f, const mhh_buffer_params* b, const mhh_force_params* p, void* stream);
+
 /* ---- Vertical ghost cells --------------------------------------------------------------
  * Boundary::set_ghost_cells: calc_ghost_cells_{bot,top}_{2nd,4th} (src/boundary.cxx:686-836); bc 0 = Dirichlet
  * (abot/atop), 1 = Neumann or flux (agradbot/agradtop); 2-D arrays are [ijcells]. set_ghost_cells_w (4th order

@@ -34,8 +34,24 @@ class MhhDiffParams(C.Structure):
                 ("buoyancy_kind", ci), ("bg_n2", cd), ("alpha", cd), ("utrans", cd)]
 
 
+class MhhBufferParams(C.Structure):
+    _fields_ = [("swbuffer", ci), ("bufferkstart", ci), ("bufferkstarth", ci), ("sigma", vp), ("sigmah", vp),
+                ("abuf_u", vp), ("abuf_v", vp), ("abuf_w", vp), ("abuf_s", vp * MAX_SCALARS)]
+
+
+class MhhForceParams(C.Structure):
+    _fields_ = [("swlspres", ci), ("order", ci), ("dpdx", cd), ("uflux", cd), ("dt", cd), ("uflux_sums", vp),
+                ("fc", cd), ("utrans", cd), ("vtrans", cd), ("ug", vp), ("vg", vp),
+                ("swls", ci), ("ls_u", vp), ("ls_v", vp), ("ls_s", vp * MAX_SCALARS),
+                ("swwls", ci), ("swwls_mom", ci), ("wls", vp),
+                ("mean_u", vp), ("mean_v", vp), ("mean_s", vp * MAX_SCALARS),
+                ("swnudge", ci), ("nudge_factor", vp), ("nudge_u", vp), ("nudge_v", vp), ("nudge_s", vp * MAX_SCALARS)]
+
+
 FP = C.POINTER(MhhFields)
 DP = C.POINTER(MhhDiffParams)
+BP = C.POINTER(MhhBufferParams)
+FRP = C.POINTER(MhhForceParams)
 PLAN = vp
 
 SIGNATURES = {
@@ -131,6 +147,14 @@ SIGNATURES = {
     "mhh_pres_slab_plan_create_order": (ci, [GP, ci, vp, vp, vp, vp, vp, vp, C.POINTER(PLAN)]),
     "mhh_pres_slab_order": (ci, [PLAN]),
     "mhh_pres_unpack_slab": (ci, [PLAN, GP, FP, vp]),
+    "mhh_field_mean_scratch_elems": (C.c_ulonglong, [GP, ci]),
+    "mhh_field_mean_chunk_rows": (ci, []),
+    "mhh_field_mean_profile": (ci, [GP, C.POINTER(vp), ci, C.POINTER(vp), vp, vp]),
+    "mhh_field_mean_sum": (ci, [GP, C.POINTER(vp), ci, vp, vp, vp]),
+    "mhh_buffer_sigma_host": (ci, [GP, cd, cd, cd, ci, vp]),
+    "mhh_buffer_exec": (ci, [GP, FP, BP, vp]),
+    "mhh_force_exec": (ci, [GP, FP, FRP, vp]),
+    "mhh_buffer_force_exec": (ci, [GP, FP, BP, FRP, vp]),
 }
 
 

@@ -870,4 +870,49 @@ MHH_HD TF div4_cell(const TF* __restrict__ u, const TF* __restrict__ v, const TF
          + cg4(w[c-kk], w[c], w[c+kk], w[c+2*kk]) * dzi4_k;
 }
 
+// =======================================================================================================
+// Buffer (src/buffer.cxx:37-58) and Force (src/force.cxx:46-305): one function per reference kernel body. Each returns what
+// the reference adds to (or, where named _sub, subtracts from) ONE tendency cell; per-level values arrive as arguments.
+// =======================================================================================================
+// calc_buffer (src/buffer.cxx:55): at -= sigmaz*(a - abuf[k])
+template<class TF> MHH_HD TF buffer_sub(TF sigmaz, TF a, TF abuf_k) { return sigmaz*(a - abuf_k); }
+// enforce_fixed_flux (src/force.cxx:71): the body force from the two volume means, all operands TF
+template<class TF> MHH_HD TF force_fixed_flux_body(TF u_flux, TF u_mean, TF ut_mean, TF u_grid, TF dt) { return (u_flux - u_mean - u_grid) / dt - ut_mean; }
+// Field3d_operators::calc_mean (src/field3d_operators.cxx:152): the double sum over the TF denominator itot*jtot*zsize
+template<class TF> MHH_HD TF mean_of_sum(double sum, TF den) { return TF(sum / den); }
+// calc_coriolis_2nd (src/force.cxx:96,105): ut += coriolis2_u, vt -= coriolis2_v
+template<class TF> MHH_HD TF coriolis2_u(const TF* __restrict__ v, int c, int jj, TF fc, TF vgrid, TF vg_k)
+{ return fc * (TF(0.25)*(v[c-1] + v[c] + v[c-1+jj] + v[c+jj]) + vgrid - vg_k); }
+template<class TF> MHH_HD TF coriolis2_v(const TF* __restrict__ u, int c, int jj, TF fc, TF ugrid, TF ug_k)
+{ return fc * (TF(0.25)*(u[c-jj] + u[c] + u[c+1-jj] + u[c+1]) + ugrid - ug_k); }
+// calc_coriolis_4th (src/force.cxx:132-136,145-149): ci0*(ci0*a + ci1*b + ci2*c + ci3*d) + ci1*(...) + ..., 16 points
+template<class TF> MHH_HD TF coriolis4_u(const TF* __restrict__ v, int c, int jj, TF fc, TF vgrid, TF vg_k)
+{
+    return fc * ( ci4( ci4(v[c-2-jj  ], v[c-1-jj  ], v[c-jj  ], v[c+1-jj  ]),
+                       ci4(v[c-2     ], v[c-1     ], v[c     ], v[c+1     ]),
+                       ci4(v[c-2+jj  ], v[c-1+jj  ], v[c+jj  ], v[c+1+jj  ]),
+                       ci4(v[c-2+2*jj], v[c-1+2*jj], v[c+2*jj], v[c+1+2*jj]) )
+                + vgrid - vg_k );
+}
+template<class TF> MHH_HD TF coriolis4_v(const TF* __restrict__ u, int c, int jj, TF fc, TF ugrid, TF ug_k)
+{
+    return fc * ( ci4( ci4(u[c-1-2*jj], u[c-2*jj], u[c+1-2*jj], u[c+2-2*jj]),
+                       ci4(u[c-1-jj  ], u[c-jj  ], u[c+1-jj  ], u[c+2-jj  ]),
+                       ci4(u[c-1     ], u[c     ], u[c+1     ], u[c+2     ]),
+                       ci4(u[c-1+jj  ], u[c+jj  ], u[c+1+jj  ], u[c+2+jj  ]) )
+                + ugrid - ug_k );
+}
+// advec_wls_2nd_mean (src/force.cxx:216-232): st -= wls[k]*(s[k]-s[k-1])*dzhi[k] (wls[k] > 0) or wls[k]*(s[k+1]-s[k])*dzhi[k+1];
+// s is the mean PROFILE
+template<class TF> MHH_HD TF wls_mean_sub(TF sm_km, TF sm_k, TF sm_kp, TF wls_k, TF dzhi_k, TF dzhi_kp)
+{ return (wls_k > 0.) ? wls_k * (sm_k-sm_km)*dzhi_k : wls_k * (sm_kp-sm_k)*dzhi_kp; }
+// advec_wls_2nd_local (src/force.cxx:250-266): the same on the field
+template<class TF> MHH_HD TF wls_local_sub(const TF* __restrict__ s, int c, int kk, TF wls_k, TF dzhi_k, TF dzhi_kp)
+{ return (wls_k > 0.) ? wls_k * (s[c]-s[c-kk])*dzhi_k : wls_k * (s[c+kk]-s[c])*dzhi_kp; }
+// advec_wls_2nd_local_w (src/force.cxx:284-302), k in (kstart, kend): wl = interp2(wls[k-1], wls[k]), dzi[k-1] or dzi[k]
+template<class TF> MHH_HD TF wls_local_w_sub(const TF* __restrict__ w, int c, int kk, TF wls_km, TF wls_k, TF dzi_km, TF dzi_k)
+{ return (i2(wls_km, wls_k) > 0.) ? i2(wls_km, wls_k) * (w[c]-w[c-kk])*dzi_km : i2(wls_km, wls_k) * (w[c+kk]-w[c])*dzi_k; }
+// calc_nudging_tendency (src/force.cxx:183): formed once per level, then added
+template<class TF> MHH_HD TF nudge_tend(TF factor_k, TF mean_k, TF ref_k) { return -factor_k * (mean_k - ref_k); }
+
 } // namespace mhh

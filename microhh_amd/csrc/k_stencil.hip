@@ -812,3 +812,8 @@ MHH_API int mhh_boundary_ghost_cells_w(const mhh_grid* g, void* w, int type, voi
     return MHH_DISPATCH(g, CALL);
 #undef CALL
 }
+
+// =======================================================================================================
+// Field3d_operators means, Buffer::exec, Force::exec and their fused pass (src/model.cxx:351,395,404)
+// =======================================================================================================
+#include "force_means.h"

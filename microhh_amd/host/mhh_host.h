@@ -48,6 +48,7 @@ template<typename TF>
 struct Field3d
 {
     TF* fld_g = nullptr;
+    TF* fld_mean_g = nullptr;          // [kcells] horizontal mean profile (Field3d::fld_mean_g, include/field3d.h:72)
     TF* flux_bot_g = nullptr; TF* flux_top_g = nullptr;
     TF visc = 0;
 };
@@ -501,6 +502,167 @@ class Pres
         }
     protected:
         Grid<TF>& grid; Fields<TF>& fields; int order; mhh_pres_plan* plan; void* work;
+};
+
+// ---- Field3d_operators (include/field3d_operators.h:32-58; src/field3d_operators.cxx:45-66,132-155) ------------------------
+// The reduction scratch is the caller's: device memory of scratch_elems(nfields) doubles (set_scratch). One rank; a slab rank
+// sums its shares over the ranks itself (the reference's master.sum).
+template<typename TF>
+class Field3d_operators
+{
+    public:
+        Field3d_operators(Grid<TF>& gridin, Fields<TF>&) : grid(gridin), scratch(nullptr) {}   // Fields: the reference's argument, not read here
+        unsigned long long scratch_elems(int nfields) const { mhh_grid g = grid.abi(); return mhh_field_mean_scratch_elems(&g, nfields); }
+        void set_scratch(double* device_scratch) { scratch = device_scratch; }
+        void calc_mean_profile_g(TF* prof, const TF* fld, void* stream = nullptr)
+        {
+            mhh_grid g = grid.abi(); const void* f[1] = {fld}; void* p[1] = {prof};
+            mhh_check(mhh_field_mean_profile(&g, f, 1, p, scratch, stream));
+        }
+        // the volume sums of several fields into DEVICE doubles (what Force's fixed flux reads without a host round trip)
+        void calc_sums_g(double* sums_device, const TF* const* flds, int n, void* stream = nullptr)
+        {
+            mhh_grid g = grid.abi();
+            mhh_check(mhh_field_mean_sum(&g, reinterpret_cast<const void* const*>(flds), n, sums_device, scratch, stream));
+        }
+        // calc_mean_g returns a host TF, as the reference's does; download(dst_host, src_device, bytes) is the caller's D2H copy
+        template<class Download> TF calc_mean_g(const TF* fld, double* sum_device, Download download, void* stream = nullptr)
+        {
+            auto& gd = grid.get_grid_data();
+            const TF* f[1] = {fld};
+            calc_sums_g(sum_device, f, 1, stream);
+            mhh_check(mhh_synchronize(stream));
+            double sum = 0; download(&sum, sum_device, sizeof(double));
+            const TF mean = sum / (gd.itot * gd.jtot * gd.zsize);
+            return mean;
+        }
+    private:
+        Grid<TF>& grid; double* scratch;
+};
+
+// ---- Buffer (include/buffer.h:38-80; src/buffer.cxx) ---------------------------------------------------------------------------
+template<typename TF>
+class Buffer
+{
+    public:
+        Buffer(Grid<TF>& gridin, Fields<TF>& fieldsin, bool swbufferin, bool swupdatein = false, TF zstartin = 0, TF sigmain = 2., TF betain = 2.) :
+            grid(gridin), fields(fieldsin), zstart(zstartin), sigma(sigmain), beta(betain), bufferkstart(0), bufferkstarth(0),
+            swbuffer(swbufferin), swupdate(swupdatein), sigma_g(nullptr), sigmah_g(nullptr) {}
+        void init() {}
+        // the starting levels of src/buffer.cxx:107-126, with its error
+        void create(Stats&)
+        {
+            if (!swbuffer) return;
+            auto& gd = grid.get_grid_data();
+            bufferkstart = gd.kstart; bufferkstarth = gd.kstart;
+            for (int k=gd.kstart; k<gd.kend; ++k)
+            {
+                if (gd.z[k] < zstart) ++bufferkstart;
+                if (gd.zh[k] < zstart) ++bufferkstarth;
+            }
+            if (bufferkstarth == gd.kend) throw std::runtime_error("Buffer is too close to the model top");
+        }
+        // sigma_device = caller-owned [2*kcells] device buffer for the two sponge tables; the fixed profiles go into bufferprofs_g
+        template<class Upload> void prepare_device(TF* sigma_device, Upload upload)
+        {
+            if (!swbuffer) return;
+            auto& gd = grid.get_grid_data();
+            std::vector<TF> sg(2*gd.kcells);
+            mhh_grid gh = grid.abi(true);
+            mhh_check(mhh_buffer_sigma_host(&gh, zstart, sigma, beta, 0, sg.data()));
+            mhh_check(mhh_buffer_sigma_host(&gh, zstart, sigma, beta, 1, sg.data() + gd.kcells));
+            upload(sigma_device, sg.data(), sg.size()*sizeof(TF));
+            sigma_g = sigma_device; sigmah_g = sigma_device + gd.kcells;
+        }
+        void clear_device() { sigma_g = sigmah_g = nullptr; }
+        mhh_buffer_params params() const
+        {
+            mhh_buffer_params b{};
+            if (!swbuffer) return b;
+            b.swbuffer = 1; b.bufferkstart = bufferkstart; b.bufferkstarth = bufferkstarth; b.sigma = sigma_g; b.sigmah = sigmah_g;
+            auto prof = [&](const std::string& nm, const Field3d<TF>& f) -> const void* {
+                if (swupdate) return f.fld_mean_g;
+                auto it = bufferprofs_g.find(nm); return it == bufferprofs_g.end() ? nullptr : it->second; };
+            b.abuf_u = prof("u", *fields.mp.at("u")); b.abuf_v = prof("v", *fields.mp.at("v")); b.abuf_w = prof("w", *fields.mp.at("w"));
+            int n = 0;
+            for (auto& it : fields.sp) b.abuf_s[n++] = prof(it.first, *it.second);
+            return b;
+        }
+        void exec(Stats&, void* stream = nullptr)
+        {
+            if (!swbuffer) return;
+            mhh_grid g = grid.abi(); mhh_fields f = abi_fields(fields); mhh_buffer_params b = params();
+            mhh_check(mhh_buffer_exec(&g, &f, &b, stream));
+        }
+        std::map<std::string, TF*> bufferprofs_g;
+        int get_bufferkstart() const { return bufferkstart; }
+        int get_bufferkstarth() const { return bufferkstarth; }
+    private:
+        Grid<TF>& grid; Fields<TF>& fields; TF zstart, sigma, beta; int bufferkstart, bufferkstarth; bool swbuffer, swupdate; TF* sigma_g; TF* sigmah_g;
+};
+
+// ---- Force (include/force.h:52-140; src/force.cxx) ------------------------------------------------------------------------------
+enum class Large_scale_pressure_type {Disabled, Fixed_flux, Geo_wind, Pressure_gradient};
+enum class Large_scale_subsidence_type {Disabled, Mean_field, Local_field};
+template<typename TF>
+class Force
+{
+    public:
+        Force(Grid<TF>& gridin, Fields<TF>& fieldsin) : swlspres(Large_scale_pressure_type::Disabled), swwls(Large_scale_subsidence_type::Disabled),
+            grid(gridin), fields(fieldsin), field3d_operators(gridin, fieldsin) {}
+        Large_scale_pressure_type swlspres; Large_scale_subsidence_type swwls; bool swls = false, swnudge = false, swwls_mom = false;
+        int swspatialorder = 2;                      // grid.get_spatial_order()
+        TF uflux = 0, dpdx = 0, fc = 0, utrans = 0, vtrans = 0;
+        TF* ug_g = nullptr; TF* vg_g = nullptr; TF* wls_g = nullptr; TF* nudge_factor_g = nullptr;
+        std::vector<std::string> lslist, nudgelist, scalednudgelist;
+        std::map<std::string, TF*> lsprofs_g, nudgeprofs_g;
+        Large_scale_pressure_type get_switch_lspres() { return swlspres; }
+        // device scratch for the two volume sums of the fixed flux: scratch_elems(2) + 2 doubles
+        unsigned long long scratch_elems() const { return field3d_operators.scratch_elems(2) + 2; }
+        void set_reduce_workspace(double* device_scratch) { work = device_scratch; field3d_operators.set_scratch(device_scratch + 2); }
+        mhh_force_params params(double dt) const
+        {
+            if (swnudge && !scalednudgelist.empty()) throw std::runtime_error("scalednudgelist: rescale the host profile before the upload");
+            mhh_force_params p{};
+            auto put = [&](const std::string& nm, const void* prof, const void*& u, const void*& v, const void** s) {
+                if (nm == "u") u = prof; else if (nm == "v") v = prof;
+                else { const int n = scalar_index(fields, nm); if (n < 0) throw std::runtime_error("force: \"" + nm + "\" is not u, v or a prognostic scalar"); s[n] = prof; } };
+            if (swlspres == Large_scale_pressure_type::Fixed_flux) { p.swlspres = MHH_LSPRES_UFLUX; p.uflux = uflux; p.dt = dt; p.utrans = utrans; p.uflux_sums = work; }
+            else if (swlspres == Large_scale_pressure_type::Pressure_gradient) { p.swlspres = MHH_LSPRES_DPDX; p.dpdx = dpdx; }
+            else if (swlspres == Large_scale_pressure_type::Geo_wind)
+            { p.swlspres = MHH_LSPRES_GEO; p.order = swspatialorder; p.fc = fc; p.utrans = utrans; p.vtrans = vtrans; p.ug = ug_g; p.vg = vg_g; }
+            if (swls) { p.swls = 1; for (auto& nm : lslist) put(nm, lsprofs_g.at(nm), p.ls_u, p.ls_v, p.ls_s); }
+            if (swwls != Large_scale_subsidence_type::Disabled)
+            { p.swwls = (swwls == Large_scale_subsidence_type::Mean_field) ? MHH_WLS_MEAN : MHH_WLS_LOCAL; p.swwls_mom = swwls_mom; p.wls = wls_g; }
+            p.mean_u = fields.mp.at("u")->fld_mean_g; p.mean_v = fields.mp.at("v")->fld_mean_g;
+            int n = 0;
+            for (auto& it : fields.sp) p.mean_s[n++] = it.second->fld_mean_g;
+            if (swnudge) { p.swnudge = 1; p.nudge_factor = nudge_factor_g; for (auto& nm : nudgelist) put(nm, nudgeprofs_g.at(nm), p.nudge_u, p.nudge_v, p.nudge_s); }
+            return p;
+        }
+        // the two volume sums of the fixed flux, left on the device for the pass
+        void calc_fixed_flux_sums(void* stream)
+        {
+            if (swlspres != Large_scale_pressure_type::Fixed_flux) return;
+            if (!work) throw std::runtime_error("Force::exec before set_reduce_workspace");
+            const TF* uu[2] = {fields.mp.at("u")->fld_g, fields.mt.at("u")->fld_g};
+            field3d_operators.calc_sums_g(work, uu, 2, stream);
+        }
+        void exec(double dt, Thermo<TF>&, Stats&, void* stream = nullptr)
+        {
+            calc_fixed_flux_sums(stream);
+            mhh_grid g = grid.abi(); mhh_fields f = abi_fields(fields); mhh_force_params p = params(dt);
+            mhh_check(mhh_force_exec(&g, &f, &p, stream));
+        }
+        // buffer->exec and force->exec (src/model.cxx:395,404) as one pass over the tendencies: the same bits
+        void exec_with_buffer(Buffer<TF>& buffer, double dt, Thermo<TF>&, Stats&, void* stream = nullptr)
+        {
+            calc_fixed_flux_sums(stream);
+            mhh_grid g = grid.abi(); mhh_fields f = abi_fields(fields); mhh_force_params p = params(dt); mhh_buffer_params b = buffer.params();
+            mhh_check(mhh_buffer_force_exec(&g, &f, &b, &p, stream));
+        }
+    private:
+        Grid<TF>& grid; Fields<TF>& fields; Field3d_operators<TF> field3d_operators; double* work = nullptr;
 };
 
 } // namespace mhh_host

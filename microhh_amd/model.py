@@ -4,6 +4,7 @@ that this package accelerates, expressed as calls into the C ABI.
     boundary->set_prognostic_cyclic_bcs   -> mhh_boundary_cyclic_n (+ N-S neighbour exchange)   (src/model.cxx:346)
     diff->exec_viscosity(thermo)          -> mhh_diff_exec_viscosity (+ N-S exchange of evisc)   (:354)
     advec->exec ; diff->exec              -> mhh_rhs_exec (fused, same bits)                     (:388, :392)
+    fields->exec ; buffer->exec ; force->exec -> mhh_field_mean_*, mhh_buffer_force_exec (forcing=..., opt-in) (:351, :395, :404)
     pres->exec(dt)                        -> mhh_pres_exec, or its slab form around 2 all-to-alls (:411)
 
 One process per GPU. With ``npy`` > 1 the grid is slab-decomposed in y (npx = 1): halos travel as ring
@@ -69,7 +70,7 @@ class HotPath:
 
     def __init__(self, case, itot, jtot, ktot, dtype=np.float64, device="cuda:0", seed=666, dt=1.0,
                  lib=None, npy=1, rank=0, group=None, global_init=None, force_slab=False, slim_halos=True, overlap=None, pres_chunks=None, igc=None,
-                 nscalars=None):
+                 nscalars=None, forcing=None):
         import torch
         self.torch = torch
         self.lib = lib if lib is not None else capi.lib()
@@ -209,6 +210,8 @@ class HotPath:
             p.evisc_ghost_rows = 1
             for k in ("dudz", "dvdz", "dbdz", "z0m"):
                 self._halo2d(self.surf[k])
+        # Buffer and Force (forcing.Forcing): their tables, the mean profiles and the reduction scratch, made once
+        self.forcing = forcing.bind(self) if forcing is not None else None
         self.cyclic_prognostic()
         self.sync()
 
@@ -458,14 +461,26 @@ class HotPath:
         with self._timed("transpose", self.master.mode == "direct"):
             self.master.all_to_all(xsend, xrecv)
 
+    def forcing_means(self):
+        """fields->exec() (src/model.cxx:351): the horizontal means the forcing switches read, summed over the slab ranks."""
+        self.forcing.means()
+
+    def buffer_force(self):
+        """buffer->exec and force->exec (src/model.cxx:395,404) in one pass over the tendencies."""
+        self.forcing.exec()
+
     def step(self):
-        """One full RHS + pressure evaluation (the BASELINE metric's unit of work)."""
+        """One full RHS + pressure evaluation (the BASELINE metric's unit of work); with `forcing`, the means it reads and the
+        fused Buffer + Force pass between the RHS and the pressure solve."""
         if self.can_overlap:
             self.halo_visc_rhs()
         else:
             self.cyclic_prognostic()
             self.exec_viscosity()
             self.rhs()
+        if self.forcing is not None:
+            self.forcing_means()
+            self.buffer_force()
         self.pres()
 
     def capture_step(self):
