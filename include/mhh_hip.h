@@ -99,7 +99,8 @@ typedef struct mhh_fields
     const void* rhoref;              /* [kcells] */
     const void* rhorefh;             /* [kcells] */
     double visc;                     /* Fields::visc                                       */
-    /* surface model inputs (Boundary_surface outputs; NULL => resolved walls, "default") */
+    /* surface model inputs (Boundary_surface outputs; NULL => resolved walls, "default"). const is the operators' view of
+     * them: mhh_boundary_surface_exec and the mhh_surface_* stages WRITE the bottom fluxes and dudz, dvdz, dbdz. */
     const void* u_fluxbot; const void* u_fluxtop;
     const void* v_fluxbot; const void* v_fluxtop;
     const void* s_fluxbot[MHH_MAX_SCALARS]; const void* s_fluxtop[MHH_MAX_SCALARS];
@@ -498,11 +499,72 @@ int mhh_buffer_force_exec(const mhh_grid* g, const mhh_fields* f, const mhh_buff
 
 /* ---- Vertical ghost cells --------------------------------------------------------------
  * Boundary::set_ghost_cells: calc_ghost_cells_{bot,top}_{2nd,4th} (src/boundary.cxx:686-836); bc 0 = Dirichlet
- * (abot/atop), 1 = Neumann or flux (agradbot/agradtop); 2-D arrays are [ijcells]. set_ghost_cells_w (4th order
+ * (abot/atop), 1 = Neumann or flux (agradbot/agradtop), -1 = that side is left alone (what the reference's kernels do for
+ * Ustar_type, which matches neither of their branches); 2-D arrays are [ijcells]. set_ghost_cells_w (4th order
  * only): type 0 = Normal (:874-907), 1 = Conservation (:838-871).                                              */
 int mhh_boundary_ghost_cells(const mhh_grid* g, int order, void* a, int bcbot, int bctop,
                              const void* abot, const void* agradbot, const void* atop, const void* agradtop, void* stream);
 int mhh_boundary_ghost_cells_w(const mhh_grid* g, void* w, int type, void* stream);
+
+/* ---- Boundary_surface: the Monin-Obukhov surface layer (src/boundary_surface.cxx:830-983) ---------------------------
+ * The device form of Boundary_surface<TF>::exec with the lookup solver (swconstantz0 = true, the default):
+ *   mbcbot Dirichlet (noslip), thermo bc Flux      : stability case 2 (:94-112)
+ *   mbcbot Dirichlet (noslip), thermo bc Dirichlet : stability case 3 (:113-133)
+ *   mbcbot Ustar,              thermo bc Flux      : stability case 1 (:83-92), surfm's Ustar branch (:222-252)
+ *   thermo_kind 0 (switch "0"), either mbcbot      : stability_neutral (:137-177)
+ * Refused with MHH_EINVAL and a text that names the reason: swconstantz0 = 0 (the iterative solvers of
+ * include/boundary_surface_kernels.h:287-470), swcharnock, and a grid with igc < 2 or jgc < 2 (calc_dutot reads u[i+2], v[j+2]).
+ * It WRITES the 2-D arrays of mhh_fields that the operators read: u_fluxbot, v_fluxbot, s_fluxbot[n] (Dirichlet scalars), dudz,
+ * dvdz, dbdz. Their `const` in mhh_fields is the operators' view; the surface layer is their producer. zsl = g->z[kstart].
+ * 2-D arrays are [ijcells] of the grid's dtype unless stated. Every call only enqueues on `stream`.                          */
+#define MHH_BC_DIRICHLET 0   /* Boundary_type::Dirichlet_type: the surface value is given (mbcbot = noslip)                  */
+#define MHH_BC_NEUMANN   1   /* Neumann_type: surfs leaves such a scalar alone                                               */
+#define MHH_BC_FLUX      2   /* Flux_type: the surface flux is given                                                         */
+#define MHH_BC_USTAR     3   /* Ustar_type (momentum only): the friction velocity is given                                   */
+#define MHH_THERMO_NONE  0
+#define MHH_THERMO_DRY   1   /* Thermo_dry: calc_buoyancy_bot / calc_buoyancy_fluxbot / get_db_ref (src/thermo_dry.cxx:133-162,629-633) */
+#define MHH_THERMO_BUOY  2   /* Thermo_buoy: plain copies, db_ref = bg_n2 (src/thermo_buoy.cxx:425-448, include/thermo_buoy.h:66)      */
+#define MHH_SURFACE_NZL  10000   /* nzL_lut (include/boundary.h:55) */
+typedef struct mhh_surface_params
+{
+    int mbcbot;                              /* MHH_BC_DIRICHLET | MHH_BC_USTAR                                             */
+    int thermobc;                            /* boundary type of the thermo scalar: == sbcbot[thermo_index]                 */
+    int thermo_kind, thermo_index;           /* MHH_THERMO_*; the scalar that is th (dry) or b (buoy)                       */
+    int swconstantz0;                        /* must be 1: the lookup solver                                                */
+    int swcharnock;                          /* must be 0                                                                   */
+    double thref_kstart, threfh_kstart, grav;/* Thermo_dry: bs.thref[kstart], bs.threfh[kstart], Constants::grav            */
+    double bg_n2;                            /* Thermo_buoy: bs.n2, what its get_db_ref returns                             */
+    const void* zL; const void* f;           /* float [MHH_SURFACE_NZL] device tables from mhh_surface_lut_host             */
+    const void* z0m; const void* z0h;
+    void* ustar; void* obuk;                 /* state: init_surface sets obuk = 1e-9 (dsmall), ustar = 1e-2 (:565-570)       */
+    void* nobuk;                             /* int [ijcells]: the table index each column's walk starts from; 0 at first   */
+    const void* ubot; const void* vbot;      /* fld_bot of u, v                                                             */
+    void* ugradbot; void* vgradbot;          /* grad_bot of u, v: input of mhh_boundary_ghost_cells                         */
+    void* sbot[MHH_MAX_SCALARS];             /* fld_bot per scalar: read (Dirichlet) or written (Flux)                      */
+    void* sgradbot[MHH_MAX_SCALARS];         /* grad_bot per scalar                                                         */
+    int   sbcbot[MHH_MAX_SCALARS];           /* sbc.at(name).bcbot                                                          */
+} mhh_surface_params;
+/* prepare_lut (include/boundary_surface_kernels.h:78-133) on the HOST with the host C library, as Boundary_surface::init_solver
+ * runs it (:812-826): zL_out, f_out are HOST float[MHH_SURFACE_NZL] for both dtypes, the temporaries are in the dtype. A pair
+ * (mbcbot, thermobc) without a table (Ustar) leaves f_out zero.                                                            */
+int mhh_surface_lut_host(double zsl, double z0m, double z0h, int mbcbot, int thermobc, int dtype, float* zL_out, float* f_out);
+/* The stages one by one, so that a test can isolate them. None of them fills ghost cells.
+ * dutot: calc_dutot on the interior (include/boundary_surface_kernels.h:136-180), without its exec_2d                      */
+int mhh_surface_dutot(const mhh_grid* g, const mhh_fields* f, const mhh_surface_params* p, void* dutot, void* stream);
+/* stability / stability_neutral (src/boundary_surface.cxx:54-177) over all cells from a filled dutot, with Thermo's
+ * get_buoyancy_surf / get_buoyancy_fluxbot / get_db_ref evaluated inline: writes obuk, ustar, nobuk                        */
+int mhh_surface_stability(const mhh_grid* g, const mhh_fields* f, const mhh_surface_params* p, const void* dutot, void* stream);
+/* surfm (:180-288): u_fluxbot, v_fluxbot on the interior (without their exec_2d), ugradbot, vgradbot on all cells          */
+int mhh_surface_momentum(const mhh_grid* g, const mhh_fields* f, const mhh_surface_params* p, void* stream);
+/* surfs (:291-339) for scalar n, all cells                                                                                 */
+int mhh_surface_scalar(const mhh_grid* g, const mhh_fields* f, const mhh_surface_params* p, int n, void* stream);
+/* calc_duvdz_mo, calc_dbdz_mo (include/boundary_surface_kernels.h:186-243), interior; dbdz unless thermo_kind == 0         */
+int mhh_surface_mo_gradients(const mhh_grid* g, const mhh_fields* f, const mhh_surface_params* p, void* stream);
+/* Boundary_surface<TF>::exec (:830-983): three kernels and three 2-D cyclic fills (dutot, u_fluxbot, v_fluxbot); the bits of
+ * dutot, fill, stability, momentum, scalar (each n), mo_gradients, fill, fill. `scratch` = [ijcells] of the dtype: dutot.
+ * One rank only: on a slab (npy > 1) the north-south rows of dutot, u_fluxbot and v_fluxbot are the caller's exchange between
+ * the stages, so the fused call returns MHH_EINVAL there and the driver calls the stages.                                  */
+int mhh_boundary_surface_exec(const mhh_grid* g, const mhh_fields* f, const mhh_surface_params* p, void* scratch, void* stream);
 
 /* ---- Timeloop RK3/RK4 substep (src/timeloop.cxx:250-334, src/timeloop.cu:35-122) -------- */
 int mhh_rk_substep(const mhh_grid* g, int rkorder, int substep, double dt, void* a, void* at, void* stream);

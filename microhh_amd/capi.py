@@ -48,7 +48,16 @@ class MhhForceParams(C.Structure):
                 ("swnudge", ci), ("nudge_factor", vp), ("nudge_u", vp), ("nudge_v", vp), ("nudge_s", vp * MAX_SCALARS)]
 
 
+class MhhSurfaceParams(C.Structure):
+    _fields_ = [("mbcbot", ci), ("thermobc", ci), ("thermo_kind", ci), ("thermo_index", ci), ("swconstantz0", ci), ("swcharnock", ci),
+                ("thref_kstart", cd), ("threfh_kstart", cd), ("grav", cd), ("bg_n2", cd),
+                ("zL", vp), ("f", vp), ("z0m", vp), ("z0h", vp), ("ustar", vp), ("obuk", vp), ("nobuk", vp),
+                ("ubot", vp), ("vbot", vp), ("ugradbot", vp), ("vgradbot", vp),
+                ("sbot", vp * MAX_SCALARS), ("sgradbot", vp * MAX_SCALARS), ("sbcbot", ci * MAX_SCALARS)]
+
+
 FP = C.POINTER(MhhFields)
+SP = C.POINTER(MhhSurfaceParams)
 DP = C.POINTER(MhhDiffParams)
 BP = C.POINTER(MhhBufferParams)
 FRP = C.POINTER(MhhForceParams)
@@ -155,6 +164,13 @@ SIGNATURES = {
     "mhh_buffer_exec": (ci, [GP, FP, BP, vp]),
     "mhh_force_exec": (ci, [GP, FP, FRP, vp]),
     "mhh_buffer_force_exec": (ci, [GP, FP, BP, FRP, vp]),
+    "mhh_surface_lut_host": (ci, [cd, cd, cd, ci, ci, ci, vp, vp]),
+    "mhh_surface_dutot": (ci, [GP, FP, SP, vp, vp]),
+    "mhh_surface_stability": (ci, [GP, FP, SP, vp, vp]),
+    "mhh_surface_momentum": (ci, [GP, FP, SP, vp]),
+    "mhh_surface_scalar": (ci, [GP, FP, SP, ci, vp]),
+    "mhh_surface_mo_gradients": (ci, [GP, FP, SP, vp]),
+    "mhh_boundary_surface_exec": (ci, [GP, FP, SP, vp, vp]),
 }
 
 

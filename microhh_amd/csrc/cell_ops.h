@@ -915,4 +915,140 @@ template<class TF> MHH_HD TF wls_local_w_sub(const TF* __restrict__ w, int c, in
 // calc_nudging_tendency (src/force.cxx:183): formed once per level, then added
 template<class TF> MHH_HD TF nudge_tend(TF factor_k, TF mean_k, TF ref_k) { return -factor_k * (mean_k - ref_k); }
 
+// =======================================================================================================
+// Boundary_surface: the Monin-Obukhov surface layer (include/monin_obukhov.h:42-150, include/boundary_surface_kernels.h:136-284,
+// src/boundary_surface.cxx:54-339). pow, log and exp are CALLS of the math library (the reference's std::pow(x, TF(0.5)) is
+// not a square root), every product and quotient keeps the reference's association.
+// =======================================================================================================
+constexpr int SURF_NZL = 10000;                                     // nzL_lut (include/boundary.h:55)
+template<class TF> MHH_HD TF most_kappa() { return TF(0.4); }       // Constants::kappa<TF>
+// gradient functions: Wilson (2001) on the unstable side, the IFS forms on the stable side (monin_obukhov.h:42-86)
+template<class TF> MHH_HD TF most_phim_unstable(TF zeta) { return std::pow(TF(1.) + TF(3.6)*std::pow(tabs(zeta), TF(2./3.)), TF(-1./2.)); }
+template<class TF> MHH_HD TF most_phih_unstable(TF zeta) { return std::pow(TF(1.) + TF(7.9)*std::pow(tabs(zeta), TF(2./3.)), TF(-1./2.)); }
+template<class TF> MHH_HD TF most_phim(TF zeta) { return (zeta <= TF(0.)) ? most_phim_unstable(zeta) : TF(1) + TF(5)*zeta; }
+template<class TF> MHH_HD TF most_phih(TF zeta) { return (zeta <= TF(0.)) ? most_phih_unstable(zeta) : sq(TF(1) + TF(4)*zeta); }
+// integrated functions (monin_obukhov.h:91-134); a = 1, b = 2/3 (a TF quotient), c = 5, d = 0.35
+template<class TF> MHH_HD TF most_psim_unstable(TF zeta) { return TF(3.)*std::log( ( TF(1.) + TF(1.)/most_phim_unstable(zeta) ) / TF(2.)); }
+template<class TF> MHH_HD TF most_psih_unstable(TF zeta) { return TF(3.) * std::log( ( TF(1.) + TF(1.) / most_phih_unstable(zeta) ) / TF(2.)); }
+template<class TF> MHH_HD TF most_psim_stable(TF zeta)
+{
+    const TF a = TF(1), b = TF(2)/TF(3), c = TF(5), d = TF(0.35);
+    return -b * (zeta - (c/d)) * std::exp(-d * zeta) - a*zeta - (b*c)/d;
+}
+template<class TF> MHH_HD TF most_psih_stable(TF zeta)
+{
+    const TF a = TF(1), b = TF(2)/TF(3), c = TF(5), d = TF(0.35);
+    return -b * (zeta - (c/d)) * std::exp(-d * zeta) - std::pow(TF(1)+ b*a*zeta, TF(1.5)) -(b*c)/d + TF(1);
+}
+// fm, fh (monin_obukhov.h:136-150)
+template<class TF> MHH_HD TF most_fm(TF zsl, TF z0m, TF L)
+{
+    return (L <= TF(0.))
+        ? most_kappa<TF>() / (std::log(zsl/z0m) - most_psim_unstable(zsl/L) + most_psim_unstable(z0m/L))
+        : most_kappa<TF>() / (std::log(zsl/z0m) - most_psim_stable  (zsl/L) + most_psim_stable  (z0m/L));
+}
+template<class TF> MHH_HD TF most_fh(TF zsl, TF z0h, TF L)
+{
+    return (L <= TF(0.))
+        ? most_kappa<TF>() / (std::log(zsl/z0h) - most_psih_unstable(zsl/L) + most_psih_unstable(z0h/L))
+        : most_kappa<TF>() / (std::log(zsl/z0h) - most_psih_stable  (zsl/L) + most_psih_stable  (z0h/L));
+}
+
+// calc_dutot (boundary_surface_kernels.h:164-179): the filtered wind at the scalar point against the surface values,
+// floored at 0.1; c = the cell at kstart, ij its column. Reads u[i-1..i+2], v[j-1..j+2]: igc >= 2 and jgc >= 2.
+template<class TF> MHH_HD TF surf_dutot(const TF* __restrict__ u, const TF* __restrict__ v, const TF* __restrict__ ubot, const TF* __restrict__ vbot,
+                                        int c, int ij, int jj)
+{
+    const int ii = 1, ii2 = 2, jj2 = 2*jj;
+    const TF minval = 1.e-1;
+    const TF u_filtered = TF(1./9) *
+        ( TF(0.5)*u[c-ii-jj] + u[c-jj] + u[c+ii-jj] + TF(0.5)*u[c+ii2-jj]
+        + TF(0.5)*u[c-ii   ] + u[c   ] + u[c+ii   ] + TF(0.5)*u[c+ii2   ]
+        + TF(0.5)*u[c-ii+jj] + u[c+jj] + u[c+ii+jj] + TF(0.5)*u[c+ii2+jj] );
+    const TF v_filtered = TF(1./9) *
+        ( TF(0.5)*v[c-ii-jj] + v[c-ii] + v[c-ii+jj] + TF(0.5)*v[c-ii+jj2]
+        + TF(0.5)*v[c   -jj] + v[c   ] + v[c   +jj] + TF(0.5)*v[c   +jj2]
+        + TF(0.5)*v[c+ii-jj] + v[c+ii] + v[c+ii+jj] + TF(0.5)*v[c+ii+jj2] );
+    const TF du2 = sq(u_filtered - TF(0.5)*(ubot[ij] + ubot[ij+ii]))
+                 + sq(v_filtered - TF(0.5)*(vbot[ij] + vbot[ij+jj]));
+    return tmax(std::pow(du2, TF(0.5)), minval);
+}
+
+// find_zL (boundary_surface_kernels.h:246-260): walk the table from the cell's stored index n, every test in float. The
+// downward loop tests n > 0 BEFORE it reads f[n-1] (the reference reads f[-1] at n == 0 and then stops on `n > 0`: the same
+// n wherever its result is defined). The interpolation runs in float and is widened to TF on return.
+template<class TF> MHH_HD TF surf_find_zL(const float* __restrict__ zL, const float* __restrict__ f, int& n, const float Ri)
+{
+    if ( (f[n]-Ri) > 0.f )
+        while ( n > 0 && (f[n-1]-Ri) > 0.f ) { --n; }
+    else
+        while ( (f[n]-Ri) < 0.f && n < (SURF_NZL-1) ) { ++n; }
+    const TF zL0 = (n == 0 || n == SURF_NZL-1) ? zL[n] : zL[n-1] + (Ri-f[n-1]) / (f[n]-f[n-1]) * (zL[n]-zL[n-1]);
+    return zL0;
+}
+// calc_obuk_noslip_flux_lookup / _dirichlet_lookup (:262-284): Ri formed in TF, narrowed to float
+template<class TF> MHH_HD TF surf_obuk_flux(const float* __restrict__ zL, const float* __restrict__ f, int& n, TF du, TF bfluxbot, TF zsl)
+{
+    const float Ri = -most_kappa<TF>() * bfluxbot * zsl / (du*du*du);
+    return zsl/surf_find_zL<TF>(zL, f, n, Ri);
+}
+template<class TF> MHH_HD TF surf_obuk_dirichlet(const float* __restrict__ zL, const float* __restrict__ f, int& n, TF du, TF db, TF zsl)
+{
+    const float Ri = most_kappa<TF>() * db * zsl / sq(du);
+    const TF zL0 = surf_find_zL<TF>(zL, f, n, Ri);
+    return zsl/zL0;
+}
+// Thermo_dry's hooks at the surface (src/thermo_dry.cxx:133-162,629-633)
+template<class TF> MHH_HD TF dry_bfluxbot(TF grav, TF threfh_ks, TF thfluxbot) { return grav/threfh_ks*thfluxbot; }
+template<class TF> MHH_HD TF dry_db(TF grav, TF thref_ks, TF threfh_ks, TF th, TF thbot)
+{
+    const TF bbot = grav/threfh_ks * (thbot - threfh_ks);
+    const TF b    = grav/thref_ks  * (th    - thref_ks );
+    const TF db_ref = grav/thref_ks*(thref_ks - threfh_ks);
+    return b - bbot + db_ref;
+}
+// stability case 1 (src/boundary_surface.cxx:90): fixed ustar and fixed buoyancy flux
+template<class TF> MHH_HD TF surf_obuk_ustar_flux(TF ustar, TF bfluxbot) { return -(ustar*ustar*ustar) / (most_kappa<TF>()*bfluxbot); }
+// surfm, Dirichlet branch (:211-214): the flux from the stability function averaged over the two neighbouring columns;
+// ijm = ij-1 for u, ij-jj for v
+template<class TF> MHH_HD TF surf_mom_flux(TF a, TF abot, const TF* __restrict__ ustar, const TF* __restrict__ obuk, const TF* __restrict__ z0m,
+                                           int ij, int ijm, TF zsl)
+{
+    return -(a-abot)*TF(0.5)*
+        (ustar[ijm]*most_fm(zsl, z0m[ijm], obuk[ijm]) + ustar[ij]*most_fm(zsl, z0m[ij], obuk[ij]));
+}
+// surfm, Ustar branch (:234-248): ustar redistributed over the two flux components
+template<class TF> MHH_HD void surf_mom_flux_ustar(TF& ufluxbot, TF& vfluxbot, const TF* __restrict__ u, const TF* __restrict__ v,
+                                                   const TF* __restrict__ ubot, const TF* __restrict__ vbot, const TF* __restrict__ ustar,
+                                                   int c, int ij, int jj)
+{
+    const int ii = 1;
+    const TF minval = 1.e-2;
+    const TF vonu2 = tmax(minval, TF(0.25)*(
+                sq(v[c-ii]-vbot[ij-ii]) + sq(v[c-ii+jj]-vbot[ij-ii+jj])
+              + sq(v[c   ]-vbot[ij   ]) + sq(v[c   +jj]-vbot[ij   +jj])) );
+    const TF uonv2 = tmax(minval, TF(0.25)*(
+                sq(u[c-jj]-ubot[ij-jj]) + sq(u[c+ii-jj]-ubot[ij+ii-jj])
+              + sq(u[c   ]-ubot[ij   ]) + sq(u[c+ii   ]-ubot[ij+ii   ])) );
+    const TF u2 = tmax(minval, sq(u[c]-ubot[ij]) );
+    const TF v2 = tmax(minval, sq(v[c]-vbot[ij]) );
+    const TF um = ustar[ij-ii], vm = ustar[ij-jj], us = ustar[ij];
+    const TF ustaronu4 = TF(0.5)*(um*um*um*um + us*us*us*us);
+    const TF ustaronv4 = TF(0.5)*(vm*vm*vm*vm + us*us*us*us);
+    ufluxbot = -std::copysign(TF(1), u[c]-ubot[ij]) * std::pow(ustaronu4 / (TF(1) + vonu2 / u2), TF(0.5));
+    vfluxbot = -std::copysign(TF(1), v[c]-vbot[ij]) * std::pow(ustaronv4 / (TF(1) + uonv2 / v2), TF(0.5));
+}
+// surfs (:316-336): the linearly interpolated gradient goes to the ghost cells, not the Monin-Obukhov one
+template<class TF> MHH_HD TF surf_scalar_flux(TF var, TF varbot, TF ustar, TF obuk, TF z0h, TF zsl) { return -(var-varbot)*ustar*most_fh(zsl, z0h, obuk); }
+template<class TF> MHH_HD TF surf_scalar_bot(TF var, TF varfluxbot, TF ustar, TF obuk, TF z0h, TF zsl) { return varfluxbot / (ustar*most_fh(zsl, z0h, obuk)) + var; }
+template<class TF> MHH_HD TF surf_lin_grad(TF var, TF varbot, TF zsl) { return (var-varbot)/zsl; }
+// calc_duvdz_mo (boundary_surface_kernels.h:214-221): d = du_c or dv_c, the velocity difference at the scalar point
+template<class TF> MHH_HD TF surf_duvdz_mo(TF d, TF ustar, TF obuk, TF z0m, TF zsl)
+{
+    const TF fluxbot = -d * ustar * most_fm(zsl, z0m, obuk);
+    return -fluxbot / (most_kappa<TF>() * zsl * ustar) * most_phim(zsl/obuk);
+}
+// calc_dbdz_mo (:241)
+template<class TF> MHH_HD TF surf_dbdz_mo(TF bfluxbot, TF ustar, TF obuk, TF zsl) { return -bfluxbot / (most_kappa<TF>() * zsl * ustar) * most_phih(zsl/obuk); }
+
 } // namespace mhh

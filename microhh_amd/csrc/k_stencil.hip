@@ -744,7 +744,7 @@ MHH_API int mhh_rk_substep(const mhh_grid* g, int rkorder, int substep, double d
 
 // =======================================================================================================
 // Vertical ghost cells: Boundary::set_ghost_cells / set_ghost_cells_w
-// (src/boundary.cxx:686-907, 919-1007; GPU src/boundary.cu:119-300). bc: 0 Dirichlet, 1 Neumann / flux.
+// (src/boundary.cxx:686-907, 919-1007; GPU src/boundary.cu:119-300). bc: 0 Dirichlet, 1 Neumann / flux, -1 neither (Ustar_type).
 // =======================================================================================================
 template<class TF>
 struct GhostOp
@@ -758,20 +758,20 @@ struct GhostOp
         const int ij = i + j*jj, b = ij + ks*kk, t = ij + (ke-1)*kk;
         if (order == 2)
         {
-            if (bcbot == 0) a[b-kk] = TF(2.)*abot[ij] - a[b]; else a[b-kk] = -agradbot[ij]*dzh[ks] + a[b];
-            if (bctop == 0) a[t+kk] = TF(2.)*atop[ij] - a[t]; else a[t+kk] = agradtop[ij]*dzh[ke] + a[t];
+            if (bcbot == 0) a[b-kk] = TF(2.)*abot[ij] - a[b]; else if (bcbot == 1) a[b-kk] = -agradbot[ij]*dzh[ks] + a[b];
+            if (bctop == 0) a[t+kk] = TF(2.)*atop[ij] - a[t]; else if (bctop == 1) a[t+kk] = agradtop[ij]*dzh[ke] + a[t];
         }
         else
         {
             const TF cg0 = TF(1./24.), cg1 = TF(-27./24.);
             if (bcbot == 0) { a[b-kk] = TF(8./3.)*abot[ij] - TF(2.)*a[b] + TF(1./3.)*a[b+kk]; a[b-2*kk] = TF(8.)*abot[ij] - TF(9.)*a[b] + TF(2.)*a[b+kk]; }
-            else
+            else if (bcbot == 1)
             {
                 const TF gr = ( - cg0*(g.z[ks+1]-g.z[ks-2]) - cg1*(g.z[ks]-g.z[ks-1]) );
                 a[b-kk] = TF(-1.)*gr*agradbot[ij] + a[b]; a[b-2*kk] = TF(-3.)*gr*agradbot[ij] + a[b+kk];
             }
             if (bctop == 0) { a[t+kk] = TF(8./3.)*atop[ij] - TF(2.)*a[t] + TF(1./3.)*a[t-kk]; a[t+2*kk] = TF(8.)*atop[ij] - TF(9.)*a[t] + TF(2.)*a[t-kk]; }
-            else
+            else if (bctop == 1)
             {
                 const TF gr = ( - cg0*(g.z[ke+1]-g.z[ke-2]) - cg1*(g.z[ke]-g.z[ke-1]) );
                 a[t+kk] = TF(1.)*gr*agradtop[ij] + a[t]; a[t+2*kk] = TF(3.)*gr*agradtop[ij] + a[t-kk];
@@ -784,8 +784,8 @@ MHH_API int mhh_boundary_ghost_cells(const mhh_grid* g, int order, void* a, int 
 {
     if (int e = check_grid(g)) return e;
     MHH_REQUIRE(order == 2 || order == 4, "order");
-    MHH_REQUIRE(a && (bcbot == 0 ? abot : agradbot) && (bctop == 0 ? atop : agradtop), "null field");
-    MHH_REQUIRE((bcbot == 0 || bcbot == 1) && (bctop == 0 || bctop == 1), "bc type: 0 Dirichlet, 1 Neumann");
+    MHH_REQUIRE(a && (bcbot == 0 ? abot != nullptr : bcbot != 1 || agradbot) && (bctop == 0 ? atop != nullptr : bctop != 1 || agradtop), "null field");
+    MHH_REQUIRE(bcbot >= -1 && bcbot <= 1 && bctop >= -1 && bctop <= 1, "bc type: 0 Dirichlet, 1 Neumann, -1 leave this side alone");
     MHH_REQUIRE(g->kgc >= (order == 2 ? 1 : 2) && g->dzh, "ghost levels");
 #define CALL(TF) [&]{ GhostOp<TF> op{make_grid<TF>(g), order, bcbot, bctop, mp<TF>(a), cp<TF>(abot), cp<TF>(agradbot), cp<TF>(atop), cp<TF>(agradtop), cp<TF>(g->dzh)}; \
                       return launch_cells(as_stream(stream), op, 0, g->icells, 0, g->jcells, 0, 1, g->icells, g->ijcells); }()
@@ -817,3 +817,8 @@ MHH_API int mhh_boundary_ghost_cells_w(const mhh_grid* g, void* w, int type, voi
 // Field3d_operators means, Buffer::exec, Force::exec and their fused pass (src/model.cxx:351,395,404)
 // =======================================================================================================
 #include "force_means.h"
+
+// =======================================================================================================
+// Boundary_surface::exec: the Monin-Obukhov surface layer (src/boundary_surface.cxx:830-983)
+// =======================================================================================================
+#include "surface_layer.h"

@@ -51,6 +51,7 @@ struct Field3d
     TF* fld_mean_g = nullptr;          // [kcells] horizontal mean profile (Field3d::fld_mean_g, include/field3d.h:72)
     TF* flux_bot_g = nullptr; TF* flux_top_g = nullptr;
     TF visc = 0;
+    TF* fld_bot_g = nullptr; TF* grad_bot_g = nullptr;    // [ijcells] surface value and gradient (Field3d::fld_bot_g, grad_bot_g): Boundary_surface
 };
 
 template<typename TF>
@@ -663,6 +664,115 @@ class Force
         }
     private:
         Grid<TF>& grid; Fields<TF>& fields; Field3d_operators<TF> field3d_operators; double* work = nullptr;
+};
+
+// ---- Boundary_surface (include/boundary_surface.h; src/boundary_surface.cxx) -----------------------------------------------------
+// The Monin-Obukhov surface layer with the lookup solver. It IS the Boundary the Diff classes read: dudz_g, dvdz_g, dbdz_g, z0m_g
+// are its outputs. Device arrays are the caller's ([ijcells] each; nobuk int, the tables float[MHH_SURFACE_NZL]); the host
+// fills travel through upload(dst_device, src_host, bytes), the caller's H2D copy, as in Diff::prepare_device.
+template<typename TF>
+class Boundary_surface : public Boundary<TF>
+{
+    public:
+        Boundary_surface(Grid<TF>& gridin, Fields<TF>& fieldsin) : grid(gridin), fields(fieldsin) { this->swboundary = "surface"; }
+        // [boundary]: mbcbot (noslip = MHH_BC_DIRICHLET | ustar = MHH_BC_USTAR), ubot, vbot, ustar, z0m, z0h, sbcbot / sbot per scalar
+        int mbcbot = MHH_BC_DIRICHLET; TF ubot = 0, vbot = 0, ustarin = 0, z0m_hom = TF(0.1), z0h_hom = TF(0.1), utrans = 0, vtrans = 0;
+        bool sw_constant_z0 = true, sw_charnock = false;
+        TF thref_kstart = 300, threfh_kstart = 300;      // bs.thref[kstart], bs.threfh[kstart] of Thermo_dry (host values)
+        std::map<std::string, int> sbcbot; std::map<std::string, TF> sbot;
+        TF* obuk_g = nullptr; TF* ustar_g = nullptr; TF* z0h_g = nullptr; TF* dutot_g = nullptr; int* nobuk_g = nullptr;
+        float* zL_sl_g = nullptr; float* f_sl_g = nullptr;
+        // what the library refuses is refused here, before anything is uploaded
+        void init()
+        {
+            auto& gd = grid.get_grid_data();
+            if (!sw_constant_z0) throw std::runtime_error("Boundary_surface: swconstantz0 = false (the iterative solvers) is not built");
+            if (sw_charnock) throw std::runtime_error("Boundary_surface: swcharnock is not built");
+            if (gd.igc < 2 || gd.jgc < 2) throw std::runtime_error("Boundary_surface: needs igc >= 2 and jgc >= 2 (calc_dutot reads u[i+2], v[j+2])");
+        }
+        // src/boundary_surface.cxx:537-574: obuk = dsmall, ustar = 1e-2, nobuk = 0, uniform z0m / z0h
+        template<class Upload> void init_surface(Upload upload)
+        {
+            const size_t n = grid.get_grid_data().ijcells;
+            fill(upload, obuk_g, n, TF(1.e-9)); fill(upload, ustar_g, n, TF(1e-2));
+            fill(upload, this->z0m_g, n, z0m_hom); fill(upload, z0h_g, n, z0h_hom);
+            std::vector<int> zero(n, 0);
+            upload(nobuk_g, zero.data(), n*sizeof(int));
+        }
+        // :748-779: the surface values of u and v (Dirichlet whatever mbcbot says), set_bc of every scalar, set_ustar, init_solver
+        template<class Upload> void set_values(Thermo<TF>& thermo, Upload upload)
+        {
+            const size_t n = grid.get_grid_data().ijcells;
+            fill(upload, fields.mp.at("u")->fld_bot_g, n, ubot - utrans); fill(upload, fields.mp.at("v")->fld_bot_g, n, vbot - vtrans);
+            for (auto& it : fields.sp)
+            {
+                const int bc = sbcbot.at(it.first); const TF val = sbot.at(it.first);
+                if (bc == MHH_BC_DIRICHLET) fill(upload, it.second->fld_bot_g, n, val);
+                else if (bc == MHH_BC_NEUMANN) fill(upload, it.second->grad_bot_g, n, val);
+                else if (bc == MHH_BC_FLUX) fill(upload, it.second->flux_bot_g, n, val);
+            }
+            if (mbcbot == MHH_BC_USTAR) set_ustar(upload);
+            init_solver(thermo, upload);
+        }
+        // :781-809: ustar limited at 1e-4
+        template<class Upload> void set_ustar(Upload upload) { fill(upload, ustar_g, grid.get_grid_data().ijcells, std::max(static_cast<TF>(0.0001), ustarin)); }
+        // :812-826: the table on the host with the host C library
+        template<class Upload> void init_solver(Thermo<TF>& thermo, Upload upload)
+        {
+            auto& gd = grid.get_grid_data();
+            std::vector<float> zL(MHH_SURFACE_NZL), f(MHH_SURFACE_NZL);
+            mhh_check(mhh_surface_lut_host(gd.z[gd.kstart], z0m_hom, z0h_hom, mbcbot, thermobc(thermo), mhh_dtype<TF>(), zL.data(), f.data()));
+            upload(zL_sl_g, zL.data(), zL.size()*sizeof(float)); upload(f_sl_g, f.data(), f.size()*sizeof(float));
+        }
+        mhh_surface_params params(Thermo<TF>& thermo) const
+        {
+            mhh_surface_params p{};
+            p.mbcbot = mbcbot; p.swconstantz0 = sw_constant_z0; p.swcharnock = sw_charnock;
+            const std::string sw = thermo.get_switch();
+            p.thermo_kind = (sw == "dry") ? MHH_THERMO_DRY : (sw == "buoy") ? MHH_THERMO_BUOY : MHH_THERMO_NONE;
+            if (p.thermo_kind) { p.thermo_index = scalar_index(fields, sw == "dry" ? thermo.th : thermo.b); p.thermobc = thermobc(thermo); }
+            if (p.thermo_kind == MHH_THERMO_DRY) { p.thref_kstart = thref_kstart; p.threfh_kstart = threfh_kstart; }
+            p.grav = thermo.grav; p.bg_n2 = thermo.n2;
+            p.zL = zL_sl_g; p.f = f_sl_g; p.z0m = this->z0m_g; p.z0h = z0h_g; p.ustar = ustar_g; p.obuk = obuk_g; p.nobuk = nobuk_g;
+            p.ubot = fields.mp.at("u")->fld_bot_g; p.vbot = fields.mp.at("v")->fld_bot_g;
+            p.ugradbot = fields.mp.at("u")->grad_bot_g; p.vgradbot = fields.mp.at("v")->grad_bot_g;
+            int n = 0;
+            for (auto& it : fields.sp) { p.sbot[n] = it.second->fld_bot_g; p.sgradbot[n] = it.second->grad_bot_g; p.sbcbot[n] = sbcbot.at(it.first); ++n; }
+            return p;
+        }
+        // :830-983 on one rank: three kernels and three 2-D cyclic fills
+        void exec(Thermo<TF>& thermo, void* stream = nullptr)
+        {
+            mhh_grid g = grid.abi(); mhh_fields f = abi_fields(fields, this); mhh_surface_params p = params(thermo);
+            mhh_check(mhh_boundary_surface_exec(&g, &f, &p, dutot_g, stream));
+        }
+        // the same on a slab: the stages, with halo2d(TF*) -- the caller's east-west wrap and north-south exchange of a 2-D array --
+        // where the reference calls boundary_cyclic.exec_2d. nobuk is per rank and never exchanged.
+        template<class Halo2d> void exec_slab(Thermo<TF>& thermo, Halo2d halo2d, void* stream = nullptr)
+        {
+            mhh_grid g = grid.abi(); mhh_fields f = abi_fields(fields, this); mhh_surface_params p = params(thermo);
+            mhh_check(mhh_surface_dutot(&g, &f, &p, dutot_g, stream));
+            halo2d(dutot_g);
+            mhh_check(mhh_surface_stability(&g, &f, &p, dutot_g, stream));
+            mhh_check(mhh_surface_momentum(&g, &f, &p, stream));
+            halo2d(fields.mp.at("u")->flux_bot_g); halo2d(fields.mp.at("v")->flux_bot_g);
+            for (int n=0; n<f.nscalars; ++n) mhh_check(mhh_surface_scalar(&g, &f, &p, n, stream));
+            mhh_check(mhh_surface_mo_gradients(&g, &f, &p, stream));
+        }
+    private:
+        int thermobc(Thermo<TF>& thermo) const
+        {
+            const std::string sw = thermo.get_switch();
+            if (sw != "dry" && sw != "buoy") return MHH_BC_DIRICHLET;
+            return sbcbot.at(sw == "dry" ? thermo.th : thermo.b);
+        }
+        template<class Upload> static void fill(Upload upload, TF* dst, size_t n, TF v)
+        {
+            if (!dst) throw std::runtime_error("Boundary_surface: a device array is missing");
+            std::vector<TF> h(n, v);
+            upload(dst, h.data(), n*sizeof(TF));
+        }
+        Grid<TF>& grid; Fields<TF>& fields;
 };
 
 } // namespace mhh_host

@@ -3,6 +3,7 @@ that this package accelerates, expressed as calls into the C ABI.
 
     boundary->set_prognostic_cyclic_bcs   -> mhh_boundary_cyclic_n (+ N-S neighbour exchange)   (src/model.cxx:346)
     diff->exec_viscosity(thermo)          -> mhh_diff_exec_viscosity (+ N-S exchange of evisc)   (:354)
+    boundary->exec ; set_ghost_cells      -> mhh_boundary_surface_exec, mhh_boundary_ghost_cells (surface=..., opt-in) (:374-375)
     advec->exec ; diff->exec              -> mhh_rhs_exec (fused, same bits)                     (:388, :392)
     fields->exec ; buffer->exec ; force->exec -> mhh_field_mean_*, mhh_buffer_force_exec (forcing=..., opt-in) (:351, :395, :404)
     pres->exec(dt)                        -> mhh_pres_exec, or its slab form around 2 all-to-alls (:411)
@@ -70,7 +71,7 @@ class HotPath:
 
     def __init__(self, case, itot, jtot, ktot, dtype=np.float64, device="cuda:0", seed=666, dt=1.0,
                  lib=None, npy=1, rank=0, group=None, global_init=None, force_slab=False, slim_halos=True, overlap=None, pres_chunks=None, igc=None,
-                 nscalars=None, forcing=None):
+                 nscalars=None, forcing=None, surface=None):
         import torch
         self.torch = torch
         self.lib = lib if lib is not None else capi.lib()
@@ -148,6 +149,8 @@ class HotPath:
             self.s = [put3(global_init["s%d" % n]) for n in range(nsc)]
             self.st = [put3(global_init["st%d" % n]) for n in range(nsc)]
             self.surf = {k: put2(global_init[k]) for k in SURF}
+        if surface is not None:          # before the mixing-length table below is made from it
+            self.surf["z0m"].fill_(float(surface.z0m))
         # solid walls: w and its tendency vanish at kstart and above kend-1
         self.w[:g.kstart+1] = 0; self.w[g.kend:] = 0
         self.wt[:g.kstart+1] = 0; self.wt[g.kend:] = 0
@@ -205,13 +208,17 @@ class HotPath:
             self.pres_chunks = pres_chunks
             self._ok(self.lib.mhh_pres_slab_set_chunks(self.plan, pres_chunks))
         self._prog = [self.u, self.v, self.w] + self.s
-        self.evisc_local_ghosts = self.slab and self.slim and cfg["diff"] == DIFF_SMAG2 and g.jgc >= 2
+        # (with a surface layer dudz, dvdz, dbdz change every sub-step and are written on the interior only, as in the reference:
+        # evisc is then exchanged like any field instead of being re-evaluated on the ghost rows)
+        self.evisc_local_ghosts = self.slab and self.slim and cfg["diff"] == DIFF_SMAG2 and g.jgc >= 2 and surface is None
         if self.evisc_local_ghosts:
             p.evisc_ghost_rows = 1
             for k in ("dudz", "dvdz", "dbdz", "z0m"):
                 self._halo2d(self.surf[k])
         # Buffer and Force (forcing.Forcing): their tables, the mean profiles and the reduction scratch, made once
         self.forcing = forcing.bind(self) if forcing is not None else None
+        # Boundary_surface (surface.Surface): its state (ustar, obuk, nobuk), the lookup table and one s_fluxbot / sbot / sgradbot per scalar
+        self.surface = surface.bind(self) if surface is not None else None
         self.cyclic_prognostic()
         self.sync()
 
@@ -469,10 +476,23 @@ class HotPath:
         """buffer->exec and force->exec (src/model.cxx:395,404) in one pass over the tendencies."""
         self.forcing.exec()
 
+    def surface_layer(self):
+        """boundary->exec and boundary->set_ghost_cells (src/model.cxx:374-375)."""
+        self.surface.exec()
+        self.surface.ghost_cells()
+
     def step(self):
         """One full RHS + pressure evaluation (the BASELINE metric's unit of work); with `forcing`, the means it reads and the
-        fused Buffer + Force pass between the RHS and the pressure solve."""
-        if self.can_overlap:
+        fused Buffer + Force pass between the RHS and the pressure solve. With `surface`, the order of src/model.cxx:346-392: the
+        cyclic fills, exec_viscosity (which reads the PREVIOUS sub-step's dudz, dvdz, dbdz, as the reference does), the surface
+        layer, the vertical ghost cells, then the RHS -- the plain sequence on a slab too (the overlapped sub-step fuses
+        exec_viscosity with the RHS, and the surface layer sits between them)."""
+        if self.surface is not None:
+            self.cyclic_prognostic()
+            self.exec_viscosity()
+            self.surface_layer()
+            self.rhs()
+        elif self.can_overlap:
             self.halo_visc_rhs()
         else:
             self.cyclic_prognostic()
