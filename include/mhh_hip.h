@@ -524,6 +524,7 @@ int mhh_boundary_ghost_cells_w(const mhh_grid* g, void* w, int type, void* strea
 #define MHH_THERMO_NONE  0
 #define MHH_THERMO_DRY   1   /* Thermo_dry: calc_buoyancy_bot / calc_buoyancy_fluxbot / get_db_ref (src/thermo_dry.cxx:133-162,629-633) */
 #define MHH_THERMO_BUOY  2   /* Thermo_buoy: plain copies, db_ref = bg_n2 (src/thermo_buoy.cxx:425-448, include/thermo_buoy.h:66)      */
+#define MHH_THERMO_MOIST 3   /* Thermo_moist: calc_buoyancy_bot / calc_buoyancy_fluxbot / get_db_ref (src/thermo_moist.cxx:637-693,1713-1717) */
 #define MHH_SURFACE_NZL  10000   /* nzL_lut (include/boundary.h:55) */
 typedef struct mhh_surface_params
 {
@@ -543,6 +544,11 @@ typedef struct mhh_surface_params
     void* sbot[MHH_MAX_SCALARS];             /* fld_bot per scalar: read (Dirichlet) or written (Flux)                      */
     void* sgradbot[MHH_MAX_SCALARS];         /* grad_bot per scalar                                                         */
     int   sbcbot[MHH_MAX_SCALARS];           /* sbc.at(name).bcbot                                                          */
+    /* Thermo_moist (thermo_kind 3): thermo_index is thl, qt_index is qt, which must have thl's kind of bc. thvref, thvrefh are the
+     * DEVICE base-state tables [kcells], read at kstart when the kernels run: the base state moves on the device every sub-step.
+     * Zero-initialised: unused.                                                                                             */
+    int   qt_index;
+    const void* thvref; const void* thvrefh;
 } mhh_surface_params;
 /* prepare_lut (include/boundary_surface_kernels.h:78-133) on the HOST with the host C library, as Boundary_surface::init_solver
  * runs it (:812-826): zL_out, f_out are HOST float[MHH_SURFACE_NZL] for both dtypes, the temporaries are in the dtype. A pair
@@ -565,6 +571,50 @@ int mhh_surface_mo_gradients(const mhh_grid* g, const mhh_fields* f, const mhh_s
  * One rank only: on a slab (npy > 1) the north-south rows of dutot, u_fluxbot and v_fluxbot are the caller's exchange between
  * the stages, so the fused call returns MHH_EINVAL there and the driver calls the stages.                                  */
 int mhh_boundary_surface_exec(const mhh_grid* g, const mhh_fields* f, const mhh_surface_params* p, void* scratch, void* stream);
+
+/* ---- Thermo_moist (src/thermo_moist.cxx, include/thermo_moist_functions.h; GPU src/thermo_moist.cu) --------------------------
+ * thl and qt are two scalars of the grid's dtype; pref, prefh, exnref, exnrefh, thvref, thvrefh, rhoref, rhorefh are the base-state
+ * profiles, [kcells] device tables. `nonconv` is an int counter in device memory (NULL: none): where the reference throws
+ * "Non-converging saturation adjustment" (niter == nitermax, thermo_moist_functions.h:277-288) the device neither traps nor prints;
+ * the cell finishes with its tenth iterate and adds one to the counter. Every entry only enqueues on its stream.
+ *
+ * get_thermo_field("N2") needs no entry of its own: calc_N2 (src/thermo_moist.cxx:460-475) is the dry expression with thvref in the
+ * place of thref, i.e. mhh_diff_params with buoyancy_kind = 0, th_for_N2 = the index of thl, thref = thvref, buoyancy = 0.
+ * The warm branch of sat_adjust holds + - * /, max and fabs only and is bit-identical to the reference; the cold branch passes
+ * through exp (esat_ice) and the base state through pow and exp, which differ between C libraries in the last bits.            */
+#define MHH_MOIST_IMPL_MARCH 0   /* one thread per column marching up in k: four array passes                                   */
+#define MHH_MOIST_IMPL_CELL  1   /* one thread per cell through the generic cell kernel: six array passes, the same bits (A/B)  */
+/* sat_adjust (thermo_moist_functions.h:186-291) on n independent cells; thl, qt, p, exn and the outputs are [n] device arrays of
+ * dtype MHH_F64 / MHH_F32; an output may be NULL.                                                                                */
+int mhh_thermo_moist_sat_adjust(int dtype, long long n, const void* thl, const void* qt, const void* p, const void* exn,
+                                void* ql, void* qi, void* t, void* qs, int* nonconv, void* stream);
+/* Thermo_moist::exec at second order, calc_buoyancy_tend_2nd (src/thermo_moist.cxx:78-120; GPU calc_buoyancy_tend_2nd_g,
+ * src/thermo_moist.cu): wt[k] += buoyancy(exnrefh[k], thl and qt at the w level, their ql and qi, thvrefh[k]) for k in (kstart, kend).
+ * exnrefh[k] is read from the table; the reference recomputes exner(prefh[k]), the expression that filled it. Run in front of
+ * mhh_rhs_exec, as thermo->exec precedes advec->exec. The levels per chunk of the marching form follow MHH_MARCH_KC_RT.          */
+int mhh_thermo_moist_buoyancy_tend(const mhh_grid* g, void* wt, const void* thl, const void* qt, const void* prefh,
+                                   const void* exnrefh, const void* thvrefh, int* nonconv, void* stream);
+/* the same with the form named (MHH_MOIST_IMPL_*)                                                                               */
+int mhh_thermo_moist_buoyancy_tend_impl(const mhh_grid* g, int impl, void* wt, const void* thl, const void* qt, const void* prefh,
+                                        const void* exnrefh, const void* thvrefh, int* nonconv, void* stream);
+/* Thermo_moist::get_thermo_field for "b", "ql", "qi", "T" (calc_buoyancy :123-167, calc_liquid_water :231-250, calc_ice :414-434,
+ * calc_T :478-496) in one pass with one sat_adjust per cell: writes whichever of b, ql, qi, T is not NULL. ql, qi, T on the
+ * interior; b on all kcells levels of the interior columns, with ql = qi = 0 outside [kstart, kend).                             */
+int mhh_thermo_moist_fields(const mhh_grid* g, const void* thl, const void* qt, const void* pref, const void* exnref, const void* thvref,
+                            void* b, void* ql, void* qi, void* T, int* nonconv, void* stream);
+/* Thermo_moist::create_basestate (:1220-1241) on the HOST with the host's C library: calc_top_and_bot (:58-75) sets the ghost
+ * entries of thl0 and qt0 (HOST [kcells], written), calc_base_state (thermo_moist_functions.h:293-349) fills the eight HOST
+ * profiles (any may be NULL), and with boussinesq != 0 rhoref, rhorefh are overwritten with 1 and thvref, thvrefh with thvref0.
+ * g_host carries HOST metric pointers. nonconv: HOST int, incremented.                                                          */
+int mhh_thermo_moist_base_state_host(const mhh_grid* g_host, void* thl0, void* qt0, double pbot, int boussinesq, double thvref0,
+                                     void* pref, void* prefh, void* rhoref, void* rhorefh, void* thvref, void* thvrefh,
+                                     void* exnref, void* exnrefh, int* nonconv);
+/* calc_base_state on the device from the mean profiles thlmean, qtmean ([kcells], ghost entries set), statement by statement, by
+ * one lane on the stream: no synchronisation, no host memory (the reference's GPU path copies the means to the host every
+ * sub-step, src/thermo_moist.cu:806-844). Any output may be NULL.                                                                */
+int mhh_thermo_moist_base_state(const mhh_grid* g, const void* thlmean, const void* qtmean, double pbot,
+                                void* pref, void* prefh, void* rhoref, void* rhorefh, void* thvref, void* thvrefh,
+                                void* exnref, void* exnrefh, int* nonconv, void* stream);
 
 /* ---- Timeloop RK3/RK4 substep (src/timeloop.cxx:250-334, src/timeloop.cu:35-122) -------- */
 int mhh_rk_substep(const mhh_grid* g, int rkorder, int substep, double dt, void* a, void* at, void* stream);

@@ -53,7 +53,8 @@ class MhhSurfaceParams(C.Structure):
                 ("thref_kstart", cd), ("threfh_kstart", cd), ("grav", cd), ("bg_n2", cd),
                 ("zL", vp), ("f", vp), ("z0m", vp), ("z0h", vp), ("ustar", vp), ("obuk", vp), ("nobuk", vp),
                 ("ubot", vp), ("vbot", vp), ("ugradbot", vp), ("vgradbot", vp),
-                ("sbot", vp * MAX_SCALARS), ("sgradbot", vp * MAX_SCALARS), ("sbcbot", ci * MAX_SCALARS)]
+                ("sbot", vp * MAX_SCALARS), ("sgradbot", vp * MAX_SCALARS), ("sbcbot", ci * MAX_SCALARS),
+                ("qt_index", ci), ("thvref", vp), ("thvrefh", vp)]
 
 
 FP = C.POINTER(MhhFields)
@@ -171,6 +172,12 @@ SIGNATURES = {
     "mhh_surface_scalar": (ci, [GP, FP, SP, ci, vp]),
     "mhh_surface_mo_gradients": (ci, [GP, FP, SP, vp]),
     "mhh_boundary_surface_exec": (ci, [GP, FP, SP, vp, vp]),
+    "mhh_thermo_moist_sat_adjust": (ci, [ci, C.c_longlong, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mhh_thermo_moist_buoyancy_tend": (ci, [GP, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mhh_thermo_moist_buoyancy_tend_impl": (ci, [GP, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mhh_thermo_moist_fields": (ci, [GP, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mhh_thermo_moist_base_state_host": (ci, [GP, vp, vp, cd, ci, cd, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mhh_thermo_moist_base_state": (ci, [GP, vp, vp, cd, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 

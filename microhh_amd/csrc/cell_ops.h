@@ -1051,4 +1051,159 @@ template<class TF> MHH_HD TF surf_duvdz_mo(TF d, TF ustar, TF obuk, TF z0m, TF z
 // calc_dbdz_mo (:241)
 template<class TF> MHH_HD TF surf_dbdz_mo(TF bfluxbot, TF ustar, TF obuk, TF zsl) { return -bfluxbot / (most_kappa<TF>() * zsl * ustar) * most_phih(zsl/obuk); }
 
+// ---- Thermo_moist (include/thermo_moist_functions.h), in the reference's expression order ---------------------------------------
+// The constants of include/constants.h:32-42,73-83, each held in TF as the reference's variable templates hold them (Ls and ep
+// are the TF sum and the TF quotient).
+template<class TF> struct MoistC
+{
+    static constexpr TF grav = TF(9.81), Rd = TF(287.04), Rv = TF(461.5), cp = TF(1005), Lv = TF(2.501e6), Lf = TF(3.337e5);
+    static constexpr TF Ls = Lv + Lf, T0 = TF(273.15), p0 = TF(1.e5), ep = Rd/Rv;
+    static constexpr TF c00 = TF(+6.1121000000E+02), c10 = TF(+4.4393067270E+01), c20 = TF(+1.4279398448E+00), c30 = TF(+2.6415206946E-02),
+                        c40 = TF(+3.0291749160E-04), c50 = TF(+2.1159987257E-06), c60 = TF(+7.5015702516E-09), c70 = TF(-1.5604873363E-12),
+                        c80 = TF(-9.9726710231E-14), c90 = TF(-4.8165754883E-17), c100 = TF(+1.3839187032E-18);
+};
+// :47-75
+template<class TF> MHH_HD TF moist_virtual_temperature(TF exn, TF thl, TF qt, TF ql, TF qi)
+{
+    typedef MoistC<TF> K;
+    const TF th = thl + K::Lv*ql/(K::cp*exn) + K::Ls*qi/(K::cp*exn);
+    return th * (TF(1.) - (TF(1.) - K::Rv/K::Rd)*qt - K::Rv/K::Rd*(ql+qi));
+}
+template<class TF> MHH_HD TF moist_buoyancy(TF exn, TF thl, TF qt, TF ql, TF qi, TF thvref)
+{
+    return MoistC<TF>::grav * (moist_virtual_temperature(exn, thl, qt, ql, qi) - thvref) / thvref;
+}
+template<class TF> MHH_HD TF moist_virtual_temperature_no_ql(TF thl, TF qt)
+{
+    typedef MoistC<TF> K;
+    return thl * (TF(1.) - (TF(1.) - K::Rv/K::Rd)*qt);
+}
+template<class TF> MHH_HD TF moist_buoyancy_no_ql(TF thl, TF qt, TF thvref)
+{
+    typedef MoistC<TF> K;
+    return K::grav * (thl * (TF(1.) - (TF(1.) - K::Rv/K::Rd)*qt) - thvref) / thvref;
+}
+template<class TF> MHH_HD TF moist_buoyancy_flux_no_ql(TF thl, TF thlflux, TF qt, TF qtflux, TF thvref)
+{
+    typedef MoistC<TF> K;
+    return K::grav/thvref * (thlflux * (TF(1.) - (TF(1.)-K::Rv/K::Rd)*qt) - (TF(1.)-K::Rv/K::Rd)*thl*qtflux);
+}
+// :86-122: the 10th-degree Horner form of Buck's curve over water; Buck's curve over ice through exp
+template<class TF> MHH_HD TF moist_esat_liq(TF T)
+{
+    typedef MoistC<TF> K;
+    const TF x = tmax(TF(-75.), T-K::T0);
+    return K::c00+x*(K::c10+x*(K::c20+x*(K::c30+x*(K::c40+x*(K::c50+x*(K::c60+x*(K::c70+x*(K::c80+x*(K::c90+x*K::c100)))))))));
+}
+template<class TF> MHH_HD TF moist_qsat_liq(TF p, TF T)
+{
+    typedef MoistC<TF> K;
+    return K::ep*moist_esat_liq(T)/(p-(TF(1.)-K::ep)*moist_esat_liq(T));
+}
+template<class TF> MHH_HD TF moist_esat_ice(TF T)
+{
+    const TF x = tmax(TF(-100.), T-MoistC<TF>::T0);
+    return TF(611.15)*std::exp(TF(22.452)*x / (TF(272.55)+x));
+}
+template<class TF> MHH_HD TF moist_qsat_ice(TF p, TF T)
+{
+    typedef MoistC<TF> K;
+    return K::ep*moist_esat_ice(T)/(p-(TF(1.)-K::ep)*moist_esat_ice(T));
+}
+// :126-141 (Tomita 2008)
+template<class TF> MHH_HD TF moist_water_fraction(TF T)
+{
+    return tmax(TF(0.), tmin((T - TF(233.15)) / (MoistC<TF>::T0 - TF(233.15)), TF(1.)));
+}
+template<class TF> MHH_HD TF moist_qsat(TF p, TF T)
+{
+    const TF alpha = moist_water_fraction(T);
+    return alpha*moist_qsat_liq(p, T) + (TF(1.)-alpha)*moist_qsat_ice(p, T);
+}
+// :151-162
+template<class TF> MHH_HD TF moist_dqsatdT_liq(TF p, TF T)
+{
+    typedef MoistC<TF> K;
+    const TF den = p - moist_esat_liq(T)*(TF(1.) - K::ep);
+    return (K::ep/den - (TF(1.) + K::ep)*K::ep*moist_esat_liq(T)/sq(den)) * K::Lv*moist_esat_liq(T) / (K::Rv*sq(T));
+}
+template<class TF> MHH_HD TF moist_dqsatdT_ice(TF p, TF T)
+{
+    typedef MoistC<TF> K;
+    const TF den = p - moist_esat_ice(T)*(TF(1.) - K::ep);
+    return (K::ep/den + (TF(1.) - K::ep)*K::ep*moist_esat_ice(T)/sq(den)) * K::Ls*moist_esat_ice(T) / (K::Rv*sq(T));
+}
+// :172-175. The reference writes an unqualified pow: with <cmath> alone that is the C library's pow(double, double) in both
+// builds, narrowed to TF on return.
+template<class TF> MHH_HD TF moist_exner(TF p)
+{
+    typedef MoistC<TF> K;
+    return TF(pow(double(p/K::p0), double(K::Rd/K::cp)));
+}
+// sat_adjust (:186-291). niter is returned beside the answer: where the reference throws (niter == nitermax) the caller counts the
+// cell and goes on with the tenth iterate. The warm branch and everything in front of the branch hold + - * /, max and fabs only.
+template<class TF> struct MoistSat { TF ql, qi, t, qs; int niter; };
+constexpr int moist_nitermax = 10;
+template<class TF> MHH_HD MoistSat<TF> moist_sat_adjust(TF thl, TF qt, TF p, TF exn)
+{
+    typedef MoistC<TF> K;
+    int niter = 0;
+    TF tnr_old = TF(1.e9);
+    const TF tl = thl * exn;
+    TF qs = moist_qsat_liq(p, tl);
+    MoistSat<TF> ans = {TF(0.), TF(0.), tl, qs, 0};
+    if (qt-ans.qs <= TF(0.))
+        return ans;
+    TF tnr = tl;
+    if (tl >= K::T0)
+    {
+        while (tabs(tnr-tnr_old)/tnr_old > TF(1.e-5) && niter < moist_nitermax)
+        {
+            ++niter;
+            tnr_old = tnr;
+            qs = moist_qsat_liq(p, tnr);
+            const TF f = tnr - tl - K::Lv/K::cp*(qt - qs);
+            const TF f_prime = TF(1.) + K::Lv/K::cp*moist_dqsatdT_liq(p, tnr);
+            tnr -= f / f_prime;
+        }
+        qs = moist_qsat_liq(p, tnr);
+        ans.ql = tmax(TF(0.), qt - qs);
+        ans.t  = tnr;
+        ans.qs = qs;
+    }
+    else
+    {
+        while (tabs(tnr-tnr_old)/tnr_old > TF(1.e-5) && niter < moist_nitermax)
+        {
+            ++niter;
+            tnr_old = tnr;
+            qs = moist_qsat(p, tnr);
+            const TF alpha_w = moist_water_fraction(tnr);
+            const TF alpha_i = TF(1.) - alpha_w;
+            const TF dalphadT = (alpha_w > TF(0.) && alpha_w < TF(1.)) ? TF(0.025) : TF(0.);
+            const TF dqsatdT_w = moist_dqsatdT_liq(p, tnr);
+            const TF dqsatdT_i = moist_dqsatdT_ice(p, tnr);
+            const TF f =
+                tnr - tl - alpha_w*K::Lv/K::cp*qt - alpha_i*K::Ls/K::cp*qt
+                         + alpha_w*K::Lv/K::cp*qs + alpha_i*K::Ls/K::cp*qs;
+            const TF f_prime = TF(1.)
+                - dalphadT*K::Lv/K::cp*qt + dalphadT*K::Ls/K::cp*qt
+                + dalphadT*K::Lv/K::cp*qs - dalphadT*K::Ls/K::cp*qs
+                + alpha_w*K::Lv/K::cp*dqsatdT_w
+                + alpha_i*K::Ls/K::cp*dqsatdT_i;
+            tnr -= f / f_prime;
+        }
+        const TF alpha_w = moist_water_fraction(tnr);
+        const TF alpha_i = TF(1.) - alpha_w;
+        qs = moist_qsat(p, tnr);
+        const TF ql_qi = tmax(TF(0.), qt - qs);
+        ans.ql = alpha_w*ql_qi;
+        ans.qi = alpha_i*ql_qi;
+        ans.t  = tnr;
+        ans.qs = qs;
+    }
+    ans.niter = niter;
+    return ans;
+}
+
 } // namespace mhh

@@ -822,3 +822,8 @@ MHH_API int mhh_boundary_ghost_cells_w(const mhh_grid* g, void* w, int type, voi
 // Boundary_surface::exec: the Monin-Obukhov surface layer (src/boundary_surface.cxx:830-983)
 // =======================================================================================================
 #include "surface_layer.h"
+
+// =======================================================================================================
+// Thermo_moist: saturation adjustment, buoyancy tendency, diagnostic fields, base state (src/thermo_moist.cxx)
+// =======================================================================================================
+#include "thermo_moist.h"

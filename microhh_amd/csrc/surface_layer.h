@@ -32,15 +32,33 @@ template<class TF> struct SurfArgs
     const TF* th; const TF* thbot; const TF* thflux;     // the thermo scalar's field, bottom value and bottom flux: s[tidx] etc., named
                                                          // so that no kernel indexes the argument block with a value it loads
     TF* dutot;
+    // Thermo_moist (kind 3): qt's field, bottom value and bottom flux, named like th's, and the base-state tables read at kstart
+    int qidx;
+    const TF* qt; const TF* qtbot; const TF* qtflux; const TF* thvref; const TF* thvrefh;
 };
 
 // ---- the stages as functions of one column, shared by the stage kernels and the fused ones ------------------------------
 template<class TF> __device__ __forceinline__ bool surf_interior(const GridDev<TF>& g, int i, int j)
 { return i >= g.istart && i < g.iend && j >= g.jstart && j < g.jend; }
 
-// buoyancy flux at the surface from the thermo scalar's flux (Thermo_dry calc_buoyancy_fluxbot / Thermo_buoy's copy)
-template<class TF> __device__ __forceinline__ TF surf_bfluxbot(const SurfArgs<TF>& A, TF sflux)
-{ return (A.kind == 1) ? dry_bfluxbot(A.grav, A.threfh, sflux) : sflux; }
+// buoyancy flux at the surface from the thermo scalar's flux (Thermo_dry calc_buoyancy_fluxbot / Thermo_buoy's copy); Thermo_moist
+// (calc_buoyancy_fluxbot, src/thermo_moist.cxx:675-693): from the first level's thl and qt (cell c) and the two bottom fluxes
+template<class TF> __device__ __forceinline__ TF surf_bfluxbot(const SurfArgs<TF>& A, int c, TF sflux, TF qflux)
+{
+    if (A.kind == 3) return moist_buoyancy_flux_no_ql(A.th[c], sflux, A.qt[c], qflux, uniform_load(A.thvrefh, A.g.kstart));
+    return (A.kind == 1) ? dry_bfluxbot(A.grav, A.threfh, sflux) : sflux;
+}
+// qt's bottom flux of column ij as it stands in memory (0 unless Thermo_moist)
+template<class TF> __device__ __forceinline__ TF surf_qflux(const SurfArgs<TF>& A, int ij) { return (A.kind == 3) ? A.qtflux[ij] : TF(0); }
+// Thermo_moist's db of the Dirichlet case: calc_buoyancy_bot (:637-655) and get_db_ref (:1713-1717)
+template<class TF> __device__ __forceinline__ TF surf_moist_db(const SurfArgs<TF>& A, int c, int ij)
+{
+    const TF thv = uniform_load(A.thvref, A.g.kstart), thvh = uniform_load(A.thvrefh, A.g.kstart);
+    const TF bbot = moist_buoyancy_no_ql(A.thbot[ij], A.qtbot[ij], thvh);
+    const TF b    = moist_buoyancy_no_ql(A.th[c], A.qt[c], thv);
+    const TF db_ref = MoistC<TF>::grav/thv*(thv - thvh);
+    return b - bbot + db_ref;
+}
 
 // stage c: stability / stability_neutral (src/boundary_surface.cxx:54-177) for column ij
 template<class TF> __device__ __forceinline__ void surf_stability_cell(const SurfArgs<TF>& A, int i, int j, int ij)
@@ -61,18 +79,18 @@ template<class TF> __device__ __forceinline__ void surf_stability_cell(const Sur
     const int c = ij + ks*A.g.ijcells;
     if (A.mbcbot == MHH_BC_USTAR)
     {
-        A.obuk[ij] = surf_obuk_ustar_flux(A.ustar[ij], surf_bfluxbot(A, A.thflux[ij]));
+        A.obuk[ij] = surf_obuk_ustar_flux(A.ustar[ij], surf_bfluxbot(A, c, A.thflux[ij], surf_qflux(A, ij)));
         return;
     }
     int n = A.nobuk[ij];
     const TF du = A.dutot[ij];
     TF L;
     if (A.thermobc == MHH_BC_FLUX)
-        L = surf_obuk_flux(A.zL, A.f, n, du, surf_bfluxbot(A, A.thflux[ij]), zsl);
+        L = surf_obuk_flux(A.zL, A.f, n, du, surf_bfluxbot(A, c, A.thflux[ij], surf_qflux(A, ij)), zsl);
     else
     {
         const TF th = A.th[c], thbot = A.thbot[ij];
-        const TF db = (A.kind == 1) ? dry_db(A.grav, A.thref, A.threfh, th, thbot) : th - thbot + A.n2;
+        const TF db = (A.kind == 3) ? surf_moist_db(A, c, ij) : (A.kind == 1) ? dry_db(A.grav, A.thref, A.threfh, th, thbot) : th - thbot + A.n2;
         L = surf_obuk_dirichlet(A.zL, A.f, n, du, db, zsl);
     }
     A.nobuk[ij] = n;
@@ -141,8 +159,9 @@ template<class TF> __device__ __forceinline__ void surf_momflux_cell(const SurfA
         A.ufluxbot[ij] = uf; A.vfluxbot[ij] = vf;
     }
 }
-// stage f: calc_duvdz_mo, calc_dbdz_mo (boundary_surface_kernels.h:186-243), interior; sflux = the thermo scalar's bottom flux
-template<class TF> __device__ __forceinline__ void surf_mograd_cell(const SurfArgs<TF>& A, int ij, TF sflux)
+// stage f: calc_duvdz_mo, calc_dbdz_mo (boundary_surface_kernels.h:186-243), interior; sflux = the thermo scalar's bottom flux,
+// qflux = qt's (Thermo_moist)
+template<class TF> __device__ __forceinline__ void surf_mograd_cell(const SurfArgs<TF>& A, int ij, TF sflux, TF qflux)
 {
     const int jj = A.g.icells, c = ij + A.g.kstart*A.g.ijcells;
     const TF zsl = uniform_load(A.g.z, A.g.kstart);
@@ -151,7 +170,7 @@ template<class TF> __device__ __forceinline__ void surf_mograd_cell(const SurfAr
     const TF dv_c = TF(0.5)*((A.v[c] - A.vbot[ij]) + (A.v[c+jj] - A.vbot[ij+jj]));
     A.dudz[ij] = surf_duvdz_mo(du_c, us, L, z0, zsl);
     A.dvdz[ij] = surf_duvdz_mo(dv_c, us, L, z0, zsl);
-    if (A.kind != 0) A.dbdz[ij] = surf_dbdz_mo(surf_bfluxbot(A, sflux), us, L, zsl);
+    if (A.kind != 0) A.dbdz[ij] = surf_dbdz_mo(surf_bfluxbot(A, c, sflux, qflux), us, L, zsl);
 }
 
 // ---- the operators the generic cell kernel runs (k is the single pseudo-level 0) ------------------------------------------
@@ -190,7 +209,7 @@ template<class TF> struct SurfMoGradOp
     __device__ void operator()(int i, int j, int, int) const
     {
         const int ij = i + j*A.g.icells;
-        surf_mograd_cell(A, ij, A.kind != 0 ? A.thflux[ij] : TF(0));
+        surf_mograd_cell(A, ij, A.kind != 0 ? A.thflux[ij] : TF(0), surf_qflux(A, ij));
     }
 };
 // K2 of the fused entry point: c, e, the gradients of d, f for one column
@@ -202,15 +221,16 @@ template<class TF> struct SurfColumnOp
         const int ij = i + j*A.g.icells;
         surf_stability_cell(A, i, j, ij);
         surf_momgrad_cell(A, ij);
-        TF sflux = TF(0);
+        TF sflux = TF(0), qflux = TF(0);
 #pragma unroll
         for (int n=0; n<MHH_MAX_SCALARS; ++n)            // constant indices into the argument block (see surf_pick)
             if (n < A.ns)
             {
                 const TF fl = surf_scalar_cell(A, n, ij);
                 if (n == A.tidx) sflux = fl;
+                if (n == A.qidx) qflux = fl;
             }
-        if (surf_interior(A.g, i, j)) surf_mograd_cell(A, ij, sflux);
+        if (surf_interior(A.g, i, j)) surf_mograd_cell(A, ij, sflux, qflux);
     }
 };
 
@@ -232,7 +252,7 @@ static int surf_check(const mhh_grid* g, const mhh_fields* f, const mhh_surface_
     if (const char* why = surf_refusal(g, p)) { set_error("Boundary_surface refused: %s", why); return MHH_EINVAL; }
     MHH_REQUIRE(g->z != nullptr, "grid.z (zsl = z[kstart])");
     MHH_REQUIRE(p->mbcbot == MHH_BC_DIRICHLET || p->mbcbot == MHH_BC_USTAR, "mbcbot: Dirichlet (noslip) or Ustar");
-    MHH_REQUIRE(p->thermo_kind >= MHH_THERMO_NONE && p->thermo_kind <= MHH_THERMO_BUOY, "thermo_kind: 0 none, 1 dry, 2 buoy");
+    MHH_REQUIRE(p->thermo_kind >= MHH_THERMO_NONE && p->thermo_kind <= MHH_THERMO_MOIST, "thermo_kind: 0 none, 1 dry, 2 buoy, 3 moist");
     MHH_REQUIRE(f->nscalars >= 0 && f->nscalars <= MHH_MAX_SCALARS, "nscalars");
     if (p->thermo_kind != MHH_THERMO_NONE)
     {
@@ -241,6 +261,14 @@ static int surf_check(const mhh_grid* g, const mhh_fields* f, const mhh_surface_
         MHH_REQUIRE(p->thermobc == MHH_BC_FLUX || (p->thermobc == MHH_BC_DIRICHLET && p->mbcbot == MHH_BC_DIRICHLET),
                     "thermo bc: Flux, or Dirichlet with mbcbot = Dirichlet (the cases of stability, src/boundary_surface.cxx:83-133)");
         if (p->thermo_kind == MHH_THERMO_DRY) MHH_REQUIRE(p->thref_kstart > 0. && p->threfh_kstart > 0., "thref[kstart], threfh[kstart]");
+        if (p->thermo_kind == MHH_THERMO_MOIST)
+        {
+            const int q = p->qt_index;
+            MHH_REQUIRE(q >= 0 && q < f->nscalars && q != p->thermo_index, "qt_index names a scalar other than thl");
+            MHH_REQUIRE(p->sbcbot[q] == p->thermobc, "Thermo_moist: qt must have the same kind of bottom bc as thl (thermobc is thl's; the buoyancy flux and the surface buoyancy need both scalars' fluxes or both surface values)");
+            MHH_REQUIRE(p->thvref && p->thvrefh, "Thermo_moist: the device tables thvref, thvrefh");
+            MHH_REQUIRE(f->s[q] && f->s_fluxbot[q] && p->sbot[q], "qt, its bottom flux and bottom value");
+        }
     }
     MHH_REQUIRE(p->ustar && p->obuk && p->z0m && p->z0h, "ustar, obuk, z0m, z0h");
     if (need & (SURF_NEED_DUTOT_IN | SURF_NEED_VEL)) MHH_REQUIRE(dutot != nullptr, "dutot");
@@ -291,6 +319,13 @@ template<class TF> static SurfArgs<TF> surf_args(const mhh_grid* g, const mhh_fi
         A.sfluxbot[n] = on ? const_cast<TF*>(cp<TF>(f->s_fluxbot[n])) : nullptr; A.sbc[n] = on ? p->sbcbot[n] : MHH_BC_NEUMANN;
     }
     if (A.tidx >= 0) { A.th = A.s[A.tidx]; A.thbot = A.sbot[A.tidx]; A.thflux = A.sfluxbot[A.tidx]; }
+    A.qidx = -1;
+    if (A.kind == MHH_THERMO_MOIST)
+    {
+        A.qidx = p->qt_index;
+        A.qt = A.s[A.qidx]; A.qtbot = A.sbot[A.qidx]; A.qtflux = A.sfluxbot[A.qidx];
+        A.thvref = cp<TF>(p->thvref); A.thvrefh = cp<TF>(p->thvrefh);
+    }
     A.dutot = mp<TF>(dutot);
     return A;
 }

@@ -775,4 +775,94 @@ class Boundary_surface : public Boundary<TF>
         Grid<TF>& grid; Fields<TF>& fields;
 };
 
+// ---- Thermo_moist (src/thermo_moist.cxx): swthermo = moist with the scalars thl and qt, second order ---------------------------
+// The base-state tables and the counter are the caller's device arrays ([kcells] of TF; nonconv_g one int, zeroed), as the other
+// classes here take theirs. `upload(dst_device, src_host, bytes)` is the caller's copy (create_basestate runs once, outside a step).
+template<typename TF>
+class Thermo_moist
+{
+    public:
+        Thermo_moist(Grid<TF>& grid_in, Fields<TF>& fields_in) : grid(grid_in), fields(fields_in) {}
+        // [thermo] pbot, swbasestate ("anelastic" | "boussinesq"), thvref0, swupdatebasestate
+        TF pbot = 0; std::string swbasestate = "anelastic"; TF thvref0 = 0; bool swupdatebasestate = true;
+        std::string thl = "thl", qt = "qt";
+        TF* pref_g = nullptr; TF* prefh_g = nullptr; TF* rhoref_g = nullptr; TF* rhorefh_g = nullptr;
+        TF* thvref_g = nullptr; TF* thvrefh_g = nullptr; TF* exnref_g = nullptr; TF* exnrefh_g = nullptr;
+        int* nonconv_g = nullptr;
+        std::vector<TF> thl0, qt0, pref, prefh, rhoref, rhorefh, thvref, thvrefh, exnref, exnrefh;      // host copies of the creation-time state
+        std::string get_switch() const { return "moist"; }
+
+        // Thermo_moist::create_basestate (:1189-1247): thl0_in, qt0_in are the ktot initial values; the tables on the host with the
+        // host's C library, uploaded; fields.rhoref / rhorefh set once (never updated)
+        template<class Upload> void create_basestate(const std::vector<TF>& thl0_in, const std::vector<TF>& qt0_in, Upload&& upload)
+        {
+            const auto& gd = grid.get_grid_data();
+            if (swbasestate != "anelastic" && swbasestate != "boussinesq") throw std::runtime_error("Invalid option for \"swbasestate\"");
+            if ((int)thl0_in.size() != gd.ktot || (int)qt0_in.size() != gd.ktot) throw std::runtime_error("create_basestate: ktot values of thl and qt");
+            if (!(pref_g && prefh_g && rhoref_g && rhorefh_g && thvref_g && thvrefh_g && exnref_g && exnrefh_g)) throw std::runtime_error("create_basestate: the eight device tables");
+            const size_t nk = gd.kcells;
+            thl0.assign(nk, 0); qt0.assign(nk, 0);
+            for (int k=0; k<gd.ktot; ++k) { thl0[gd.kstart+k] = thl0_in[k]; qt0[gd.kstart+k] = qt0_in[k]; }
+            for (std::vector<TF>* v : {&pref, &prefh, &rhoref, &rhorefh, &thvref, &thvrefh, &exnref, &exnrefh}) v->assign(nk, 0);
+            mhh_grid g = grid.abi(true);
+            int nonconv = 0;
+            mhh_check(mhh_thermo_moist_base_state_host(&g, thl0.data(), qt0.data(), pbot, swbasestate == "boussinesq" ? 1 : 0, thvref0,
+                                                       pref.data(), prefh.data(), rhoref.data(), rhorefh.data(), thvref.data(), thvrefh.data(),
+                                                       exnref.data(), exnrefh.data(), &nonconv));
+            if (nonconv) throw std::runtime_error("Non-converging saturation adjustment in the base state");
+            TF* dst[8] = {pref_g, prefh_g, rhoref_g, rhorefh_g, thvref_g, thvrefh_g, exnref_g, exnrefh_g};
+            const std::vector<TF>* src[8] = {&pref, &prefh, &rhoref, &rhorefh, &thvref, &thvrefh, &exnref, &exnrefh};
+            for (int n=0; n<8; ++n) upload(dst[n], src[n]->data(), nk*sizeof(TF));
+            fields.rhoref = rhoref; fields.rhorefh = rhorefh;
+            if (fields.rhoref_g && fields.rhorefh_g) { upload(fields.rhoref_g, rhoref.data(), nk*sizeof(TF)); upload(fields.rhorefh_g, rhorefh.data(), nk*sizeof(TF)); }
+        }
+        // Thermo_moist::exec (:1273-1303): with swupdatebasestate the base state from fld_mean_g of thl and qt (Field3d_operators'
+        // calc_mean_profile, the caller's), all eight profiles on the device; then the buoyancy tendency of w
+        void exec(void* stream = nullptr)
+        {
+            const auto& gd = grid.get_grid_data();
+            if (gd.kgc < 1) throw std::runtime_error("Thermo_moist: one vertical ghost cell");
+            mhh_grid g = grid.abi();
+            auto& a = *fields.sp.at(thl); auto& q = *fields.sp.at(qt);
+            if (swupdatebasestate)
+            {
+                if (!a.fld_mean_g || !q.fld_mean_g) throw std::runtime_error("Thermo_moist::exec: fld_mean_g of thl and qt (swupdatebasestate)");
+                mhh_check(mhh_thermo_moist_base_state(&g, a.fld_mean_g, q.fld_mean_g, pbot, pref_g, prefh_g, rhoref_g, rhorefh_g, thvref_g, thvrefh_g,
+                                                      exnref_g, exnrefh_g, nonconv_g, stream));
+            }
+            mhh_check(mhh_thermo_moist_buoyancy_tend(&g, fields.mt.at("w")->fld_g, a.fld_g, q.fld_g, prefh_g, exnrefh_g, thvrefh_g, nonconv_g, stream));
+        }
+        // Thermo_moist::get_thermo_field_g (:1418-1500) for b | ql | qi | T | N2 into a caller-owned 3-D device field; with
+        // swupdatebasestate the pressure and Exner profiles are refreshed from the means first. Any other name is refused.
+        void get_thermo_field(TF* out, const std::string& name, void* stream = nullptr)
+        {
+            if (name != "b" && name != "ql" && name != "qi" && name != "T" && name != "N2")
+                throw std::runtime_error("get_thermo_field: \"" + name + "\" is not built (b | ql | qi | T | N2)");
+            mhh_grid g = grid.abi();
+            auto& a = *fields.sp.at(thl); auto& q = *fields.sp.at(qt);
+            if (swupdatebasestate && a.fld_mean_g && q.fld_mean_g)
+                mhh_check(mhh_thermo_moist_base_state(&g, a.fld_mean_g, q.fld_mean_g, pbot, pref_g, prefh_g, nullptr, nullptr, nullptr, nullptr,
+                                                      exnref_g, exnrefh_g, nonconv_g, stream));
+            if (name == "N2") { mhh_check(mhh_calc_N2(&g, out, a.fld_g, thvref_g, 9.81, stream)); return; }       // calc_N2 (:460-475)
+            mhh_check(mhh_thermo_moist_fields(&g, a.fld_g, q.fld_g, pref_g, exnref_g, thvref_g, name == "b" ? out : nullptr, name == "ql" ? out : nullptr,
+                                              name == "qi" ? out : nullptr, name == "T" ? out : nullptr, nonconv_g, stream));
+        }
+        // get_buoyancy_surf, get_buoyancy_fluxbot, get_db_ref (:1610-1717) are evaluated inside the surface layer's kernels from the
+        // device tables: these three name what they set in its parameter block (thermo_kind 3; thl_index, qt_index = the scalars)
+        void get_buoyancy_surf(mhh_surface_params& p, int thl_index, int qt_index) const
+        { p.thermo_kind = MHH_THERMO_MOIST; p.thermo_index = thl_index; p.qt_index = qt_index; p.thvref = thvref_g; p.thvrefh = thvrefh_g; }
+        void get_buoyancy_fluxbot(mhh_surface_params& p, int thl_index, int qt_index) const { get_buoyancy_surf(p, thl_index, qt_index); }
+        // the creation-time value (the kernels evaluate the current one from the tables)
+        TF get_db_ref() const { const int ks = grid.get_grid_data().kstart; return TF(9.81)/thvref[ks]*(thvref[ks] - thvrefh[ks]); }
+        // get_basestate_vector: the device table by name
+        TF* get_basestate_vector(const std::string& name) const
+        {
+            if (name == "pref") return pref_g; if (name == "prefh") return prefh_g; if (name == "rhoref") return rhoref_g; if (name == "rhorefh") return rhorefh_g;
+            if (name == "thvref") return thvref_g; if (name == "thvrefh") return thvrefh_g; if (name == "exnref") return exnref_g; if (name == "exnrefh") return exnrefh_g;
+            throw std::runtime_error("get_basestate_vector: " + name);
+        }
+    private:
+        Grid<TF>& grid; Fields<TF>& fields;
+};
+
 } // namespace mhh_host

@@ -3,6 +3,7 @@ that this package accelerates, expressed as calls into the C ABI.
 
     boundary->set_prognostic_cyclic_bcs   -> mhh_boundary_cyclic_n (+ N-S neighbour exchange)   (src/model.cxx:346)
     diff->exec_viscosity(thermo)          -> mhh_diff_exec_viscosity (+ N-S exchange of evisc)   (:354)
+    thermo->exec (Thermo_moist)           -> mhh_thermo_moist_base_state, mhh_thermo_moist_buoyancy_tend (thermo=..., opt-in) (:366)
     boundary->exec ; set_ghost_cells      -> mhh_boundary_surface_exec, mhh_boundary_ghost_cells (surface=..., opt-in) (:374-375)
     advec->exec ; diff->exec              -> mhh_rhs_exec (fused, same bits)                     (:388, :392)
     fields->exec ; buffer->exec ; force->exec -> mhh_field_mean_*, mhh_buffer_force_exec (forcing=..., opt-in) (:351, :395, :404)
@@ -40,6 +41,10 @@ CASES = {
                    thermo="buoy"),
     "sbl": dict(advec=ADVEC_2I5, diff=DIFF_SMAG2, pres=2, order=2, gc=(3, 3, 1), size=(27.386127875258303, 27.386127875258303, 18.074844397670482),
                 nscalars=1, sm=1, visc=1.5e-5, tPr=10., thermo="buoy"),
+    # bomex (cases/bomex): Thermo_moist with scalar 0 = thl, 1 = qt, pbot = 101500 Pa; HotPath(..., thermo=thermo.Moist(pbot)) switches
+    # the thermodynamics on. The schemes are upstream's choice for the case; this fork's cases/bomex/bomex.ini says swadvec=2.
+    "bomex": dict(advec=ADVEC_2I5, diff=DIFF_SMAG2, pres=2, order=2, gc=(3, 3, 1), size=(6400., 6400., 3000.), nscalars=2, sm=1, visc=1e-5,
+                  thermo="moist", pbot=101500.),
 }
 
 FIELDS3 = ("u", "v", "w", "ut", "vt", "wt")
@@ -60,6 +65,9 @@ def synthetic_global(case, itot, jtot, ktot, dtype=np.float64, seed=666, nscalar
     for n in range(cfg["nscalars"] if nscalars is None else nscalars):
         out["s%d" % n] = 300. + 0.003*z[:, None, None] + rs.uniform(-.05, .05, n3)
         out["st%d" % n] = rs.uniform(0, 1e-4, n3)
+    if cfg.get("thermo") == "moist" and "s1" in out:
+        from .thermo import bomex_interior
+        out["s0"], out["s1"] = bomex_interior(z, n3, rs)
     for k in SURF:
         out[k] = rs.uniform(0, 1e-4 if k == "dbdz" else 1e-2, n2)
     out["z0m"][:] = 0.1
@@ -71,7 +79,7 @@ class HotPath:
 
     def __init__(self, case, itot, jtot, ktot, dtype=np.float64, device="cuda:0", seed=666, dt=1.0,
                  lib=None, npy=1, rank=0, group=None, global_init=None, force_slab=False, slim_halos=True, overlap=None, pres_chunks=None, igc=None,
-                 nscalars=None, forcing=None, surface=None):
+                 nscalars=None, forcing=None, surface=None, thermo=None):
         import torch
         self.torch = torch
         self.lib = lib if lib is not None else capi.lib()
@@ -118,6 +126,9 @@ class HotPath:
         self.G = g.device_struct(self.device) if self.on_gpu else g.host_struct()
         self.td = td = torch.float64 if np.dtype(dtype) == np.float64 else torch.float32
         n3, n2 = g.shape3, g.shape2
+        if global_init is None and cfg.get("thermo") == "moist" and nsc >= 2:
+            # thl and qt are the one BOMEX recipe (thermo.bomex_interior), which synthetic_global draws on the host
+            global_init = synthetic_global(case, itot, jtot, ktot, dtype=dtype, seed=seed, nscalars=nsc)
         if global_init is None:
             gen = torch.Generator(device=self.device); gen.manual_seed(seed + 7919*rank)
 
@@ -149,6 +160,9 @@ class HotPath:
             self.s = [put3(global_init["s%d" % n]) for n in range(nsc)]
             self.st = [put3(global_init["st%d" % n]) for n in range(nsc)]
             self.surf = {k: put2(global_init[k]) for k in SURF}
+            if cfg.get("thermo") == "moist":     # the mean profiles of thl and qt are read on the ghost levels too: zero gradient there
+                for t in self.s[:2]:
+                    t[:g.kstart] = t[g.kstart]; t[g.kend:] = t[g.kend-1]
         if surface is not None:          # before the mixing-length table below is made from it
             self.surf["z0m"].fill_(float(surface.z0m))
         # solid walls: w and its tendency vanish at kstart and above kend-1
@@ -161,6 +175,10 @@ class HotPath:
         self.rhoref, self.rhorefh = torch.from_numpy(ones.copy()).to(self.device), torch.from_numpy(ones.copy()).to(self.device)
         self.thref = torch.full((g.kcells,), 300., device=self.device, dtype=td)
         self.work = torch.zeros(16, device=self.device, dtype=torch.float64)
+        # Thermo_moist (thermo.Moist): the base-state tables, and the density of the dynamics before the pressure plan is made from it
+        self.thermo = None
+        if thermo is not None:
+            self.thermo = thermo.bind(self)
         # Diff_smag2::prepare_device: per-level mixing-length table from the host libm
         self.params = p = capi.MhhDiffParams()
         p.cs, p.tPr, p.surface_model, p.neutral, p.N2, p.th_for_N2, p.grav = cfg.get("cs", 0.23), cfg.get("tPr", 1./3.), cfg["sm"], 0, None, 0, 9.81
@@ -170,6 +188,8 @@ class HotPath:
         self.buoyant = cfg.get("thermo") == "buoy" and nsc >= 1
         if self.buoyant:
             p.buoyancy, p.buoyancy_kind, p.bg_n2, p.alpha, p.utrans = cfg["order"], 1, 0., 0., 0.
+        if self.thermo is not None:           # N2 inside exec_viscosity from thl and thvref; the tendency is a pass of its own
+            self.thermo.diff_params(p)
         if cfg["diff"] == DIFF_SMAG2:
             ml = np.zeros(g.kcells, dtype=g.np_dtype)
             self._ok(self.lib.mhh_smag2_mlen0_host(g.host_struct(), p.cs, ml.ctypes.data))
@@ -476,6 +496,13 @@ class HotPath:
         """buffer->exec and force->exec (src/model.cxx:395,404) in one pass over the tendencies."""
         self.forcing.exec()
 
+    def thermo_moist(self):
+        """thermo->exec (src/model.cxx:366; Thermo_moist::exec, src/thermo_moist.cxx:1273-1303): with swupdatebasestate the base state
+        from the means on the device, then the buoyancy tendency of w."""
+        if self.thermo.swupdate:
+            self.thermo.update_base_state()
+        self.thermo.tend()
+
     def surface_layer(self):
         """boundary->exec and boundary->set_ghost_cells (src/model.cxx:374-375)."""
         self.surface.exec()
@@ -486,8 +513,22 @@ class HotPath:
         fused Buffer + Force pass between the RHS and the pressure solve. With `surface`, the order of src/model.cxx:346-392: the
         cyclic fills, exec_viscosity (which reads the PREVIOUS sub-step's dudz, dvdz, dbdz, as the reference does), the surface
         layer, the vertical ghost cells, then the RHS -- the plain sequence on a slab too (the overlapped sub-step fuses
-        exec_viscosity with the RHS, and the surface layer sits between them)."""
-        if self.surface is not None:
+        exec_viscosity with the RHS, and the surface layer sits between them). With `thermo` (thermo.Moist), the same plain sequence
+        with the means of thl and qt in front of exec_viscosity and Thermo_moist::exec behind it."""
+        means_done = False
+        if self.thermo is not None:
+            # Thermo_moist, in the order of Model::exec (src/model.cxx:346-392): the cyclic fills; fields->exec, the means of thl and qt
+            # (:351); exec_viscosity, whose N2 reads the thvref the previous sub-step left (:354); thermo->exec, the base state from
+            # the means and the buoyancy tendency in front of advec->exec (:366, :388)
+            self.cyclic_prognostic()
+            if self.thermo.swupdate:
+                means_done = self.thermo.means()
+            self.exec_viscosity()
+            self.thermo_moist()
+            if self.surface is not None:       # boundary->exec (:376) reads the thvref, thvrefh thermo->exec has just written
+                self.surface_layer()
+            self.rhs()
+        elif self.surface is not None:
             self.cyclic_prognostic()
             self.exec_viscosity()
             self.surface_layer()
@@ -499,7 +540,8 @@ class HotPath:
             self.exec_viscosity()
             self.rhs()
         if self.forcing is not None:
-            self.forcing_means()
+            if not means_done:
+                self.forcing_means()
             self.buffer_force()
         self.pres()
 

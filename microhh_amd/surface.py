@@ -33,7 +33,9 @@ class Surface:
     mbcbot "noslip" (ubot, vbot) or "ustar" (ustar); sbcbot per scalar "dirichlet" | "flux" | "neumann" with sbot the value,
     flux or gradient that set_bc fills in; z0m, z0h (uniform: swconstantz0); mbctop / sbctop / stop: the top conditions, used for
     the ghost cells. thermo: None = the case's (Thermo_buoy where the case says so, Thermo_dry with scalar 0 = th otherwise,
-    "0" without scalars), or "0" | "dry" | "buoy".
+    "0" without scalars, Thermo_moist where the HotPath has thermo=Moist(...)), or "0" | "dry" | "buoy" | "moist". With "moist"
+    scalar 0 is thl, scalar 1 is qt, both with the same kind of bottom bc, and the kernels read thvref, thvrefh at kstart from the
+    device tables the base state writes.
 
     bind() raises on what the library refuses: swconstantz0 = False (the iterative solvers), swcharnock, igc < 2 or jgc < 2.
     """
@@ -45,8 +47,8 @@ class Surface:
             raise ValueError("mbcbot: noslip | ustar; mbctop: noslip | freeslip | neumann")
         if mbcbot == "ustar" and ustar is None:
             raise ValueError("mbcbot = ustar needs ustar")
-        if thermo not in (None, "0", "dry", "buoy"):
-            raise ValueError("thermo: 0 | dry | buoy")
+        if thermo not in (None, "0", "dry", "buoy", "moist"):
+            raise ValueError("thermo: 0 | dry | buoy | moist")
         self.mbcbot, self.ubot, self.vbot, self.ustar_in = mbcbot, ubot, vbot, ustar
         self.sbcbot, self.sbot_in, self.z0m, self.z0h = sbcbot, sbot, z0m, z0h
         self.mbctop, self.utop, self.vtop, self.sbctop, self.stop_in = mbctop, utop, vtop, sbctop, stop
@@ -67,11 +69,19 @@ class Surface:
         self.hp = hp
         ns = self.ns = len(hp.s)
         n2 = g.shape2
-        thermo = self.thermo if self.thermo is not None else ("0" if ns == 0 else "buoy" if hp.cfg.get("thermo") == "buoy" else "dry")
+        moist = getattr(hp, "thermo", None)
+        thermo = self.thermo if self.thermo is not None else ("0" if ns == 0 else "moist" if moist is not None else
+                                                              "buoy" if hp.cfg.get("thermo") == "buoy" else "dry")
         if thermo != "0" and ns == 0:
             raise ValueError("thermo = %s needs scalar 0 (th or b)" % thermo)
-        self.kind = {"0": 0, "dry": 1, "buoy": 2}[thermo]
+        self.kind = {"0": 0, "dry": 1, "buoy": 2, "moist": 3}[thermo]
         bcs = [SBC[b] for b in _per_scalar(self.sbcbot, ns, "sbcbot")]
+        if self.kind == 3:
+            if moist is None or ns < 2:
+                raise ValueError("thermo = moist needs HotPath(..., thermo=Moist(...)) and the scalars 0 = thl, 1 = qt")
+            if bcs[1] != bcs[0]:
+                raise ValueError("thermo = moist: qt has another kind of bottom bc than thl (sbcbot %s): the buoyancy flux and the "
+                                 "surface buoyancy need both scalars' fluxes or both surface values" % (self.sbcbot,))
         self.bctop = [SBC[b] for b in _per_scalar(self.sbctop, ns, "sbctop")]
         vals, tops = _per_scalar(self.sbot_in, ns, "sbot"), _per_scalar(self.stop_in, ns, "stop")
         mbc = MBC[self.mbcbot]
@@ -112,6 +122,8 @@ class Surface:
             setattr(p, k, t.data_ptr())
         for n in range(ns):
             p.sbot[n], p.sgradbot[n], p.sbcbot[n] = self.sbot[n].data_ptr(), self.sgradbot[n].data_ptr(), bcs[n]
+        if self.kind == 3:
+            p.qt_index, p.thvref, p.thvrefh = 1, moist.tab["thvref"].data_ptr(), moist.tab["thvrefh"].data_ptr()
         self.bcs, self.mbc = bcs, mbc
         return self
 
