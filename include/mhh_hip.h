@@ -616,6 +616,48 @@ int mhh_thermo_moist_base_state(const mhh_grid* g, const void* thlmean, const vo
                                 void* pref, void* prefh, void* rhoref, void* rhorefh, void* thvref, void* thvrefh,
                                 void* exnref, void* exnrefh, int* nonconv, void* stream);
 
+/* ---- Microphys_2mom_warm (src/microphys_2mom_warm.cxx; Seifert & Beheng 2006, Stevens & Seifert 2008) and Limiter (src/limiter.cxx)
+ * Four scalars of the grid's dtype: thl, qt, qr (rain water specific humidity) and nr (rain drop number density), with their
+ * tendencies. rhoref, pref, exnref are [kcells] device tables (Thermo_moist's base state); ql is not an input: it is
+ * get_thermo_field("ql_qi"), max(qt - sat_adjust(thl, qt, pref[k], exnref[k]).qs, 0), evaluated per cell, and `nonconv` counts as in
+ * Thermo_moist. Column-local: nothing is read across a cell's column, so a slab rank needs no exchange. Every entry but the CFL
+ * number only enqueues on its stream.                                                                                            */
+#define MHH_MICRO_AUTO  1    /* autoconversion (:94-128)                                                  */
+#define MHH_MICRO_ACCR  2    /* accretion (:131-158)                                                       */
+#define MHH_MICRO_EVAP  4    /* evaporation (:278-318)                                                     */
+#define MHH_MICRO_SCBR  8    /* selfcollection and breakup (:321-370)                                      */
+#define MHH_MICRO_SEDI  16   /* sedimentation_ss08 (:373-539)                                              */
+#define MHH_MICRO_CLIP  32   /* remove_negative_values on qr and nr (:51-64), interior, in place           */
+#define MHH_MICRO_ALL   63
+typedef struct mhh_micro_params
+{
+    double Nc0;        /* the fixed cloud droplet number [m-3] (micro.Nc0)                                                   */
+    double dt;         /* the FULL time step, timeloop->get_dt(): sedimentation's CFL numbers and its limiter use it         */
+    int processes;     /* mask of MHH_MICRO_*: all of them is Microphys_2mom_warm::exec; one process into zeroed tendencies
+                          is a term of the swmicrobudget statistics (:831-925)                                                */
+} mhh_micro_params;
+#define MHH_MICRO_IMPL_MARCH 0   /* the local processes and the CFL numbers / slopes by one thread per column marching up in k */
+#define MHH_MICRO_IMPL_CELL  1   /* the same by one thread per cell and level (three levels of w recomputed): the same bits (A/B) */
+/* Microphys_2mom_warm::exec (:639-752). qr and nr are WRITTEN with MHH_MICRO_CLIP; their vertical ghost levels (kstart-1, kend) are
+ * read by the slopes and must be set. Per cell the tendencies take autoconversion, accretion, evaporation, selfcollection, breakup,
+ * then the sedimentation flux divergence. rr_bot: [ijcells], the surface rain rate -flux_qr[kstart] [kg m-2 s-1], written on the
+ * interior with MHH_MICRO_SEDI. scratch: a HOST array of four device pointers, each to kcells * ijcells elements of the dtype
+ * (sedimentation's CFL numbers and slopes of qr and nr: four tmp fields); may be NULL without MHH_MICRO_SEDI. The levels per chunk of the marching form follow MHH_MARCH_KC_RT.                             */
+int mhh_micro_2mom_warm_exec(const mhh_grid* g, const mhh_micro_params* params, void* qr, void* nr, const void* thl, const void* qt,
+                             void* qrt, void* nrt, void* thlt, void* qtt, void* rr_bot, const void* rhoref, const void* pref,
+                             const void* exnref, void* const* scratch, int* nonconv, void* stream);
+/* the same with the form named (MHH_MICRO_IMPL_*)                                                                               */
+int mhh_micro_2mom_warm_exec_impl(const mhh_grid* g, int impl, const mhh_micro_params* params, void* qr, void* nr, const void* thl, const void* qt,
+                                  void* qrt, void* nrt, void* thlt, void* qtt, void* rr_bot, const void* rhoref, const void* pref,
+                                  const void* exnref, void* const* scratch, int* nonconv, void* stream);
+/* calc_max_sedimentation_cfl (:163-234): the largest sedimentation CFL number of qr for the step dt, at least 1e-5; its velocity
+ * has no density correction and is mirrored over both ghost levels. work: mhh_reduce_work_bytes() of device memory. Synchronises
+ * the stream (the result is a host number), as mhh_advec_cfl does.                                                              */
+int mhh_micro_2mom_warm_cfl(const mhh_grid* g, const void* qr, const void* nr, const void* rhoref, double dt, void* work, double* out, void* stream);
+/* Limiter::tendency_limiter (src/limiter.cxx:54-75): at += (a + dt*at < 0) ? (-(a + dt*at) + eps)/dt : 0 on the interior, eps the
+ * double epsilon narrowed to the dtype; dt is the sub-step (src/model.cxx:415).                                                  */
+int mhh_limiter_exec(const mhh_grid* g, void* at, const void* a, double dt, void* stream);
+
 /* ---- Timeloop RK3/RK4 substep (src/timeloop.cxx:250-334, src/timeloop.cu:35-122) -------- */
 int mhh_rk_substep(const mhh_grid* g, int rkorder, int substep, double dt, void* a, void* at, void* stream);
 /* pres->exec(sub_dt) followed by timeloop.exec() for u, v, w (src/model.cxx:411,484): the sub-step rides in the pres_2 kernel that

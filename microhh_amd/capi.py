@@ -57,11 +57,16 @@ class MhhSurfaceParams(C.Structure):
                 ("qt_index", ci), ("thvref", vp), ("thvrefh", vp)]
 
 
+class MhhMicroParams(C.Structure):
+    _fields_ = [("Nc0", cd), ("dt", cd), ("processes", ci)]
+
+
 FP = C.POINTER(MhhFields)
 SP = C.POINTER(MhhSurfaceParams)
 DP = C.POINTER(MhhDiffParams)
 BP = C.POINTER(MhhBufferParams)
 FRP = C.POINTER(MhhForceParams)
+MP = C.POINTER(MhhMicroParams)
 PLAN = vp
 
 SIGNATURES = {
@@ -178,6 +183,10 @@ SIGNATURES = {
     "mhh_thermo_moist_fields": (ci, [GP, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "mhh_thermo_moist_base_state_host": (ci, [GP, vp, vp, cd, ci, cd, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "mhh_thermo_moist_base_state": (ci, [GP, vp, vp, cd, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mhh_micro_2mom_warm_exec": (ci, [GP, MP] + [vp]*15),
+    "mhh_micro_2mom_warm_exec_impl": (ci, [GP, ci, MP] + [vp]*15),
+    "mhh_micro_2mom_warm_cfl": (ci, [GP, vp, vp, vp, cd, vp, C.POINTER(cd), vp]),
+    "mhh_limiter_exec": (ci, [GP, vp, vp, cd, vp]),
 }
 
 

@@ -1206,4 +1206,168 @@ template<class TF> MHH_HD MoistSat<TF> moist_sat_adjust(TF thl, TF qt, TF p, TF 
     return ans;
 }
 
+// ---- Microphys_2mom_warm (src/microphys_2mom_warm.cxx, include/microphys_2mom_warm.h; Seifert & Beheng 2006, Stevens & Seifert
+// 2008), in the reference's expression order. pow, exp and sqrt are the unqualified calls the reference writes.
+// Micro_2mom_warm_constants (include/microphys_2mom_warm.h:52-68): each a double literal narrowed to TF, pirhow the TF quotient.
+template<class TF> struct MicroC
+{
+    static constexpr TF pi = TF(3.14159265359), K_t = TF(2.5e-2), D_v = TF(3.e-5), rho_w = TF(1.e3), rho_0 = TF(1.225);
+    static constexpr TF pirhow = pi*rho_w/TF(6.), mr_min = TF(2.6e-10), mr_max = TF(3e-6), ql_min = TF(1.e-6), qr_min = TF(1.e-15);
+    static constexpr double dsmall = 1.e-9;                   // include/constants.h:97: a double in both builds
+};
+// the process mask of mhh_micro_params (include/mhh_hip.h)
+constexpr int MICRO_AUTO = 1, MICRO_ACCR = 2, MICRO_EVAP = 4, MICRO_SCBR = 8, MICRO_SEDI = 16, MICRO_CLIP = 32;
+constexpr int MICRO_LOCAL = MICRO_AUTO | MICRO_ACCR | MICRO_EVAP | MICRO_SCBR;
+// :76-117
+template<class TF> MHH_HD TF micro_tanh2(TF x) { return x * (TF(27) + x * x) / (TF(27) + TF(9) * x * x); }
+template<class TF> MHH_HD TF micro_rain_mass(TF qr, TF nr, TF rho)
+{
+    const TF mr = rho * qr / tmax(nr, TF(1.));
+    return tmin(tmax(mr, MicroC<TF>::mr_min), MicroC<TF>::mr_max);
+}
+template<class TF> MHH_HD TF micro_rain_diameter(TF mr) { return pow(mr/MicroC<TF>::pirhow, TF(1.)/TF(3.)); }
+template<class TF> MHH_HD TF micro_mu_r(TF dr) { return TF(10) * (TF(1) + micro_tanh2(TF(1200) * (dr - TF(0.0015)))); }
+template<class TF> MHH_HD TF micro_lambda_r(TF mur, TF dr) { return pow((mur+3)*(mur+2)*(mur+1), TF(1.)/TF(3.)) / dr; }
+// :120-127: copysign(1, a) is exact, so the precision it is multiplied in does not show
+template<class TF> MHH_HD TF micro_minmod(TF a, TF b)
+{
+    const TF s = TF(__builtin_copysign(1., double(a)));
+    return s * tmax(TF(0.), tmin(tabs(a), s*b));
+}
+// prepare_microphysics_slice (src/microphys_2mom_warm.cxx:243-275): zeros where qr <= qr_min
+template<class TF> struct MicroRain { TF mr, dr, mur, lambdar; };
+template<class TF> MHH_HD MicroRain<TF> micro_rain(TF qr, TF nr, TF rho)
+{
+    MicroRain<TF> r = {TF(0), TF(0), TF(0), TF(0)};
+    if (qr > MicroC<TF>::qr_min)
+    {
+        r.mr = micro_rain_mass(qr, nr, rho);
+        r.dr = micro_rain_diameter(r.mr);
+        r.mur = micro_mu_r(r.dr);
+        r.lambdar = micro_lambda_r(r.mur, r.dr);
+    }
+    return r;
+}
+// The tendencies of one cell; the kernels add the processes of the mask in the order autoconversion, accretion, evaporation,
+// selfcollection, breakup, as Microphys_2mom_warm::exec's calls do per cell (:694-730).
+template<class TF> struct MicroTend { TF qrt, nrt, thlt, qtt; };
+// autoconversion (:94-128)
+template<class TF> MHH_HD void micro_autoconversion(MicroTend<TF>& t, TF qr, TF ql, TF rho, TF exner, TF nc)
+{
+    typedef MicroC<TF> K;
+    const TF x_star = 2.6e-10;
+    const TF k_cc   = 9.44e9;
+    const TF nu_c   = 1;
+    const TF kccxs  = k_cc / (TF(20.) * x_star) * (nu_c+2)*(nu_c+4) / sq(nu_c+1);
+    if (ql > K::ql_min)
+    {
+        const TF xc      = rho * ql / nc;
+        const TF tau     = TF(TF(1.) - ql / (ql + qr + K::dsmall));
+        const auto p68   = TF(1.) - pow(tau, TF(0.68));     // fm::pow3 deduces its type from the argument
+        const TF phi_au  = TF(600.) * pow(tau, TF(0.68)) * (p68*p68*p68);
+        const TF au_tend = K::rho_0 * kccxs * sq(ql) * sq(xc) *
+                               (TF(1.) + phi_au / sq(TF(1.)-tau));
+        t.qrt  += au_tend;
+        t.nrt  += au_tend * rho / x_star;
+        t.qtt  -= au_tend;
+        t.thlt += MoistC<TF>::Lv / (MoistC<TF>::cp * exner) * au_tend;
+    }
+}
+// accretion (:131-158)
+template<class TF> MHH_HD void micro_accretion(MicroTend<TF>& t, TF qr, TF ql, TF rho, TF exner)
+{
+    typedef MicroC<TF> K;
+    const TF k_cr = 5.25;
+    if (ql > K::ql_min && qr > K::qr_min)
+    {
+        const TF tau     = TF(1.) - ql / (ql + qr);
+        const TF t5      = tau / (tau + TF(5e-5));
+        const TF phi_ac  = t5*t5*t5*t5;
+        const TF ac_tend = k_cr * ql *  qr * phi_ac * sqrt(K::rho_0 / rho);
+        t.qrt  += ac_tend;
+        t.qtt  -= ac_tend;
+        t.thlt += MoistC<TF>::Lv / (MoistC<TF>::cp * exner) * ac_tend;
+    }
+}
+// evaporation (:278-318)
+template<class TF> MHH_HD void micro_evaporation(MicroTend<TF>& t, TF qr, TF nr, TF ql, TF qt, TF thl, TF rho, TF exner, TF p, const MicroRain<TF>& r)
+{
+    typedef MicroC<TF> K; typedef MoistC<TF> M;
+    const TF lambda_evap = 1.;
+    if (qr > K::qr_min)
+    {
+        const TF mr  = r.mr;
+        const TF dr  = r.dr;
+        const TF T   = thl * exner + (M::Lv * ql) / (M::cp * exner);
+        const TF Glv = TF(1.) / (M::Rv * T / (moist_esat_liq(T) * K::D_v) +
+                           (M::Lv / (K::K_t * T)) * (M::Lv / (M::Rv * T) - TF(1.)));
+        const TF S   = (qt - ql) / moist_qsat_liq(p, T) - TF(1.);
+        const TF F   = 1.;
+        const TF ev_tend = TF(2.) * K::pi * dr * Glv * S * F * nr / rho;
+        t.qrt  += ev_tend;
+        t.nrt  += lambda_evap * ev_tend * rho / mr;
+        t.qtt  -= ev_tend;
+        t.thlt += M::Lv / (M::cp * exner) * ev_tend;
+    }
+}
+// selfcollection_breakup (:321-370)
+template<class TF> MHH_HD void micro_selfcollection_breakup(MicroTend<TF>& t, TF qr, TF nr, TF rho, const MicroRain<TF>& r)
+{
+    typedef MicroC<TF> K;
+    const TF k_rr     = 7.12;
+    const TF kappa_rr = 60.7;
+    const TF D_eq     = 0.9e-3;
+    const TF k_br1    = 1.0e3;
+    const TF k_br2    = 2.3e3;
+    if (qr > K::qr_min)
+    {
+        const TF dr      = r.dr;
+        const TF lambdar = r.lambdar;
+        const auto a9 = TF(1.) + kappa_rr / lambdar * pow(K::pirhow, TF(1.)/TF(3.));     // fm::pow9 deduces its type from the argument
+        const TF sc_tend = -k_rr * nr * qr*rho / (a9*a9*a9*a9*a9*a9*a9*a9*a9) * sqrt(K::rho_0 / rho);
+        t.nrt += sc_tend;
+        const TF dDr = dr - D_eq;
+        if (dr > TF(0.35e-3))
+        {
+            TF phi_br;
+            if (dr <= D_eq)
+                phi_br = k_br1 * dDr;
+            else
+                phi_br = TF(2.) * exp(k_br2 * dDr) - TF(1.);
+            const TF br_tend = -(phi_br + TF(1.)) * sc_tend;
+            t.nrt += br_tend;
+        }
+    }
+}
+// The sedimentation velocities of qr (4) and nr (1): step 1 of sedimentation_ss08 (:398-419) with rho_n = sqrt(1.2/rho[k]), and
+// calc_max_sedimentation_cfl's (:185-198) with rho_n = 1 left out of the expression (its a_R stands alone).
+template<class TF> MHH_HD TF micro_b_R() { const TF a_R = 9.65; const TF c_R = 600; const TF Dv = 25.0e-6; return a_R * exp(c_R*Dv); }
+template<class TF> MHH_HD TF micro_w_sedi(TF qr, const MicroRain<TF>& r, TF rho_n, TF b_R, TF moment)
+{
+    const TF w_max = 9.65; const TF a_R = 9.65; const TF c_R = 600;
+    if (qr > MicroC<TF>::qr_min)
+        return tmin(w_max, tmax(TF(0.1), rho_n * a_R - b_R * TF(pow(TF(1.) + c_R/r.lambdar, TF(-1.)*(r.mur+moment)))));
+    return TF(0.);
+}
+template<class TF> MHH_HD TF micro_w_cfl(TF qr, TF nr, TF rho, TF b_R)
+{
+    const TF w_max = 9.65; const TF a_R = 9.65; const TF c_R = 600;
+    if (qr > MicroC<TF>::qr_min)
+    {
+        const TF mr      = micro_rain_mass(qr, nr, rho);
+        const TF dr      = micro_rain_diameter(mr);
+        const TF mur     = micro_mu_r(dr);
+        const TF lambdar = micro_lambda_r(mur, dr);
+        return tmin(w_max, tmax(TF(0.1), a_R - b_R * TF(pow(TF(1.) + c_R/lambdar, TF(-1.)*(mur+TF(4.))))));
+    }
+    return TF(0.);
+}
+// Limiter::tendency_limiter (src/limiter.cxx:54-75): eps is the double epsilon narrowed to TF
+template<class TF> MHH_HD TF limiter_increment(TF a, TF at, TF dt, TF dti)
+{
+    constexpr TF eps = TF(2.220446049250313e-16);
+    const TF a_new = a + dt*at;
+    return (a_new < TF(0.)) ? (-a_new + eps) * dti : TF(0.);
+}
+
 } // namespace mhh

@@ -827,3 +827,4 @@ MHH_API int mhh_boundary_ghost_cells_w(const mhh_grid* g, void* w, int type, voi
 // Thermo_moist: saturation adjustment, buoyancy tendency, diagnostic fields, base state (src/thermo_moist.cxx)
 // =======================================================================================================
 #include "thermo_moist.h"
+#include "microphys_2mom_warm.h"

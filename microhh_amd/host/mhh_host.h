@@ -865,4 +865,65 @@ class Thermo_moist
         Grid<TF>& grid; Fields<TF>& fields;
 };
 
+// ---- Microphys_2mom_warm (src/microphys_2mom_warm.cxx): swmicro = 2mom_warm with the scalars thl, qt, qr and nr ------------------
+// rr_bot_g ([ijcells]), the four scratch fields ([ncells] each: the reference's get_tmp_g) and work_g (mhh_reduce_work_bytes()) are
+// the caller's device arrays. The base state, rhoref included, comes from the Thermo_moist it is handed, as the reference's exec
+// takes its thermo.
+template<typename TF>
+class Microphys_2mom_warm
+{
+    public:
+        Microphys_2mom_warm(Grid<TF>& grid_in, Fields<TF>& fields_in) : grid(grid_in), fields(fields_in) {}
+        // [micro] Nc0, cflmax
+        TF Nc0 = 0; TF cflmax = 2.;
+        int processes = MHH_MICRO_ALL;
+        TF* rr_bot_g = nullptr; TF* scratch_g[4] = {nullptr, nullptr, nullptr, nullptr}; void* work_g = nullptr;
+        std::string get_switch() const { return "2mom_warm"; }
+
+        // Microphys_2mom_warm::exec (:639-752); dt is the full step, timeloop->get_dt()
+        void exec(Thermo_moist<TF>& thermo, const double dt, void* stream = nullptr)
+        {
+            if (!(Nc0 > 0)) throw std::runtime_error("Microphys_2mom_warm: Nc0 (no default)");
+            mhh_grid g = grid.abi();
+            mhh_micro_params p{}; p.Nc0 = Nc0; p.dt = dt; p.processes = processes;
+            void* const scratch[4] = {scratch_g[0], scratch_g[1], scratch_g[2], scratch_g[3]};
+            mhh_check(mhh_micro_2mom_warm_exec(&g, &p, fields.sp.at("qr")->fld_g, fields.sp.at("nr")->fld_g, fields.sp.at("thl")->fld_g, fields.sp.at("qt")->fld_g,
+                                               fields.st.at("qr")->fld_g, fields.st.at("nr")->fld_g, fields.st.at("thl")->fld_g, fields.st.at("qt")->fld_g, rr_bot_g,
+                                               fields.rhoref_g, thermo.pref_g, thermo.exnref_g, scratch, thermo.nonconv_g, stream));
+        }
+        // get_time_limit (:965-982): idt * cflmax / cfl in TF, truncated. `max_over_ranks` is Master::max (the identity on one rank).
+        template<class Max> unsigned long get_time_limit(unsigned long idt, const double dt, Max&& max_over_ranks, void* stream = nullptr)
+        {
+            mhh_grid g = grid.abi();
+            double out = 0;
+            mhh_check(mhh_micro_2mom_warm_cfl(&g, fields.sp.at("qr")->fld_g, fields.sp.at("nr")->fld_g, fields.rhoref_g, dt, work_g, &out, stream));
+            TF cfl = TF(out);
+            max_over_ranks(&cfl);
+            return idt * cflmax / cfl;
+        }
+        unsigned long get_time_limit(unsigned long idt, const double dt) { return get_time_limit(idt, dt, [](TF*) {}); }
+        // get_surface_rain_rate: the device array exec wrote
+        TF* get_surface_rain_rate() const { return rr_bot_g; }
+    private:
+        Grid<TF>& grid; Fields<TF>& fields;
+};
+
+// ---- Limiter (src/limiter.cxx): [limiter] limitlist ----------------------------------------------------------------------------
+template<typename TF>
+class Limiter
+{
+    public:
+        Limiter(Grid<TF>& grid_in, Fields<TF>& fields_in) : grid(grid_in), fields(fields_in) {}
+        std::vector<std::string> limit_list;
+        // Limiter::exec (:78-94) with the sub-step dt
+        void exec(const double dt, void* stream = nullptr)
+        {
+            mhh_grid g = grid.abi();
+            for (const std::string& name : limit_list)
+                mhh_check(mhh_limiter_exec(&g, fields.st.at(name)->fld_g, fields.sp.at(name)->fld_g, dt, stream));
+        }
+    private:
+        Grid<TF>& grid; Fields<TF>& fields;
+};
+
 } // namespace mhh_host

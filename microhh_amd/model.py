@@ -4,6 +4,7 @@ that this package accelerates, expressed as calls into the C ABI.
     boundary->set_prognostic_cyclic_bcs   -> mhh_boundary_cyclic_n (+ N-S neighbour exchange)   (src/model.cxx:346)
     diff->exec_viscosity(thermo)          -> mhh_diff_exec_viscosity (+ N-S exchange of evisc)   (:354)
     thermo->exec (Thermo_moist)           -> mhh_thermo_moist_base_state, mhh_thermo_moist_buoyancy_tend (thermo=..., opt-in) (:366)
+    microphys->exec ; limiter->exec       -> mhh_micro_2mom_warm_exec, mhh_limiter_exec (micro=..., opt-in) (:369, :415)
     boundary->exec ; set_ghost_cells      -> mhh_boundary_surface_exec, mhh_boundary_ghost_cells (surface=..., opt-in) (:374-375)
     advec->exec ; diff->exec              -> mhh_rhs_exec (fused, same bits)                     (:388, :392)
     fields->exec ; buffer->exec ; force->exec -> mhh_field_mean_*, mhh_buffer_force_exec (forcing=..., opt-in) (:351, :395, :404)
@@ -45,6 +46,10 @@ CASES = {
     # the thermodynamics on. The schemes are upstream's choice for the case; this fork's cases/bomex/bomex.ini says swadvec=2.
     "bomex": dict(advec=ADVEC_2I5, diff=DIFF_SMAG2, pres=2, order=2, gc=(3, 3, 1), size=(6400., 6400., 3000.), nscalars=2, sm=1, visc=1e-5,
                   thermo="moist", pbot=101500.),
+    # rico (cases/rico/rico.ini): Thermo_moist with Microphys_2mom_warm, scalars 0 = thl, 1 = qt, 2 = qr, 3 = nr, pbot = 101540 Pa, the
+    # schemes of bomex; HotPath(..., thermo=thermo.Moist(pbot), micro=microphys.Warm2mom(Nc0)) switches the physics on.
+    "rico": dict(advec=ADVEC_2I5, diff=DIFF_SMAG2, pres=2, order=2, gc=(3, 3, 1), size=(12800., 12800., 4000.), nscalars=4, sm=1, visc=1e-5,
+                 thermo="moist", pbot=101540., micro="2mom_warm", Nc0=70.e6),
 }
 
 FIELDS3 = ("u", "v", "w", "ut", "vt", "wt")
@@ -68,6 +73,10 @@ def synthetic_global(case, itot, jtot, ktot, dtype=np.float64, seed=666, nscalar
     if cfg.get("thermo") == "moist" and "s1" in out:
         from .thermo import bomex_interior
         out["s0"], out["s1"] = bomex_interior(z, n3, rs)
+    if cfg.get("micro") == "2mom_warm" and "s3" in out:
+        from .microphys import synthetic_rain
+        out["s2"], out["s3"] = synthetic_rain(z, n3, rs)
+        out["st2"], out["st3"] = rs.uniform(-1e-8, 1e-8, n3), rs.uniform(-1., 1., n3)
     for k in SURF:
         out[k] = rs.uniform(0, 1e-4 if k == "dbdz" else 1e-2, n2)
     out["z0m"][:] = 0.1
@@ -79,7 +88,7 @@ class HotPath:
 
     def __init__(self, case, itot, jtot, ktot, dtype=np.float64, device="cuda:0", seed=666, dt=1.0,
                  lib=None, npy=1, rank=0, group=None, global_init=None, force_slab=False, slim_halos=True, overlap=None, pres_chunks=None, igc=None,
-                 nscalars=None, forcing=None, surface=None, thermo=None):
+                 nscalars=None, forcing=None, surface=None, thermo=None, micro=None):
         import torch
         self.torch = torch
         self.lib = lib if lib is not None else capi.lib()
@@ -161,7 +170,7 @@ class HotPath:
             self.st = [put3(global_init["st%d" % n]) for n in range(nsc)]
             self.surf = {k: put2(global_init[k]) for k in SURF}
             if cfg.get("thermo") == "moist":     # the mean profiles of thl and qt are read on the ghost levels too: zero gradient there
-                for t in self.s[:2]:
+                for t in self.s[:2] + (self.s[2:4] if micro is not None else []):      # (as are qr and nr by sedimentation's slopes)
                     t[:g.kstart] = t[g.kstart]; t[g.kend:] = t[g.kend-1]
         if surface is not None:          # before the mixing-length table below is made from it
             self.surf["z0m"].fill_(float(surface.z0m))
@@ -239,6 +248,8 @@ class HotPath:
         self.forcing = forcing.bind(self) if forcing is not None else None
         # Boundary_surface (surface.Surface): its state (ustar, obuk, nobuk), the lookup table and one s_fluxbot / sbot / sgradbot per scalar
         self.surface = surface.bind(self) if surface is not None else None
+        # Microphys_2mom_warm and Limiter (microphys.Warm2mom): the rain rate, sedimentation's scratch
+        self.micro = micro.bind(self) if micro is not None else None
         self.cyclic_prognostic()
         self.sync()
 
@@ -525,6 +536,8 @@ class HotPath:
                 means_done = self.thermo.means()
             self.exec_viscosity()
             self.thermo_moist()
+            if self.micro is not None:         # microphys->exec (:369), between thermo->exec and boundary->exec
+                self.micro.exec()
             if self.surface is not None:       # boundary->exec (:376) reads the thvref, thvrefh thermo->exec has just written
                 self.surface_layer()
             self.rhs()
@@ -544,6 +557,8 @@ class HotPath:
                 self.forcing_means()
             self.buffer_force()
         self.pres()
+        if self.micro is not None:             # limiter->exec with the sub-step (:415), the last tendency
+            self.micro.limit()
 
     def capture_step(self):
         """One step recorded as a hipGraph (single GPU): every entry point of the library only enqueues work on the stream it is
