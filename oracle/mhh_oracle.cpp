@@ -1752,6 +1752,41 @@ ORC_API void orc_pres2_coeffs(const mhh_grid* g, const void* rh, double* bmati, 
     std::copy(aa.begin(), aa.end(), a); std::copy(cc.begin(), cc.end(), c);
 }
 
+// the same tables in the grid's own type, as Pres_2 / Pres_4::set_values keep them: bmati[itot], bmatj[jtot] and the bands, kmax values
+// each: a, c (order 2) or m1..m7 (order 4)
+template<class TF>
+static void pres_coeffs_t(const mhh_grid& g, int order, const void* rh, void* bmati, void* bmatj, void* bands)
+{
+    std::vector<TF> bi, bj;
+    std::vector<std::vector<TF>> b;
+    if (order == 2)
+    {
+        b.resize(2);
+        pres2_set_values<TF>(g, P<TF>(rh), bi, bj, b[0], b[1]);
+    }
+    else
+    {
+        Pres4Mat<TF> M; pres4_set_values<TF>(g, M);
+        bi = M.bmati; bj = M.bmatj;
+        b = {M.m1, M.m2, M.m3, M.m4, M.m5, M.m6, M.m7};
+    }
+    std::copy(bi.begin(), bi.end(), P<TF>(bmati)); std::copy(bj.begin(), bj.end(), P<TF>(bmatj));
+    for (size_t n=0; n<b.size(); ++n) std::copy(b[n].begin(), b[n].end(), P<TF>(bands) + n*g.kmax);
+}
+ORC_API void orc_pres_coeffs(const mhh_grid* g, int order, const void* rh, void* bmati, void* bmatj, void* bands)
+{ DISPATCH(g, pres_coeffs_t<double>(*g, order, rh, bmati, bmatj, bands), pres_coeffs_t<float>(*g, order, rh, bmati, bmatj, bands)); }
+
+// the tail of Pres::solve alone: packed values onto the grid, the Neumann ghost levels, the cyclic fill
+ORC_API void orc_pres_unpack(const mhh_grid* g, int order, void* p, const void* p_packed)
+{
+    if (order == 2) DISPATCH(g, pres2_unpack<double>(*g, D(p), D(p_packed)), pres2_unpack<float>(*g, F(p), F(p_packed)));
+    else            DISPATCH(g, pres4_unpack<double>(*g, D(p), D(p_packed)), pres4_unpack<float>(*g, F(p), F(p_packed)));
+}
+
+// Boundary_cyclic::exec / exec_2d (unsigned int*), src/boundary_cyclic.cxx:510-647
+ORC_API void orc_boundary_cyclic_uint(const mhh_grid* g, unsigned int* a, int edge) { cyclic<unsigned int>(*g, a, edge); }
+ORC_API void orc_boundary_cyclic_2d_uint(const mhh_grid* g, unsigned int* a) { cyclic_2d<unsigned int>(*g, a); }
+
 ORC_API void orc_rk_substep(const mhh_grid* g, int order, int substep, double dt, void* a, void* at)
 { DISPATCH(g, rk_substep<double>(*g, order, substep, dt, D(a), D(at)), rk_substep<float>(*g, order, substep, (float)dt, F(a), F(at))); }
 

@@ -1,7 +1,7 @@
 #include "/root/reference/src/diff_smag2.cxx"
 #include "ref_common.h"
-// calc_evisc / calc_evisc_neutral are NOT wrapped: they end in Boundary_cyclic::exec -> Grid::get_grid_data,
-// and src/grid.cxx needs netcdf.h, which this image lacks (see DESIGN.md "Oracle").
+// calc_evisc / calc_evisc_neutral are not wrapped HERE: they end in Boundary_cyclic::exec -> Grid::get_grid_data, which this
+// stub-free library does not define. tests/cpp/ref_pres_shim.cpp wraps them behind its seam (see DESIGN.md "Oracle", item 3).
 template<class TF> static void strain2(const mhh_grid* g, int sm, void* s2, const void* u, const void* v, const void* w, const void* dudz, const void* dvdz)
 {
     // call-site argument spelling of Diff_smag2::exec_viscosity (src/diff_smag2.cxx:1059-1089): 1./gd.dx narrowed to TF

@@ -1,5 +1,6 @@
-"""Pin the oracle's pressure solver (pres_2 / pres_4). The reference TUs for this stage need fftw3.h and
-cannot be built here, so the restatement is pinned by independent mathematics instead:
+"""Pin the oracle's pressure solver (pres_2 / pres_4) by independent mathematics. Since tests/test_pres_ref.py the restatement is also
+held bit for bit against the reference's own src/pres_2.cxx and src/pres_4.cxx (coefficients, input, the spectral solve, unpack, output),
+with the oracle's DFT in the reference's FFT seam. What only this module pins is that DFT itself, which FFTW's plan-dependent bits cannot:
   * FFT stage vs numpy.fft (pocketfft) through the FFTW half-complex mapping (src/fft.cxx:143-150),
   * modified wave numbers / tridiagonal coefficients vs their closed forms (src/pres_2.cxx:125-153),
   * the spectral solve vs a dense numpy solve of the same banded system,
@@ -54,6 +55,35 @@ def test_pres2_coefficients():
     k = np.arange(g.kmax) + g.kgc
     assert np.allclose(a, g.dz[k]*c.rhorefh[k]*g.dzhi[k], rtol=1e-15)
     assert np.allclose(cc, g.dz[k]*c.rhorefh[k+1]*g.dzhi[k+1], rtol=1e-15)
+
+
+def test_pres2_coefficients_fp32():
+    """The fp32 tables, where Pres_2::set_values mixes double and float (2. * (std::cos(2.*pi*(TF)j/(TF)jtot)-1.) * dyidyi): the
+    reference's own values from tests/golden/pres_ref.npz against the closed forms, within the roundings of one float table entry (the
+    quotient j/jtot and dyidyi are floats: 2 eps32 of the entry each, the cosine's argument error enters as sin/(1-cos) <= 2/x times
+    eps32, bounded here by the absolute term), and the oracle's fp32 tables against them bit for bit."""
+    import pres_ref as R
+    case = R.CASES[0]
+    assert case == (2, (16, 12, 10), (1, 1, 1))
+    g, c = R.inputs(case, np.float32)
+    key = "coeffs/%s/f32/" % R.case_id(case)
+    z = R.golden()
+    bi, bj, bands = z[key + "bmati"], z[key + "bmatj"], z[key + "bands"]
+    assert bi.dtype == np.float32 and bands.shape == (2, g.kmax)
+    got = [np.zeros(g.itot, np.float32), np.zeros(g.jtot, np.float32), np.zeros((2, g.kmax), np.float32)]
+    cm.oracle().orc_pres_coeffs(g.host_struct(), 2, ptr(c.rhorefh), *[ptr(a) for a in got])
+    assert cm.same(got[0], bi) and cm.same(got[1], bj) and cm.same(got[2], bands)
+    eps = float(np.finfo(np.float32).eps)
+    i = np.arange(g.itot); i = np.minimum(i, g.itot - i)
+    j = np.arange(g.jtot); j = np.minimum(j, g.jtot - j)
+    wi = 2.*(np.cos(2*np.pi*i/g.itot)-1.)/float(g.dx)**2
+    wj = 2.*(np.cos(2*np.pi*j/g.jtot)-1.)/float(g.dy)**2
+    assert np.allclose(bi, wi, rtol=4*eps, atol=4*eps*np.abs(wi).max())
+    assert np.allclose(bj, wj, rtol=4*eps, atol=4*eps*np.abs(wj).max())
+    k = np.arange(g.kmax) + g.kgc
+    d = np.float64
+    assert np.allclose(bands[0], g.dz[k].astype(d)*c.rhorefh[k].astype(d)*g.dzhi[k].astype(d), rtol=2*eps)
+    assert np.allclose(bands[1], g.dz[k].astype(d)*c.rhorefh[k+1].astype(d)*g.dzhi[k+1].astype(d), rtol=2*eps)
 
 
 def test_pres2_spectral_solve_is_tridiagonal_solve():
