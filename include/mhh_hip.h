@@ -658,6 +658,39 @@ int mhh_micro_2mom_warm_cfl(const mhh_grid* g, const void* qr, const void* nr, c
  * double epsilon narrowed to the dtype; dt is the sub-step (src/model.cxx:415).                                                  */
 int mhh_limiter_exec(const mhh_grid* g, void* at, const void* a, double dt, void* stream);
 
+/* ---- Radiation_gcss (src/radiation_gcss.cxx: the GCSS long- and short-wave fluxes of DYCOMS-II, swradiation = gcss) -------------
+ * The parity target is the reference's CPU path; its CUDA file (src/radiation_gcss.cu) differs from it in physics (no max(0, .),
+ * dz for z[k]-z[k-1], lwp subtracted on the way up, the flux difference shifted by a level). Column-local: a slab rank exchanges
+ * nothing. The fluxes need ql, thl's tendency takes their vertical difference. What looks like a slip in the reference is kept
+ * (csrc/cell_ops.h names each with its line). Every entry but the zenith angle only enqueues on its stream, so a sub-step with it
+ * still captures into a graph; `mu` is a HOST number fixed at capture, as dt is for the microphysics: re-capture when the sun moved. */
+#define MHH_RAD_LW 1      /* the long-wave term of thlt (calc_gcss_rad_LW :203-252, the tendency :273-285)                       */
+#define MHH_RAD_SW 2      /* the short-wave term (calc_gcss_rad_SW + sunray :101-200, :287-308); applied only where mu > 0.035 in the dtype */
+typedef struct mhh_radiation_gcss_params
+{
+    double xka, fr0, fr1, div;   /* radiation.xka, fr0, fr1, div (:317-320): narrowed to the dtype on entry, the members are TF   */
+    double mu;                   /* the cosine of the zenith angle, from mhh_radiation_gcss_zenith_host; narrowed likewise       */
+    int parts;                   /* MHH_RAD_LW | MHH_RAD_SW: the terms thlt takes; both is Radiation_gcss::exec                    */
+} mhh_radiation_gcss_params;
+#define MHH_RAD_IMPL_SWEEP 0   /* one kernel, an upward and a downward sweep per column, one scratch field between them          */
+#define MHH_RAD_IMPL_PLAIN 1   /* the reference's sequence: a column kernel per flux array, a cell kernel for thlt: the same bits (A/B) */
+/* calc_zenith (:39-76) with the host's C library in the dtype; day_of_year as Timeloop::calc_day_of_year gives it (the day of the
+ * year counted from 1, plus the fraction of the day: 2001-06-09 00:00 UTC is 160.0).                                              */
+int mhh_radiation_gcss_zenith_host(int dtype, double lat, double lon, double day_of_year, double* mu);
+/* Radiation_gcss::exec (:353-379: exec_gcss_rad :253-309) and get_radiation_field (:392-436) in one call.
+ * thlt: the tendency of thl, interior levels kstart+1 .. kend-1 (NULL: fields only). ql: [ncells] (NULL: it is
+ * get_thermo_field("ql") of thl, qt, pref, exnref, written to scratch[0]; `nonconv` counts as in Thermo_moist). lflx, sflx:
+ * get_radiation_field("lflx" / "sflx"), either may be NULL; lflx is written on the interior, sflx on the interior over a zero fill
+ * of all ncells, and stays all zero at night (mu <= 0.035). Both are formed whatever `parts` says. scratch: a HOST array of two
+ * device pointers to ncells elements of the dtype each (two tmp fields; the reference's CPU path takes four).                      */
+int mhh_radiation_gcss_exec(const mhh_grid* g, const mhh_radiation_gcss_params* params, void* thlt, const void* ql, const void* thl,
+                            const void* qt, const void* rhoref, const void* pref, const void* exnref, void* lflx, void* sflx,
+                            void* const* scratch, int* nonconv, void* stream);
+/* the same with the form named (MHH_RAD_IMPL_*)                                                                                  */
+int mhh_radiation_gcss_exec_impl(const mhh_grid* g, int impl, const mhh_radiation_gcss_params* params, void* thlt, const void* ql, const void* thl,
+                                 const void* qt, const void* rhoref, const void* pref, const void* exnref, void* lflx, void* sflx,
+                                 void* const* scratch, int* nonconv, void* stream);
+
 /* ---- Timeloop RK3/RK4 substep (src/timeloop.cxx:250-334, src/timeloop.cu:35-122) -------- */
 int mhh_rk_substep(const mhh_grid* g, int rkorder, int substep, double dt, void* a, void* at, void* stream);
 /* pres->exec(sub_dt) followed by timeloop.exec() for u, v, w (src/model.cxx:411,484): the sub-step rides in the pres_2 kernel that

@@ -61,12 +61,17 @@ class MhhMicroParams(C.Structure):
     _fields_ = [("Nc0", cd), ("dt", cd), ("processes", ci)]
 
 
+class MhhRadiationGcssParams(C.Structure):
+    _fields_ = [("xka", cd), ("fr0", cd), ("fr1", cd), ("div", cd), ("mu", cd), ("parts", ci)]
+
+
 FP = C.POINTER(MhhFields)
 SP = C.POINTER(MhhSurfaceParams)
 DP = C.POINTER(MhhDiffParams)
 BP = C.POINTER(MhhBufferParams)
 FRP = C.POINTER(MhhForceParams)
 MP = C.POINTER(MhhMicroParams)
+RP = C.POINTER(MhhRadiationGcssParams)
 PLAN = vp
 
 SIGNATURES = {
@@ -187,6 +192,9 @@ SIGNATURES = {
     "mhh_micro_2mom_warm_exec_impl": (ci, [GP, ci, MP] + [vp]*15),
     "mhh_micro_2mom_warm_cfl": (ci, [GP, vp, vp, vp, cd, vp, C.POINTER(cd), vp]),
     "mhh_limiter_exec": (ci, [GP, vp, vp, cd, vp]),
+    "mhh_radiation_gcss_zenith_host": (ci, [ci, cd, cd, cd, C.POINTER(cd)]),
+    "mhh_radiation_gcss_exec": (ci, [GP, RP] + [vp]*12),
+    "mhh_radiation_gcss_exec_impl": (ci, [GP, ci, RP] + [vp]*12),
 }
 
 

@@ -1370,4 +1370,126 @@ template<class TF> MHH_HD TF limiter_increment(TF a, TF at, TF dt, TF dti)
     return (a_new < TF(0.)) ? (-a_new + eps) * dti : TF(0.);
 }
 
+// ---- Radiation_gcss (src/radiation_gcss.cxx: the GCSS long- and short-wave parameterisation of DYCOMS), the CPU path, in the
+// reference's expression order. std::exp, std::sqrt and std::pow are the calls the reference writes: the overload of TF in the
+// device and in the emulation build. What looks like a slip there is kept and named with its line.
+constexpr int RAD_LW = 1, RAD_SW = 2;
+template<class TF> MHH_HD TF rad_gcss_mu_min() { return TF(0.035); }                       // include/radiation_gcss.h: mu_min
+// :186, :226: the layer depth z[k] - z[km1] with km1 = max(1, k-1), a literal 1 and not kstart: depth 0 at the bottom level with
+// one ghost level, the ghost z with more
+template<class TF> MHH_HD TF rad_gcss_depth(const TF* __restrict__ z, int k) { const int km1 = (1 < k-1) ? k-1 : 1; return z[k] - z[km1]; }
+// :227: the liquid water path accumulates max(0, .) upward
+template<class TF> MHH_HD TF rad_gcss_lwp(TF lwp, TF ql, TF rho, TF depth) { return lwp + tmax(TF(0.0), ql * rho * depth); }
+// :228
+template<class TF> MHH_HD TF rad_gcss_flx_up(TF fr1, TF xka, TF lwp) { return fr1 * std::exp(TF(-1.0) * xka * lwp); }
+// :229: the inversion index ki is the LAST level that passes this (kend where none does)
+template<class TF> MHH_HD bool rad_gcss_in_pbl(TF ql, TF qt) { return (ql > TF(0.01E-3)) && (qt >= TF(0.008)); }
+// :233: rho_ki = rhoref[ki], the ghost entry rhoref[kend] in a column without such a level
+template<class TF> MHH_HD TF rad_gcss_fact(TF div, TF rho_ki) { return div * MoistC<TF>::cp * rho_ki; }
+// :235 and :243: fr0*exp(-xka*lwp) with the column TOTAL lwp (the subtraction that would make it a path from above is commented
+// out, :241-242): one value per column. At kstart it is formed with TF(-1.0), in TF; from kstart+1 up with the double literal -1.0,
+// so that in fp32 the product, the exp, the product with fr0 and the sum with flx are double and narrowed at the store.
+template<class TF> MHH_HD TF     rad_gcss_down_kstart(TF fr0, TF xka, TF lwp) { return fr0 * std::exp(TF(-1.0) * xka * lwp); }
+template<class TF> MHH_HD double rad_gcss_down_above(TF fr0, TF xka, TF lwp)  { return fr0 * std::exp(-1.0 * xka * lwp); }
+// the long-wave flux of level k from flx_up of :228; :245-248: above the inversion, with `ki > 1` a literal again and the
+// exponents 1.333 and 0.33333 as written
+template<class TF> MHH_HD TF rad_gcss_flx(TF flx_up, int k, int kstart, TF down_kstart, double down_above, int ki, TF fact, const TF* __restrict__ z)
+{
+    if (k == kstart)
+        return flx_up + down_kstart;
+    TF flx = TF(flx_up + down_above);
+    if ((k > ki) && (ki > 1) && (fact > 0.))
+        flx = flx + fact * ( TF(0.25) * std::pow(z[k]-z[ki], TF(1.333)) + z[ki] * std::pow(z[k]-z[ki], TF(0.33333)) );
+    return flx;
+}
+// :282, :304: k in [kstart+1, kend) against km = max(kstart+1, k-1), so that kstart is untouched and kstart+1 sees a zero
+// difference; dzi is the parameter's name, exec passes gd.dzhi (:369); the long-wave term goes first (tt - .), then the short-wave
+// one (tt + .)
+template<class TF> MHH_HD TF rad_gcss_tend(TF f, TF fm, TF dzhi, TF rho) { return (f - fm) * dzhi / (rho * MoistC<TF>::cp); }
+// :188-192: ql > 1.E-5 is a DOUBLE comparison (a float ql is widened); tau is zero elsewhere, tauc their sum upward
+template<class TF> MHH_HD TF rad_gcss_tau(TF ql, TF rho, TF depth)
+{
+    const TF rho_l = 1000.;
+    const TF reff = 1.E-5;
+    if (ql > 1.E-5)
+        return tmax(TF(0.0), TF(1.5) * ql * rho * depth / reff / rho_l);
+    return TF(0.0);
+}
+// sunray (:101-159), line by line: what does not depend on the level. de = 1 - omega*ff is the factor of taude[k] (:125).
+template<class TF> struct RadSun { TF de, rk, rp, beta, c1, c2; };
+template<class TF> MHH_HD RadSun<TF> rad_gcss_sunray(TF mu, TF tauc)
+{
+    TF o_c1 = TF(0.9);
+    TF o_c2 = TF(2.75);
+    TF o_c3 = TF(0.09);
+    TF gc  = TF(0.85);
+    TF sfc_albedo = TF(0.05);
+    TF omega  = TF(1.) - TF(1.e-3) * (o_c1 + o_c2 * (mu+TF(1.)) * std::exp(-o_c3 * tauc));
+    TF ff     = gc * gc;
+    TF gcde   = gc / (TF(1.) + gc);
+    TF taucde = ( TF(1.0) - omega*ff) * tauc;
+    TF omegade = (TF(1.)-ff) * omega/(TF(1.) - omega*ff);
+    TF x1  = TF(1.) - omegade * gcde;
+    TF x2  = TF(1.) - omegade;
+    TF rk  = std::sqrt(TF(3.) * x2 * x1);
+    TF mu2 = mu * mu;
+    TF x3  = TF(4.) * (TF(1.) - rk*rk*mu2);
+    TF rp  = std::sqrt(TF(3.) * x2/x1);
+    TF alpha = TF(3.) * omegade * mu2 * (TF(1.) + gcde*x2) / x3;
+    TF beta  = TF(3.) * omegade * mu * (TF(1.) + TF(3.)*gcde*mu2*x2) / x3;
+
+    TF rtt = TF(2.0/3.0);
+    TF exmu0 = std::exp(-taucde / mu);
+    TF expk  = std::exp(rk * taucde);
+    TF exmk  = TF(1.) / expk;
+    TF xp23p = TF(1.) + rtt*rp;
+    TF xm23p = TF(1.) - rtt*rp;
+    TF ap23b = alpha + rtt*beta;
+
+    TF t1 = TF(1.) - sfc_albedo - rtt * (TF(1.) + sfc_albedo) * rp;
+    TF t2 = TF(1.) - sfc_albedo + rtt * (TF(1.) + sfc_albedo) * rp;
+    TF t3 = (TF(1.) - sfc_albedo) * alpha - rtt * (TF(1.) + sfc_albedo) * beta + sfc_albedo*mu;
+    TF c2 = (xp23p*t3*exmu0 - t1*ap23b*exmk) / (xp23p*t2*expk - xm23p*t1*exmk);
+    TF c1 = (ap23b - c2*xm23p)/xp23p;
+    RadSun<TF> s = {TF(1.) - omega*ff, rk, rp, beta, c1, c2};
+    return s;
+}
+// :125, :154: taude[k] is formed first and then added to taupath, going DOWN from kend-1
+template<class TF> MHH_HD TF rad_gcss_taupath(const RadSun<TF>& s, TF taupath, TF tau) { const TF taude = s.de * tau; return taupath + taude; }
+// :155-157
+template<class TF> MHH_HD TF rad_gcss_swn(const RadSun<TF>& s, TF mu, TF taupath)
+{
+    TF sw0 = TF(1100.);
+    return sw0 * TF(4./3.) * (s.rp * (s.c1*std::exp(-s.rk*taupath)
+        - s.c2 * std::exp(s.rk*taupath)) - s.beta * std::exp(-taupath/mu))
+        + mu * sw0 * std::exp(-taupath / mu);
+}
+// calc_zenith (:39-76), a host function evaluated with the host's C library in TF: day_of_year + 1 + lon/360. is double arithmetic
+// narrowed into TF, and std::round(time2sec) in d (whole days) is kept as written.
+template<class TF> inline TF rad_gcss_zenith(const TF lat, const TF lon, const double day_of_year)
+{
+    const TF pi    = TF(M_PI);
+    const TF twopi = TF(2.*M_PI);
+    const TF year2days = TF(365.);
+    const TF pi_angle  = TF(180.);
+    const TF z1 = TF(279.934);
+    const TF z2 = TF(1.914827);
+    const TF z3 = TF(0.7952);
+    const TF z4 = TF(0.019938);
+    const TF z5 = TF(0.00162);
+    const TF z6 = TF(23.4439);
+    const TF time2sec = day_of_year + 1 + lon/360.;
+    const TF day = std::floor(time2sec);
+    const TF lambda = lat * pi / pi_angle;
+    const TF d = twopi * std::round(time2sec) / year2days;
+    const TF sig = d + pi/pi_angle * (z1 + z2*std::sin(d)
+                                         - z3*std::cos(d)
+                                         + z4*std::sin(TF(2.)*d)
+                                         - z5*std::cos(TF(2.)*d));
+    const TF del = std::asin(std::sin(z6*pi / pi_angle)*std::sin(sig));
+    const TF h = twopi * ((time2sec - day) - TF(0.5));
+    const TF mu = std::sin(lambda) * std::sin(del) + std::cos(lambda) * std::cos(del) * std::cos(h);
+    return mu;
+}
+
 } // namespace mhh

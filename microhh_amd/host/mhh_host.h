@@ -42,6 +42,7 @@ struct Grid_data
     TF* z_g = nullptr; TF* zh_g = nullptr; TF* dz_g = nullptr; TF* dzh_g = nullptr;
     TF* dzi_g = nullptr; TF* dzhi_g = nullptr; TF* dzi4_g = nullptr; TF* dzhi4_g = nullptr;   // device copies (Grid::prepare_device)
     int npy = 1, mpicoordy = 0;                                                // slab decomposition (npx == 1)
+    TF lat = 0, lon = 0;                                                       // [grid] lat, lon in degrees: Radiation_gcss's zenith angle
 };
 
 template<typename TF>
@@ -923,6 +924,57 @@ class Limiter
                 mhh_check(mhh_limiter_exec(&g, fields.st.at(name)->fld_g, fields.sp.at(name)->fld_g, dt, stream));
         }
     private:
+        Grid<TF>& grid; Fields<TF>& fields;
+};
+
+// ---- Radiation_gcss (src/radiation_gcss.cxx): swradiation = gcss, the CPU path's physics ---------------------------------------
+// The two scratch fields ([ncells] each: the reference's get_tmp_g; its CPU path takes four) are the caller's device arrays. ql is
+// the saturation adjustment of the Thermo_moist it is handed, as the reference's exec takes its thermo. day_of_year is
+// Timeloop::calc_day_of_year(); the zenith angle is a host number, so a captured step keeps the one it was captured with.
+template<typename TF>
+class Radiation_gcss
+{
+    public:
+        Radiation_gcss(Grid<TF>& grid_in, Fields<TF>& fields_in) : grid(grid_in), fields(fields_in) {}
+        // [radiation] xka, fr0, fr1, div (no defaults in the reference)
+        TF xka = 0, fr0 = 0, fr1 = 0, div = 0;
+        const TF mu_min = 0.035;
+        const std::string tend_name = "rad";
+        int parts = MHH_RAD_LW | MHH_RAD_SW;
+        TF* scratch_g[2] = {nullptr, nullptr};
+        std::string get_switch() const { return "gcss"; }
+        unsigned long get_time_limit(unsigned long) const { return ~0ul; }            // Constants::ulhuge (:345-349)
+        bool check_field_exists(const std::string& name) const { return name == "rflx" || name == "sflx"; }      // (:383-389, as written)
+
+        // calc_zenith (:39-76) at grid.lat, grid.lon
+        TF calc_zenith(const double day_of_year) const
+        {
+            double mu = 0;
+            const auto& gd = grid.get_grid_data();
+            mhh_check(mhh_radiation_gcss_zenith_host(mhh_dtype<TF>(), gd.lat, gd.lon, day_of_year, &mu));
+            return TF(mu);
+        }
+        // Radiation_gcss::exec (:353-379)
+        void exec(Thermo_moist<TF>& thermo, const double day_of_year, void* stream = nullptr)
+        {
+            call(thermo, day_of_year, fields.st.at("thl")->fld_g, nullptr, nullptr, stream);
+        }
+        // get_radiation_field (:392-436) into a caller-owned 3-D device field: lflx | sflx, other names are refused
+        void get_radiation_field(TF* fld, const std::string& name, Thermo_moist<TF>& thermo, const double day_of_year, void* stream = nullptr)
+        {
+            if (name != "lflx" && name != "sflx")
+                throw std::runtime_error("get_radiation_field: \"" + name + "\" is not built (lflx | sflx)");
+            call(thermo, day_of_year, nullptr, name == "lflx" ? fld : nullptr, name == "sflx" ? fld : nullptr, stream);
+        }
+    private:
+        void call(Thermo_moist<TF>& thermo, const double day_of_year, TF* thlt, TF* lflx, TF* sflx, void* stream)
+        {
+            mhh_grid g = grid.abi();
+            mhh_radiation_gcss_params p{}; p.xka = xka; p.fr0 = fr0; p.fr1 = fr1; p.div = div; p.mu = calc_zenith(day_of_year); p.parts = parts;
+            void* const scratch[2] = {scratch_g[0], scratch_g[1]};
+            mhh_check(mhh_radiation_gcss_exec(&g, &p, thlt, nullptr, fields.sp.at("thl")->fld_g, fields.sp.at("qt")->fld_g, fields.rhoref_g,
+                                              thermo.pref_g, thermo.exnref_g, lflx, sflx, scratch, thermo.nonconv_g, stream));
+        }
         Grid<TF>& grid; Fields<TF>& fields;
 };
 

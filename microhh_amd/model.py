@@ -5,6 +5,7 @@ that this package accelerates, expressed as calls into the C ABI.
     diff->exec_viscosity(thermo)          -> mhh_diff_exec_viscosity (+ N-S exchange of evisc)   (:354)
     thermo->exec (Thermo_moist)           -> mhh_thermo_moist_base_state, mhh_thermo_moist_buoyancy_tend (thermo=..., opt-in) (:366)
     microphys->exec ; limiter->exec       -> mhh_micro_2mom_warm_exec, mhh_limiter_exec (micro=..., opt-in) (:369, :415)
+    radiation->exec (Radiation_gcss)      -> mhh_radiation_gcss_exec (radiation=..., opt-in)      (:372)
     boundary->exec ; set_ghost_cells      -> mhh_boundary_surface_exec, mhh_boundary_ghost_cells (surface=..., opt-in) (:374-375)
     advec->exec ; diff->exec              -> mhh_rhs_exec (fused, same bits)                     (:388, :392)
     fields->exec ; buffer->exec ; force->exec -> mhh_field_mean_*, mhh_buffer_force_exec (forcing=..., opt-in) (:351, :395, :404)
@@ -50,6 +51,13 @@ CASES = {
     # schemes of bomex; HotPath(..., thermo=thermo.Moist(pbot), micro=microphys.Warm2mom(Nc0)) switches the physics on.
     "rico": dict(advec=ADVEC_2I5, diff=DIFF_SMAG2, pres=2, order=2, gc=(3, 3, 1), size=(12800., 12800., 4000.), nscalars=4, sm=1, visc=1e-5,
                  thermo="moist", pbot=101540., micro="2mom_warm", Nc0=70.e6),
+    # dycoms (cases/dycoms/dycoms.ini): rico's physics plus Radiation_gcss, pbot = 101780 Pa, datetime_utc = 2001-06-09 00:00:00 (day 160
+    # of the year plus the day fraction); HotPath(..., thermo=thermo.Moist(pbot), micro=microphys.Warm2mom(Nc0),
+    # radiation=radiation.Gcss(xka, fr0, fr1, div, lat, lon, day_of_year)) switches the physics on. The schemes are those of bomex and
+    # rico; this fork's dycoms.ini names advec_2i3.
+    "dycoms": dict(advec=ADVEC_2I5, diff=DIFF_SMAG2, pres=2, order=2, gc=(3, 3, 1), size=(6400., 6400., 1500.), nscalars=4, sm=1, visc=1e-5,
+                   thermo="moist", pbot=101780., micro="2mom_warm", Nc0=70.e6,
+                   radiation="gcss", xka=85., fr0=70., fr1=22., div=3.75e-6, lat=32.5, lon=0., day_of_year=160.),
 }
 
 FIELDS3 = ("u", "v", "w", "ut", "vt", "wt")
@@ -73,6 +81,9 @@ def synthetic_global(case, itot, jtot, ktot, dtype=np.float64, seed=666, nscalar
     if cfg.get("thermo") == "moist" and "s1" in out:
         from .thermo import bomex_interior
         out["s0"], out["s1"] = bomex_interior(z, n3, rs)
+    if cfg.get("radiation") == "gcss" and "s1" in out:
+        from .radiation import synthetic_stratocumulus
+        out["s0"], out["s1"] = synthetic_stratocumulus(z, n3, rs)
     if cfg.get("micro") == "2mom_warm" and "s3" in out:
         from .microphys import synthetic_rain
         out["s2"], out["s3"] = synthetic_rain(z, n3, rs)
@@ -88,7 +99,7 @@ class HotPath:
 
     def __init__(self, case, itot, jtot, ktot, dtype=np.float64, device="cuda:0", seed=666, dt=1.0,
                  lib=None, npy=1, rank=0, group=None, global_init=None, force_slab=False, slim_halos=True, overlap=None, pres_chunks=None, igc=None,
-                 nscalars=None, forcing=None, surface=None, thermo=None, micro=None):
+                 nscalars=None, forcing=None, surface=None, thermo=None, micro=None, radiation=None):
         import torch
         self.torch = torch
         self.lib = lib if lib is not None else capi.lib()
@@ -250,6 +261,8 @@ class HotPath:
         self.surface = surface.bind(self) if surface is not None else None
         # Microphys_2mom_warm and Limiter (microphys.Warm2mom): the rain rate, sedimentation's scratch
         self.micro = micro.bind(self) if micro is not None else None
+        # Radiation_gcss (radiation.Gcss): the zenith angle, two scratch fields
+        self.radiation = radiation.bind(self) if radiation is not None else None
         self.cyclic_prognostic()
         self.sync()
 
@@ -538,6 +551,8 @@ class HotPath:
             self.thermo_moist()
             if self.micro is not None:         # microphys->exec (:369), between thermo->exec and boundary->exec
                 self.micro.exec()
+            if self.radiation is not None:     # radiation->exec (:372), between microphys->exec and boundary->exec
+                self.radiation.exec()
             if self.surface is not None:       # boundary->exec (:376) reads the thvref, thvrefh thermo->exec has just written
                 self.surface_layer()
             self.rhs()

@@ -1,0 +1,332 @@
+"""Shared plumbing of the GCSS radiation tests (tests/test_radiation_*.py): the seeded cases and their reference results.
+
+The reference is the reference's OWN source (src/radiation_gcss.cxx) behind tests/cpp/ref_radiation_shim.cpp, compiled into a
+temporary directory where the reference tree exists. Where it is absent the same cases read tests/golden/radiation_ref.npz, recorded
+with MHH_RECORD_RADIATION_GOLDEN=1 python -m pytest tests/test_radiation_exec.py: reference OUTPUTS only (thlt from zero tendencies,
+lflx, sflx, mu). The inputs are not stored: every draw is numpy's seeded legacy generator, everything derived from a draw uses
++ - * / only and is narrowed to values a float holds exactly, so they are the same numbers on every host; the file holds their
+digest per case. ql and qt are INPUTS here (handed to the ql pointer), so that every threshold sees the same bits in the reference
+and in the kernel and no cell has to be left out of a comparison.
+"""
+import ctypes as C
+import hashlib
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+
+import common as cm
+import moist_ref as M
+from microhh_amd.grid import Grid
+
+REF_ROOT = os.path.dirname(os.path.normpath(M.REF_INC))
+GOLDEN = os.path.join(cm.ROOT, "tests", "golden", "radiation_ref.npz")
+RECORD = os.environ.get("MHH_RECORD_RADIATION_GOLDEN") == "1"
+ZSIZE = 1500.
+LW, SW = 1, 2
+SWEEP, PLAIN = 0, 1
+LAT = 32.5
+
+SHAPES = M.SHAPES
+STRETCHED = {(70, 9, 10): False, (17, 9, 8): True, (20, 1, 12): False, (130, 6, 40): True}
+GCS = M.GCS
+SMALL = [(17, 9, 8), (20, 1, 12)]
+OUT = ("thlt", "lflx", "sflx")
+
+# cases/dycoms/dycoms.ini, and the two that fail `fact > 0.`
+PARAMS = {"dycoms": dict(xka=85., fr0=70., fr1=22., div=3.75e-6), "div0": dict(xka=85., fr0=70., fr1=22., div=0.),
+          "divneg": dict(xka=85., fr0=70., fr1=22., div=-3.75e-6)}
+# the sun: noon of 2001-06-09 at lon = 0 (calc_day_of_year gives 160 + the day fraction), a low sun just above mu_min, midnight;
+# "edge" is mu = TF(0.035) exactly, which is not above mu_min: no short wave
+MU_DAYS = {"day": 160.5, "low": 160.215, "night": 160.0}
+MUS = ("day", "low", "night", "edge")
+ZENITH_DAYS = (160.0, 160.25, 160.5)
+ZENITH_LONS = (0., -120.)
+# (parameters, sun) of every run; the golden file holds all of them for the SMALL shapes and the first for the others
+RUNS = [("dycoms", "day"), ("div0", "day"), ("divneg", "day"), ("dycoms", "low"), ("dycoms", "night"), ("dycoms", "edge")]
+
+tag, code, f32exact = M.tag, M.code, M.f32exact
+
+
+KGC2 = ((17, 9, 8), (1, 1, 2))       # the one layout with two vertical ghost levels: the literal-1 layer depth reads the ghost z
+
+
+def stored(shape, run, gc=(1, 1, 1)):
+    """The outputs of a run that the golden file holds: of the largest shape thlt alone (the file stays below 1 MB); with two
+    vertical ghost levels the first run of KGC2's shape."""
+    if gc[2] != 1:
+        return OUT if (shape == KGC2[0] and run == RUNS[0]) else ()
+    if shape not in SMALL and run != RUNS[0]:
+        return ()
+    return ("thlt",) if shape == SHAPES[3] else OUT
+
+
+def grid_of(shape, gc, dtype):
+    z = None
+    if STRETCHED[shape]:
+        s = (np.arange(shape[2]) + 0.5)/shape[2]
+        z = f32exact(ZSIZE*(s + 0.6*s*s)/1.6)
+    return Grid(shape[0], shape[1], shape[2], 6400., 6400., ZSIZE, order=2, igc=gc[0], jgc=gc[1], kgc=gc[2], dtype=dtype, z=z)
+
+
+# the kinds of column, by a draw per column
+CLEAR, TOP, BOTTOM, DRYQT, TWO, BAND = range(6)
+KIND_EDGES = (0.12, 0.19, 0.26, 0.33, 0.48)
+
+
+class CloudCase:
+    """ql, qt and a non-zero thlt on the ktot interior levels of jtot x itot columns (the same for every ghost layout).
+    Columns: clear; cloud in the top level only; in the bottom level only; cloud with qt < 0.008 throughout; two cloud layers with
+    a gap; one band of cloud (the rest, more than half). In the last two kinds single cells outside the cloud hold 0 < ql < 1e-5, a
+    ql equal to float32(1e-5) = 9.99999975e-06 (not above the double 1e-5 the optical depth compares with, nor above TF(0.01E-3)),
+    its upper neighbour among the floats (above both) and negative ql."""
+
+    def __init__(self, shape):
+        self.shape = shape
+        self.key = "%dx%dx%d" % shape
+        itot, jtot, ktot = shape
+        rs = np.random.RandomState(9100 + itot + 7*ktot)
+        n3, n2 = (ktot, jtot, itot), (1, jtot, itot)
+        lev = np.arange(ktot)[:, None, None]
+        self.kind = np.digitize(rs.random_sample(n2), KIND_EDGES)
+        self.kind.reshape(-1)[:6] = np.arange(6)                 # every kind in every shape, the one of 20 columns too
+        kind = self.kind
+        # one band: base in the lower half, at least one level thick, top below the domain's top so that levels lie above ki
+        kb = np.floor(ktot*(0.25 + 0.2*rs.random_sample(n2)))
+        kt = np.minimum(kb + 1 + np.floor(0.3*ktot*rs.random_sample(n2)), ktot - 2)
+        band = (lev >= kb) & (lev <= kt)
+        # two layers of two levels with a gap of one
+        k1 = 1 + np.floor((ktot - 6)*rs.random_sample(n2))
+        two = ((lev >= k1) & (lev <= k1 + 1)) | ((lev >= k1 + 3) & (lev <= k1 + 4))
+        cloud = np.where(kind == TOP, lev == ktot - 1, np.where(kind == BOTTOM, lev == 0, np.where(kind == TWO, two, band)))
+        cloud = cloud & (kind != CLEAR)
+        ql = np.where(cloud, 1.e-4 + 7.e-4*rs.random_sample(n3), 0.)
+        few = rs.random_sample(n3)
+        special = ~cloud & (kind >= TWO)
+        ql = np.where(special & (few < 0.03), 9.e-6*few/0.03, ql)                                  # 0 < ql < 1e-5
+        ql = np.where(special & (few > 0.03) & (few < 0.06), float(np.float32(1e-5)), ql)          # the float below the double 1e-5
+        ql = np.where(special & (few > 0.09) & (few < 0.12), float(np.nextafter(np.float32(1e-5), np.float32(1.))), ql)   # and the one above
+        ql = np.where(special & (few > 0.06) & (few < 0.09), -1.e-5*few, ql)                       # spurious negative values
+        qt = np.where(lev <= np.where(kind == TWO, k1 + 4, kt), 0.0085 + 0.001*rs.random_sample(n3), 0.0015 + 0.003*rs.random_sample(n3))
+        qt = np.where((kind == TOP) | (kind == BOTTOM), 0.0085 + 0.001*rs.random_sample(n3), qt)
+        qt = np.where(kind == DRYQT, 0.004 + 0.003*rs.random_sample(n3), qt)
+        self.ql, self.qt = f32exact(ql), f32exact(qt)
+        self.thlt = f32exact(1.e-3*(rs.random_sample(n3) - 0.5))
+
+    def digest(self):
+        h = hashlib.sha256()
+        for a in (self.ql, self.qt, self.thlt):
+            h.update(np.ascontiguousarray(a).tobytes())
+        return h.hexdigest()
+
+    def embed(self, a3, g, fill):
+        """The (ktot, jtot, itot) block inside a [kcells][jcells][icells] array of g's dtype; every ghost cell holds `fill`, which no
+        kernel of this module may read into a result."""
+        out = np.full(g.shape3, fill, dtype=g.np_dtype)
+        out[g.interior] = a3
+        return out
+
+    def inputs(self, g, zero_tend=False):
+        """Host arrays of grid g: ql, qt, thlt, the two outputs (sentinels) and the density table. The ghost cells of ql hold thick
+        cloud and those of qt a moist value: a kernel that read them would move ki, lwp and tauc."""
+        t = g.np_dtype
+        h = {"ql": self.embed(np.asarray(self.ql, dtype=t), g, 2.e-3), "qt": self.embed(np.asarray(self.qt, dtype=t), g, 0.02)}
+        h["thlt"] = self.embed(np.zeros_like(self.thlt, dtype=t) if zero_tend else np.asarray(self.thlt, dtype=t), g, 777.)
+        h["lflx"] = np.full(g.shape3, 555., dtype=t)
+        h["sflx"] = np.full(g.shape3, 444., dtype=t)
+        h["rho"] = np.ascontiguousarray(f32exact(1.16*(1. - g.z.astype(np.float64)/22000.)), dtype=t)
+        return h
+
+
+_cases = {}
+
+
+def cloud_case(shape):
+    if shape not in _cases:
+        _cases[shape] = CloudCase(shape)
+    return _cases[shape]
+
+
+# ---- the shim ---------------------------------------------------------------------------------------------------------------
+_shim = {}
+have_reference = M.have_reference
+
+
+def shim():
+    """The shim compiled against the reference's tree into a temporary directory (kept for the session); None without the tree."""
+    if "lib" not in _shim:
+        if not have_reference():
+            _shim["lib"] = None
+        else:
+            _shim["tmp"] = tempfile.TemporaryDirectory()
+            so = os.path.join(_shim["tmp"].name, "libref_radiation.so")
+            src = os.path.join(REF_ROOT, "src")
+            subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-DRESTRICTKEYWORD=__restrict__", "-I" + M.REF_INC, "-I" + src,
+                            "-fPIC", "-shared", "-fvisibility=hidden", "-ffunction-sections", "-fdata-sections", "-Wl,--gc-sections", "-o", so,
+                            os.path.join(cm.ROOT, "tests", "cpp", "ref_radiation_shim.cpp"), os.path.join(src, "master.cxx"),
+                            os.path.join(src, "master_serial.cxx")], check=True)
+            lib = C.CDLL(so)
+            vp, ci, cd = C.c_void_p, C.c_int, C.c_double
+            lib.ref_rad_zenith.argtypes = [ci, cd, cd, cd]; lib.ref_rad_zenith.restype = cd
+            lib.ref_rad_exec.argtypes = [ci, C.POINTER(M.Dims)] + [cd]*5 + [vp]*8; lib.ref_rad_exec.restype = None
+            lib.ref_rad_lw.argtypes = [ci, C.POINTER(M.Dims)] + [cd]*4 + [vp]*6; lib.ref_rad_lw.restype = None
+            lib.ref_rad_sw.argtypes = [ci, C.POINTER(M.Dims), cd] + [vp]*6; lib.ref_rad_sw.restype = None
+            _shim["lib"] = lib
+    return _shim["lib"]
+
+
+def ref_zenith(dtype, lon, day):
+    return shim().ref_rad_zenith(code(dtype), LAT, lon, day)
+
+
+def zenith_key(dtype, lon, day):
+    return "zenith/%g/%g/%s" % (day, lon, tag(dtype))
+
+
+def mu_of(name, dtype, be=None):
+    """The cosine of the zenith angle of a sun by name, a value of the dtype: from the shim on this host, else from the golden file."""
+    if name == "edge":
+        return float(np.dtype(dtype).type(0.035))
+    return float(ref("mu/%s/%s" % (name, tag(dtype)), be)[0])
+
+
+def ref_exec(shape, dtype, par, mu, parts=LW | SW, zero_tend=False, gc=(1, 1, 1)):
+    """The reference on the case: thlt as exec_gcss_rad leaves it (one part: the other's term is taken out by running the parts the
+    reference runs and keeping the wanted one), lflx and sflx as get_radiation_field gives them."""
+    c, g = cloud_case(shape), grid_of(shape, gc, dtype)
+    h = c.inputs(g, zero_tend)
+    d = M.dims_of(g)
+    p = PARAMS[par]
+    lib = shim()
+    t = np.dtype(dtype).type
+    day = t(mu) > t(0.035)
+    flx, swn = np.zeros(g.shape3, dtype=dtype), np.zeros(g.shape3, dtype=dtype)
+    if parts == (LW | SW):
+        lib.ref_rad_exec(code(dtype), C.byref(d), p["xka"], p["fr0"], p["fr1"], p["div"], mu, cm.ptr(h["thlt"]), cm.ptr(h["ql"]), cm.ptr(h["qt"]),
+                         cm.ptr(flx), cm.ptr(swn), cm.ptr(h["rho"]), cm.ptr(g.z), cm.ptr(g.dzhi))
+    elif parts == LW:          # exec_gcss_rad at night is the long-wave term alone
+        lib.ref_rad_exec(code(dtype), C.byref(d), p["xka"], p["fr0"], p["fr1"], p["div"], -1., cm.ptr(h["thlt"]), cm.ptr(h["ql"]), cm.ptr(h["qt"]),
+                         cm.ptr(flx), cm.ptr(swn), cm.ptr(h["rho"]), cm.ptr(g.z), cm.ptr(g.dzhi))
+    else:                      # the short-wave loop of :295-307 on the reference's own swn, in numpy's IEEE arithmetic of the dtype
+        if day:
+            lib.ref_rad_sw(code(dtype), C.byref(d), mu, cm.ptr(swn), cm.ptr(h["ql"]), cm.ptr(h["qt"]), cm.ptr(h["rho"]), cm.ptr(g.z), cm.ptr(g.dzi))
+            ks, ke = g.kstart, g.kend
+            js, ie = slice(g.jstart, g.jend), slice(g.istart, g.iend)
+            for k in range(ks + 1, ke):
+                km = max(ks + 1, k - 1)
+                h["thlt"][k, js, ie] = h["thlt"][k, js, ie] + (swn[k, js, ie] - swn[km, js, ie]) * g.dzhi[k] / (h["rho"][k] * t(1005.))
+    # get_radiation_field: both whatever the parts
+    h["lflx"] = np.full(g.shape3, 555., dtype=dtype)
+    lib.ref_rad_lw(code(dtype), C.byref(d), p["xka"], p["fr0"], p["fr1"], p["div"], cm.ptr(h["ql"]), cm.ptr(h["qt"]), cm.ptr(h["lflx"]),
+                   cm.ptr(h["rho"]), cm.ptr(g.z), cm.ptr(g.dzi))
+    h["sflx"] = np.zeros(g.shape3, dtype=dtype)
+    if day:
+        lib.ref_rad_sw(code(dtype), C.byref(d), mu, cm.ptr(h["sflx"]), cm.ptr(h["ql"]), cm.ptr(h["qt"]), cm.ptr(h["rho"]), cm.ptr(g.z), cm.ptr(g.dzi))
+    return h
+
+
+def run_key(shape, run, dtype, gc=(1, 1, 1)):
+    return "exec%s/%dx%dx%d/%s/%s/%s/" % (("" if gc[2] == 1 else "-kgc%d" % gc[2],) + shape + run + (tag(dtype),))
+
+
+def _compute_all():
+    rec = {}
+    for dt in cm.DTYPES:
+        for name, day in MU_DAYS.items():
+            rec["mu/%s/%s" % (name, tag(dt))] = np.array([ref_zenith(dt, 0., day)])
+        for day in ZENITH_DAYS:
+            for lon in ZENITH_LONS:
+                rec[zenith_key(dt, lon, day)] = np.array([ref_zenith(dt, lon, day)])
+        for shape, gc in [(s, (1, 1, 1)) for s in SHAPES] + [KGC2]:
+            g = grid_of(shape, gc, dt)
+            for run in RUNS:
+                names = stored(shape, run, gc)
+                if not names:
+                    continue
+                mu = float(np.dtype(dt).type(0.035)) if run[1] == "edge" else float(rec["mu/%s/%s" % (run[1], tag(dt))][0])
+                r = ref_exec(shape, dt, run[0], mu, zero_tend=True, gc=gc)
+                for n in names:
+                    rec[run_key(shape, run, dt, gc) + n] = r[n][g.interior].copy()
+    for shape in SHAPES:
+        rec["digest/%s" % cloud_case(shape).key] = np.array(cloud_case(shape).digest())
+    return rec
+
+
+_all, _golden = {}, {}
+
+
+def golden():
+    if "z" not in _golden:
+        _golden["z"] = np.load(GOLDEN) if os.path.exists(GOLDEN) else None
+    return _golden["z"]
+
+
+def computed():
+    if "rec" not in _all:
+        _all["rec"] = _compute_all() if have_reference() else None
+    return _all["rec"]
+
+
+def exact_here(be):
+    """emul with the shim compiled on this host: the same C library and no contraction, so what passes through exp, pow and sqrt
+    must agree bit for bit too."""
+    return be.name == "emul" and have_reference() and not RECORD
+
+
+def ref(key, be=None):
+    if have_reference() and (be is None or be.name == "emul") and not RECORD:
+        return computed()[key]
+    z = golden()
+    assert z is not None, "tests/golden/radiation_ref.npz is missing: record it where the reference tree exists"
+    return z[key]
+
+
+# ---- the device -------------------------------------------------------------------------------------------------------------
+class Dev:
+    """The arrays of one (shape, gc, dtype) on a backend and the call on them."""
+
+    def __init__(self, be, shape, gc, dtype, zero_tend=False, host=None):
+        from microhh_amd import capi
+        self.capi = capi
+        self.be, self.c, self.g = be, cloud_case(shape), grid_of(shape, gc, dtype)
+        self.h = self.c.inputs(self.g, zero_tend) if host is None else host
+        self.G = be.grid(self.g)
+        self.d = {n: be.arr(a) for n, a in self.h.items()}
+        self.scratch = [be.arr(np.full(self.g.ncells, -9.e9, dtype=dtype)) for _ in range(2)]
+        self.scratch_ptrs = (C.c_void_p*2)(*[be.ptr(a).value for a in self.scratch])
+        self.keep, self.cptr, self.count = M.counter(be)
+
+    def params(self, par, mu, parts):
+        p = PARAMS[par] if isinstance(par, str) else par
+        return self.capi.MhhRadiationGcssParams(p["xka"], p["fr0"], p["fr1"], p["div"], mu, parts)
+
+    def args(self, thlt=True, ql=True, lflx=True, sflx=True, extra=None):
+        be, d = self.be, self.d
+        e = extra or {}
+        return [be.ptr(d["thlt"]) if thlt else None, be.ptr(d["ql"]) if ql else None, e.get("thl"), be.ptr(e["qt"]) if "qt" in e else be.ptr(d["qt"]),
+                be.ptr(d["rho"]), e.get("p"), e.get("exn"), be.ptr(d["lflx"]) if lflx else None, be.ptr(d["sflx"]) if sflx else None,
+                self.scratch_ptrs, self.cptr, be.stream]
+
+    def exec(self, par, mu, parts=LW | SW, impl=None, **kw):
+        be = self.be
+        p = self.params(par, mu, parts)
+        a = self.args(**kw)
+        if impl is None:
+            rc = be.lib.mhh_radiation_gcss_exec(self.G, C.byref(p), *a)
+        else:
+            rc = be.lib.mhh_radiation_gcss_exec_impl(self.G, impl, C.byref(p), *a)
+        self.capi.check(rc, be.lib)
+        be.sync()
+        return self.out()
+
+    def out(self):
+        return {n: self.be.host(self.d[n]).reshape(self.g.shape3) for n in OUT}
+
+
+def record_if_asked():
+    """MHH_RECORD_RADIATION_GOLDEN=1: write the golden file from the shim (the first test of tests/test_radiation_exec.py calls this)."""
+    if RECORD:
+        rec = _compute_all()
+        np.savez_compressed(GOLDEN, **rec)
+        _golden.clear()
