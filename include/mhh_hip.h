@@ -602,6 +602,11 @@ int mhh_thermo_moist_buoyancy_tend_impl(const mhh_grid* g, int impl, void* wt, c
  * interior; b on all kcells levels of the interior columns, with ql = qi = 0 outside [kstart, kend).                             */
 int mhh_thermo_moist_fields(const mhh_grid* g, const void* thl, const void* qt, const void* pref, const void* exnref, const void* thvref,
                             void* b, void* ql, void* qi, void* T, int* nonconv, void* stream);
+/* get_thermo_field("ql_h"): calc_liquid_water_h (:368-411), what the ql mask of Thermo_moist::get_mask (:1314-1329) thresholds on
+ * the half levels. thl and qt interpolated to the half level and the per-cell saturation adjustment at prefh, exnrefh: levels
+ * kstart+1 .. kend of the interior columns (kend reads the ghost level of thl and qt), zero at kstart.                            */
+int mhh_thermo_moist_ql_h(const mhh_grid* g, const void* thl, const void* qt, const void* prefh, const void* exnrefh, void* ql_h,
+                          int* nonconv, void* stream);
 /* Thermo_moist::create_basestate (:1220-1241) on the HOST with the host's C library: calc_top_and_bot (:58-75) sets the ghost
  * entries of thl0 and qt0 (HOST [kcells], written), calc_base_state (thermo_moist_functions.h:293-349) fills the eight HOST
  * profiles (any may be NULL), and with boussinesq != 0 rhoref, rhorefh are overwritten with 1 and thvref, thvrefh with thvref0.
@@ -690,6 +695,80 @@ int mhh_radiation_gcss_exec(const mhh_grid* g, const mhh_radiation_gcss_params* 
 int mhh_radiation_gcss_exec_impl(const mhh_grid* g, int impl, const mhh_radiation_gcss_params* params, void* thlt, const void* ql, const void* thl,
                                  const void* qt, const void* rhoref, const void* pref, const void* exnref, void* lflx, void* sflx,
                                  void* const* scratch, int* nonconv, void* stream);
+
+/* ---- Stats (src/stats.cxx: the sampling of second-order cases; the parity target is the reference's CPU path) --------------------
+ * Masks live in ONE unsigned int field mfield [ncells] and a 2-D mfield_bot [ijcells]; mask n (0 .. MHH_STATS_MAX_MASKS-1, in the
+ * order of add_mask, :841-850) has flag = 1 << 2n on full levels and flagh = 1 << (2n+1) on half levels. Every reduction is
+ * deterministic (chunk partials, then an ordered finish: no floating-point atomics) and is split into a SUMS call that leaves
+ * doubles in device memory and a FINISH call that turns them into values of the grid's dtype, so that a slab rank can add sums
+ * and counts over the ranks in between. Every entry only enqueues on its stream. `scratch`: device memory of
+ * mhh_stats_scratch_elems(g, nmasks, njobs) DOUBLES. One vertical ghost level is required (the profiles read kend and kstart-1). */
+#define MHH_STATS_MAX_MASKS 8
+#define MHH_STATS_MAX_JOBS  16
+#define MHH_STATS_MASK_PLUS 0   /* Stats_mask_type::Plus: a cell leaves the mask where value <= threshold                            */
+#define MHH_STATS_MASK_MIN  1   /* Stats_mask_type::Min:  ... where value > threshold                                               */
+#define MHH_STATS_MEAN     0    /* calc_mean (:263-287); also the mean of w under flagh and calc_tend (:1893-1919)                 */
+#define MHH_STATS_MOMENT2  2    /* calc_moment (:341-365), power 2, 3, 4: needs `mean`                                             */
+#define MHH_STATS_MOMENT3  3
+#define MHH_STATS_MOMENT4  4
+#define MHH_STATS_FRAC     5    /* calc_frac (:410-433)                                                                            */
+#define MHH_STATS_GRAD     6    /* calc_grad_2nd (:2171-2195): averaged under the flag of the OTHER level (!fld.loc[2])            */
+#define MHH_STATS_COUNT    7    /* calc_nmask (:224-261) over 0 .. kcells; used by mhh_stats_mask_count                            */
+#define MHH_STATS_MEAN2D   8    /* calc_mean_2d (:289-306): fld is [ijcells], no mask, the value is element 0 of the profile      */
+#define MHH_STATS_FLUX_W    9   /* the resolved flux (:1668-1733): advec.get_advec_flux of fld - mean[k] and w - wmean[k], evaluated on the
+                                 * fly: advec_flux_u / _v / _s of advec_2 (src/advec_2.cxx:206-252) and advec_2i5 (src/advec_2i5.cxx:730-913),
+                                 * advec_flux_s_lim (include/advec_monotonic.h:183); averaged under flagh; needs `mean`, `w`, `wmean`    */
+#define MHH_STATS_FLUX_DIFF 10  /* the diffusive flux (:1735-1760): Diff_smag2::diff_flux (src/diff_smag2.cxx:739-842, :1217-1276) and
+                                 * Diff_2::diff_flux (src/diff_2.cxx:88-105); averaged under flagh                                    */
+#define MHH_STATS_FLUX_SUM  11  /* add_fluxes (:400-407) in the finish: the finished values of jobs a and b of the same call, added   */
+typedef struct mhh_stats_job
+{
+    const void* fld;             /* the variable, [ncells] of the grid's dtype ([ijcells] for MEAN2D)                               */
+    const void* mean;            /* moments: the FINISHED mean profiles of the variable, [nmasks][kcells] (offset and fill included,
+                                  * as calc_moment reads profs.at(varname)); NULL otherwise                                         */
+    int loc;                     /* fld.loc[2]: 0 full level, 1 half level                                                           */
+    int op;                      /* MHH_STATS_*                                                                                      */
+    double offset, threshold;    /* narrowed to the dtype on entry                                                                   */
+    /* the fluxes only (MHH_STATS_FLUX_*); a full-level variable: a half-level one is refused, as the reference throws             */
+    int kind;                    /* where the variable lives horizontally: 0 scalar, 1 u, 2 v (fld.loc[0], fld.loc[1])                */
+    int scheme;                  /* FLUX_W: MHH_ADVEC_2 | MHH_ADVEC_2I5; FLUX_DIFF: MHH_DIFF_2 | MHH_DIFF_SMAG2                       */
+    int limit;                   /* FLUX_W of a scalar in advec.fluxlimit_list: advec_flux_s_lim                                      */
+    int surface_model;           /* FLUX_DIFF, smag2: boundary.get_switch() != "default": flux_bot / flux_top on the two boundary levels */
+    const void* w;               /* FLUX_W, and FLUX_DIFF of u and v with smag2: the vertical velocity [ncells]                       */
+    const void* wmean;           /* FLUX_W: calc_mean of w under flagh, [nmasks][kcells] (a MEAN job of w with loc 1, offset 0)       */
+    const void* evisc;           /* FLUX_DIFF, smag2                                                                                 */
+    const void* flux_bot; const void* flux_top;   /* FLUX_DIFF, smag2 with a surface model: [ijcells]                                */
+    double visc, tPr;            /* FLUX_DIFF: the variable's visc (fields.visc for u and v), diff.tPr                                */
+    int a, b;                    /* FLUX_SUM: the jobs of THIS call that hold _w and _diff                                            */
+} mhh_stats_job;
+unsigned long long mhh_stats_scratch_elems(const mhh_grid* g, int nmasks, int njobs);
+int mhh_stats_chunk_rows(void);
+/* Stats::initialize_masks (:1214-1227): every word of both fields, ghosts included, is the sum of the flags of nmasks masks        */
+int mhh_stats_mask_init(const mhh_grid* g, void* mfield, void* mfield_bot, int nmasks, void* stream);
+/* Stats::set_mask_thres / calc_mask_thres (:95-172, :1264-1301), all six loops; fld, fldh [ncells], fld_bot [ijcells]. Integer
+ * logic: a bit whose test fails is cleared; NaN fails neither test and clears nothing.                                            */
+int mhh_stats_mask_thres(const mhh_grid* g, void* mfield, void* mfield_bot, int mask, const void* fld, const void* fldh, const void* fld_bot,
+                         double threshold, int mode, void* stream);
+/* Stats::finalize_masks (:1229-1262) in two halves. count: the two cyclic fills (mhh_boundary_cyclic_u32, _2d_u32) and calc_nmask
+ * over 0 .. kcells as doubles csums[2][nmasks][kcells] (full, half). finish: nmask int[nmasks][2][kcells] (full, half),
+ * nmask_bot int[nmasks] = nmaskh[kstart], area and areah [nmasks][kcells] of the dtype (calc_area, :209-221).                       */
+int mhh_stats_mask_count(const mhh_grid* g, void* mfield, void* mfield_bot, int nmasks, void* csums, void* scratch, void* stream);
+int mhh_stats_mask_finish(const mhh_grid* g, int nmasks, const void* csums, void* nmask, void* nmask_bot, void* area, void* areah, void* stream);
+/* The loops of Stats::calc_stats (:1607-1890), calc_tend (:1893-1919) and calc_stats_2d (:1921-1937): sums[job][mask][kcells]
+ * doubles over kstart .. kend INCLUSIVE (zero elsewhere), then out[job][mask][kcells] of the dtype: sum / nmask[k], the offset
+ * added to a mean, the fill value (NC_FILL_DOUBLE / NC_FILL_FLOAT) where nmask[k] == 0. The second pass (moments) reads the
+ * finished means of the first from device memory. Unknown operations return MHH_EINVAL with a message.                              */
+int mhh_stats_sums(const mhh_grid* g, const void* mfield, int nmasks, const mhh_stats_job* jobs, int njobs, void* sums, void* scratch, void* stream);
+int mhh_stats_finish(const mhh_grid* g, int nmasks, const mhh_stats_job* jobs, int njobs, const void* sums, const void* nmask, void* out, void* stream);
+/* calc_cover (:475-507) and calc_path (:435-473) of one variable, one thread per column: sums[nmasks][3] doubles = cover,
+ * nmaskcover, path (a column's path serially in the dtype, as `data*rho*dz`); then out[nmasks][2] of the dtype = cover / nmaskcover
+ * (0 without a column) and path / nmask_proj (NaN without a column, as in the reference).                                          */
+int mhh_stats_columns(const mhh_grid* g, const void* mfield, int nmasks, const void* fld, int loc, double offset, double threshold,
+                      const void* rhoref, void* sums, void* scratch, void* stream);
+int mhh_stats_columns_finish(const mhh_grid* g, int nmasks, const void* sums, void* out, void* stream);
+/* Grid::interpolate_2nd(wf, w, wloc, sloc) (src/grid.cxx:455-486) for the wplus / wmin masks of Fields::get_mask
+ * (src/fields.cxx:631-643): wf [ncells] is zeroed, then written on the levels 0 .. kcells-2 of the interior columns.               */
+int mhh_stats_interpolate_w(const mhh_grid* g, const void* w, void* wf, void* stream);
 
 /* ---- Timeloop RK3/RK4 substep (src/timeloop.cxx:250-334, src/timeloop.cu:35-122) -------- */
 int mhh_rk_substep(const mhh_grid* g, int rkorder, int substep, double dt, void* a, void* at, void* stream);

@@ -65,6 +65,12 @@ class MhhRadiationGcssParams(C.Structure):
     _fields_ = [("xka", cd), ("fr0", cd), ("fr1", cd), ("div", cd), ("mu", cd), ("parts", ci)]
 
 
+class MhhStatsJob(C.Structure):
+    _fields_ = [("fld", vp), ("mean", vp), ("loc", ci), ("op", ci), ("offset", cd), ("threshold", cd),
+                ("kind", ci), ("scheme", ci), ("limit", ci), ("surface_model", ci), ("w", vp), ("wmean", vp), ("evisc", vp),
+                ("flux_bot", vp), ("flux_top", vp), ("visc", cd), ("tPr", cd), ("a", ci), ("b", ci)]
+
+
 FP = C.POINTER(MhhFields)
 SP = C.POINTER(MhhSurfaceParams)
 DP = C.POINTER(MhhDiffParams)
@@ -72,6 +78,7 @@ BP = C.POINTER(MhhBufferParams)
 FRP = C.POINTER(MhhForceParams)
 MP = C.POINTER(MhhMicroParams)
 RP = C.POINTER(MhhRadiationGcssParams)
+SJP = C.POINTER(MhhStatsJob)
 PLAN = vp
 
 SIGNATURES = {
@@ -195,6 +202,18 @@ SIGNATURES = {
     "mhh_radiation_gcss_zenith_host": (ci, [ci, cd, cd, cd, C.POINTER(cd)]),
     "mhh_radiation_gcss_exec": (ci, [GP, RP] + [vp]*12),
     "mhh_radiation_gcss_exec_impl": (ci, [GP, ci, RP] + [vp]*12),
+    "mhh_thermo_moist_ql_h": (ci, [GP, vp, vp, vp, vp, vp, vp, vp]),
+    "mhh_stats_interpolate_w": (ci, [GP, vp, vp, vp]),
+    "mhh_stats_scratch_elems": (C.c_ulonglong, [GP, ci, ci]),
+    "mhh_stats_chunk_rows": (ci, []),
+    "mhh_stats_mask_init": (ci, [GP, vp, vp, ci, vp]),
+    "mhh_stats_mask_thres": (ci, [GP, vp, vp, ci, vp, vp, vp, cd, ci, vp]),
+    "mhh_stats_mask_count": (ci, [GP, vp, vp, ci, vp, vp, vp]),
+    "mhh_stats_mask_finish": (ci, [GP, ci, vp, vp, vp, vp, vp, vp]),
+    "mhh_stats_sums": (ci, [GP, vp, ci, SJP, ci, vp, vp, vp]),
+    "mhh_stats_finish": (ci, [GP, ci, SJP, ci, vp, vp, vp, vp]),
+    "mhh_stats_columns": (ci, [GP, vp, ci, vp, ci, cd, cd, vp, vp, vp, vp]),
+    "mhh_stats_columns_finish": (ci, [GP, ci, vp, vp, vp]),
 }
 
 

@@ -829,3 +829,8 @@ MHH_API int mhh_boundary_ghost_cells_w(const mhh_grid* g, void* w, int type, voi
 #include "thermo_moist.h"
 #include "microphys_2mom_warm.h"
 #include "radiation_gcss.h"
+
+// =======================================================================================================
+// Stats: masks, masked profiles in two passes, cover and path (src/stats.cxx)
+// =======================================================================================================
+#include "stats.h"

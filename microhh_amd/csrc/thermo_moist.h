@@ -156,6 +156,24 @@ struct MoistFieldsOp
 };
 
 // =======================================================================================================
+// get_thermo_field("ql_h"): calc_liquid_water_h (:368-411). thl and qt interpolated to the half level, the saturation adjustment
+// at prefh; levels kstart+1 .. kend, and zero at kstart. exnrefh[k] is the table's exner(prefh[k]), the reference's `exnh`.
+// =======================================================================================================
+template<class TF>
+struct MoistQlhOp
+{
+    GridDev<TF> g; const TF* __restrict__ thl; const TF* __restrict__ qt;
+    const TF* __restrict__ prefh; const TF* __restrict__ exnrefh; TF* __restrict__ qlh; int* nonconv;
+    __device__ void operator()(int, int, int k, int c) const
+    {
+        if (k == g.kstart) { qlh[c] = TF(0.); return; }
+        const MoistSat<TF> s = moist_sat_adjust(i2(thl[c-g.ijcells], thl[c]), i2(qt[c-g.ijcells], qt[c]), prefh[k], exnrefh[k]);
+        moist_count(nonconv, s.niter);
+        qlh[c] = s.ql;
+    }
+};
+
+// =======================================================================================================
 // calc_base_state (thermo_moist_functions.h:293-349), statement by statement. OUT writes through to the caller's profile where
 // there is one; what the recurrence itself reads back (the pressures) it keeps in registers.
 // =======================================================================================================
@@ -281,6 +299,18 @@ MHH_API int mhh_thermo_moist_fields(const mhh_grid* g, const void* thl, const vo
 #define CALL(TF) [&]{ MoistFieldsOp<TF> op{make_grid<TF>(g), cp<TF>(thl), cp<TF>(qt), cp<TF>(pref), cp<TF>(exnref), cp<TF>(thvref), \
                                            mp<TF>(b), mp<TF>(ql), mp<TF>(qi), mp<TF>(T), nonconv}; \
                       return launch_interior(as_stream(stream), op.g, b ? 0 : g->kstart, b ? g->kcells : g->kend, op); }()
+    return MHH_DISPATCH(g, CALL);
+#undef CALL
+}
+
+MHH_API int mhh_thermo_moist_ql_h(const mhh_grid* g, const void* thl, const void* qt, const void* prefh, const void* exnrefh, void* ql_h,
+                                  int* nonconv, void* stream)
+{
+    if (int e = check_grid(g)) return e;
+    MHH_REQUIRE(thl && qt && prefh && exnrefh && ql_h, "null field");
+    MHH_REQUIRE(g->kgc >= 1, "the half level kend reads the ghost level of thl and qt");
+#define CALL(TF) [&]{ MoistQlhOp<TF> op{make_grid<TF>(g), cp<TF>(thl), cp<TF>(qt), cp<TF>(prefh), cp<TF>(exnrefh), mp<TF>(ql_h), nonconv}; \
+                      return launch_interior(as_stream(stream), op.g, g->kstart, g->kend + 1, op); }()
     return MHH_DISPATCH(g, CALL);
 #undef CALL
 }

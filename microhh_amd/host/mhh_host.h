@@ -15,6 +15,7 @@
 #include <array>
 #include <cmath>
 #include <cstdio>
+#include <functional>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -976,6 +977,223 @@ class Radiation_gcss
                                               thermo.pref_g, thermo.exnref_g, lflx, sflx, scratch, thermo.nonconv_g, stream));
         }
         Grid<TF>& grid; Fields<TF>& fields;
+};
+
+// ---- Stats (src/stats.cxx): the sampling of second-order cases on the device ----------------------------------------------------
+// The reference's call surface as far as it is built: add_mask, add_profs, add_time_series, add_tendency, initialize_masks,
+// set_mask_thres, finalize_masks, calc_stats, calc_tend, calc_stats_2d; get_prof and get_time_series are accessors in place of the
+// NetCDF writer and return DEVICE pointers (a profile of kcells, one value). The host Field3d carries no location, so add_profs takes
+// the zloc of the reference ("z" | "zh") and calc_stats finds it by name. The device memory is the caller's, as everywhere in this
+// header (the reference's own vectors and tmp fields): mfield_g [ncells] and mfield_bot_g [ijcells] words, zero2d_g [ijcells] zeros,
+// nmask_g [nmask_elems()] ints, work_g [work_elems()] doubles, prof_g [prof_elems()] of TF, sized once every mask, profile and
+// series is registered. Operations: "mean", "2", "3", "4", "frac", "grad", "path", "cover", and the fluxes "w", "diff", "flux" of a
+// full-level variable (set flux_of(name) and the schemes first; the variable "w" must be registered with its mean, and its
+// calc_stats come first, as Fields::exec_stats has it). A slab rank (npy > 1) sets sum_ranks, the sum over the ranks of n device
+// doubles (Master::sum): it runs between every sums call and its finish call; without it a slab grid is refused.
+// (`Stats` itself is this header's placeholder that the operators' create() and exec() take: the class is Stats_sampler<TF>.)
+enum class Stats_mask_type { Plus, Min };
+template<typename TF>
+class Stats_sampler
+{
+    public:
+        Stats_sampler(Grid<TF>& grid_in, Fields<TF>& fields_in) : grid(grid_in), fields(fields_in) {}
+        unsigned int* mfield_g = nullptr; unsigned int* mfield_bot_g = nullptr;
+        TF* zero2d_g = nullptr; int* nmask_g = nullptr; double* work_g = nullptr; TF* prof_g = nullptr;
+        std::function<void(double*, size_t)> sum_ranks;              // the sum over the ranks, in place, of device doubles
+        // what the fluxes need beyond the field: the schemes (MHH_ADVEC_2 | _2I5, MHH_DIFF_2 | _SMAG2), boundary.get_switch() !=
+        // "default", diff.tPr, and per variable where it lives (0 scalar, 1 u, 2 v), its visc, whether advec.fluxlimit_list holds it
+        int swadvec = MHH_ADVEC_2I5, swdiff = MHH_DIFF_SMAG2; bool surface_model = true; TF tPr = TF(1./3.);
+        struct Flux_info { int kind = 0; TF visc = 0; bool limit = false; };
+        Flux_info& flux_of(const std::string& name) { return flux_info[name]; }
+
+        void add_mask(const std::string& name)                       // (:841-850): flag = 1 << 2n, flagh = 1 << (2n+1)
+        {
+            if (masks.size() >= MHH_STATS_MAX_MASKS) throw std::runtime_error("Stats: at most MHH_STATS_MAX_MASKS masks");
+            masks.push_back(name);
+        }
+        void add_profs(const std::string& name, const std::string& zloc, const std::vector<std::string>& operations)   // (:853-911)
+        {
+            if (zloc != "z" && zloc != "zh") throw std::runtime_error("Stats: zloc is \"z\" or \"zh\"");
+            Var v; v.loc = (zloc == "zh");
+            auto has = [&](const char* op) { for (auto& o : operations) if (o == op) return true; return false; };
+            for (auto& o : operations)
+                if (o != "mean" && o != "2" && o != "3" && o != "4" && o != "frac" && o != "grad" && o != "path" && o != "cover" && o != "w" && o != "diff" && o != "flux")
+                    throw std::runtime_error("Stats: unknown operation \"" + o + "\"");
+            if (has("w") || has("diff") || has("flux"))
+            {
+                if (v.loc) throw std::runtime_error("Stats: the flux of a half-level variable cannot be delivered at that location");
+                if (!has("mean") || (has("flux") && !(has("w") && has("diff")))) throw std::runtime_error("Stats: a flux needs the mean; _flux needs _w and _diff");
+            }
+            if ((has("2") || has("3") || has("4")) && !has("mean")) throw std::runtime_error("Stats: a moment needs the mean of its variable");
+            if (has("mean")) { v.mean = nslots; slot[name] = nslots++; }
+            v.first_b = nslots;                                   // pass B: one slot per operation, contiguous, in the order given
+            for (auto& o : operations)
+                if (o == "2" || o == "3" || o == "4" || o == "frac" || o == "grad")
+                {
+                    v.ops_b.push_back(o == "2" ? MHH_STATS_MOMENT2 : o == "3" ? MHH_STATS_MOMENT3 : o == "4" ? MHH_STATS_MOMENT4 : o == "frac" ? MHH_STATS_FRAC : MHH_STATS_GRAD);
+                    slot[name + "_" + o] = nslots++;
+                }
+            if (v.ops_b.size() > MHH_STATS_MAX_JOBS) throw std::runtime_error("Stats: too many operations");
+            v.first_f = nslots;                                   // the fluxes: _w, _diff, _flux, contiguous, in that order
+            for (const char* o : {"w", "diff", "flux"})
+                if (has(o)) { v.ops_f.push_back(o[0] == 'w' ? MHH_STATS_FLUX_W : o[0] == 'd' ? MHH_STATS_FLUX_DIFF : MHH_STATS_FLUX_SUM); slot[name + "_" + o] = nslots++; }
+            if (has("path") || has("cover"))
+            {
+                if (v.loc) throw std::runtime_error("Stats: path and cover are taken of full-level variables");
+                v.column = nslots++;                              // cover and path per mask: [nmasks][2] at the head of the slot
+                if (has("cover")) series[name + "_cover"] = {v.column, 0};
+                if (has("path"))  series[name + "_path"]  = {v.column, 1};
+            }
+            vars[name] = v;
+        }
+        void add_time_series(const std::string& name) { series2d[name] = nslots++; }                                    // (:1177-1211)
+        void add_tendency(const std::string& var, const std::string& zloc, const std::string& tend_name)                // (:913-927)
+        {
+            tends[var + "_" + tend_name] = (zloc == "zh"); slot[var + "_" + tend_name] = nslots++;
+        }
+        size_t nmask_elems() const { return masks.size()*(2*(size_t)grid.gd.kcells + 1); }
+        size_t prof_elems() const { return (size_t)(nslots + 2)*masks.size()*grid.gd.kcells; }      // + area, areah
+        size_t work_elems() const
+        {
+            mhh_grid g = grid.abi();
+            const size_t nm = masks.size(), kc = grid.gd.kcells;
+            return (size_t)mhh_stats_scratch_elems(&g, (int)nm, MHH_STATS_MAX_JOBS) + (MHH_STATS_MAX_JOBS + 2)*nm*kc + 3*nm;
+        }
+
+        void initialize_masks(void* stream = nullptr)                // (:1214-1227)
+        {
+            mhh_grid g = grid.abi();
+            mhh_check(mhh_stats_mask_init(&g, mfield_g, mfield_bot_g, (int)masks.size(), stream));
+        }
+        // (:1264-1301): fldh's fld_bot is what the reference passes; zeros where the field has none
+        void set_mask_thres(const std::string& mask_name, Field3d<TF>& fld, Field3d<TF>& fldh, TF threshold, Stats_mask_type mode, void* stream = nullptr)
+        {
+            mhh_grid g = grid.abi();
+            mhh_check(mhh_stats_mask_thres(&g, mfield_g, mfield_bot_g, mask_index(mask_name), fld.fld_g, fldh.fld_g, fldh.fld_bot_g ? fldh.fld_bot_g : zero2d_g,
+                                           threshold, mode == Stats_mask_type::Plus ? MHH_STATS_MASK_PLUS : MHH_STATS_MASK_MIN, stream));
+        }
+        void finalize_masks(void* stream = nullptr)                  // (:1229-1262)
+        {
+            mhh_grid g = grid.abi();
+            const int nm = (int)masks.size();
+            mhh_check(mhh_stats_mask_count(&g, mfield_g, mfield_bot_g, nm, csums(), work_g, stream));
+            all_ranks(csums(), 2*(size_t)nm*grid.gd.kcells);
+            mhh_check(mhh_stats_mask_finish(&g, nm, csums(), nmask_g, nmask_g + (size_t)nm*2*grid.gd.kcells, prof(nslots), prof(nslots + 1), stream));
+        }
+        // (:1607-1890): the mean, then what reads it, then the column pass
+        void calc_stats(const std::string& varname, const Field3d<TF>& fld, const TF offset, const TF threshold, void* stream = nullptr)
+        {
+            auto it = vars.find(varname);
+            if (it == vars.end()) return;                            // not in the varlist
+            const Var& v = it->second;
+            if (v.mean >= 0)
+            {
+                mhh_stats_job j{}; j.fld = fld.fld_g; j.loc = v.loc; j.op = MHH_STATS_MEAN; j.offset = offset; j.threshold = threshold;
+                run(&j, 1, prof(v.mean), stream);
+            }
+            if (!v.ops_b.empty())
+            {
+                std::vector<mhh_stats_job> jobs(v.ops_b.size());
+                for (size_t n=0; n<jobs.size(); ++n)
+                {
+                    mhh_stats_job& j = jobs[n];
+                    j.fld = fld.fld_g; j.loc = v.loc; j.op = v.ops_b[n]; j.offset = offset; j.threshold = threshold;
+                    j.mean = (j.op >= MHH_STATS_MOMENT2 && j.op <= MHH_STATS_MOMENT4) ? prof(v.mean) : nullptr;
+                }
+                run(jobs.data(), (int)jobs.size(), prof(v.first_b), stream);
+            }
+            if (!v.ops_f.empty())
+            {
+                auto w = vars.find("w");
+                if (w == vars.end() || w->second.mean < 0) throw std::runtime_error("Stats: the resolved flux needs the variable w registered with its mean");
+                const Flux_info& fi = flux_info[varname];
+                std::vector<mhh_stats_job> jobs(v.ops_f.size());
+                for (size_t n=0; n<jobs.size(); ++n)
+                {
+                    mhh_stats_job& j = jobs[n];
+                    j.fld = fld.fld_g; j.loc = v.loc; j.op = v.ops_f[n]; j.offset = offset; j.threshold = threshold; j.mean = prof(v.mean);
+                    j.kind = fi.kind; j.w = fields.mp.at("w")->fld_g; j.wmean = prof(w->second.mean);
+                    j.scheme = (j.op == MHH_STATS_FLUX_W) ? swadvec : swdiff; j.limit = fi.limit; j.surface_model = surface_model;
+                    j.evisc = fields.sd.count("evisc") ? fields.sd.at("evisc")->fld_g : nullptr;
+                    j.flux_bot = fld.flux_bot_g; j.flux_top = fld.flux_top_g; j.visc = fi.visc; j.tPr = tPr; j.a = 0; j.b = 1;
+                }
+                run(jobs.data(), (int)jobs.size(), prof(v.first_f), stream);
+            }
+            if (v.column >= 0)
+            {
+                mhh_grid g = grid.abi();
+                const int nm = (int)masks.size();
+                mhh_check(mhh_stats_columns(&g, mfield_g, nm, fld.fld_g, v.loc, offset, threshold, fields.rhoref_g, colsums(), work_g, stream));
+                all_ranks(colsums(), 3*(size_t)nm);
+                mhh_check(mhh_stats_columns_finish(&g, nm, colsums(), prof(v.column), stream));
+            }
+        }
+        void calc_tend(Field3d<TF>& fld, const std::string& var, const std::string& tend_name, void* stream = nullptr)   // (:1893-1919)
+        {
+            auto it = tends.find(var + "_" + tend_name);
+            if (it == tends.end()) return;
+            mhh_stats_job j{}; j.fld = fld.fld_g; j.loc = it->second; j.op = MHH_STATS_MEAN;
+            run(&j, 1, prof(slot.at(it->first)), stream);
+        }
+        void calc_stats_2d(const std::string& varname, const TF* fld_g, const TF offset, void* stream = nullptr)         // (:1921-1937)
+        {
+            auto it = series2d.find(varname);
+            if (it == series2d.end()) return;
+            mhh_stats_job j{}; j.fld = fld_g; j.op = MHH_STATS_MEAN2D; j.offset = offset;
+            run(&j, 1, prof(it->second), stream);
+        }
+        // accessors: DEVICE pointers, valid once the stream has run
+        const TF* get_prof(const std::string& mask, const std::string& name) const
+        {
+            const int m = mask_index(mask);
+            const int s = (name == "area") ? nslots : (name == "areah") ? nslots + 1 : slot.at(name);
+            return prof(s) + (size_t)m*grid.gd.kcells;
+        }
+        const TF* get_time_series(const std::string& mask, const std::string& name) const
+        {
+            const int m = mask_index(mask);
+            auto it = series.find(name);
+            if (it != series.end()) return prof(it->second.first) + m*2 + it->second.second;
+            return prof(series2d.at(name)) + (size_t)m*grid.gd.kcells;
+        }
+        const int* get_nmask(const std::string& mask, bool half) const { return nmask_g + ((size_t)mask_index(mask)*2 + (half ? 1 : 0))*grid.gd.kcells; }
+        const int* get_nmask_bot(const std::string& mask) const { return nmask_g + masks.size()*2*(size_t)grid.gd.kcells + mask_index(mask); }
+
+    private:
+        struct Var { int loc = 0, mean = -1, first_b = 0, first_f = 0, column = -1; std::vector<int> ops_b, ops_f; };
+        // the sum over the ranks between a sums call and its finish call; a slab grid without the hook is refused
+        void all_ranks(double* d, size_t n)
+        {
+            if (grid.gd.npy == 1) return;
+            if (!sum_ranks) throw std::runtime_error("Stats: a slab rank (npy > 1) needs sum_ranks, the sum over the ranks");
+            sum_ranks(d, n);
+        }
+        std::map<std::string, Flux_info> flux_info;
+        int mask_index(const std::string& name) const
+        {
+            for (size_t n=0; n<masks.size(); ++n) if (masks[n] == name) return (int)n;
+            throw std::runtime_error("Invalid mask name in set_mask_thres()");
+        }
+        TF* prof(int s) const { return prof_g + (size_t)s*masks.size()*grid.gd.kcells; }
+        double* sums() const { mhh_grid g = grid.abi(); return work_g + mhh_stats_scratch_elems(&g, (int)masks.size(), MHH_STATS_MAX_JOBS); }
+        double* csums() const { return sums() + (size_t)MHH_STATS_MAX_JOBS*masks.size()*grid.gd.kcells; }
+        double* colsums() const { return csums() + 2*masks.size()*(size_t)grid.gd.kcells; }
+        // sums, the sum over the ranks, the finish
+        void run(const mhh_stats_job* jobs, int njobs, TF* out, void* stream)
+        {
+            mhh_grid g = grid.abi();
+            const int nm = (int)masks.size();
+            mhh_check(mhh_stats_sums(&g, mfield_g, nm, jobs, njobs, sums(), work_g, stream));
+            all_ranks(sums(), (size_t)njobs*nm*grid.gd.kcells);
+            mhh_check(mhh_stats_finish(&g, nm, jobs, njobs, sums(), nmask_g, out, stream));
+        }
+        Grid<TF>& grid; Fields<TF>& fields;
+        std::vector<std::string> masks;
+        std::map<std::string, Var> vars;
+        std::map<std::string, int> slot, series2d;
+        std::map<std::string, std::pair<int, int>> series;
+        std::map<std::string, bool> tends;
+        int nslots = 0;
 };
 
 } // namespace mhh_host

@@ -99,7 +99,7 @@ class HotPath:
 
     def __init__(self, case, itot, jtot, ktot, dtype=np.float64, device="cuda:0", seed=666, dt=1.0,
                  lib=None, npy=1, rank=0, group=None, global_init=None, force_slab=False, slim_halos=True, overlap=None, pres_chunks=None, igc=None,
-                 nscalars=None, forcing=None, surface=None, thermo=None, micro=None, radiation=None):
+                 nscalars=None, forcing=None, surface=None, thermo=None, micro=None, radiation=None, stats=None):
         import torch
         self.torch = torch
         self.lib = lib if lib is not None else capi.lib()
@@ -263,6 +263,8 @@ class HotPath:
         self.micro = micro.bind(self) if micro is not None else None
         # Radiation_gcss (radiation.Gcss): the zenith angle, two scratch fields
         self.radiation = radiation.bind(self) if radiation is not None else None
+        # Stats (stats.Stats): the mask words, counts and reduction scratch; sampled outside the step by hp.stats.sample()
+        self.stats = stats.bind(self) if stats is not None else None
         self.cyclic_prognostic()
         self.sync()
 

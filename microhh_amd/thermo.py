@@ -77,7 +77,7 @@ class Moist:
     reference's call does, in the Boussinesq mode too -- and the buoyancy tendency is added to wt in front of the RHS pass.
     thl0, qt0: the ktot initial values the base state starts from (default: the BOMEX profiles on the grid's levels)."""
 
-    FIELDS = ("b", "ql", "qi", "T", "N2")
+    FIELDS = ("b", "ql", "qi", "T", "N2", "ql_h")
 
     def __init__(self, pbot, swbasestate="anelastic", thvref0=None, swupdatebasestate=True, thl0=None, qt0=None):
         if swbasestate not in ("anelastic", "boussinesq"):
@@ -145,7 +145,7 @@ class Moist:
 
     # -- diagnostics -------------------------------------------------------------------------------------------------
     def field(self, name):
-        """Thermo_moist::get_thermo_field for b | ql | qi | T | N2, as a new device tensor; with swupdatebasestate the pressure and
+        """Thermo_moist::get_thermo_field for b | ql | qi | T | N2 | ql_h, as a new device tensor; with swupdatebasestate the pressure and
         Exner profiles are refreshed from the current means first (:1418-1432). Other names are refused."""
         if name not in self.FIELDS:
             raise ValueError("get_thermo_field: %r is not one of %s" % (name, " | ".join(self.FIELDS)))
@@ -156,6 +156,10 @@ class Moist:
             self.update_base_state(("pref", "prefh", "exnref", "exnrefh"))
         if name == "N2":
             capi.check(hp.lib.mhh_calc_N2(hp.G, out.data_ptr(), hp.s[0].data_ptr(), self.tab["thvref"].data_ptr(), 9.81, hp.stream), hp.lib)
+            return out
+        if name == "ql_h":               # calc_liquid_water_h (:368-411): the half levels kstart .. kend
+            capi.check(hp.lib.mhh_thermo_moist_ql_h(hp.G, hp.s[0].data_ptr(), hp.s[1].data_ptr(), *self._p("prefh", "exnrefh"), out.data_ptr(),
+                                                    self.nonconv.data_ptr(), hp.stream), hp.lib)
             return out
         ptrs = [out.data_ptr() if n == name else None for n in ("b", "ql", "qi", "T")]
         capi.check(hp.lib.mhh_thermo_moist_fields(hp.G, hp.s[0].data_ptr(), hp.s[1].data_ptr(), *self._p("pref", "exnref", "thvref"), *ptrs,
