@@ -770,6 +770,55 @@ int mhh_stats_columns_finish(const mhh_grid* g, int nmasks, const void* sums, vo
  * (src/fields.cxx:631-643): wf [ncells] is zeroed, then written on the levels 0 .. kcells-2 of the interior columns.               */
 int mhh_stats_interpolate_w(const mhh_grid* g, const void* w, void* wf, void* stream);
 
+/* ---- Budget_2 (src/budget_2.cxx: Budget_2<TF>::exec_stats for second-order cases) ----------------------------------------------
+ * The kinetic energies and the terms of the u2, v2, w2, tke, uw, vw, b2 and bw budgets as masked profiles, evaluated per cell and
+ * per mask and reduced in the same launch: no term field reaches memory. EVERY profile, the "zh" ones included, is averaged under
+ * the full-level flag and divided by the full-level nmask over kstart .. kend, as calc_mask_stats does with a tmp field of
+ * loc {0,0,0} (src/fields.cxx:805); a level the loops of a term do not write counts as zero. Split into sums and finish like Stats;
+ * the reductions are deterministic. `scratch`: mhh_budget_2_scratch_elems(g, nmasks) DOUBLES. Needs the cyclic ghost cells of
+ * u, v, w, p, evisc, b and one vertical ghost level of each; the LES diffusion group two horizontal ghost cells. */
+#define MHH_BUDGET_KE      0x001u  /* calc_kinetic_energy (:51-94): ke, tke                                                        */
+#define MHH_BUDGET_SHEAR   0x002u  /* calc_shear_terms (:100-135): u2_shear, v2_shear, tke_shear, uw_shear, vw_shear               */
+#define MHH_BUDGET_TURB    0x004u  /* calc_turb_terms (:141-233): u2_turb, v2_turb, w2_turb, tke_turb, uw_turb, vw_turb            */
+#define MHH_BUDGET_COR     0x008u  /* calc_coriolis_terms (:239-279): u2_cor, v2_cor, uw_cor, vw_cor (swlspres=geo)                */
+#define MHH_BUDGET_PRES    0x010u  /* calc_pressure_transport_terms (:285-352): w2_pres, tke_pres, uw_pres, vw_pres                */
+#define MHH_BUDGET_RDSTR   0x020u  /* calc_pressure_redistribution_terms (:358-419): u2_rdstr, v2_rdstr, w2_rdstr, uw_rdstr, vw_rdstr */
+#define MHH_BUDGET_DIFF    0x040u  /* calc_diffusion_terms_les (:680-1038), diff_smag2: u2_diff, v2_diff, w2_diff, tke_diff, uw_diff, vw_diff */
+#define MHH_BUDGET_BUOY    0x080u  /* calc_buoyancy_terms (:1044-1090): w2_buoy, tke_buoy, uw_buoy, vw_buoy                         */
+#define MHH_BUDGET_BW_BUOY 0x100u  /* calc_buoyancy_terms_scalar (:1096-1115) with s = b: bw_buoy                                   */
+#define MHH_BUDGET_ADV_S   0x200u  /* calc_advection_terms_scalar (:1121-1156): b2_shear, b2_turb, bw_shear, bw_turb                */
+#define MHH_BUDGET_PRES_S  0x400u  /* calc_pressure_terms_scalar (:1257-1279): bw_pres, bw_rdstr                                    */
+typedef struct mhh_budget_2_desc
+{
+    const void *u, *v, *w, *p, *evisc, *b;       /* [ncells]; p, evisc, b may be NULL where no selected group reads them            */
+    const void *u_fluxbot, *v_fluxbot;           /* [ijcells]: the LES diffusion group                                               */
+    const void *umodel, *vmodel, *wmodel;        /* [nmasks][kcells]: mhh_budget_2_model_finish (Stats::calc_mask_mean_profile)      */
+    const void *bmean, *pmean;                   /* [kcells]: field3d_operators.calc_mean_profile of b and p (mhh_field_mean_profile) */
+    double utrans, vtrans, fc;                   /* gd.utrans, gd.vtrans, force.get_coriolis_parameter(); narrowed on entry          */
+    int order;                                   /* grid.swspatialorder: 2; anything else is refused (Budget_4 is not built)         */
+    int diff_scheme;                             /* MHH_DIFF_*: the LES diffusion group is diff_smag2's                              */
+    unsigned int groups;                         /* MHH_BUDGET_* bits; profiles come in the order of the bits                         */
+} mhh_budget_2_desc;
+/* the number of profiles of a group set (-1: unknown bit) and the n-th one's name (Budget_2::create, :1315-1412) with *half = 0 for
+ * "z", 1 for "zh"; NULL past the end */
+int mhh_budget_2_nprofs(unsigned int groups);
+const char* mhh_budget_2_prof_name(unsigned int groups, int n, int* half);
+unsigned long long mhh_budget_2_scratch_elems(const mhh_grid* g, int nmasks);
+/* Stats::calc_mask_mean_profile (src/stats.cxx:1328-1347) of u, v (full-level flag and nmask) and w (half-level flag and nmaskh):
+ * calc_mean over ALL levels 0 .. kcells-1. sums[3][nmasks][kcells] doubles, then out[3][nmasks][kcells] of the dtype = umodel,
+ * vmodel, wmodel. A level with nmask[k] == 0 holds 0 (the reference leaves what the vector held: the previous mask's value). */
+int mhh_budget_2_model_sums(const mhh_grid* g, const void* mfield, int nmasks, const void* u, const void* v, const void* w, void* sums, void* scratch, void* stream);
+int mhh_budget_2_model_finish(const mhh_grid* g, int nmasks, const void* sums, const void* nmask, void* out, void* stream);
+/* The calc_* loops of Budget_2::exec_stats (src/budget_2.cxx:1414-1818) with the calc_mean of calc_mask_stats (src/stats.cxx:1350-1390)
+ * over each: sums[nprofs][nmasks][kcells] doubles, then out[nprofs][nmasks][kcells] of the dtype with the fill value where
+ * nmask[k] == 0. Refused with MHH_EINVAL and a message: order != 2; the LES diffusion group with igc < 2 or jgc < 2, with a scheme
+ * other than diff_smag2; a buoyancy, b2 or bw group without b; an unknown group bit. */
+int mhh_budget_2_sums(const mhh_grid* g, const void* mfield, int nmasks, const mhh_budget_2_desc* desc, void* sums, void* scratch, void* stream);
+int mhh_budget_2_finish(const mhh_grid* g, int nmasks, const mhh_budget_2_desc* desc, const void* sums, const void* nmask, void* out, void* stream);
+/* Thermo_dry::get_thermo_field("b") (calc_buoyancy, src/thermo_dry.cxx:51-63): b = grav/thref[k]*(th - thref[k]) on all kcells
+ * levels of the interior columns */
+int mhh_thermo_dry_buoyancy(const mhh_grid* g, void* b, const void* th, const void* thref, double grav, void* stream);
+
 /* ---- Timeloop RK3/RK4 substep (src/timeloop.cxx:250-334, src/timeloop.cu:35-122) -------- */
 int mhh_rk_substep(const mhh_grid* g, int rkorder, int substep, double dt, void* a, void* at, void* stream);
 /* pres->exec(sub_dt) followed by timeloop.exec() for u, v, w (src/model.cxx:411,484): the sub-step rides in the pres_2 kernel that

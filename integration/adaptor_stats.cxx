@@ -66,6 +66,7 @@ namespace
         dev.sums = mhh_alloc<double>((size_t)MHH_STATS_MAX_JOBS*nmasks*gd.kcells); dev.csums = mhh_alloc<double>((size_t)2*nmasks*gd.kcells + 3*nmasks);
         dev.out = mhh_alloc<TF>((size_t)MHH_STATS_MAX_JOBS*nmasks*gd.kcells);
         dev.mean = mhh_alloc<TF>((size_t)nmasks*gd.kcells); dev.wmean = mhh_alloc<TF>((size_t)nmasks*gd.kcells);
+        mhh_stats_device() = Mhh_stats_device{dev.mfield, dev.nmask, nmasks};      // Budget_2::exec_stats averages under the same words
     }
     inline int mhh_mask_index(unsigned int flag) { int n = 0; while ((1u << (2*n)) != flag) ++n; return n; }   // flag = 1 << 2n (:841-850)
     void mhh_d2h(void* dst, const void* src, size_t bytes) { if (hipMemcpy(dst, src, bytes, 2) != 0) throw std::runtime_error("hipMemcpy"); }

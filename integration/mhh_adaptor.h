@@ -49,6 +49,11 @@ mhh_fields mhh_make_fields(Fields<TF>& f)
     a.v_fluxbot = f.mp.at("v")->flux_bot_g; a.v_fluxtop = f.mp.at("v")->flux_top_g;
     return a;
 }
+// What adaptor_stats.cxx leaves on the device for the other statistics adaptors (adaptor_budget_2.cxx): the mask words of
+// finalize_masks and the counts nmask[mask][2][kcells]. One object for all translation units.
+struct Mhh_stats_device { unsigned int* mfield = nullptr; int* nmask = nullptr; int nmasks = 0; };
+inline Mhh_stats_device& mhh_stats_device() { static Mhh_stats_device d; return d; }
+
 template<typename TF>
 int mhh_scalar_index(Fields<TF>& f, const std::string& name)
 {

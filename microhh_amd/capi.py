@@ -71,6 +71,12 @@ class MhhStatsJob(C.Structure):
                 ("flux_bot", vp), ("flux_top", vp), ("visc", cd), ("tPr", cd), ("a", ci), ("b", ci)]
 
 
+class MhhBudget2Desc(C.Structure):
+    _fields_ = [("u", vp), ("v", vp), ("w", vp), ("p", vp), ("evisc", vp), ("b", vp), ("u_fluxbot", vp), ("v_fluxbot", vp),
+                ("umodel", vp), ("vmodel", vp), ("wmodel", vp), ("bmean", vp), ("pmean", vp),
+                ("utrans", cd), ("vtrans", cd), ("fc", cd), ("order", ci), ("diff_scheme", ci), ("groups", C.c_uint)]
+
+
 FP = C.POINTER(MhhFields)
 SP = C.POINTER(MhhSurfaceParams)
 DP = C.POINTER(MhhDiffParams)
@@ -79,6 +85,7 @@ FRP = C.POINTER(MhhForceParams)
 MP = C.POINTER(MhhMicroParams)
 RP = C.POINTER(MhhRadiationGcssParams)
 SJP = C.POINTER(MhhStatsJob)
+BDP = C.POINTER(MhhBudget2Desc)
 PLAN = vp
 
 SIGNATURES = {
@@ -214,6 +221,14 @@ SIGNATURES = {
     "mhh_stats_finish": (ci, [GP, ci, SJP, ci, vp, vp, vp, vp]),
     "mhh_stats_columns": (ci, [GP, vp, ci, vp, ci, cd, cd, vp, vp, vp, vp]),
     "mhh_stats_columns_finish": (ci, [GP, ci, vp, vp, vp]),
+    "mhh_budget_2_nprofs": (ci, [C.c_uint]),
+    "mhh_budget_2_prof_name": (C.c_char_p, [C.c_uint, ci, C.POINTER(ci)]),
+    "mhh_budget_2_scratch_elems": (C.c_ulonglong, [GP, ci]),
+    "mhh_budget_2_model_sums": (ci, [GP, vp, ci, vp, vp, vp, vp, vp, vp]),
+    "mhh_budget_2_model_finish": (ci, [GP, ci, vp, vp, vp, vp]),
+    "mhh_budget_2_sums": (ci, [GP, vp, ci, BDP, vp, vp, vp]),
+    "mhh_budget_2_finish": (ci, [GP, ci, BDP, vp, vp, vp, vp]),
+    "mhh_thermo_dry_buoyancy": (ci, [GP, vp, vp, vp, cd, vp]),
 }
 
 

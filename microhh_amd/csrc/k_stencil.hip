@@ -834,3 +834,8 @@ MHH_API int mhh_boundary_ghost_cells_w(const mhh_grid* g, void* w, int type, voi
 // Stats: masks, masked profiles in two passes, cover and path (src/stats.cxx)
 // =======================================================================================================
 #include "stats.h"
+
+// =======================================================================================================
+// Budget_2: the kinetic energies and the budget terms as masked profiles (src/budget_2.cxx)
+// =======================================================================================================
+#include "budget_2.h"

@@ -1158,6 +1158,7 @@ class Stats_sampler
         }
         const int* get_nmask(const std::string& mask, bool half) const { return nmask_g + ((size_t)mask_index(mask)*2 + (half ? 1 : 0))*grid.gd.kcells; }
         const int* get_nmask_bot(const std::string& mask) const { return nmask_g + masks.size()*2*(size_t)grid.gd.kcells + mask_index(mask); }
+        const std::vector<std::string>& get_masks() const { return masks; }      // Budget_2_sampler averages under the same masks
 
     private:
         struct Var { int loc = 0, mean = -1, first_b = 0, first_f = 0, column = -1; std::vector<int> ops_b, ops_f; };
@@ -1194,6 +1195,104 @@ class Stats_sampler
         std::map<std::string, std::pair<int, int>> series;
         std::map<std::string, bool> tends;
         int nslots = 0;
+};
+
+// Budget_2<TF>::exec_stats (src/budget_2.cxx:1414-1818) on the device, under the masks of a Stats_sampler whose finalize_masks has
+// run: the model profiles (Stats::calc_mask_mean_profile), bmean and pmean (field3d_operators.calc_mean_profile) and every calc_*
+// loop with the calc_mask_stats that follows it, as mhh_budget_2_sums + mhh_budget_2_finish (csrc/budget_2.h). `groups` are the
+// MHH_BUDGET_* bits Budget_2::create (:1315-1412) would register: MHH_BUDGET_COR with a geostrophic forcing, MHH_BUDGET_DIFF with
+// diff_smag2, the four buoyancy bits with a thermo, whose b (get_thermo_field "b" with its cyclic fill) is b_g. fields.mp holds u, v, w
+// (u and v with flux_bot_g for the LES diffusion group), fields.sd p and evisc. The device memory is the caller's: work_g
+// [work_elems()] doubles, prof_g [prof_elems()] of TF. A slab rank adds the double sums over the ranks through the Stats_sampler's
+// sum_ranks between every sums call and its finish call, and the shares of bmean and pmean -- profiles of TF, summed as the
+// reference's master.sum(prof, kcells) does after the division -- through sum_ranks_prof (TF = double: sum_ranks where it is unset).
+// get_prof returns DEVICE pointers.
+template<typename TF>
+class Budget_2_sampler
+{
+    public:
+        Budget_2_sampler(Grid<TF>& grid_in, Fields<TF>& fields_in, Stats_sampler<TF>& stats_in) : grid(grid_in), fields(fields_in), stats(stats_in) {}
+        double* work_g = nullptr; TF* prof_g = nullptr; const TF* b_g = nullptr;
+        unsigned int groups = MHH_BUDGET_KE | MHH_BUDGET_SHEAR | MHH_BUDGET_TURB | MHH_BUDGET_PRES | MHH_BUDGET_RDSTR;
+        int swdiff = MHH_DIFF_SMAG2; TF utrans = 0, vtrans = 0, fc = 0;
+        std::function<void(TF*, size_t)> sum_ranks_prof;             // the sum over the ranks, in place, of device values of TF
+
+        int nprofs() const { const int n = mhh_budget_2_nprofs(groups); if (n < 0) throw std::runtime_error("Budget_2: unknown group bit"); return n; }
+        size_t work_elems() const
+        {
+            mhh_grid g = grid.abi();
+            return (size_t)mhh_budget_2_scratch_elems(&g, nm()) + (size_t)mhh_field_mean_scratch_elems(&g, 2) + (size_t)(nprofs() + 3)*nm()*grid.gd.kcells;
+        }
+        size_t prof_elems() const { return ((size_t)(nprofs() + 3)*nm() + 2)*grid.gd.kcells; }
+
+        void exec_stats(void* stream = nullptr)
+        {
+            mhh_grid g = grid.abi();
+            const int n = nm(), np = nprofs();
+            const size_t kc = grid.gd.kcells;
+            double* scratch = work_g;
+            double* mscratch = scratch + mhh_budget_2_scratch_elems(&g, n);
+            double* sums = mscratch + mhh_field_mean_scratch_elems(&g, 2);
+            TF* model = prof_g + (size_t)np*n*kc;                    // umodel, vmodel, wmodel [nmasks][kcells] each, then bmean, pmean
+            TF* means = model + 3*(size_t)n*kc;
+            const TF* u = fields.mp.at("u")->fld_g; const TF* v = fields.mp.at("v")->fld_g; const TF* w = fields.mp.at("w")->fld_g;
+            const TF* p = fields.sd.count("p") ? fields.sd.at("p")->fld_g : nullptr;
+            mhh_check(mhh_budget_2_model_sums(&g, stats.mfield_g, n, u, v, w, sums, scratch, stream));
+            all_ranks(sums, 3*(size_t)n*kc, stream);
+            mhh_check(mhh_budget_2_model_finish(&g, n, sums, stats.nmask_g, model, stream));
+            const bool thermo = groups & (MHH_BUDGET_BUOY | MHH_BUDGET_BW_BUOY | MHH_BUDGET_ADV_S | MHH_BUDGET_PRES_S);
+            if (thermo)
+            {
+                if (!b_g || !p) throw std::runtime_error("Budget_2: the buoyancy, b2 and bw groups need b and p");
+                const void* flds[2] = {b_g, p}; void* profs[2] = {means, means + kc};
+                mhh_check(mhh_field_mean_profile(&g, flds, 2, profs, mscratch, stream));      // a slab rank: its share of the means
+                if (grid.gd.npy != 1)
+                {
+                    if (sum_ranks_prof) sum_ranks_prof(means, 2*kc);
+                    else if (sizeof(TF) == sizeof(double)) all_ranks(reinterpret_cast<double*>(means), 2*kc, stream);
+                    else throw std::runtime_error("Budget_2: a slab rank (npy > 1) needs sum_ranks_prof, the sum over the ranks of a profile");
+                }
+            }
+            mhh_budget_2_desc d{};
+            d.u = u; d.v = v; d.w = w; d.p = p; d.b = b_g;
+            d.evisc = fields.sd.count("evisc") ? fields.sd.at("evisc")->fld_g : nullptr;
+            d.u_fluxbot = fields.mp.at("u")->flux_bot_g; d.v_fluxbot = fields.mp.at("v")->flux_bot_g;
+            d.umodel = model; d.vmodel = model + (size_t)n*kc; d.wmodel = model + 2*(size_t)n*kc;
+            if (thermo) { d.bmean = means; d.pmean = means + kc; }
+            d.utrans = utrans; d.vtrans = vtrans; d.fc = fc; d.order = 2; d.diff_scheme = swdiff; d.groups = groups;
+            mhh_check(mhh_budget_2_sums(&g, stats.mfield_g, n, &d, sums, scratch, stream));
+            all_ranks(sums, (size_t)np*n*kc, stream);
+            mhh_check(mhh_budget_2_finish(&g, n, &d, sums, stats.nmask_g, prof_g, stream));
+        }
+        const TF* get_prof(const std::string& mask, const std::string& name) const
+        {
+            const auto& masks = stats.get_masks();
+            size_t m = 0;
+            while (m < masks.size() && masks[m] != mask) ++m;
+            if (m == masks.size()) throw std::runtime_error("Budget_2: no such mask");
+            for (int n=0; n<nprofs(); ++n)
+                if (name == mhh_budget_2_prof_name(groups, n, nullptr)) return prof_g + ((size_t)n*masks.size() + m)*grid.gd.kcells;
+            throw std::runtime_error("Budget_2: no such profile: " + name);
+        }
+        const TF* get_model(int which, const std::string& mask) const      // 0 umodel, 1 vmodel, 2 wmodel
+        {
+            const auto& masks = stats.get_masks();
+            size_t m = 0;
+            while (m < masks.size() && masks[m] != mask) ++m;
+            if (m == masks.size()) throw std::runtime_error("Budget_2: no such mask");
+            if (which < 0 || which > 2) throw std::runtime_error("Budget_2: model profiles are 0 umodel, 1 vmodel, 2 wmodel");
+            return prof_g + (((size_t)nprofs() + which)*masks.size() + m)*grid.gd.kcells;
+        }
+
+    private:
+        int nm() const { return (int)stats.get_masks().size(); }
+        void all_ranks(double* d, size_t n, void*)
+        {
+            if (grid.gd.npy == 1) return;
+            if (!stats.sum_ranks) throw std::runtime_error("Budget_2: a slab rank (npy > 1) needs the Stats_sampler's sum_ranks");
+            stats.sum_ranks(d, n);
+        }
+        Grid<TF>& grid; Fields<TF>& fields; Stats_sampler<TF>& stats;
 };
 
 } // namespace mhh_host

@@ -4,7 +4,8 @@ The sampling of Stats<TF> (src/stats.cxx) for second-order cases, with the field
 (initialize_masks, set_mask_thres, finalize_masks), the masked profiles of calc_stats in two passes (means; then moments, frac and
 the vertical gradient, which read the means of the first from device memory), calc_tend, calc_stats_2d, and the column pass of
 cover and path, and the resolved, diffusive and total fluxes (_w, _diff, _flux) of advec_2 / advec_2i5 / the limited scalar flux and
-diff_2 / diff_smag2. The parity target is the reference's CPU path. Not built here: covariances, budgets and the qlcore / bplus /
+diff_2 / diff_smag2. The parity target is the reference's CPU path. With HotPath(..., budget=Budget2()) a sample also holds the
+profiles of Budget_2 (budget.py). Not built here: covariances and the qlcore / bplus /
 bmin masks (they need b at the half level). On a slab (npy > 1) the double sums and the counts of a rank's rows are added over the ranks (Master.sum_) between every sums call and its finish call.
 """
 import ctypes as C
@@ -302,7 +303,11 @@ class Stats:
         where the reference has it, and nmask, nmaskh, area, areah per mask."""
         sm, hp = self.sampler, self.hp
         na, outa, nb, outb, cols = self.enqueue()
+        # Budget_2::exec_stats (src/budget_2.cxx:1414-1818) after Stats' own passes, under the masks they left
+        bud = getattr(hp, "budget", None)
+        outd = bud.enqueue() if bud is not None else None
         hp.sync()
+        hd = outd.cpu().numpy() if outd is not None else None
         ha = outa.cpu().numpy() if outa is not None else None
         hb = outb.cpu().numpy() if outb is not None else None
         nmask, area, areah = sm.nmask.cpu().numpy(), sm.area.cpu().numpy(), sm.areah.cpu().numpy()
@@ -315,6 +320,9 @@ class Stats:
                 r[name] = float(ha[n, m, 0]) if name in n2d else ha[n, m].copy()
             for n, name in enumerate(nb):
                 r[name] = hb[n, m].copy()
+            if hd is not None:
+                for n, (name, _) in enumerate(bud.names):
+                    r[name] = hd[n, m].copy()
             for name, t, loc, ops, off, thr in self.vars:
                 if name in hc:
                     c = hc[name]
