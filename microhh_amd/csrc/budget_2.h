@@ -2,13 +2,13 @@
 // w2, tke, uw, vw, b2 and bw budgets as masked profiles. One __device__ evaluation function per term group restates the loop bodies
 // of the reference statement by statement; a term is never stored: the kernel evaluates it per cell and per mask (the mask-mean
 // profiles umodel, vmodel, wmodel are the mask's) and adds it under the FULL-level flag, which is what calc_mask_stats does with a
-// tmp field of loc {0,0,0} (src/fields.cxx:805), the half-level terms included. The reduction is that of stats.h: a block owns one
-// level and a chunk of STATS_ROWS rows, a second kernel adds the chunks in index order; no floating-point atomics. A level that the
-// loops of a term do not write counts as zero (the tmp field of a first sample).
+// tmp field of loc {0,0,0} (src/fields.cxx:805), the half-level terms included. The reduction is that of level_reduce.h, with
+// block_sums as the block's order. A level that the loops of a term do not write counts as zero (the tmp field of a first sample).
 // pow(x, 2) is x*x and pow(x, 3) is x*x*x, both in double as std::pow(TF, int) returns double: bp2 and bp3 return double, so that the
 // products and differences around them promote exactly as the reference's statements do; every store narrows once into TF.
-// Kernels and C-ABI entry points; included from k_stencil.hip after stats.h.
+// Kernels and C-ABI entry points; included from k_stencil.hip. stats.h gives stats_fill and stats_check.
 #pragma once
+#include "level_reduce.h"
 #include "stats.h"
 
 namespace mhh
@@ -42,7 +42,8 @@ template<class TF> struct BudgetArgs
     const TF *dzi, *dzhi;
     const unsigned int* mfield;
     TF utrans, vtrans, fc, dxi, dyi;
-    int nmasks, icells, ijcells, kcells, istart, iend, jstart, jend, kstart, kend;
+    LevelDomain dom;
+    int nmasks, kcells, kstart, kend;
     int p0;                                                        // the group's first profile in part and sums
     int lastrank;                                                  // this rank holds the last rows of the domain (mpicoordy == npy-1)
 };
@@ -76,7 +77,7 @@ template<class TF> __device__ __forceinline__ void budget_ke(const BudgetArgs<TF
 {
     if (L.k >= L.ke) return;
     const TF* __restrict__ u = A.u; const TF* __restrict__ v = A.v; const TF* __restrict__ w = A.w;
-    const int ii = 1, jj = A.icells, kk = A.ijcells;
+    const int ii = 1, jj = A.dom.icells, kk = A.dom.ijcells;
     {
         const TF t = i2(TF(u[c]+A.utrans), TF(u[c+ii]+A.utrans)); const TF u2 = t*t;
         const TF s = i2(TF(v[c]+A.vtrans), TF(v[c+jj]+A.vtrans)); const TF v2 = s*s;
@@ -96,7 +97,7 @@ template<class TF> __device__ __forceinline__ void budget_shear(const BudgetArgs
 {
     if (L.k >= L.ke) return;
     const TF* __restrict__ u = A.u; const TF* __restrict__ v = A.v; const TF* __restrict__ w = A.w;
-    const int jj = A.icells, kk = A.ijcells;
+    const int jj = A.dom.icells, kk = A.dom.ijcells;
     const TF dudz = (i2(L.um[1], L.um[2]) - i2(L.um[0], L.um[1])) * L.dzi[1];
     const TF dvdz = (i2(L.vm[1], L.vm[2]) - i2(L.vm[0], L.vm[1])) * L.dzi[1];
     const TF wx = budget_wx(w, c), wxt = budget_wx(w, c+kk), wy = budget_wy(w, c, jj), wyt = budget_wy(w, c+kk, jj);
@@ -113,7 +114,7 @@ template<class TF> __device__ __forceinline__ void budget_shear(const BudgetArgs
 template<class TF> __device__ __forceinline__ void budget_turb(const BudgetArgs<TF>& A, const BudgetLev<TF>& L, size_t c, TF (&o)[BNP])
 {
     const TF* __restrict__ u = A.u; const TF* __restrict__ v = A.v; const TF* __restrict__ w = A.w;
-    const int jj = A.icells, kk = A.ijcells, k = L.k;
+    const int jj = A.dom.icells, kk = A.dom.ijcells, k = L.k;
     const TF wx = budget_wx(w, c), wxb = budget_wx(w, c-kk), wy = budget_wy(w, c, jj), wyb = budget_wy(w, c-kk, jj);
     if (k < L.ke)
     {
@@ -157,7 +158,7 @@ template<class TF> __device__ __forceinline__ void budget_cor(const BudgetArgs<T
 {
     if (L.k >= L.ke) return;
     const TF* __restrict__ u = A.u; const TF* __restrict__ v = A.v; const TF* __restrict__ w = A.w;
-    const int ii = 1, jj = A.icells, kk = A.ijcells;
+    const int ii = 1, jj = A.dom.icells, kk = A.dom.ijcells;
     const TF fc = A.fc;
     o[0] = TF( 2.) * (u[c]-L.um[1]) * (i22(v[c-ii], v[c], v[c-ii+jj], v[c+jj])-L.vm[1]) * fc;
     o[1] = TF(-2.) * (v[c]-L.vm[1]) * (i22(u[c-jj], u[c], u[c+ii-jj], u[c+ii])-L.um[1]) * fc;
@@ -176,7 +177,7 @@ template<class TF> __device__ __forceinline__ void budget_pres(const BudgetArgs<
 {
     if (L.k >= L.ke) return;
     const TF* __restrict__ u = A.u; const TF* __restrict__ v = A.v; const TF* __restrict__ w = A.w; const TF* __restrict__ p = A.p;
-    const int ii = 1, jj = A.icells, kk = A.ijcells;
+    const int ii = 1, jj = A.dom.icells, kk = A.dom.ijcells;
     const TF dxi = A.dxi, dyi = A.dyi;
     o[1] = - ( i2(p[c], p[c+kk]) * (w[c+kk] -L.wm[2])-
                i2(p[c], p[c-kk]) * (w[c   ] -L.wm[1])) * L.dzi[1];
@@ -202,7 +203,7 @@ template<class TF> __device__ __forceinline__ void budget_rdstr(const BudgetArgs
 {
     if (L.k >= L.ke) return;
     const TF* __restrict__ u = A.u; const TF* __restrict__ v = A.v; const TF* __restrict__ w = A.w; const TF* __restrict__ p = A.p;
-    const int ii = 1, jj = A.icells, kk = A.ijcells;
+    const int ii = 1, jj = A.dom.icells, kk = A.dom.ijcells;
     const TF dxi = A.dxi, dyi = A.dyi;
     o[0] = TF(2.) * i2(p[c], p[c-ii]) *
         ( i2(TF(u[c]-L.um[1]), TF(u[c+ii]-L.um[1])) -
@@ -255,7 +256,7 @@ template<class TF, int PART> __device__ __forceinline__ void budget_diff_les(con
 {
     if (L.k >= L.ke) return;
     const TF* __restrict__ u = A.u; const TF* __restrict__ v = A.v; const TF* __restrict__ w = A.w; const TF* __restrict__ evisc = A.evisc;
-    const int ii = 1, ii2 = 2, jj = A.icells, jj2 = 2*A.icells, kk = A.ijcells, kk2 = 2*A.ijcells, k = L.k;
+    const int ii = 1, ii2 = 2, jj = A.dom.icells, jj2 = 2*A.dom.icells, kk = A.dom.ijcells, kk2 = 2*A.dom.ijcells, k = L.k;
     const TF dxi = A.dxi, dyi = A.dyi;
     const TF umk = L.um[1], vmk = L.vm[1], wmk = L.wm[1];
     const TF dzik = L.dzi[1], dzikm = L.dzi[0], dzhik = L.dzhi[1], dzhikp = L.dzhi[2];
@@ -317,8 +318,8 @@ template<class TF, int PART> __device__ __forceinline__ void budget_diff_les(con
         {
             const TF wzt = budget_wz(w, c, kk, 1, Z), wzb = budget_wz(w, c, kk, -1, Z);
             const TF evisch   = budget_evisch(evisc, c,    jj, kk, true);
-            const TF evischn  = budget_evisch(evisc, c+jj, jj, kk, j + 1 < A.jend || !A.lastrank);
-            const TF evische  = budget_evisch(evisc, c+ii, jj, kk, i + 1 < A.iend);
+            const TF evischn  = budget_evisch(evisc, c+jj, jj, kk, j + 1 < A.dom.jend || !A.lastrank);
+            const TF evische  = budget_evisch(evisc, c+ii, jj, kk, i + 1 < A.dom.iend);
 
             u2 += TF(2.) * (u[c]-umk) * ( evisc_utop * (u[c+kk] - u[c   ]) * dzhikp -
                                           evisc_ubot * (u[c   ] - u[c-kk]) * dzhik  ) * dzik;
@@ -472,7 +473,7 @@ template<class TF> __device__ __forceinline__ void budget_buoy(const BudgetArgs<
 {
     if (L.k >= L.ke) return;
     const TF* __restrict__ u = A.u; const TF* __restrict__ v = A.v; const TF* __restrict__ w = A.w; const TF* __restrict__ b = A.b;
-    const int ii = 1, jj = A.icells, kk = A.ijcells;
+    const int ii = 1, jj = A.dom.icells, kk = A.dom.ijcells;
     o[1] = i2(TF(w[c]-L.wm[1]), TF(w[c+kk]-L.wm[2])) * (b[c] - L.bm[1]);
     if (L.k == L.ks) return;
     o[0] = TF(2.) * i2(TF(b[c]-L.bm[1]), TF(b[c-kk]-L.bm[0])) * (w[c]-L.wm[1]);
@@ -487,7 +488,7 @@ template<class TF> __device__ __forceinline__ void budget_bwbuoy(const BudgetArg
 {
     if (L.k >= L.ke) return;
     const TF* __restrict__ b = A.b;
-    const int kk = A.ijcells;
+    const int kk = A.dom.ijcells;
     o[0] = i2(TF(b[c]-L.bm[1]), TF(b[c-kk]-L.bm[0])) * i2(TF(b[c]-L.bm[1]), TF(b[c-kk]-L.bm[0]));
 }
 
@@ -497,7 +498,7 @@ template<class TF> __device__ __forceinline__ void budget_advs(const BudgetArgs<
 {
     if (L.k >= L.ke) return;
     const TF* __restrict__ w = A.w; const TF* __restrict__ s = A.b;
-    const int kk = A.ijcells;
+    const int kk = A.dom.ijcells;
     const TF dsdz  = (i2(L.bm[1], L.bm[2]) - i2(L.bm[1], L.bm[0])) * L.dzi[1];
     const TF dsdzh = (L.bm[1] - L.bm[0]) * L.dzhi[1];
     o[0] = - TF(2.) * (s[c] - L.bm[1]) * i2(w[c], w[c+kk]) * dsdz;
@@ -513,7 +514,7 @@ template<class TF> __device__ __forceinline__ void budget_press(const BudgetArgs
 {
     if (L.k >= L.ke) return;
     const TF* __restrict__ s = A.b; const TF* __restrict__ p = A.p;
-    const int kk = A.ijcells;
+    const int kk = A.dom.ijcells;
     o[0] = - ((p[c]-L.pm[1]) * (s[c]-L.bm[1]) - (p[c-kk]-L.pm[0]) * (s[c-kk]-L.bm[0])) * L.dzhi[1];
     o[1] = i2(TF(p[c]-L.pm[1]), TF(p[c-kk]-L.pm[0])) * ((s[c]-L.bm[1])-(s[c-kk]-L.bm[0])) * L.dzhi[1];
 }
@@ -522,18 +523,14 @@ template<class TF> __device__ __forceinline__ void budget_press(const BudgetArgs
 // G == BG_MODEL: Stats::calc_mask_mean_profile (src/stats.cxx:1328-1347), calc_mean of u, v under the full-level flag and of w under
 // the half-level flag over ALL levels 0 .. kcells-1.
 template<class TF, int G, int NM>
-__global__ void __launch_bounds__(STATS_THREADS) budget_partial_kernel(const BudgetArgs<TF> A, const Tiling t, double* __restrict__ part, int k0, int nk, int nchunks)
+__global__ void __launch_bounds__(LEVEL_THREADS) budget_partial_kernel(const BudgetArgs<TF> A, const Tiling t, double* __restrict__ part, int k0, int nk, int nchunks)
 {
     constexpr int NP = (G == BG_MODEL) ? 3 : (G == BG_DIFF) ? 4 : (G == BG_DIFF_UW || G == BG_DIFF_VW) ? 1 : budget_np(G);
-    __shared__ double red[NM*STATS_THREADS];
-    __shared__ double red2[NM*16];
-    int bx, by, kz;
-    if (!decode_tile(t, blockIdx.x, bx, by, kz)) return;          // the whole block leaves: no thread is left at a barrier
-    if (kz >= nk) return;
-    const int k = k0 + kz, kk = A.ijcells;
+    LevelTile T;
+    if (!level_tile(t, blockIdx.x, k0, A.dom, T)) return;
+    if (T.kz >= nk) return;
+    const int k = T.k, kk = A.dom.ijcells;
     const unsigned int* __restrict__ msk = A.mfield + (size_t)k*kk;
-    const int j0 = A.jstart + by*STATS_ROWS;
-    const int j1 = (j0 + STATS_ROWS < A.jend) ? j0 + STATS_ROWS : A.jend;
     BudgetLev<TF> L[NM];
     double acc[NP][NM];
 #pragma unroll
@@ -558,83 +555,67 @@ __global__ void __launch_bounds__(STATS_THREADS) budget_partial_kernel(const Bud
 #pragma unroll
         for (int p=0; p<NP; ++p) acc[p][n] = 0.;
     }
-    for (int j=j0+(int)threadIdx.y; j<j1; j+=BY)
+    for_chunk_cells(A.dom, T.j0, T.j1, [&](int i, int j, int ij) __attribute__((always_inline))
     {
-        for (int i=A.istart+(int)threadIdx.x; i<A.iend; i+=BX)
+        const unsigned int m = msk[ij];
+        const size_t c = (size_t)ij + (size_t)k*kk;
+        if (G == BG_MODEL)
         {
-            const int ij = i + j*A.icells;
-            const unsigned int m = msk[ij];
-            const size_t c = (size_t)ij + (size_t)k*kk;
-            if (G == BG_MODEL)
-            {
-                const double vu = double(A.u[c]), vv = double(A.v[c]), vw = double(A.w[c]);
+            const double vu = double(A.u[c]), vv = double(A.v[c]), vw = double(A.w[c]);
 #pragma unroll
-                for (int n=0; n<NM; ++n)
-                {
-                    acc[0][n] += double((m >> (2*n)) & 1u) * vu;
-                    acc[1][n] += double((m >> (2*n)) & 1u) * vv;
-                    acc[2 % NP][n] += double((m >> (2*n + 1)) & 1u) * vw;
-                }
-            }
-            else if (G == BG_DIFF_UW || G == BG_DIFF_VW)
+            for (int n=0; n<NM; ++n)
             {
-                // uw_diff and vw_diff read no mask-mean profile: one evaluation per cell serves every mask
+                acc[0][n] += double((m >> (2*n)) & 1u) * vu;
+                acc[1][n] += double((m >> (2*n)) & 1u) * vv;
+                acc[2 % NP][n] += double((m >> (2*n + 1)) & 1u) * vw;
+            }
+        }
+        else if (G == BG_DIFF_UW || G == BG_DIFF_VW)
+        {
+            // uw_diff and vw_diff read no mask-mean profile: one evaluation per cell serves every mask
+            TF o[BNP];
+#pragma unroll
+            for (int p=0; p<BNP; ++p) o[p] = TF(0);
+            if (G == BG_DIFF_UW) budget_diff_les<TF, 1>(A, L[0], c, i, j, o);
+            else                 budget_diff_les<TF, 2>(A, L[0], c, i, j, o);
+            const double term = double(o[0]);
+#pragma unroll
+            for (int n=0; n<NM; ++n)
+                if (n < A.nmasks) acc[0][n] += double((m >> (2*n)) & 1u) * term;
+        }
+        else
+        {
+#pragma unroll
+            for (int n=0; n<NM; ++n)
+            {
+                if (n >= A.nmasks) continue;                          // block-uniform: a mask that does not exist costs no evaluation
                 TF o[BNP];
 #pragma unroll
                 for (int p=0; p<BNP; ++p) o[p] = TF(0);
-                if (G == BG_DIFF_UW) budget_diff_les<TF, 1>(A, L[0], c, i, j, o);
-                else                 budget_diff_les<TF, 2>(A, L[0], c, i, j, o);
-                const double term = double(o[0]);
+                if (G == BG_KE)          budget_ke(A, L[n], c, o);
+                else if (G == BG_SHEAR)  budget_shear(A, L[n], c, o);
+                else if (G == BG_TURB)   budget_turb(A, L[n], c, o);
+                else if (G == BG_COR)    budget_cor(A, L[n], c, o);
+                else if (G == BG_PRES)   budget_pres(A, L[n], c, o);
+                else if (G == BG_RDSTR)  budget_rdstr(A, L[n], c, o);
+                else if (G == BG_DIFF)   budget_diff_les<TF, 0>(A, L[n], c, i, j, o);
+                else if (G == BG_BUOY)   budget_buoy(A, L[n], c, o);
+                else if (G == BG_BWBUOY) budget_bwbuoy(A, L[n], c, o);
+                else if (G == BG_ADVS)   budget_advs(A, L[n], c, o);
+                else if (G == BG_PRESS)  budget_press(A, L[n], c, o);
+                const double in = double((m >> (2*n)) & 1u);          // in_mask<double>(mask, flag) * fld (calc_mean, :281)
 #pragma unroll
-                for (int n=0; n<NM; ++n)
-                    if (n < A.nmasks) acc[0][n] += double((m >> (2*n)) & 1u) * term;
-            }
-            else
-            {
-#pragma unroll
-                for (int n=0; n<NM; ++n)
-                {
-                    if (n >= A.nmasks) continue;                          // block-uniform: a mask that does not exist costs no evaluation
-                    TF o[BNP];
-#pragma unroll
-                    for (int p=0; p<BNP; ++p) o[p] = TF(0);
-                    if (G == BG_KE)          budget_ke(A, L[n], c, o);
-                    else if (G == BG_SHEAR)  budget_shear(A, L[n], c, o);
-                    else if (G == BG_TURB)   budget_turb(A, L[n], c, o);
-                    else if (G == BG_COR)    budget_cor(A, L[n], c, o);
-                    else if (G == BG_PRES)   budget_pres(A, L[n], c, o);
-                    else if (G == BG_RDSTR)  budget_rdstr(A, L[n], c, o);
-                    else if (G == BG_DIFF)   budget_diff_les<TF, 0>(A, L[n], c, i, j, o);
-                    else if (G == BG_BUOY)   budget_buoy(A, L[n], c, o);
-                    else if (G == BG_BWBUOY) budget_bwbuoy(A, L[n], c, o);
-                    else if (G == BG_ADVS)   budget_advs(A, L[n], c, o);
-                    else if (G == BG_PRESS)  budget_press(A, L[n], c, o);
-                    const double in = double((m >> (2*n)) & 1u);          // in_mask<double>(mask, flag) * fld (calc_mean, :281)
-#pragma unroll
-                    for (int p=0; p<NP; ++p) acc[p][n] += in * double(o[p]);
-                }
+                for (int p=0; p<NP; ++p) acc[p][n] += in * double(o[p]);
             }
         }
-    }
+    });
     const int tid = threadIdx.x + threadIdx.y*BX;
 #pragma unroll
     for (int p=0; p<NP; ++p)
     {
-        const double sum = stats_block_sums<NM>(acc[p], red, red2, tid);
-        if (tid < NM && tid < A.nmasks) part[(((size_t)(A.p0 + p)*A.nmasks + tid)*A.kcells + k)*nchunks + by] = sum;
+        const double sum = block_sums<NM>(acc[p]);
+        if (tid < NM && tid < A.nmasks) part[(((size_t)(A.p0 + p)*A.nmasks + tid)*A.kcells + k)*nchunks + T.by] = sum;
     }
-}
-
-// sums[prof][mask][k]: the chunks of a level in index order; zero outside k0 .. k0+nk-1. One thread per (prof, mask, level).
-__global__ void __launch_bounds__(256) budget_sums_kernel(const double* __restrict__ part, double* __restrict__ sums, int kcells, int k0, int nk, int nchunks)
-{
-    const int k = blockIdx.x*256 + threadIdx.x;
-    if (k >= kcells) return;
-    const size_t o = (size_t)blockIdx.y*kcells + k;
-    double tmp = 0.;
-    if (k >= k0 && k < k0 + nk)
-        for (int c=0; c<nchunks; ++c) tmp += part[o*nchunks + c];
-    sums[o] = tmp;
 }
 
 // A budget profile: calc_mean under the full-level flag over kstart .. kend, then set_fillvalue_prof over all levels
@@ -706,21 +687,16 @@ static BudgetArgs<TF> budget_args(const mhh_grid* g, const void* mfield, int nma
     A.mfield = static_cast<const unsigned int*>(mfield);
     { const GridDev<TF> gd = make_grid<TF>(g); A.dxi = gd.dxi_d; A.dyi = gd.dyi_d; }
     A.lastrank = (g->mpicoordy == g->npy - 1);
-    A.nmasks = nmasks; A.icells = g->icells; A.ijcells = g->ijcells; A.kcells = g->kcells;
-    A.istart = g->istart; A.iend = g->iend; A.jstart = g->jstart; A.jend = g->jend; A.kstart = g->kstart; A.kend = g->kend;
+    A.nmasks = nmasks; A.dom = level_domain(g); A.kcells = g->kcells; A.kstart = g->kstart; A.kend = g->kend;
     return A;
 }
 
 template<class TF, int G>
 static int budget_group_launch(const BudgetArgs<TF>& A, const mhh_grid* g, int nmasks, double* part, int k0, int nk, hipStream_t st)
 {
-    const int nchunks = stats_chunks(g);
-    const Tiling t = make_tiling(BX, nchunks*BY, nk);              // one block column, nchunks block rows: k fixed per block
+    const Tiling t = level_tiling(g, nk);
     const dim3 grid(tiling_blocks(t)), block(BX, BY, 1);
-    if (nmasks == 1)      hipLaunchKernelGGL((budget_partial_kernel<TF, G, 1>), grid, block, 0, st, A, t, part, k0, nk, nchunks);
-    else if (nmasks == 2) hipLaunchKernelGGL((budget_partial_kernel<TF, G, 2>), grid, block, 0, st, A, t, part, k0, nk, nchunks);
-    else if (nmasks <= 4) hipLaunchKernelGGL((budget_partial_kernel<TF, G, 4>), grid, block, 0, st, A, t, part, k0, nk, nchunks);
-    else                  hipLaunchKernelGGL((budget_partial_kernel<TF, G, 8>), grid, block, 0, st, A, t, part, k0, nk, nchunks);
+    with_mask_width(nmasks, [&](auto nm) { hipLaunchKernelGGL((budget_partial_kernel<TF, G, decltype(nm)::value>), grid, block, 0, st, A, t, part, k0, nk, level_chunks(g)); });
     MHH_LAUNCH_CHECK();
     return MHH_OK;
 }
@@ -742,9 +718,7 @@ static int budget_sums_launch(const mhh_grid* g, const void* mfield, int nmasks,
     }
     MHH_BUDGET_GROUP(BG_BUOY) MHH_BUDGET_GROUP(BG_BWBUOY) MHH_BUDGET_GROUP(BG_ADVS) MHH_BUDGET_GROUP(BG_PRESS)
 #undef MHH_BUDGET_GROUP
-    hipLaunchKernelGGL(budget_sums_kernel, dim3((g->kcells + 255)/256, p0*nmasks), dim3(256), 0, st, scratch, sums, g->kcells, k0, nk, stats_chunks(g));
-    MHH_LAUNCH_CHECK();
-    return MHH_OK;
+    return level_sums_launch(g, scratch, sums, p0*nmasks, LevelRanges{p0*nmasks, {k0}, {nk}}, st);       // one range for every profile
 }
 
 template<class TF>
@@ -753,9 +727,7 @@ static int budget_model_sums_launch(const mhh_grid* g, const void* mfield, int n
     BudgetArgs<TF> A = budget_args<TF>(g, mfield, nmasks, nullptr);
     A.u = cp<TF>(u); A.v = cp<TF>(v); A.w = cp<TF>(w);
     if (int e = budget_group_launch<TF, BG_MODEL>(A, g, nmasks, scratch, 0, g->kcells, st)) return e;
-    hipLaunchKernelGGL(budget_sums_kernel, dim3((g->kcells + 255)/256, 3*nmasks), dim3(256), 0, st, scratch, sums, g->kcells, 0, g->kcells, stats_chunks(g));
-    MHH_LAUNCH_CHECK();
-    return MHH_OK;
+    return level_sums_launch(g, scratch, sums, 3*nmasks, LevelRanges{3*nmasks, {0}, {g->kcells}}, st);
 }
 } // namespace mhh
 
@@ -775,7 +747,7 @@ MHH_API const char* mhh_budget_2_prof_name(unsigned int groups, int n, int* half
 MHH_API unsigned long long mhh_budget_2_scratch_elems(const mhh_grid* g, int nmasks)
 {
     if (!g || nmasks < 1) return 0;
-    return (unsigned long long)budget_nprofs(BUDGET_ALL) * nmasks * g->kcells * stats_chunks(g);
+    return (unsigned long long)budget_nprofs(BUDGET_ALL) * nmasks * g->kcells * level_chunks(g);
 }
 
 // Stats::calc_mask_mean_profile (src/stats.cxx:1328-1347) of u, v, w as double sums[3][nmasks][kcells] over ALL levels; a slab rank

@@ -2,54 +2,35 @@
 // the reductions they read (src/model.cxx:351): Field3d_operators' horizontal means, Buffer::exec, Force::exec and the fused
 // pass of the two. Kernels and C-ABI entry points; included from k_stencil.hip. The per-cell arithmetic is in cell_ops.h.
 #pragma once
-#include "k_common.h"
+#include "level_reduce.h"
 #include <gfx950_prims.h>
 
 namespace mhh
 {
 // =======================================================================================================
 // Field3d_operators: calc_mean_profile (src/field3d_operators.cxx:45-66), the sum of calc_mean (:132-155)
-// A block owns one level and a chunk of MEAN_ROWS rows; every thread adds its cells in a fixed order into a double; the block
-// reduces through LDS and writes ONE partial; a second kernel adds the partials in index order. No atomics: deterministic.
+// The reduction is that of level_reduce.h, with the tree as the block's order: one double per thread, ONE partial per block.
 // =======================================================================================================
 constexpr int NMF = MHH_MAX_MEAN_FIELDS;
-constexpr int MEAN_ROWS = 32;
-constexpr int MEAN_THREADS = BX*BY;
 template<class TF> struct MeanArgs
 {
     const TF* f[NMF]; TF* prof[NMF];
     const TF* dz;
-    int icells, ijcells, istart, iend, jstart, jend, k0;
+    LevelDomain dom; int k0;
 };
 
 template<class TF, bool WEIGHTED>
-__global__ void __launch_bounds__(MEAN_THREADS) mean_partial_kernel(const MeanArgs<TF> A, const Tiling t, double* __restrict__ part, int nk, int nchunks)
+__global__ void __launch_bounds__(LEVEL_THREADS) mean_partial_kernel(const MeanArgs<TF> A, const Tiling t, double* __restrict__ part, int nk, int nchunks)
 {
-    __shared__ double red[MEAN_THREADS];
-    int bx, by, kz;
-    if (!decode_tile(t, blockIdx.x, bx, by, kz)) return;          // the whole block leaves: no thread is left at a barrier
-    const int k = A.k0 + kz;
-    const TF* __restrict__ fld = A.f[blockIdx.y] + (size_t)k*A.ijcells;
-    const int j0 = A.jstart + by*MEAN_ROWS;
-    const int j1 = (j0 + MEAN_ROWS < A.jend) ? j0 + MEAN_ROWS : A.jend;
-    const TF dzk = WEIGHTED ? uniform_load(A.dz, k) : TF(0);
+    LevelTile T;
+    if (!level_tile(t, blockIdx.x, A.k0, A.dom, T)) return;
+    const TF* __restrict__ fld = A.f[blockIdx.y] + (size_t)T.k*A.dom.ijcells;
+    const TF dzk = WEIGHTED ? uniform_load(A.dz, T.k) : TF(0);
     double acc = 0.;
-    for (int j=j0+(int)threadIdx.y; j<j1; j+=BY)
-    {
-        const TF* __restrict__ row = fld + j*A.icells;
-#pragma unroll 4
-        for (int i=A.istart+(int)threadIdx.x; i<A.iend; i+=BX)
-            acc += WEIGHTED ? double(row[i]*dzk) : double(row[i]);     // the product in TF, as `fld[ijk] * gd.dz[k]` is (:148)
-    }
-    const int tid = threadIdx.x + threadIdx.y*BX;
-    red[tid] = acc;
-    __syncthreads();
-    for (int s=MEAN_THREADS/2; s>0; s>>=1)
-    {
-        if (tid < s) red[tid] += red[tid+s];
-        __syncthreads();
-    }
-    if (tid == 0) part[((size_t)blockIdx.y*nk + kz)*nchunks + by] = red[0];
+    for_chunk_cells<4>(A.dom, T.j0, T.j1, [&](int, int, int ij)
+        { acc += WEIGHTED ? double(fld[ij]*dzk) : double(fld[ij]); });         // the product in TF, as `fld[ijk] * gd.dz[k]` is (:148)
+    const double sum = block_tree_sum(acc);
+    if (threadIdx.x == 0 && threadIdx.y == 0) part[((size_t)blockIdx.y*nk + T.kz)*nchunks + T.by] = sum;
 }
 
 // prof[k] = TF(tmp / n), n = double(itot*jtot) (:49,62): one thread per (field, level), the chunks in index order
@@ -64,29 +45,20 @@ __global__ void __launch_bounds__(256) mean_profile_finish_kernel(const MeanArgs
     A.prof[blockIdx.y][k] = TF(tmp / n);
 }
 // one block per field: each level's partials in index order, thread t the levels t, t+256, ... in order, then the tree
-__global__ void __launch_bounds__(256) mean_sum_finish_kernel(const double* __restrict__ part, double* __restrict__ sums, int nk, int nchunks)
+__global__ void __launch_bounds__(LEVEL_THREADS) mean_sum_finish_kernel(const double* __restrict__ part, double* __restrict__ sums, int nk, int nchunks)
 {
-    __shared__ double red[256];
     const int tid = threadIdx.x;
     double acc = 0.;
-    for (int k=tid; k<nk; k+=256)
+    for (int k=tid; k<nk; k+=LEVEL_THREADS)
     {
         const double* __restrict__ q = part + ((size_t)blockIdx.x*nk + k)*nchunks;
         double lev = 0.;
         for (int c=0; c<nchunks; ++c) lev += q[c];
         acc += lev;
     }
-    red[tid] = acc;
-    __syncthreads();
-    for (int s=128; s>0; s>>=1)
-    {
-        if (tid < s) red[tid] += red[tid+s];
-        __syncthreads();
-    }
-    if (tid == 0) sums[blockIdx.x] = red[0];
+    const double sum = block_tree_sum(acc);
+    if (tid == 0) sums[blockIdx.x] = sum;
 }
-
-inline int mean_chunks(const mhh_grid* g) { return (g->jmax + MEAN_ROWS-1)/MEAN_ROWS; }
 
 template<class TF>
 static int mean_launch(const mhh_grid* g, const void* const* fields, int nf, void* const* profs, double* sums, double* scratch, hipStream_t st)
@@ -94,15 +66,15 @@ static int mean_launch(const mhh_grid* g, const void* const* fields, int nf, voi
     MeanArgs<TF> A{};
     for (int n=0; n<NMF; ++n) { A.f[n] = cp<TF>(fields[n < nf ? n : 0]); A.prof[n] = profs ? mp<TF>(profs[n < nf ? n : 0]) : nullptr; }
     A.dz = cp<TF>(g->dz);
-    A.icells = g->icells; A.ijcells = g->ijcells; A.istart = g->istart; A.iend = g->iend; A.jstart = g->jstart; A.jend = g->jend;
+    A.dom = level_domain(g);
     const bool weighted = (sums != nullptr);
     A.k0 = weighted ? g->kstart : 0;
-    const int nk = weighted ? g->kmax : g->kcells, nchunks = mean_chunks(g);
-    const Tiling t = make_tiling(BX, nchunks*BY, nk);             // one block column, nchunks block rows, nk levels: k fixed per block
+    const int nk = weighted ? g->kmax : g->kcells, nchunks = level_chunks(g);
+    const Tiling t = level_tiling(g, nk);
     if (weighted) hipLaunchKernelGGL((mean_partial_kernel<TF, true>),  dim3(tiling_blocks(t), nf), dim3(BX, BY, 1), 0, st, A, t, scratch, nk, nchunks);
     else          hipLaunchKernelGGL((mean_partial_kernel<TF, false>), dim3(tiling_blocks(t), nf), dim3(BX, BY, 1), 0, st, A, t, scratch, nk, nchunks);
     MHH_LAUNCH_CHECK();
-    if (weighted) hipLaunchKernelGGL(mean_sum_finish_kernel, dim3(nf), dim3(256), 0, st, scratch, sums, nk, nchunks);
+    if (weighted) hipLaunchKernelGGL(mean_sum_finish_kernel, dim3(nf), dim3(LEVEL_THREADS), 0, st, scratch, sums, nk, nchunks);
     else          hipLaunchKernelGGL(mean_profile_finish_kernel<TF>, dim3((nk + 255)/256, nf), dim3(256), 0, st, A, scratch, nk, nchunks, double(g->itot * g->jtot));
     MHH_LAUNCH_CHECK();
     return MHH_OK;
@@ -290,9 +262,9 @@ using namespace mhh;
 MHH_API unsigned long long mhh_field_mean_scratch_elems(const mhh_grid* g, int nfields)
 {
     if (!g || nfields < 1) return 0;
-    return (unsigned long long)nfields * (unsigned long long)g->kcells * (unsigned long long)mean_chunks(g);
+    return (unsigned long long)nfields * (unsigned long long)g->kcells * (unsigned long long)level_chunks(g);
 }
-MHH_API int mhh_field_mean_chunk_rows(void) { return MEAN_ROWS; }
+MHH_API int mhh_field_mean_chunk_rows(void) { return LEVEL_ROWS; }
 MHH_API int mhh_field_mean_profile(const mhh_grid* g, const void* const* fields, int nfields, void* const* profs, void* scratch, void* stream)
 {
     if (int e = mean_check(g, fields, nfields, scratch)) return e;

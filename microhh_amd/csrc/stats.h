@@ -1,46 +1,20 @@
 // stats.h -- the sampling of Stats<TF> for second-order cases (src/stats.cxx): the mask words, the masked per-level sums in two
 // passes, the column pass of cover and path, and the finish kernels that turn sums and counts into profiles and time series.
-// Kernels and C-ABI entry points; included from k_stencil.hip. The reductions have the form of mean_partial_kernel
-// (force_means.h): a block owns one level and a chunk of STATS_ROWS rows, every thread adds its cells in a fixed order into
-// doubles, the block reduces through LDS and writes ONE partial per mask, a second kernel adds the partials in index order.
-// No floating-point atomics anywhere: the same bits on every run.
+// Kernels and C-ABI entry points; included from k_stencil.hip. The masked sums are reduced as level_reduce.h says, with
+// block_sums as the block's order: no floating-point atomics anywhere, the same bits on every run.
 #pragma once
-#include "k_common.h"
+#include "level_reduce.h"
 #include <gfx950_prims.h>
 
 namespace mhh
 {
 constexpr int SNM = MHH_STATS_MAX_MASKS;
 constexpr int SNJ = MHH_STATS_MAX_JOBS;
-constexpr int STATS_ROWS = 32;
-constexpr int STATS_THREADS = BX*BY;
+static_assert(SNJ <= LEVEL_MAX_RANGES, "a level range per job");
 
 template<class TF> __host__ __device__ inline TF stats_fill();      // netcdf_fp_fillvalue (src/stats.cxx:51-53): NC_FILL_DOUBLE / NC_FILL_FLOAT
 template<> __host__ __device__ inline double stats_fill<double>() { return 9.9692099683868690e+36; }
 template<> __host__ __device__ inline float  stats_fill<float>()  { return 9.9692099683868690e+36f; }
-
-// The block's sums of NM values per thread: out, valid in thread n < NM, is the sum of v[n] over the 256 threads in a fixed order
-// (sixteen runs of sixteen threads, then the sixteen runs). Three barriers whatever NM is; every thread of the block calls it.
-template<int NM>
-__device__ __forceinline__ double stats_block_sums(const double (&v)[NM], double* red, double* red2, int tid)
-{
-    __syncthreads();                                               // the previous use of red and red2 is over
-#pragma unroll
-    for (int n=0; n<NM; ++n) red[n*STATS_THREADS + tid] = v[n];
-    __syncthreads();
-    if (tid < NM*16)
-    {
-        const double* q = red + (tid >> 4)*STATS_THREADS + (tid & 15)*16;
-        double t = 0.;
-        for (int c=0; c<16; ++c) t += q[c];
-        red2[tid] = t;
-    }
-    __syncthreads();
-    double out = 0.;
-    if (tid < NM)
-        for (int c=0; c<16; ++c) out += red2[tid*16 + c];
-    return out;
-}
 
 // =======================================================================================================
 // initialize_masks (:1214-1227): every word, ghosts included, is the sum of all flags
@@ -124,28 +98,25 @@ template<class TF> struct StatsArgs
     TF dxi, dyi; int kstart, kend;
     unsigned char gjob[SNJ][SGJ]; unsigned char gn[SNJ];     // the groups: consecutive jobs of the same variable and level range
     const unsigned int* mfield; const TF* dzhi;
-    int nmasks, ngroups, icells, ijcells, kcells, istart, iend, jstart, jend;
+    LevelDomain dom;
+    int nmasks, ngroups, kcells;
 };
 
 // blockIdx.y is a GROUP of up to SGJ jobs of one variable: the variable, the level below it (where a gradient is among them) and
 // the mask word are read once per cell and serve every job of the group. SGJ x NM double accumulators per thread, indexed
-// statically (the loops over slots and masks are unrolled): registers, no scratch.
+// statically (the loops over slots and masks are unrolled): registers, no scratch. part[job][mask][kcells][nchunks].
 template<class TF, int NM>
-__global__ void __launch_bounds__(STATS_THREADS) stats_partial_kernel(const StatsArgs<TF> A, const Tiling t, double* __restrict__ part, int nkmax, int nchunks)
+__global__ void __launch_bounds__(LEVEL_THREADS) stats_partial_kernel(const StatsArgs<TF> A, const Tiling t, double* __restrict__ part, int nchunks)
 {
-    __shared__ double red[NM*STATS_THREADS];
-    __shared__ double red2[NM*16];
-    int bx, by, kz;
-    if (!decode_tile(t, blockIdx.x, bx, by, kz)) return;          // the whole block leaves: no thread is left at a barrier
     const int ng = A.gn[blockIdx.y];
     const StatsJob<TF>& J0 = A.job[A.gjob[blockIdx.y][0]];        // the variable and the level range are the group's
-    if (kz >= J0.nk || J0.op >= MHH_STATS_FLUX_W) return;         // a flux job is a group of its own, served by stats_flux_kernel
-    const int k = J0.k0 + kz, kk = A.ijcells;
+    LevelTile T;
+    if (!level_tile(t, blockIdx.x, J0.k0, A.dom, T)) return;
+    if (T.kz >= J0.nk || J0.op >= MHH_STATS_FLUX_W) return;       // a flux job is a group of its own, served by stats_flux_kernel
+    const int k = T.k, kk = A.dom.ijcells;
     const bool flat = (J0.op == MHH_STATS_MEAN2D), ones = (J0.op == MHH_STATS_COUNT);
     const TF* __restrict__ fld = J0.fld + (flat ? (size_t)0 : (size_t)k*kk);
     const unsigned int* __restrict__ msk = A.mfield + (size_t)k*kk;
-    const int j0 = A.jstart + by*STATS_ROWS;
-    const int j1 = (j0 + STATS_ROWS < A.jend) ? j0 + STATS_ROWS : A.jend;
     const double dzhik = A.dzhi ? double(uniform_load(A.dzhi, k)) : 0.;
     int op[SGJ], sh[SGJ];
     TF offset[SGJ], thres[SGJ], mean[SGJ][NM];
@@ -165,53 +136,49 @@ __global__ void __launch_bounds__(STATS_THREADS) stats_partial_kernel(const Stat
             mean[s][n] = (moment && n < A.nmasks) ? uniform_load(J.mean, n*A.kcells + k) : TF(0);
         }
     }
-    for (int j=j0+(int)threadIdx.y; j<j1; j+=BY)
+    for_chunk_cells(A.dom, T.j0, T.j1, [&](int, int, int ij) __attribute__((always_inline))
     {
-        for (int i=A.istart+(int)threadIdx.x; i<A.iend; i+=BX)
+        const unsigned int m = flat ? 0xffffffffu : msk[ij];
+        const TF v = ones ? TF(1) : fld[ij];
+        const TF below = grad ? fld[ij - kk] : TF(0);
+#pragma unroll
+        for (int s=0; s<SGJ; ++s)
         {
-            const int ij = i + j*A.icells;
-            const unsigned int m = flat ? 0xffffffffu : msk[ij];
-            const TF v = ones ? TF(1) : fld[ij];
-            const TF below = grad ? fld[ij - kk] : TF(0);
-#pragma unroll
-            for (int s=0; s<SGJ; ++s)
+            if (op[s] < 0) continue;
+            if (op[s] >= MHH_STATS_MOMENT2 && op[s] <= MHH_STATS_MOMENT4)
             {
-                if (op[s] < 0) continue;
-                if (op[s] >= MHH_STATS_MOMENT2 && op[s] <= MHH_STATS_MOMENT4)
-                {
 #pragma unroll
-                    for (int n=0; n<NM; ++n)
-                    {
-                        const double x = double(TF(TF(v - mean[s][n]) + offset[s]));
-                        const double x2 = x*x;
-                        const double p = (op[s] == MHH_STATS_MOMENT2) ? x2 : (op[s] == MHH_STATS_MOMENT3) ? x2*x : x2*x2;
-                        acc[s][n] += double((m >> (2*n + sh[s])) & 1u) * p;
-                    }
+                for (int n=0; n<NM; ++n)
+                {
+                    const double x = double(TF(TF(v - mean[s][n]) + offset[s]));
+                    const double x2 = x*x;
+                    const double p = (op[s] == MHH_STATS_MOMENT2) ? x2 : (op[s] == MHH_STATS_MOMENT3) ? x2*x : x2*x2;
+                    acc[s][n] += double((m >> (2*n + sh[s])) & 1u) * p;
                 }
-                else
-                {
-                    const bool g = (op[s] == MHH_STATS_GRAD);
-                    double term;
-                    if (op[s] == MHH_STATS_FRAC) term = (TF(v + offset[s]) > thres[s]) ? 1. : 0.;
-                    else if (g)                  term = double(TF(v - below));
-                    else                         term = double(v);
+            }
+            else
+            {
+                const bool g = (op[s] == MHH_STATS_GRAD);
+                double term;
+                if (op[s] == MHH_STATS_FRAC) term = (TF(v + offset[s]) > thres[s]) ? 1. : 0.;
+                else if (g)                  term = double(TF(v - below));
+                else                         term = double(v);
 #pragma unroll
-                    for (int n=0; n<NM; ++n)
-                    {
-                        const double q = double((m >> (2*n + sh[s])) & 1u) * term;
-                        acc[s][n] += g ? q*dzhik : q;                         // in_mask * (d[k] - d[k-1]) * dzhi[k], left to right
-                    }
+                for (int n=0; n<NM; ++n)
+                {
+                    const double q = double((m >> (2*n + sh[s])) & 1u) * term;
+                    acc[s][n] += g ? q*dzhik : q;                             // in_mask * (d[k] - d[k-1]) * dzhi[k], left to right
                 }
             }
         }
-    }
+    });
     const int tid = threadIdx.x + threadIdx.y*BX;
 #pragma unroll
     for (int s=0; s<SGJ; ++s)
     {
         if (s >= ng) break;                                        // block-uniform: every thread takes the same barriers
-        const double sum = stats_block_sums<NM>(acc[s], red, red2, tid);
-        if (tid < NM && tid < A.nmasks) part[(((size_t)A.gjob[blockIdx.y][s]*A.nmasks + tid)*nkmax + kz)*nchunks + by] = sum;
+        const double sum = block_sums<NM>(acc[s]);
+        if (tid < NM && tid < A.nmasks) part[(((size_t)A.gjob[blockIdx.y][s]*A.nmasks + tid)*A.kcells + k)*nchunks + T.by] = sum;
     }
 }
 
@@ -232,21 +199,17 @@ __global__ void __launch_bounds__(STATS_THREADS) stats_partial_kernel(const Stat
 // with the reference's double literals (0.5 *, 0.25 *) and narrowed once, as `const TF eviscc = ...` does.
 // =======================================================================================================
 template<class TF, int NM>
-__global__ void __launch_bounds__(STATS_THREADS) stats_flux_kernel(const StatsArgs<TF> A, const Tiling t, double* __restrict__ part, int nkmax, int nchunks)
+__global__ void __launch_bounds__(LEVEL_THREADS) stats_flux_kernel(const StatsArgs<TF> A, const Tiling t, double* __restrict__ part, int nchunks)
 {
-    __shared__ double red[NM*STATS_THREADS];
-    __shared__ double red2[NM*16];
-    int bx, by, kz;
-    if (!decode_tile(t, blockIdx.x, bx, by, kz)) return;
     const StatsJob<TF>& J = A.job[blockIdx.y];
     const StatsFlux<TF>& F = A.flux[blockIdx.y];
-    if ((J.op != MHH_STATS_FLUX_W && J.op != MHH_STATS_FLUX_DIFF) || kz >= J.nk) return;
-    const int k = J.k0 + kz, kk = A.ijcells, jj = A.icells, ks = A.kstart, ke = A.kend;
+    LevelTile T;
+    if (!level_tile(t, blockIdx.x, J.k0, A.dom, T)) return;
+    if ((J.op != MHH_STATS_FLUX_W && J.op != MHH_STATS_FLUX_DIFF) || T.kz >= J.nk) return;
+    const int k = T.k, kk = A.dom.ijcells, jj = A.dom.icells, ks = A.kstart, ke = A.kend;
     const bool resolved = (J.op == MHH_STATS_FLUX_W);
     const int hoff = (F.kind == 1) ? 1 : (F.kind == 2 ? jj : 0);   // the neighbour of u or v that shares the face
     const unsigned int* __restrict__ msk = A.mfield + (size_t)k*kk;
-    const int j0 = A.jstart + by*STATS_ROWS;
-    const int j1 = (j0 + STATS_ROWS < A.jend) ? j0 + STATS_ROWS : A.jend;
     const TF dzhik = uniform_load(A.dzhi, k);
     // the body of this level: 0 zero flux, 2 second order, 4 fourth / third, 6 sixth / fifth; limited: 1 bottom, 3 top, 5 interior
     int body = 2;
@@ -267,86 +230,64 @@ __global__ void __launch_bounds__(STATS_THREADS) stats_flux_kernel(const StatsAr
             mean[n][d] = (resolved && n < A.nmasks && kl >= ks && kl < ke) ? uniform_load(J.mean, n*A.kcells + kl) : TF(0);
         }
     }
-    for (int j=j0+(int)threadIdx.y; j<j1; j+=BY)
+    for_chunk_cells(A.dom, T.j0, T.j1, [&](int, int, int ij) __attribute__((always_inline))
     {
-        for (int i=A.istart+(int)threadIdx.x; i<A.iend; i+=BX)
+        const unsigned int m = msk[ij];
+        if (resolved)
         {
-            const int ij = i + j*jj;
-            const unsigned int m = msk[ij];
-            if (resolved)
+            TF sv[6];
+#pragma unroll
+            for (int d=0; d<6; ++d)
             {
-                TF sv[6];
+                const int kl = k - 3 + d;
+                sv[d] = (body != 0 && kl >= ks && kl < ke) ? J.fld[ij + (size_t)kl*kk] : TF(0);
+            }
+            const TF w0 = F.w[ij + (size_t)k*kk];
+            const TF w1 = hoff ? F.w[ij - hoff + (size_t)k*kk] : TF(0);
+#pragma unroll
+            for (int n=0; n<NM; ++n)
+            {
+                TF sp[6];
 #pragma unroll
                 for (int d=0; d<6; ++d)
                 {
                     const int kl = k - 3 + d;
-                    sv[d] = (body != 0 && kl >= ks && kl < ke) ? J.fld[ij + (size_t)kl*kk] : TF(0);
+                    sp[d] = (kl >= ks && kl < ke) ? TF(sv[d] - mean[n][d]) : TF(0);
                 }
-                const TF w0 = F.w[ij + (size_t)k*kk];
-                const TF w1 = hoff ? F.w[ij - hoff + (size_t)k*kk] : TF(0);
-#pragma unroll
-                for (int n=0; n<NM; ++n)
-                {
-                    TF sp[6];
-#pragma unroll
-                    for (int d=0; d<6; ++d)
-                    {
-                        const int kl = k - 3 + d;
-                        sp[d] = (kl >= ks && kl < ke) ? TF(sv[d] - mean[n][d]) : TF(0);
-                    }
-                    const TF W = hoff ? i2(TF(w1 - wm[n]), TF(w0 - wm[n])) : TF(w0 - wm[n]);
-                    TF f;
-                    if (body == 0)      f = TF(0);
-                    else if (body == 2) f = W * i2(sp[2], sp[3]);
-                    else if (body == 4) f = W * i4ws(sp[1], sp[2], sp[3], sp[4]) - tabs(W) * i3ws(sp[1], sp[2], sp[3], sp[4]);
-                    else if (body == 6) f = W * i6(sp[0], sp[1], sp[2], sp[3], sp[4], sp[5]) - tabs(W) * i5(sp[0], sp[1], sp[2], sp[3], sp[4], sp[5]);
-                    else                f = koren_flux(body == 1 ? 1 : (body == 3 ? 2 : 0), W, sp[1], sp[2], sp[3], sp[4]);
-                    acc[n] += double((m >> (2*n + 1)) & 1u) * double(f);
-                }
+                const TF W = hoff ? i2(TF(w1 - wm[n]), TF(w0 - wm[n])) : TF(w0 - wm[n]);
+                TF f;
+                if (body == 0)      f = TF(0);
+                else if (body == 2) f = W * i2(sp[2], sp[3]);
+                else if (body == 4) f = W * i4ws(sp[1], sp[2], sp[3], sp[4]) - tabs(W) * i3ws(sp[1], sp[2], sp[3], sp[4]);
+                else if (body == 6) f = W * i6(sp[0], sp[1], sp[2], sp[3], sp[4], sp[5]) - tabs(W) * i5(sp[0], sp[1], sp[2], sp[3], sp[4], sp[5]);
+                else                f = koren_flux(body == 1 ? 1 : (body == 3 ? 2 : 0), W, sp[1], sp[2], sp[3], sp[4]);
+                acc[n] += double((m >> (2*n + 1)) & 1u) * double(f);
+            }
+        }
+        else
+        {
+            const size_t c = ij + (size_t)k*kk;
+            TF f;
+            if (F.scheme == MHH_DIFF_2) f = - F.visc*(J.fld[c] - J.fld[c-kk])*dzhik;
+            else if (F.sm && k == ks)   f = F.flux_bot[ij];
+            else if (F.sm && k == ke)   f = F.flux_top[ij];
+            else if (F.kind == 0)
+            {
+                const TF eviscc = 0.5*(F.evisc[c-kk]+F.evisc[c])/F.tPr + F.visc;
+                f = - eviscc*(J.fld[c] - J.fld[c-kk])*dzhik;
             }
             else
             {
-                const size_t c = ij + (size_t)k*kk;
-                TF f;
-                if (F.scheme == MHH_DIFF_2) f = - F.visc*(J.fld[c] - J.fld[c-kk])*dzhik;
-                else if (F.sm && k == ks)   f = F.flux_bot[ij];
-                else if (F.sm && k == ke)   f = F.flux_top[ij];
-                else if (F.kind == 0)
-                {
-                    const TF eviscc = 0.5*(F.evisc[c-kk]+F.evisc[c])/F.tPr + F.visc;
-                    f = - eviscc*(J.fld[c] - J.fld[c-kk])*dzhik;
-                }
-                else
-                {
-                    const TF evisch = 0.25*(F.evisc[c-hoff-kk]+F.evisc[c-hoff]+F.evisc[c-kk]+F.evisc[c]) + F.visc;
-                    f = - evisch*( (J.fld[c]-J.fld[c-kk])*dzhik + (F.w[c]-F.w[c-hoff])*(F.kind == 1 ? A.dxi : A.dyi) );
-                }
-#pragma unroll
-                for (int n=0; n<NM; ++n) acc[n] += double((m >> (2*n + 1)) & 1u) * double(f);
+                const TF evisch = 0.25*(F.evisc[c-hoff-kk]+F.evisc[c-hoff]+F.evisc[c-kk]+F.evisc[c]) + F.visc;
+                f = - evisch*( (J.fld[c]-J.fld[c-kk])*dzhik + (F.w[c]-F.w[c-hoff])*(F.kind == 1 ? A.dxi : A.dyi) );
             }
+#pragma unroll
+            for (int n=0; n<NM; ++n) acc[n] += double((m >> (2*n + 1)) & 1u) * double(f);
         }
-    }
+    });
     const int tid = threadIdx.x + threadIdx.y*BX;
-    const double sum = stats_block_sums<NM>(acc, red, red2, tid);
-    if (tid < NM && tid < A.nmasks) part[(((size_t)blockIdx.y*A.nmasks + tid)*nkmax + kz)*nchunks + by] = sum;
-}
-
-// sums[job][mask][k]: the chunks of a level in index order; zero outside the job's levels. One thread per (job, mask, level).
-template<class TF>
-__global__ void __launch_bounds__(256) stats_sums_kernel(const StatsArgs<TF> A, const double* __restrict__ part, double* __restrict__ sums, int nkmax, int nchunks)
-{
-    const int k = blockIdx.x*256 + threadIdx.x;
-    if (k >= A.kcells) return;
-    const int job = blockIdx.y / A.nmasks, n = blockIdx.y % A.nmasks;
-    const StatsJob<TF>& J = A.job[job];
-    const int kz = k - J.k0;
-    double tmp = 0.;
-    if (kz >= 0 && kz < J.nk)
-    {
-        const double* __restrict__ q = part + (((size_t)job*A.nmasks + n)*nkmax + kz)*nchunks;
-        for (int c=0; c<nchunks; ++c) tmp += q[c];
-    }
-    sums[((size_t)job*A.nmasks + n)*A.kcells + k] = tmp;
+    const double sum = block_sums<NM>(acc);
+    if (tid < NM && tid < A.nmasks) part[(((size_t)blockIdx.y*A.nmasks + tid)*A.kcells + k)*nchunks + T.by] = sum;
 }
 
 // prof[k] = tmp / nmask[k] (double by int, narrowed to TF), the offset added to a mean on EVERY level (:1635), the fill value where
@@ -405,34 +346,33 @@ __global__ void __launch_bounds__(256) stats_mask_finish_kernel(const double* __
 // covered has one). calc_path's nmask_proj is a running count, so its `nmask_proj > 0` lets every column at or after the first
 // non-empty one in; but what a column adds is its MASKED cells alone, so the columns let in early or late add nothing and the
 // running count ends as the number of non-empty columns: path = the sum over masked cells, nmask_proj = nmaskcover. A column's
-// sum runs serially in TF as `data*rho*dz`; columns are added in double, a block's in a tree, the blocks in index order.
+// sum runs serially in TF as `data*rho*dz`; columns are added in double, a block's by block_sums (level_reduce.h), the blocks in index order.
 // part[block][mask][3] = cover, nmaskcover, path.
 // =======================================================================================================
 template<class TF> struct StatsColArgs
 {
     const unsigned int* mfield; const TF* fld; const TF* rho; const TF* dz;
     TF offset, threshold;
-    int nmasks, half, icells, ijcells, istart, iend, jstart, jend, kstart, kend, nbx;
+    LevelDomain dom;
+    int nmasks, half, kstart, kend, nbx;
 };
 template<class TF, int NM>
-__global__ void __launch_bounds__(STATS_THREADS) stats_column_kernel(const StatsColArgs<TF> A, double* __restrict__ part)
+__global__ void __launch_bounds__(LEVEL_THREADS) stats_column_kernel(const StatsColArgs<TF> A, double* __restrict__ part)
 {
-    __shared__ double red[NM*STATS_THREADS];
-    __shared__ double red2[NM*16];
     const int bx = blockIdx.x % A.nbx, by = blockIdx.x / A.nbx;
-    const int i = A.istart + bx*BX + (int)threadIdx.x, j = A.jstart + by*BY + (int)threadIdx.y;
-    const bool live = (i < A.iend && j < A.jend);
+    const int i = A.dom.istart + bx*BX + (int)threadIdx.x, j = A.dom.jstart + by*BY + (int)threadIdx.y;
+    const bool live = (i < A.dom.iend && j < A.dom.jend);
     unsigned int has = 0, cov = 0;
     TF path[NM];
 #pragma unroll
     for (int n=0; n<NM; ++n) path[n] = TF(0);
     if (live)
     {
-        const int ij = i + j*A.icells;
+        const int ij = i + j*A.dom.icells;
         for (int k=A.kstart; k<A.kend; ++k)
         {
-            const unsigned int m = A.mfield[ij + (size_t)k*A.ijcells];
-            const TF v = A.fld[ij + (size_t)k*A.ijcells];
+            const unsigned int m = A.mfield[ij + (size_t)k*A.dom.ijcells];
+            const TF v = A.fld[ij + (size_t)k*A.dom.ijcells];
             const TF t = v*uniform_load(A.rho, k)*uniform_load(A.dz, k);
             const bool above = TF(v + A.offset) > A.threshold;
 #pragma unroll
@@ -447,9 +387,9 @@ __global__ void __launch_bounds__(STATS_THREADS) stats_column_kernel(const Stats
     double vc[NM], vh[NM], vp[NM];
 #pragma unroll
     for (int n=0; n<NM; ++n) { vc[n] = double((cov >> n) & 1u); vh[n] = double((has >> n) & 1u); vp[n] = double(path[n]); }
-    const double c = stats_block_sums<NM>(vc, red, red2, tid);
-    const double h = stats_block_sums<NM>(vh, red, red2, tid);
-    const double p = stats_block_sums<NM>(vp, red, red2, tid);
+    const double c = block_sums<NM>(vc);
+    const double h = block_sums<NM>(vh);
+    const double p = block_sums<NM>(vp);
     if (tid < NM && tid < A.nmasks)
     {
         double* q = part + ((size_t)blockIdx.x*A.nmasks + tid)*3;
@@ -478,7 +418,6 @@ __global__ void __launch_bounds__(64) stats_column_finish_kernel(const double* _
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------
-inline int stats_chunks(const mhh_grid* g) { return (g->jmax + STATS_ROWS-1)/STATS_ROWS; }
 inline int stats_col_blocks(const mhh_grid* g) { return ((g->imax + BX-1)/BX) * ((g->jmax + BY-1)/BY); }
 
 static int stats_check(const mhh_grid* g, int nmasks)
@@ -494,8 +433,7 @@ static int stats_fill_args(const mhh_grid* g, const void* mfield, int nmasks, co
 {
     A = StatsArgs<TF>{};
     A.mfield = static_cast<const unsigned int*>(mfield); A.dzhi = cp<TF>(g->dzhi);
-    A.nmasks = nmasks; A.icells = g->icells; A.ijcells = g->ijcells; A.kcells = g->kcells;
-    A.istart = g->istart; A.iend = g->iend; A.jstart = g->jstart; A.jend = g->jend;
+    A.nmasks = nmasks; A.dom = level_domain(g); A.kcells = g->kcells;
     { const GridDev<TF> gd = make_grid<TF>(g); A.dxi = gd.dxi_d; A.dyi = gd.dyi_d; }
     A.kstart = g->kstart; A.kend = g->kend;
     nkmax = 1;
@@ -567,28 +505,22 @@ static int stats_sums_launch(const mhh_grid* g, const void* mfield, int nmasks, 
 {
     StatsArgs<TF> A; int nkmax;
     if (int e = stats_fill_args<TF>(g, mfield, nmasks, jobs, njobs, A, nkmax)) return e;
-    const int nchunks = stats_chunks(g);
-    const Tiling t = make_tiling(BX, nchunks*BY, nkmax);          // one block column, nchunks block rows: k fixed per block
+    const int nchunks = level_chunks(g);
+    const Tiling t = level_tiling(g, nkmax);
     const dim3 grid(tiling_blocks(t), A.ngroups), block(BX, BY, 1);
-    if (nmasks == 1)      hipLaunchKernelGGL((stats_partial_kernel<TF, 1>), grid, block, 0, st, A, t, scratch, nkmax, nchunks);
-    else if (nmasks == 2) hipLaunchKernelGGL((stats_partial_kernel<TF, 2>), grid, block, 0, st, A, t, scratch, nkmax, nchunks);
-    else if (nmasks <= 4) hipLaunchKernelGGL((stats_partial_kernel<TF, 4>), grid, block, 0, st, A, t, scratch, nkmax, nchunks);
-    else                  hipLaunchKernelGGL((stats_partial_kernel<TF, 8>), grid, block, 0, st, A, t, scratch, nkmax, nchunks);
+    with_mask_width(nmasks, [&](auto nm) { hipLaunchKernelGGL((stats_partial_kernel<TF, decltype(nm)::value>), grid, block, 0, st, A, t, scratch, nchunks); });
     MHH_LAUNCH_CHECK();
     bool any_flux = false;
     for (int n=0; n<njobs; ++n) any_flux = any_flux || jobs[n].op == MHH_STATS_FLUX_W || jobs[n].op == MHH_STATS_FLUX_DIFF;
     if (any_flux)
     {
         const dim3 fgrid(tiling_blocks(t), njobs);
-        if (nmasks == 1)      hipLaunchKernelGGL((stats_flux_kernel<TF, 1>), fgrid, block, 0, st, A, t, scratch, nkmax, nchunks);
-        else if (nmasks == 2) hipLaunchKernelGGL((stats_flux_kernel<TF, 2>), fgrid, block, 0, st, A, t, scratch, nkmax, nchunks);
-        else if (nmasks <= 4) hipLaunchKernelGGL((stats_flux_kernel<TF, 4>), fgrid, block, 0, st, A, t, scratch, nkmax, nchunks);
-        else                  hipLaunchKernelGGL((stats_flux_kernel<TF, 8>), fgrid, block, 0, st, A, t, scratch, nkmax, nchunks);
+        with_mask_width(nmasks, [&](auto nm) { hipLaunchKernelGGL((stats_flux_kernel<TF, decltype(nm)::value>), fgrid, block, 0, st, A, t, scratch, nchunks); });
         MHH_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(stats_sums_kernel<TF>, dim3((g->kcells + 255)/256, njobs*nmasks), dim3(256), 0, st, A, scratch, sums, nkmax, nchunks);
-    MHH_LAUNCH_CHECK();
-    return MHH_OK;
+    LevelRanges R{nmasks};                                         // the masks of a job share its levels
+    for (int n=0; n<njobs; ++n) { R.k0[n] = A.job[n].k0; R.nk[n] = A.job[n].nk; }
+    return level_sums_launch(g, scratch, sums, njobs*nmasks, R, st);
 }
 
 template<class TF>
@@ -624,14 +556,10 @@ static int stats_columns_launch(const mhh_grid* g, const void* mfield, int nmask
     StatsColArgs<TF> A{};
     A.mfield = static_cast<const unsigned int*>(mfield); A.fld = cp<TF>(fld); A.rho = cp<TF>(rhoref); A.dz = cp<TF>(g->dz);
     A.offset = TF(offset); A.threshold = TF(threshold); A.nmasks = nmasks; A.half = loc;
-    A.icells = g->icells; A.ijcells = g->ijcells; A.istart = g->istart; A.iend = g->iend; A.jstart = g->jstart; A.jend = g->jend;
-    A.kstart = g->kstart; A.kend = g->kend; A.nbx = (g->imax + BX-1)/BX;
+    A.dom = level_domain(g); A.kstart = g->kstart; A.kend = g->kend; A.nbx = (g->imax + BX-1)/BX;
     const int nblocks = stats_col_blocks(g);
     const dim3 grid(nblocks), block(BX, BY, 1);
-    if (nmasks == 1)      hipLaunchKernelGGL((stats_column_kernel<TF, 1>), grid, block, 0, st, A, scratch);
-    else if (nmasks == 2) hipLaunchKernelGGL((stats_column_kernel<TF, 2>), grid, block, 0, st, A, scratch);
-    else if (nmasks <= 4) hipLaunchKernelGGL((stats_column_kernel<TF, 4>), grid, block, 0, st, A, scratch);
-    else                  hipLaunchKernelGGL((stats_column_kernel<TF, 8>), grid, block, 0, st, A, scratch);
+    with_mask_width(nmasks, [&](auto nm) { hipLaunchKernelGGL((stats_column_kernel<TF, decltype(nm)::value>), grid, block, 0, st, A, scratch); });
     MHH_LAUNCH_CHECK();
     hipLaunchKernelGGL(stats_column_sums_kernel, dim3(1), dim3(64), 0, st, scratch, sums, nblocks, nmasks);
     MHH_LAUNCH_CHECK();
@@ -640,11 +568,11 @@ static int stats_columns_launch(const mhh_grid* g, const void* mfield, int nmask
 } // namespace mhh
 using namespace mhh;
 
-MHH_API int mhh_stats_chunk_rows(void) { return STATS_ROWS; }
+MHH_API int mhh_stats_chunk_rows(void) { return LEVEL_ROWS; }
 MHH_API unsigned long long mhh_stats_scratch_elems(const mhh_grid* g, int nmasks, int njobs)
 {
     if (!g || nmasks < 1 || njobs < 1) return 0;
-    const unsigned long long a = (unsigned long long)njobs * nmasks * g->kcells * stats_chunks(g);
+    const unsigned long long a = (unsigned long long)njobs * nmasks * g->kcells * level_chunks(g);
     const unsigned long long b = (unsigned long long)stats_col_blocks(g) * nmasks * 3;
     return a > b ? a : b;
 }
