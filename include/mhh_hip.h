@@ -663,6 +663,43 @@ int mhh_micro_2mom_warm_cfl(const mhh_grid* g, const void* qr, const void* nr, c
  * double epsilon narrowed to the dtype; dt is the sub-step (src/model.cxx:415).                                                  */
 int mhh_limiter_exec(const mhh_grid* g, void* at, const void* a, double dt, void* stream);
 
+/* ---- Microphys_nsw6 (src/microphys_nsw6.cxx; Tomita 2008, the single-moment six-class ice scheme; swmicro = nsw6) ----------------
+ * Five scalars of the grid's dtype: thl, qt, qr (rain), qs (snow), qg (graupel), with their tendencies; no field is written.
+ * rhoref, pref, exnref are [kcells] device tables (Thermo_moist's base state). Column-local: a slab rank needs no exchange. Every
+ * entry but the CFL number only enqueues on its stream. params is mhh_micro_params: Nc0, dt (the FULL step) and a mask of:       */
+#define MHH_NSW6_CONV   1    /* conversion (:125-650): the 25 process rates folded into 15 transfers between the six classes  */
+#define MHH_NSW6_SEDI_R 2    /* sedimentation_ss08 (:686-825) of rain                                                        */
+#define MHH_NSW6_SEDI_S 4    /* ... of snow                                                                                  */
+#define MHH_NSW6_SEDI_G 8    /* ... of graupel                                                                               */
+#define MHH_NSW6_ALL    15
+/* the two forms of the powers of the slope parameters (A/B): std::pow wherever the reference has it, or none at all: b = 3 makes
+ * lambda a fourth root and every other exponent a multiple of 1/8, so square roots and products do. Every std::tgamma of the file
+ * and D_d (:139) are evaluated on the host in the dtype in both forms.                                                          */
+#define MHH_NSW6_POW  0
+#define MHH_NSW6_SQRT 1
+#define MHH_NSW6_IMPL_DEFAULT MHH_NSW6_SQRT
+/* Microphys_nsw6::exec (:983-1073): conversion, then the sedimentation of rain, snow and graupel. ql, qi: get_thermo_field("ql")
+ * and ("qi") as the reference's function takes them, or BOTH NULL: then sat_adjust(thl, qt, pref[k], exnref[k]) runs per cell and
+ * `nonconv` counts as in Thermo_moist. The vertical ghost levels (kstart-1, kend) of qr, qs, qg are read by the slopes and must be
+ * set. r?_bot: [ijcells], the surface rates -flux[kstart] [kg m-2 s-1], written on the interior by the species' sedimentation.
+ * scratch: a HOST array of six device pointers, each to kcells * ijcells elements of the dtype (CFL numbers and slopes: scratch[2s],
+ * scratch[2s+1] of species s = 0 rain, 1 snow, 2 graupel); only those of the species in the mask are read.                        */
+int mhh_micro_nsw6_exec(const mhh_grid* g, const mhh_micro_params* params, const void* qr, const void* qs, const void* qg, const void* thl,
+                        const void* qt, const void* ql, const void* qi, void* qrt, void* qst, void* qgt, void* thlt, void* qtt, void* rr_bot,
+                        void* rs_bot, void* rg_bot, const void* rhoref, const void* pref, const void* exnref, void* const* scratch, int* nonconv,
+                        void* stream);
+/* the same with the form named (MHH_NSW6_POW, MHH_NSW6_SQRT)                                                                     */
+int mhh_micro_nsw6_exec_impl(const mhh_grid* g, int impl, const mhh_micro_params* params, const void* qr, const void* qs, const void* qg,
+                             const void* thl, const void* qt, const void* ql, const void* qi, void* qrt, void* qst, void* qgt, void* thlt, void* qtt,
+                             void* rr_bot, void* rs_bot, void* rg_bot, const void* rhoref, const void* pref, const void* exnref,
+                             void* const* scratch, int* nonconv, void* stream);
+/* The largest of the three calc_cfl_ss08 of get_time_limit (:1119-1177) for the step dt, at least 1e-5 (a double, :1174). work:
+ * mhh_reduce_work_bytes() of device memory. Synchronises the stream (the result is a host number), as mhh_advec_cfl does.        */
+int mhh_micro_nsw6_cfl(const mhh_grid* g, const void* qr, const void* qs, const void* qg, const void* rhoref, double dt, void* work, double* out,
+                       void* stream);
+int mhh_micro_nsw6_cfl_impl(const mhh_grid* g, int impl, const void* qr, const void* qs, const void* qg, const void* rhoref, double dt, void* work,
+                            double* out, void* stream);
+
 /* ---- Radiation_gcss (src/radiation_gcss.cxx: the GCSS long- and short-wave fluxes of DYCOMS-II, swradiation = gcss) -------------
  * The parity target is the reference's CPU path; its CUDA file (src/radiation_gcss.cu) differs from it in physics (no max(0, .),
  * dz for z[k]-z[k-1], lwp subtracted on the way up, the flux difference shifted by a level). Column-local: a slab rank exchanges

@@ -206,6 +206,10 @@ SIGNATURES = {
     "mhh_micro_2mom_warm_exec_impl": (ci, [GP, ci, MP] + [vp]*15),
     "mhh_micro_2mom_warm_cfl": (ci, [GP, vp, vp, vp, cd, vp, C.POINTER(cd), vp]),
     "mhh_limiter_exec": (ci, [GP, vp, vp, cd, vp]),
+    "mhh_micro_nsw6_exec": (ci, [GP, MP] + [vp]*21),
+    "mhh_micro_nsw6_exec_impl": (ci, [GP, ci, MP] + [vp]*21),
+    "mhh_micro_nsw6_cfl": (ci, [GP, vp, vp, vp, vp, cd, vp, C.POINTER(cd), vp]),
+    "mhh_micro_nsw6_cfl_impl": (ci, [GP, ci, vp, vp, vp, vp, cd, vp, C.POINTER(cd), vp]),
     "mhh_radiation_gcss_zenith_host": (ci, [ci, cd, cd, cd, C.POINTER(cd)]),
     "mhh_radiation_gcss_exec": (ci, [GP, RP] + [vp]*12),
     "mhh_radiation_gcss_exec_impl": (ci, [GP, ci, RP] + [vp]*12),

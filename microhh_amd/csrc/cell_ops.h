@@ -1492,4 +1492,355 @@ template<class TF> inline TF rad_gcss_zenith(const TF lat, const TF lon, const d
     return mu;
 }
 
+// ---- Microphys_nsw6 (src/microphys_nsw6.cxx: the single-moment six-class scheme of Tomita 2008), in the reference's expression
+// order. The constants of :45-113, each a double literal narrowed to TF; a_r, a_s, a_g and the two pi are double expressions
+// narrowed once. Lv, Ls, Lf, cp, Rv, T0 are MoistC's.
+template<class TF> struct Nsw6C
+{
+    static constexpr TF qv_min = TF(1.e-7), ql_min = TF(1.e-7), qi_min = TF(1.e-7), qr_min = TF(1.e-12), qs_min = TF(1.e-12), qg_min = TF(1.e-12);
+    static constexpr TF q_tiny = TF(1.e-15);
+    static constexpr TF pi = TF(M_PI), pi_2 = TF(M_PI*M_PI);
+    static constexpr TF rho_w = TF(1.e3), rho_s = TF(1.e2), rho_g = TF(4.e2);
+    static constexpr TF N_0r = TF(8.e6), N_0s = TF(3.e6), N_0g = TF(4.e6);
+    static constexpr TF a_r = TF(M_PI*rho_w/6.), a_s = TF(M_PI*rho_s/6.), a_g = TF(M_PI*rho_g/6.);
+    static constexpr TF b_r = TF(3.), b_s = TF(3.), b_g = TF(3.);
+    static constexpr TF c_r = TF(130.), c_s = TF(4.84), c_g = TF(82.5);
+    static constexpr TF d_r = TF(0.5), d_s = TF(0.25), d_g = TF(0.5);
+    static constexpr TF C_l = TF(4218.);
+    static constexpr TF f_1r = TF(0.78), f_1s = TF(0.65), f_1g = TF(0.78), f_2r = TF(0.27), f_2s = TF(0.39), f_2g = TF(0.27);
+    static constexpr TF E_ri = TF(1.), E_rw = TF(1.), E_sw = TF(1.), E_gw = TF(1.), E_gi = TF(0.1), E_sr = TF(1.), E_gr = TF(0.1);
+    static constexpr TF K_a = TF(2.43e-2), K_d = TF(2.26e-5), M_i = TF(4.19e-13);
+    static constexpr TF beta_saut = TF(6.e-3), beta_gaut = TF(0.e-3);
+    static constexpr TF gamma_sacr = TF(25.e-3), gamma_saut = TF(60.e-3), gamma_gacs = TF(90.e-3), gamma_gaut = TF(90.e-3);
+    static constexpr TF nu = TF(1.5e-5);
+    static constexpr TF V_Tmin = TF(0.1), V_Tmax = TF(10.);
+};
+// the process mask and the two forms of the powers (include/mhh_hip.h)
+constexpr int NSW6_CONV = 1, NSW6_SEDI_R = 2, NSW6_SEDI_S = 4, NSW6_SEDI_G = 8, NSW6_ALL = 15;
+constexpr int NSW6_POW = 0, NSW6_SQRT = 1;
+
+// What the scheme holds that depends on no cell: every std::tgamma of the file (its arguments are constants of the scheme), D_d
+// (:139) and the constant factors in front of a level's or a cell's values, evaluated on the HOST in TF, in the reference's order
+// of operations. The kernels get it in their argument block.
+template<class TF> struct Nsw6Tab
+{
+    TF nc_c;       // TF(3.66e-2) * TF(1.e-6)*Nc0 (:333)
+    TF D_d;        // :139
+    TF lam[3];     // a_x * N_0x * tgamma(b_x + 1) of r, s, g (:213-226, :717-719)
+    TF g_b1;       // tgamma(b_x + 1), the same for r, s, g
+    TF g_bd1[3];   // tgamma(b_x + d_x + 1)
+    TF fac[7];     // fac_iacr, raci, racw, sacw, saci, gacw, gaci (:146-185) up to their `* rho0_rho_sqrt`
+    TF acc[3];     // tgamma(b+1)*tgamma(3), 2*tgamma(b+2)*tgamma(2), tgamma(b+3)*tgamma(1) (:289-319; b_r == b_s)
+    TF f1g2[3];    // f_1x * tgamma(2) (:381, :389, :397)
+    TF g_vent[3];  // tgamma(0.5*(5 + d_x))
+    TF dt;         // TF(dt) (:1005)
+    // sedimentation_ss08 and calc_cfl_ss08 take a_c ... N_0c as function PARAMETERS (:695, :835), so their std::tgamma(b_c + d_c + 1)
+    // is a call of the C library at run time, where conversion's arguments are constant expressions that a compiler folds (correctly
+    // rounded). The two differ in the last bit for some arguments (4.5 in fp64), so the velocity keeps a value of its own, evaluated
+    // through nsw6_runtime. tgamma(b_c + 1) is 3! in all three calls: exact, and folded in the reference too (b_c is the same
+    // constant at every call site).
+    TF sed_g_bd1[3]; // tgamma(b_c + d_c + 1) (:724)
+};
+template<class TF> inline TF nsw6_runtime(TF x) { volatile TF v = x; return v; }
+template<class TF> inline Nsw6Tab<TF> nsw6_tab(double Nc0_in, double dt)
+{
+    typedef Nsw6C<TF> K;
+    const TF Nc0 = TF(Nc0_in);
+    Nsw6Tab<TF> H;
+    H.nc_c = TF(3.66e-2) * TF(1.e-6)*Nc0;
+    H.D_d = TF(0.146) - TF(5.964e-2)*std::log((Nc0*TF(1.e-6)) / TF(2.e3));
+    H.lam[0] = K::a_r * K::N_0r * std::tgamma(K::b_r + TF(1.));
+    H.lam[1] = K::a_s * K::N_0s * std::tgamma(K::b_s + TF(1.));
+    H.lam[2] = K::a_g * K::N_0g * std::tgamma(K::b_g + TF(1.));
+    H.g_b1 = std::tgamma(K::b_r + TF(1.));
+    H.g_bd1[0] = std::tgamma(K::b_r + K::d_r + TF(1.));
+    H.g_bd1[1] = std::tgamma(K::b_s + K::d_s + TF(1.));
+    H.g_bd1[2] = std::tgamma(K::b_g + K::d_g + TF(1.));
+    H.fac[0] = K::pi_2 * K::E_ri * K::N_0r * K::c_r * K::rho_w * std::tgamma(TF(6.) + K::d_r) / (TF(24.) * K::M_i);
+    H.fac[1] = K::pi * K::E_ri * K::N_0r * K::c_r * std::tgamma(TF(3.) + K::d_r) / TF(4.);
+    H.fac[2] = K::pi * K::E_rw * K::N_0r * K::c_r * std::tgamma(TF(3.) + K::d_r) / TF(4.);
+    H.fac[3] = K::pi * K::E_sw * K::N_0s * K::c_s * std::tgamma(TF(3.) + K::d_s) / TF(4.);
+    H.fac[4] = K::pi * K::N_0s * K::c_s * std::tgamma(TF(3.) + K::d_s) / TF(4.);
+    H.fac[5] = K::pi * K::E_gw * K::N_0g * K::c_g * std::tgamma(TF(3.) + K::d_g) / TF(4.);
+    H.fac[6] = K::pi * K::E_gi * K::N_0g * K::c_g * std::tgamma(TF(3.) + K::d_g) / TF(4.);
+    H.acc[0] = std::tgamma(K::b_r + TF(1.)) * std::tgamma(TF(3.));
+    H.acc[1] = TF(2.) * std::tgamma(K::b_r + TF(2.)) * std::tgamma(TF(2.));
+    H.acc[2] = std::tgamma(K::b_r + TF(3.)) * std::tgamma(TF(1.));
+    H.f1g2[0] = K::f_1r * std::tgamma(TF(2.));
+    H.f1g2[1] = K::f_1s * std::tgamma(TF(2.));
+    H.f1g2[2] = K::f_1g * std::tgamma(TF(2.));
+    H.g_vent[0] = std::tgamma( TF(0.5) * (TF(5.) + K::d_r) );
+    H.g_vent[1] = std::tgamma( TF(0.5) * (TF(5.) + K::d_s) );
+    H.g_vent[2] = std::tgamma( TF(0.5) * (TF(5.) + K::d_g) );
+    H.dt = TF(dt);
+    const TF b_c[3] = {K::b_r, K::b_s, K::b_g}, d_c[3] = {K::d_r, K::d_s, K::d_g};
+    for (int s=0; s<3; ++s)
+        H.sed_g_bd1[s] = std::tgamma(b_c[s] + nsw6_runtime(d_c[s]) + TF(1.));
+    return H;
+}
+// What depends on the level alone (:143-185, the ventilation roots of :382-430, the three latent factors of :596-647)
+template<class TF> struct Nsw6Level { TF rho, p, exner, r0, fac[7], vent[3], lv, ls, lf; };
+template<class TF> MHH_HD Nsw6Level<TF> nsw6_level(const Nsw6Tab<TF>& H, TF rho_kstart, TF rho, TF p, TF exner)
+{
+    typedef Nsw6C<TF> K; typedef MoistC<TF> M;
+    Nsw6Level<TF> L;
+    L.rho = rho; L.p = p; L.exner = exner;
+    L.r0 = std::sqrt(rho_kstart/rho);
+    for (int n=0; n<7; ++n) L.fac[n] = H.fac[n] * L.r0;
+    L.vent[0] = std::sqrt(K::c_r * L.r0 / K::nu);
+    L.vent[1] = std::sqrt(K::c_s * L.r0 / K::nu);
+    L.vent[2] = std::sqrt(K::c_g * L.r0 / K::nu);
+    L.lv = M::Lv / (M::cp * exner); L.ls = M::Ls / (M::cp * exner); L.lf = M::Lf / (M::cp * exner);
+    return L;
+}
+// The powers of one species' slope parameter. NSW6_POW: std::pow wherever the reference has it, with its arguments. NSW6_SQRT: b = 3
+// makes lambda a fourth root and every other exponent of the file a multiple of 1/8, so each is a product of integer powers of
+// lambda, lambda^(1/2), lambda^(1/4) and lambda^(1/8). S: 0 rain, 1 snow, 2 graupel (d_s = 1/4, d_r = d_g = 1/2).
+template<class TF> struct Nsw6Pow { TF l, l2, l3, p4, p5, p6, md, p3d, pv, p6d; };
+template<int FORM, int S, class TF> MHH_HD Nsw6Pow<TF> nsw6_powers(TF x)
+{
+    typedef Nsw6C<TF> K;
+    const TF b = (S == 0) ? K::b_r : (S == 1) ? K::b_s : K::b_g;
+    const TF d = (S == 0) ? K::d_r : (S == 1) ? K::d_s : K::d_g;
+    Nsw6Pow<TF> P;
+    if (FORM == NSW6_POW)
+    {
+        P.l = std::pow(x, TF(1.) / (b + TF(1.)));
+        P.l2 = P.l*P.l; P.l3 = P.l*P.l*P.l;
+        P.p4 = std::pow(P.l, b + TF(1.)); P.p5 = std::pow(P.l, b + TF(2.)); P.p6 = std::pow(P.l, b + TF(3.));
+        P.md = std::pow(P.l, -d);
+        P.p3d = std::pow(P.l, TF(3.) + d);
+        P.pv = std::pow(P.l, TF(0.5) * (TF(5.) + d));
+        P.p6d = std::pow(P.l, TF(6.) + d);
+    }
+    else
+    {
+        P.l = std::sqrt(std::sqrt(x));
+        const TF h = std::sqrt(P.l), q = std::sqrt(h);
+        P.l2 = P.l*P.l; P.l3 = P.l2*P.l;
+        P.p4 = P.l2*P.l2; P.p5 = P.p4*P.l; P.p6 = P.p4*P.l2;
+        if (S == 1) { P.md = TF(1.)/q; P.p3d = P.l3*q; P.pv = P.l2*h*std::sqrt(q); P.p6d = P.p6*q; }
+        else        { P.md = TF(1.)/h; P.p3d = P.l3*h; P.pv = P.l2*h*q;            P.p6d = P.p6*h; }
+    }
+    return P;
+}
+template<class TF> MHH_HD bool nsw6_idle(TF ql, TF qi, TF qr, TF qs, TF qg)
+{
+    typedef Nsw6C<TF> K;
+    return !((ql > K::ql_min) || (qi > K::qi_min) || (qr > K::qr_min) || (qs > K::qs_min) || (qg > K::qg_min));      // :209
+}
+// The ventilation bracket of :381-384 and its siblings
+template<class TF> MHH_HD TF nsw6_vent(TF f1g2, TF f_2, TF vent, TF g_vent, const Nsw6Pow<TF>& P)
+{
+    return f1g2 / P.l2 + f_2 * vent * g_vent / P.pv;
+}
+// conversion (:125-650) on one cell that is not idle: the five tendencies take the fifteen transfers in the reference's order.
+template<class TF> struct Nsw6Tend { TF qrt, qst, qgt, qtt, thlt; };
+template<int FORM, class TF> MHH_HD void nsw6_conversion(Nsw6Tend<TF>& t, const Nsw6Tab<TF>& H, const Nsw6Level<TF>& L, TF qr, TF qs, TF qg, TF qt,
+                                                         TF thl, TF ql, TF qi)
+{
+    typedef Nsw6C<TF> K; typedef MoistC<TF> M;
+    const TF rho = L.rho;
+    const TF T = L.exner*thl + M::Lv/M::cp*ql + M::Ls/M::cp*qi;
+    const TF qv = qt - ql - qi;
+    const TF T_pos = TF(T >= M::T0);
+    const TF T_neg = TF(1.) - T_pos;
+    const bool has_vapor = (qv > K::qv_min), has_liq = (ql > K::ql_min), has_ice = (qi > K::qi_min);
+    const bool has_rain = (qr > K::qr_min), has_snow = (qs > K::qs_min), has_graupel = (qg > K::qg_min);
+
+    // Tomita Eq. 27
+    const Nsw6Pow<TF> R = nsw6_powers<FORM, 0>(H.lam[0] / (rho * (qr + K::q_tiny)));
+    const Nsw6Pow<TF> S = nsw6_powers<FORM, 1>(H.lam[1] / (rho * (qs + K::q_tiny)));
+    const Nsw6Pow<TF> G = nsw6_powers<FORM, 2>(H.lam[2] / (rho * (qg + K::q_tiny)));
+    // Eq. 28
+    const TF V_Tr = !(has_rain)    ? TF(0.) : K::c_r * L.r0 * H.g_bd1[0] / H.g_b1 * R.md;
+    const TF V_Ts = !(has_snow)    ? TF(0.) : K::c_s * L.r0 * H.g_bd1[1] / H.g_b1 * S.md;
+    const TF V_Tg = !(has_graupel) ? TF(0.) : K::c_g * L.r0 * H.g_bd1[2] / H.g_b1 * G.md;
+
+    // accretion, Eq. 29-38
+    const TF P_iacr = !(has_rain && has_ice) ? TF(0.) : L.fac[0] / R.p6d * qi;
+    const TF delta_1 = TF(qr >= TF(1.e-4));
+    TF P_iacr_s = (TF(1.) - delta_1) * P_iacr;
+    TF P_iacr_g = delta_1 * P_iacr;
+    const TF P_raci = !(has_rain && has_ice) ? TF(0.) : L.fac[1] / R.p3d * qi;
+    TF P_raci_s = (TF(1.) - delta_1) * P_raci;
+    TF P_raci_g = delta_1 * P_raci;
+    TF P_racw = !(has_liq && has_rain) ? TF(0.) : L.fac[2] / R.p3d * ql;
+    TF P_sacw = !(has_liq && has_snow) ? TF(0.) : L.fac[3] / S.p3d * ql;
+    const TF E_si = std::exp(K::gamma_sacr * (T - M::T0));                                                // Eq. 39
+    TF P_saci = !(has_snow && has_ice)    ? TF(0.) : L.fac[4] * E_si / S.p3d * qi;
+    TF P_gacw = !(has_graupel && has_liq) ? TF(0.) : L.fac[5] / G.p3d * ql;
+    TF P_gaci = !(has_graupel && has_ice) ? TF(0.) : L.fac[6] / G.p3d * qi;
+
+    // accretion of falling hydrometeors, Eq. 41-49
+    const TF delta_2 = TF(1.) - TF( (qr >= TF(1.e-4)) || (qs >= TF(1.e-4)) );
+    TF P_racs = !(has_rain && has_snow) ? TF(0.) :
+        (TF(1.) - delta_2)
+        * K::pi * K::a_s * tabs(V_Tr - V_Ts) * K::E_sr * K::N_0s * K::N_0r / (TF(4.)*rho)
+        * (   H.acc[2] / ( S.p6 * R.l )
+            + H.acc[1] / ( S.p5 * R.l2 )
+            + H.acc[0] / ( S.p4 * R.l3 ) );
+    const TF P_sacr = !(has_snow && has_rain) ? TF(0.) :
+          K::pi * K::a_r * tabs(V_Ts - V_Tr) * K::E_sr * K::N_0r * K::N_0s / (TF(4.)*rho)
+        * (   H.acc[0] / ( R.p4 * S.l3 )
+            + H.acc[1] / ( R.p5 * S.l2 )
+            + H.acc[2] / ( R.p6 * S.l ) );
+    TF P_sacr_g = (TF(1.) - delta_2) * P_sacr;
+    TF P_sacr_s = delta_2 * P_sacr;
+    const TF E_gs = tmin( TF(1.), TF(std::exp(K::gamma_gacs * (T - M::T0))) );
+    TF P_gacr = !(has_graupel && has_rain) ? TF(0.) :
+          K::pi * K::a_r * tabs(V_Tg - V_Tr) * K::E_gr * K::N_0g * K::N_0r / (TF(4.)*rho)
+        * (   H.acc[0] / ( R.p4 * G.l3 )
+            + H.acc[1] / ( R.p5 * G.l2 )
+            + H.acc[2] / ( R.p6 * G.l ) );
+    TF P_gacs = !(has_graupel && has_snow) ? TF(0.) :
+          K::pi * K::a_s * tabs(V_Tg - V_Ts) * E_gs * K::N_0g * K::N_0s / (TF(4.)*rho)
+        * (   H.acc[0] / ( S.p4 * G.l3 )
+            + H.acc[1] / ( S.p5 * G.l2 )
+            + H.acc[2] / ( S.p6 * G.l ) );
+
+    // autoconversion, Eq. 50-54. beta_2 is min(0, 0*exp(..)) as written; the second form spends no exp on it.
+    constexpr TF q_icrt = TF(0.);
+    constexpr TF q_scrt = TF(6.e-4);
+    const TF beta_1 = tmin( K::beta_saut, TF(K::beta_saut*std::exp(K::gamma_saut * (T - M::T0))) );
+    const TF beta_2 = (FORM == NSW6_POW) ? tmin( K::beta_gaut, TF(K::beta_gaut*std::exp(K::gamma_gaut * (T - M::T0))) ) : K::beta_gaut;
+    TF P_raut = !(has_liq) ? TF(0.) :
+        TF(16.7)/rho * sq(rho*ql) / (TF(5.) + H.nc_c / (H.D_d*rho*ql));
+    TF P_saut = !(has_ice)  ? TF(0.) : tmax(beta_1*(qi - q_icrt), TF(0.));
+    TF P_gaut = !(has_snow) ? TF(0.) : tmax(beta_2*(qs - q_scrt), TF(0.));
+
+    // phase changes, Eq. 57-65; the exp of esat_ice once for G_i and S_i
+    const TF es_liq = moist_esat_liq(T), es_ice = moist_esat_ice(T);
+    const TF G_w = TF(1.) / (
+        M::Lv / (K::K_a * T) * (M::Lv / (M::Rv * T) - TF(1.))
+        + M::Rv*T / (K::K_d * es_liq) );
+    const TF G_i = TF(1.) / (
+        M::Ls / (K::K_a * T) * (M::Ls / (M::Rv * T) - TF(1.))
+        + M::Rv*T / (K::K_d * es_ice) );
+    const TF S_w = (qt - ql - qi) / (M::ep*es_liq/(L.p-(TF(1.)-M::ep)*es_liq));
+    const TF S_i = (qt - ql - qi) / (M::ep*es_ice/(L.p-(TF(1.)-M::ep)*es_ice));
+    const TF delta_3 = TF(S_i <= TF(1.));
+    const TF vent_r = nsw6_vent(H.f1g2[0], K::f_2r, L.vent[0], H.g_vent[0], R);
+    const TF vent_s = nsw6_vent(H.f1g2[1], K::f_2s, L.vent[1], H.g_vent[1], S);
+    const TF vent_g = nsw6_vent(H.f1g2[2], K::f_2g, L.vent[2], H.g_vent[2], G);
+    TF P_revp = !(has_rain) ? TF(0.) :
+        - TF(2.)*K::pi * K::N_0r * (tmin(S_w, TF(1.)) - TF(1.)) * G_w / rho * vent_r;
+    const TF P_sdep_ssub = TF(2.)*K::pi * K::N_0s * (S_i - TF(1.)) * G_i / rho * vent_s;
+    const TF P_gdep_gsub = TF(2.)*K::pi * K::N_0g * (S_i - TF(1.)) * G_i / rho * vent_g;
+    TF P_sdep = !(has_vapor)   ? TF(0.) : (TF(1.) - delta_3) * P_sdep_ssub;
+    TF P_gdep = !(has_vapor)   ? TF(0.) : (TF(1.) - delta_3) * P_gdep_gsub;
+    TF P_ssub = !(has_snow)    ? TF(0.) : - delta_3 * P_sdep_ssub;
+    TF P_gsub = !(has_graupel) ? TF(0.) : - delta_3 * P_gdep_gsub;
+
+    // freezing and melting, Eq. 67-70
+    TF P_smlt = !(has_snow) ? TF(0.) :
+        TF(2.)*K::pi * K::K_a * (T - M::T0) * K::N_0s / (rho*M::Lf) * vent_s
+        + K::C_l * (T - M::T0) / M::Lf * (P_sacw + P_sacr);
+    TF P_gmlt = !(has_graupel) ? TF(0.) :
+        TF(2.)*K::pi * K::K_a * (T - M::T0) * K::N_0g / (rho*M::Lf) * vent_g
+        + K::C_l * (T - M::T0) / M::Lf * (P_gacw + P_gacr);
+    constexpr TF A_prime = TF(0.66);
+    constexpr TF B_prime = TF(100.);
+    TF P_gfrz = !(has_rain) ? TF(0.) :
+        TF(20.) * K::pi_2 * B_prime * K::N_0r * K::rho_w / rho
+        * (TF(std::exp(A_prime * (M::T0 - T))) - TF(1.)) / (R.l*R.l*R.l*R.l*R.l*R.l*R.l);
+
+    // limit the production terms on the availability of their source (:444-486)
+    const TF dt = H.dt;
+    const TF dqv_dt_max = qv / dt, dqi_dt_max = qi / dt, dql_dt_max = ql / dt;
+    const TF dqr_dt_max = qr / dt, dqs_dt_max = qs / dt, dqg_dt_max = qg / dt;
+#define NSW6_LIMIT(tend, lim) tend = tmax(TF(0.), tmin(tend, lim))
+    NSW6_LIMIT(P_iacr_s, dqr_dt_max); NSW6_LIMIT(P_iacr_g, dqr_dt_max); NSW6_LIMIT(P_raci_s, dqi_dt_max); NSW6_LIMIT(P_raci_g, dqi_dt_max);
+    NSW6_LIMIT(P_racw, dql_dt_max);   NSW6_LIMIT(P_sacw, dql_dt_max);   NSW6_LIMIT(P_saci, dqi_dt_max);   NSW6_LIMIT(P_gacw, dql_dt_max);
+    NSW6_LIMIT(P_gaci, dqi_dt_max);   NSW6_LIMIT(P_racs, dqs_dt_max);   NSW6_LIMIT(P_sacr_s, dqr_dt_max); NSW6_LIMIT(P_sacr_g, dqr_dt_max);
+    NSW6_LIMIT(P_gacr, dqr_dt_max);   NSW6_LIMIT(P_gacs, dqs_dt_max);
+    NSW6_LIMIT(P_raut, dql_dt_max);   NSW6_LIMIT(P_saut, dqi_dt_max);   NSW6_LIMIT(P_gaut, dqs_dt_max);
+    NSW6_LIMIT(P_revp, dqr_dt_max);   NSW6_LIMIT(P_sdep, dqv_dt_max);   NSW6_LIMIT(P_ssub, dqs_dt_max);   NSW6_LIMIT(P_gdep, dqv_dt_max);
+    NSW6_LIMIT(P_gsub, dqg_dt_max);   NSW6_LIMIT(P_smlt, dqs_dt_max);   NSW6_LIMIT(P_gmlt, dqg_dt_max);   NSW6_LIMIT(P_gfrz, dqr_dt_max);
+#undef NSW6_LIMIT
+
+    TF vapor_to_snow = P_sdep;
+    TF vapor_to_graupel = P_gdep;
+    TF cloud_to_rain = P_racw + P_sacw * T_pos + P_raut;
+    TF cloud_to_graupel = P_gacw;
+    TF cloud_to_snow = P_sacw * T_neg;
+    TF rain_to_vapor = P_revp;
+    TF rain_to_graupel = P_gacr + P_iacr_g + P_sacr_g * T_neg + P_gfrz * T_neg;
+    TF rain_to_snow = P_sacr_s * T_neg + P_iacr_s;
+    TF ice_to_snow = P_raci_s + P_saci + P_saut;
+    TF ice_to_graupel = P_raci_g + P_gaci;
+    TF snow_to_graupel = P_gacs + P_racs + P_gaut;
+    TF snow_to_rain = P_smlt;
+    TF snow_to_vapor = P_ssub;
+    TF graupel_to_rain = P_gmlt * T_pos;
+    TF graupel_to_vapor = P_gsub;
+
+    const TF dqv_dt = - vapor_to_snow - vapor_to_graupel;
+    const TF dql_dt = - cloud_to_rain - cloud_to_graupel - cloud_to_snow;
+    const TF dqi_dt = - ice_to_snow - ice_to_graupel;
+    const TF dqr_dt = + cloud_to_rain + snow_to_rain + graupel_to_rain - rain_to_vapor - rain_to_graupel - rain_to_snow;
+    const TF dqs_dt = + cloud_to_snow + ice_to_snow + vapor_to_snow - snow_to_graupel - snow_to_vapor - snow_to_rain;
+    const TF dqg_dt = + cloud_to_graupel + rain_to_graupel + ice_to_graupel + vapor_to_graupel + snow_to_graupel - graupel_to_rain - graupel_to_vapor;
+#define NSW6_FACTOR(tend, lim) (((tend) < TF(0.)) ? tmin(-(lim)/(tend), TF(1.)) : TF(1.))
+    const TF dqv_dt_fac = NSW6_FACTOR(dqv_dt, dqv_dt_max), dql_dt_fac = NSW6_FACTOR(dql_dt, dql_dt_max), dqi_dt_fac = NSW6_FACTOR(dqi_dt, dqi_dt_max);
+    const TF dqr_dt_fac = NSW6_FACTOR(dqr_dt, dqr_dt_max), dqs_dt_fac = NSW6_FACTOR(dqs_dt, dqs_dt_max), dqg_dt_fac = NSW6_FACTOR(dqg_dt, dqg_dt_max);
+#undef NSW6_FACTOR
+    vapor_to_snow    *= dqv_dt_fac * dqs_dt_fac;
+    vapor_to_graupel *= dqv_dt_fac * dqg_dt_fac;
+    cloud_to_rain    *= dql_dt_fac * dqr_dt_fac;
+    cloud_to_graupel *= dql_dt_fac * dqg_dt_fac;
+    cloud_to_snow    *= dql_dt_fac * dqs_dt_fac;
+    rain_to_vapor    *= dqr_dt_fac * dqv_dt_fac;
+    rain_to_graupel  *= dqr_dt_fac * dqg_dt_fac;
+    rain_to_snow     *= dqr_dt_fac * dqs_dt_fac;
+    ice_to_snow      *= dqi_dt_fac * dqs_dt_fac;
+    ice_to_graupel   *= dqi_dt_fac * dqg_dt_fac;
+    snow_to_graupel  *= dqs_dt_fac * dqg_dt_fac;
+    snow_to_vapor    *= dqs_dt_fac * dqv_dt_fac;
+    snow_to_rain     *= dqs_dt_fac * dqr_dt_fac;
+    graupel_to_rain  *= dqg_dt_fac * dqr_dt_fac;
+    graupel_to_vapor *= dqg_dt_fac * dqv_dt_fac;
+
+    // :593-647
+    t.qtt -= cloud_to_rain;    t.qrt += cloud_to_rain;    t.thlt += L.lv * cloud_to_rain;
+    t.qtt -= cloud_to_graupel; t.qgt += cloud_to_graupel; t.thlt += L.ls * cloud_to_graupel;
+    t.qtt -= cloud_to_snow;    t.qst += cloud_to_snow;    t.thlt += L.ls * cloud_to_snow;
+    t.qrt -= rain_to_vapor;    t.qtt += rain_to_vapor;    t.thlt -= L.lv * rain_to_vapor;
+    t.qrt -= rain_to_graupel;  t.qgt += rain_to_graupel;  t.thlt += L.lf * rain_to_graupel;
+    t.qrt -= rain_to_snow;     t.qst += rain_to_snow;     t.thlt += L.lf * rain_to_snow;
+    t.qtt -= ice_to_snow;      t.qst += ice_to_snow;      t.thlt += L.ls * ice_to_snow;
+    t.qtt -= ice_to_graupel;   t.qgt += ice_to_graupel;   t.thlt += L.ls * ice_to_graupel;
+    t.qst -= snow_to_graupel;  t.qgt += snow_to_graupel;
+    t.qst -= snow_to_vapor;    t.qtt += snow_to_vapor;    t.thlt -= L.ls * snow_to_vapor;
+    t.qst -= snow_to_rain;     t.qrt += snow_to_rain;     t.thlt -= L.lf * snow_to_rain;
+    t.qgt -= graupel_to_rain;  t.qrt += graupel_to_rain;  t.thlt -= L.lf * graupel_to_rain;
+    t.qgt -= graupel_to_vapor; t.qtt += graupel_to_vapor; t.thlt -= L.ls * graupel_to_vapor;
+}
+// The terminal velocity of one level of sedimentation_ss08 / calc_cfl_ss08 (:704-735, :846-877): no q_tiny here, clamped to
+// [0.1, 10] m/s, zero without the species. S as in nsw6_powers.
+template<int FORM, int S, class TF> MHH_HD TF nsw6_w_sedi(const Nsw6Tab<TF>& H, TF qc, TF rho, TF r0)
+{
+    typedef Nsw6C<TF> K;
+    const TF c_c = (S == 0) ? K::c_r : (S == 1) ? K::c_s : K::c_g;
+    const TF d_c = (S == 0) ? K::d_r : (S == 1) ? K::d_s : K::d_g;
+    const TF b_c = (S == 0) ? K::b_r : (S == 1) ? K::b_s : K::b_g;
+    const TF qc_min = (S == 0) ? K::qr_min : (S == 1) ? K::qs_min : K::qg_min;
+    if (!(qc > qc_min))
+        return TF(0.);
+    const TF x = H.lam[S] / (rho * qc);
+    TF md;
+    if (FORM == NSW6_POW)
+    {
+        const TF lambda_c = std::pow(x, TF(1.) / (b_c + TF(1.)));
+        md = std::pow(lambda_c, -d_c);
+    }
+    else
+    {
+        const TF h = std::sqrt(std::sqrt(std::sqrt(x)));                      // lambda^(1/2)
+        md = TF(1.) / ((S == 1) ? std::sqrt(h) : h);
+    }
+    const TF V_T = c_c * r0 * H.sed_g_bd1[S] / H.g_b1 * md;
+    return tmax(K::V_Tmin, tmin(V_T, K::V_Tmax));
+}
+
 } // namespace mhh

@@ -828,6 +828,7 @@ MHH_API int mhh_boundary_ghost_cells_w(const mhh_grid* g, void* w, int type, voi
 // =======================================================================================================
 #include "thermo_moist.h"
 #include "microphys_2mom_warm.h"
+#include "microphys_nsw6.h"
 #include "radiation_gcss.h"
 
 // =======================================================================================================

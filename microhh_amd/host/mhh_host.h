@@ -910,6 +910,56 @@ class Microphys_2mom_warm
         Grid<TF>& grid; Fields<TF>& fields;
 };
 
+// ---- Microphys_nsw6 (src/microphys_nsw6.cxx): swmicro = nsw6 with the scalars thl, qt, qr, qs and qg ---------------------------
+// The three surface rates ([ijcells] each), the six scratch fields ([ncells] each: the reference's get_tmp_g, two per species) and
+// work_g (mhh_reduce_work_bytes()) are the caller's device arrays. ql and qi are the saturation adjustment of the Thermo_moist it
+// is handed, evaluated per cell inside the conversion kernel; the base state, rhoref included, comes from it too.
+template<typename TF>
+class Microphys_nsw6
+{
+    public:
+        Microphys_nsw6(Grid<TF>& grid_in, Fields<TF>& fields_in) : grid(grid_in), fields(fields_in) {}
+        // [micro] Nc0, cflmax
+        TF Nc0 = 0; TF cflmax = 1.2;
+        int processes = MHH_NSW6_ALL;
+        int impl = MHH_NSW6_IMPL_DEFAULT;
+        TF* rr_bot_g = nullptr; TF* rs_bot_g = nullptr; TF* rg_bot_g = nullptr;
+        TF* scratch_g[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; void* work_g = nullptr;
+        std::string get_switch() const { return "nsw6"; }
+
+        // Microphys_nsw6::exec (:983-1073); dt is the full step, timeloop->get_dt()
+        void exec(Thermo_moist<TF>& thermo, const double dt, void* stream = nullptr)
+        {
+            if (!(Nc0 > 0)) throw std::runtime_error("Microphys_nsw6: Nc0 (no default)");
+            mhh_grid g = grid.abi();
+            mhh_micro_params p{}; p.Nc0 = Nc0; p.dt = dt; p.processes = processes;
+            void* const scratch[6] = {scratch_g[0], scratch_g[1], scratch_g[2], scratch_g[3], scratch_g[4], scratch_g[5]};
+            mhh_check(mhh_micro_nsw6_exec_impl(&g, impl, &p, fields.sp.at("qr")->fld_g, fields.sp.at("qs")->fld_g, fields.sp.at("qg")->fld_g,
+                                               fields.sp.at("thl")->fld_g, fields.sp.at("qt")->fld_g, nullptr, nullptr,
+                                               fields.st.at("qr")->fld_g, fields.st.at("qs")->fld_g, fields.st.at("qg")->fld_g,
+                                               fields.st.at("thl")->fld_g, fields.st.at("qt")->fld_g, rr_bot_g, rs_bot_g, rg_bot_g,
+                                               fields.rhoref_g, thermo.pref_g, thermo.exnref_g, scratch, thermo.nonconv_g, stream));
+        }
+        // get_time_limit (:1119-1177): the CFL number is a double there, idt * cflmax a TF. `max_over_ranks` is Master::max (the
+        // identity on one rank).
+        template<class Max> unsigned long get_time_limit(unsigned long idt, const double dt, Max&& max_over_ranks, void* stream = nullptr)
+        {
+            mhh_grid g = grid.abi();
+            double cfl = 0;
+            mhh_check(mhh_micro_nsw6_cfl_impl(&g, impl, fields.sp.at("qr")->fld_g, fields.sp.at("qs")->fld_g, fields.sp.at("qg")->fld_g, fields.rhoref_g, dt,
+                                              work_g, &cfl, stream));
+            max_over_ranks(&cfl);
+            return idt * cflmax / cfl;
+        }
+        unsigned long get_time_limit(unsigned long idt, const double dt) { return get_time_limit(idt, dt, [](double*) {}); }
+        // the device arrays exec wrote; get_surface_rain_rate (:1194-1202) is their sum, the caller's to form
+        TF* get_surface_rain_rate() const { return rr_bot_g; }
+        TF* get_surface_snow_rate() const { return rs_bot_g; }
+        TF* get_surface_graupel_rate() const { return rg_bot_g; }
+    private:
+        Grid<TF>& grid; Fields<TF>& fields;
+};
+
 // ---- Limiter (src/limiter.cxx): [limiter] limitlist ----------------------------------------------------------------------------
 template<typename TF>
 class Limiter

@@ -4,7 +4,7 @@ that this package accelerates, expressed as calls into the C ABI.
     boundary->set_prognostic_cyclic_bcs   -> mhh_boundary_cyclic_n (+ N-S neighbour exchange)   (src/model.cxx:346)
     diff->exec_viscosity(thermo)          -> mhh_diff_exec_viscosity (+ N-S exchange of evisc)   (:354)
     thermo->exec (Thermo_moist)           -> mhh_thermo_moist_base_state, mhh_thermo_moist_buoyancy_tend (thermo=..., opt-in) (:366)
-    microphys->exec ; limiter->exec       -> mhh_micro_2mom_warm_exec, mhh_limiter_exec (micro=..., opt-in) (:369, :415)
+    microphys->exec ; limiter->exec       -> mhh_micro_2mom_warm_exec or mhh_micro_nsw6_exec, mhh_limiter_exec (micro=..., opt-in) (:369, :415)
     radiation->exec (Radiation_gcss)      -> mhh_radiation_gcss_exec (radiation=..., opt-in)      (:372)
     boundary->exec ; set_ghost_cells      -> mhh_boundary_surface_exec, mhh_boundary_ghost_cells (surface=..., opt-in) (:374-375)
     advec->exec ; diff->exec              -> mhh_rhs_exec (fused, same bits)                     (:388, :392)
@@ -58,6 +58,11 @@ CASES = {
     "dycoms": dict(advec=ADVEC_2I5, diff=DIFF_SMAG2, pres=2, order=2, gc=(3, 3, 1), size=(6400., 6400., 1500.), nscalars=4, sm=1, visc=1e-5,
                    thermo="moist", pbot=101780., micro="2mom_warm", Nc0=70.e6,
                    radiation="gcss", xka=85., fr0=70., fr1=22., div=3.75e-6, lat=32.5, lon=0., day_of_year=160.),
+    # rcemip (cases/rcemip/rcemip.ini: 1600 m x 1600 m x 32250 m at 8 x 8 columns, the horizontal size scaled with the column count):
+    # Thermo_moist with Microphys_nsw6, scalars 0 = thl, 1 = qt, 2 = qr, 3 = qs, 4 = qg, pbot = 101480 Pa;
+    # HotPath(..., thermo=thermo.Moist(pbot), micro=microphys.Nsw6(Nc0)) switches the physics on. Its radiation (rrtmgp) is not here.
+    "rcemip": dict(advec=ADVEC_2I5, diff=DIFF_SMAG2, pres=2, order=2, gc=(3, 3, 1), size=(12800., 12800., 32250.), nscalars=5, sm=1, visc=1e-5,
+                   thermo="moist", pbot=101480., micro="nsw6", Nc0=100.e6),
 }
 
 FIELDS3 = ("u", "v", "w", "ut", "vt", "wt")
@@ -81,6 +86,9 @@ def synthetic_global(case, itot, jtot, ktot, dtype=np.float64, seed=666, nscalar
     if cfg.get("thermo") == "moist" and "s1" in out:
         from .thermo import bomex_interior
         out["s0"], out["s1"] = bomex_interior(z, n3, rs)
+    if case == "rcemip" and "s1" in out:
+        from .thermo import rcemip_interior
+        out["s0"], out["s1"] = rcemip_interior(z, n3, rs)
     if cfg.get("radiation") == "gcss" and "s1" in out:
         from .radiation import synthetic_stratocumulus
         out["s0"], out["s1"] = synthetic_stratocumulus(z, n3, rs)
@@ -88,6 +96,10 @@ def synthetic_global(case, itot, jtot, ktot, dtype=np.float64, seed=666, nscalar
         from .microphys import synthetic_rain
         out["s2"], out["s3"] = synthetic_rain(z, n3, rs)
         out["st2"], out["st3"] = rs.uniform(-1e-8, 1e-8, n3), rs.uniform(-1., 1., n3)
+    if cfg.get("micro") == "nsw6" and "s4" in out:
+        from .microphys import synthetic_precip
+        out["s2"], out["s3"], out["s4"] = synthetic_precip(z, n3, rs)
+        out["st2"], out["st3"], out["st4"] = (rs.uniform(-1e-8, 1e-8, n3) for _ in range(3))
     for k in SURF:
         out[k] = rs.uniform(0, 1e-4 if k == "dbdz" else 1e-2, n2)
     out["z0m"][:] = 0.1
@@ -183,7 +195,7 @@ class HotPath:
             self.st = [put3(global_init["st%d" % n]) for n in range(nsc)]
             self.surf = {k: put2(global_init[k]) for k in SURF}
             if cfg.get("thermo") == "moist":     # the mean profiles of thl and qt are read on the ghost levels too: zero gradient there
-                for t in self.s[:2] + (self.s[2:4] if micro is not None else []):      # (as are qr and nr by sedimentation's slopes)
+                for t in self.s[:2] + (self.s[2:] if micro is not None else []):       # (as are qr and nr, or qr, qs and qg, by sedimentation's slopes)
                     t[:g.kstart] = t[g.kstart]; t[g.kend:] = t[g.kend-1]
         if surface is not None:          # before the mixing-length table below is made from it
             self.surf["z0m"].fill_(float(surface.z0m))

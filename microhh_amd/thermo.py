@@ -20,6 +20,25 @@ def bomex_profiles(z):
     return np.interp(z, zb, [298.7, 298.7, 302.4, 308.2, 311.85]), np.interp(z, zb, [17.0e-3, 16.3e-3, 10.7e-3, 4.2e-3, 3.0e-3])
 
 
+def rcemip_profiles(z):
+    """Initial profiles for the deep-convection case (cases/rcemip): a troposphere of 15 km in which thl rises by 4 K/km from the
+    surface value of rcemip.ini (about 6.5 K/km in temperature: the freezing level lies near 4.3 km, -40 C near 10 km), a
+    stratosphere close to isothermal above, and qt falling off with a scale height of 2.8 km from 19 g/kg, at least 1e-6. Returns
+    thl [K] and qt [kg/kg] at the heights z [m]."""
+    z = np.asarray(z, dtype=np.float64)
+    thl = np.where(z < 15000., 298.7438128523857 + 4.e-3*z, 358.7438128523857 + 17.e-3*(z - 15000.))
+    return thl, np.maximum(19.e-3*np.exp(-z/2800.), 1.e-6)
+
+
+def rcemip_interior(z, n3, rs):
+    """The synthetic state of the deep-convection case: the profiles plus uniform noise of +-0.5 K and +-60 % of qt drawn from the
+    numpy generator rs. Liquid-only cloud forms below the freezing level, mixed-phase cloud between it and -40 C, ice cloud above."""
+    thl0, qt0 = rcemip_profiles(z)
+    thl = thl0[:, None, None] + rs.uniform(-.5, .5, n3)
+    qt = qt0[:, None, None]*(1. + rs.uniform(-.6, .6, n3))
+    return thl, qt
+
+
 def bomex_interior(z, n3, rs):
     """The one recipe of the synthetic BOMEX state: thl and qt on n3 = (ktot, jtot, itot) cells at the heights z, the initial profiles
     plus uniform noise of +-0.5 K and +-3e-3 kg/kg drawn from the numpy generator rs, qt clipped at 0. The profiles alone are
@@ -75,7 +94,8 @@ class Moist:
     the reference would have thrown "Non-converging saturation adjustment". Per sub-step (Thermo_moist::exec, :1273-1303): with
     swupdatebasestate the base state is recomputed on the device from the horizontal means of thl and qt -- all eight profiles, as the
     reference's call does, in the Boussinesq mode too -- and the buoyancy tendency is added to wt in front of the RHS pass.
-    thl0, qt0: the ktot initial values the base state starts from (default: the BOMEX profiles on the grid's levels)."""
+    thl0, qt0: the ktot initial values the base state starts from (default: the BOMEX profiles on the grid's levels; those of
+    rcemip_profiles for the case rcemip)."""
 
     FIELDS = ("b", "ql", "qi", "T", "N2", "ql_h")
 
@@ -97,7 +117,8 @@ class Moist:
         if hp.cfg.get("thermo") == "buoy":
             raise ValueError("thermo=Moist on a Thermo_buoy case: scalar 0 is the buoyancy b there, not thl")
         self.hp = hp
-        thl0, qt0 = (self.thl0, self.qt0) if self.thl0 is not None else bomex_profiles(g.z[g.kstart:g.kend])
+        profiles = rcemip_profiles if hp.case == "rcemip" else bomex_profiles
+        thl0, qt0 = (self.thl0, self.qt0) if self.thl0 is not None else profiles(g.z[g.kstart:g.kend])
         prof = base_state(hp.lib, g, thl0, qt0, self.pbot, self.swbasestate, self.thvref0)
         self.tab = {n: torch.from_numpy(prof[n].copy()).to(hp.device) for n in BASE_STATE}
         self.mean = [torch.from_numpy(prof[n].copy()).to(hp.device) for n in ("thl0", "qt0")]
