@@ -863,6 +863,45 @@ int mhh_rk_substep(const mhh_grid* g, int rkorder, int substep, double dt, void*
  * mhh_rk_substep(u), (v), (w), which is also what it falls back to (pres_4, the last sub-step of a step). f->u, v, w are WRITTEN. */
 int mhh_pres_exec_rk(mhh_pres_plan* plan, const mhh_grid* g, const mhh_fields* f, double sub_dt, int rkorder, int substep, double dt, void* stream);
 
+/* ---- Cross (src/cross.cxx: the cross-section files; src/field3d_io.cxx:754-861 save_xy_slice / save_xz_slice / save_yz_slice) -----
+ * The reference runs Cross on the host, also in its GPU build, which copies every prognostic field back first (src/model.cxx:444-451).
+ * Here the planes are gathered on the device: a JOB is one plane of one field, written PACKED (interior cells only, the layout the
+ * writers put on disk) at its own place of a staging buffer that the caller copies to the host once and writes from there.
+ * Indices are ARRAY indices of this rank, ghost cells included (a level k, a row j, a column i): a half-level xz row jend is the
+ * north ghost row, as the serial writer reads it. Every entry only enqueues on its stream. */
+#define MHH_CROSS_XY    0   /* level `index`:               out [jmax][imax]   (save_xy_slice, :828-861)                               */
+#define MHH_CROSS_XZ    1   /* row `index`, levels k0..k1:  out [k1-k0][imax]  (save_xz_slice, :753-788)                               */
+#define MHH_CROSS_YZ    2   /* column `index`, k0..k1:      out [k1-k0][jmax]  (save_yz_slice, :790-826): strided by nature            */
+#define MHH_CROSS_PLANE 3   /* fld is a 2-D [ijcells] array: out [jmax][imax]  (Cross::cross_plane, src/cross.cxx:638-651)             */
+#define MHH_CROSS_MAX_JOBS 32   /* jobs that travel with one launch; a call takes any number and launches per batch                    */
+typedef struct mhh_cross_job
+{
+    const void* fld;             /* [ncells] of the grid's dtype ([ijcells] for PLANE)                                               */
+    int kind;                    /* MHH_CROSS_*                                                                                      */
+    int index;                   /* XY: k, XZ: j, YZ: i of the array; PLANE: not read                                                */
+    int k0, k1;                  /* XZ, YZ: the levels k0 .. k1-1 (gd.kstart, gd.kend of cross_simple)                                */
+    double offset;               /* data0: narrowed to the dtype, then added (TF data0)                                              */
+    void* out;                   /* where the packed plane goes                                                                      */
+} mhh_cross_job;
+/* Cross::cross_simple / cross_plane (src/cross.cxx:564-651) without the write: out = data + offset per job. Refused with a reason:
+ * an unknown kind, an index outside [0, kcells) / [0, jcells) / [0, icells), k0 / k1 outside [0, kcells].                           */
+int mhh_cross_gather(const mhh_grid* g, const mhh_cross_job* jobs, int njobs, void* stream);
+/* Cross::cross_lngrad (:653-703): calc_lngrad_2nd (:136-167, order 2) or calc_lngrad_4th (:42-133, order 4) evaluated on the cells
+ * of the jobs' planes only (XY | XZ | YZ, inside the interior; the offset is not read), log(dtiny + gx^2 + gy^2 + gz^2) with the sum
+ * and the log in double. Needs the filled ghost cells of fld: one in every direction (order 2), three (order 4).                   */
+int mhh_cross_lngrad(const mhh_grid* g, int order, const mhh_cross_job* jobs, int njobs, void* stream);
+/* Cross::cross_path (:705-725), calc_cross_path (:170-197): out [jmax][imax] = sum over kstart..kend-1 of rhoref[k]*fld*dz[k], serially in
+ * the dtype in that operand order                                                                                                 */
+int mhh_cross_path(const mhh_grid* g, const void* fld, const void* rhoref, void* out, void* stream);
+/* Cross::cross_height_threshold (:738-760), calc_cross_height_threshold (:200-250): out [jmax][imax] = z[k] of the lowest (upward != 0)
+ * or highest level with fld > threshold, the fill value TF(-1e-9) (:748) where there is none                                      */
+int mhh_cross_height_threshold(const mhh_grid* g, const void* fld, double threshold, int upward, void* out, void* stream);
+/* The search of Cross::create (:323-460) for the locations loc[nloc] of one direction (MHH_CROSS_XY: heights, XZ: y, YZ: x), in GLOBAL
+ * interior indices: full[*nfull] and half[*nhalf] (room for nloc each), duplicates dropped per list. loc == size decrements the full
+ * index (:337, :382); loc == zsize gives kmax-1 and kmax (:425-429); the half offset applies from z[k] on (:437). The metric pointers
+ * of g are HOST pointers. A location outside the domain is refused and the message names it.                                      */
+int mhh_cross_indices_host(const mhh_grid* g, int kind, const double* loc, int nloc, int* full, int* nfull, int* half, int* nhalf);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,10 @@ class MhhStatsJob(C.Structure):
                 ("flux_bot", vp), ("flux_top", vp), ("visc", cd), ("tPr", cd), ("a", ci), ("b", ci)]
 
 
+class MhhCrossJob(C.Structure):
+    _fields_ = [("fld", vp), ("kind", ci), ("index", ci), ("k0", ci), ("k1", ci), ("offset", cd), ("out", vp)]
+
+
 class MhhBudget2Desc(C.Structure):
     _fields_ = [("u", vp), ("v", vp), ("w", vp), ("p", vp), ("evisc", vp), ("b", vp), ("u_fluxbot", vp), ("v_fluxbot", vp),
                 ("umodel", vp), ("vmodel", vp), ("wmodel", vp), ("bmean", vp), ("pmean", vp),
@@ -86,6 +90,7 @@ MP = C.POINTER(MhhMicroParams)
 RP = C.POINTER(MhhRadiationGcssParams)
 SJP = C.POINTER(MhhStatsJob)
 BDP = C.POINTER(MhhBudget2Desc)
+CJP = C.POINTER(MhhCrossJob)
 PLAN = vp
 
 SIGNATURES = {
@@ -233,6 +238,11 @@ SIGNATURES = {
     "mhh_budget_2_sums": (ci, [GP, vp, ci, BDP, vp, vp, vp]),
     "mhh_budget_2_finish": (ci, [GP, ci, BDP, vp, vp, vp, vp]),
     "mhh_thermo_dry_buoyancy": (ci, [GP, vp, vp, vp, cd, vp]),
+    "mhh_cross_gather": (ci, [GP, CJP, ci, vp]),
+    "mhh_cross_lngrad": (ci, [GP, ci, CJP, ci, vp]),
+    "mhh_cross_path": (ci, [GP, vp, vp, vp, vp]),
+    "mhh_cross_height_threshold": (ci, [GP, vp, cd, ci, vp, vp]),
+    "mhh_cross_indices_host": (ci, [GP, ci, C.POINTER(cd), ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),
 }
 
 

@@ -840,3 +840,8 @@ MHH_API int mhh_boundary_ghost_cells_w(const mhh_grid* g, void* w, int type, voi
 // Budget_2: the kinetic energies and the budget terms as masked profiles (src/budget_2.cxx)
 // =======================================================================================================
 #include "budget_2.h"
+
+// =======================================================================================================
+// Cross: the planes of the cross-sections, lngrad, path and threshold heights (src/cross.cxx)
+// =======================================================================================================
+#include "cross.h"

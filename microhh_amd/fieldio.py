@@ -6,6 +6,10 @@ tooling and vice versa.
                  src/field3d_io.cxx:54-140 and :143-230; the MPI build writes the same global file through a
                  subarray view, which is what `rank`/`npy` reproduce here with positioned writes of each y-slab)
   grid.0000000   x, xh [itot], y, yh [jtot], z, zh [ktot] as raw TF (reader: cases/taylorgreen/taylorgreen_test.py:53-68)
+  name.xy.KKKKK.NNNNNNN, name.xz.JJJJJ.NNNNNNN, name.yz.IIIII.NNNNNNN, name.xy.NNNNNNN
+                 the cross-sections of Cross (src/cross.cxx:564-651): raw TF of ONE plane of interior cells, (jtot, itot), (kmax, itot),
+                 (kmax, jtot); the index is the global interior index. Created exclusively ("wbx", src/field3d_io.cxx:779-785): an
+                 existing file is an error. The MPI writers (:234-…) put the same global file together from the ranks' rows.
 
 Host-side only: arrays are numpy, ghosted (kcells, jcells, icells) like everything else in this package.
 """
@@ -104,3 +108,83 @@ def load_grid(path, itot, jtot, ktot, dtype=np.float64):
     for name, n in (("x", itot), ("xh", itot), ("y", jtot), ("yh", jtot), ("z", ktot), ("zh", ktot)):
         out[name] = raw[o:o+n].copy(); o += n
     return out
+
+
+# ---- cross-sections (Field3d_io::save_xy_slice / save_xz_slice / save_yz_slice, src/field3d_io.cxx:754-861; MPI forms :234-...) ----
+def cross_filename(path, name, kind, index, iotime):
+    """name.xy.%05d.%07d, name.xz..., name.yz... (Cross::cross_simple, src/cross.cxx:581-629); index None: the plane name.xy.%07d
+    of Cross::cross_plane (:647)."""
+    if index is None:
+        return os.path.join(path, "%s.%s.%07d" % (name, kind, iotime))
+    return os.path.join(path, "%s.%s.%05d.%07d" % (name, kind, index, iotime))
+
+
+def prepare_slice_file(filename, nbytes):
+    """Create the one global file of a slab-decomposed xy or yz section at its final size, exclusively (MPI_MODE_CREATE |
+    MPI_MODE_EXCL, src/field3d_io.cxx:329). ONE rank calls this ahead of a barrier, as with prepare_global_file."""
+    with open(filename, "xb") as f:
+        f.truncate(nbytes)
+    return nbytes
+
+
+def _rows(filename, shape, dtype):
+    nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
+    if not os.path.exists(filename) or os.path.getsize(filename) != nbytes:
+        raise FileNotFoundError("%s must be created at %d bytes (fieldio.prepare_slice_file) before the slab ranks write into it" % (filename, nbytes))
+    return np.memmap(filename, dtype=dtype, mode="r+", shape=shape)
+
+
+def _create(filename, a):
+    with open(filename, "xb") as f:                 # "wbx": FileExistsError where the file is there already
+        np.ascontiguousarray(a).tofile(f)
+
+
+def save_xy_slice(filename, plane, grid, rank=0, npy=1):
+    """plane: the packed interior (jmax, imax) of this rank, offset included. With npy > 1 every rank writes its rows into the
+    global (jtot, itot) file that one rank prepared."""
+    g = grid
+    a = np.asarray(plane, dtype=g.np_dtype).reshape(g.jmax, g.imax)
+    if npy == 1:
+        return _create(filename, a)
+    mm = _rows(filename, (g.jmax*npy, g.imax), g.np_dtype)
+    mm[rank*g.jmax:(rank+1)*g.jmax, :] = a
+    mm.flush()
+    del mm
+
+
+def save_xz_slice(filename, plane, grid):
+    """plane: (kmax, imax) of the row; on a slab the rank that owns the row is the one that calls this."""
+    a = np.asarray(plane, dtype=grid.np_dtype)
+    _create(filename, a.reshape(-1, grid.imax))
+
+
+def save_yz_slice(filename, plane, grid, rank=0, npy=1):
+    """plane: (kmax, jmax) of this rank's rows of the column; the global file is (kmax, jtot)."""
+    g = grid
+    a = np.asarray(plane, dtype=g.np_dtype).reshape(-1, g.jmax)
+    if npy == 1:
+        return _create(filename, a)
+    mm = _rows(filename, (a.shape[0], g.jmax*npy), g.np_dtype)
+    mm[:, rank*g.jmax:(rank+1)*g.jmax] = a
+    mm.flush()
+    del mm
+
+
+def _load_slice(filename, shape, dtype):
+    expect = int(np.prod(shape)) * np.dtype(dtype).itemsize
+    if os.path.getsize(filename) != expect:
+        raise ValueError("%s: %d bytes, expected %d for a %s %s section" % (filename, os.path.getsize(filename), expect, shape, np.dtype(dtype).name))
+    return np.fromfile(filename, dtype=dtype).reshape(shape)
+
+
+def load_xy_slice(filename, grid, npy=1):
+    """The global (jtot, itot) plane of an xy section."""
+    return _load_slice(filename, (grid.jmax*npy, grid.imax), grid.np_dtype)
+
+
+def load_xz_slice(filename, grid, kmax=None):
+    return _load_slice(filename, (grid.kmax if kmax is None else kmax, grid.imax), grid.np_dtype)
+
+
+def load_yz_slice(filename, grid, npy=1, kmax=None):
+    return _load_slice(filename, (grid.kmax if kmax is None else kmax, grid.jmax*npy), grid.np_dtype)

@@ -12,6 +12,7 @@
 // Header-only, C++17, no HIP or torch types: device memory is owned by the caller (Field3d::init_device,
 // src/field3d.cu:32-47) and travels as raw pointers.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdio>
@@ -1343,6 +1344,186 @@ class Budget_2_sampler
             stats.sum_ranks(d, n);
         }
         Grid<TF>& grid; Fields<TF>& fields; Stats_sampler<TF>& stats;
+};
+
+// ---- Cross (include/cross.h; src/cross.cxx) ---------------------------------------------------------------------------------
+// The cross-section files with the fields left on the device: the index lists of Cross::create (:323-460, mhh_cross_indices_host), a
+// staging buffer the planes of one call are packed into (one launch), ONE copy of it to the host, and the slice writers of
+// src/field3d_io.cxx (:754-861; the MPI forms :234-...): exclusive creation ("wbx"), the global file on a slab. Every `data` is a
+// DEVICE pointer. The memory is the caller's: staging_g [staging_elems()] of TF on the device; to_host copies device memory to the
+// host (hipMemcpy, device to host) after synchronising the stream. A slab rank (npy > 1) needs barrier, and the filled north halo
+// of a field whose half-level xz row jtot is asked for; lngrad needs the filled ghost cells of its field.
+enum class Cross_direction { Top_to_bottom, Bottom_to_top };
+template<typename TF>
+class Cross_sampler
+{
+    public:
+        Cross_sampler(Grid<TF>& grid_in, Fields<TF>& fields_in, const std::string& path_in = ".") : grid(grid_in), fields(fields_in), path(path_in) {}
+        std::vector<TF> xy, xz, yz;                                  // [cross] xy, xz, yz: heights, y and x locations
+        std::vector<int> kxy, kxyh, jxz, jxzh, ixz, ixzh;            // global interior indices, full and half
+        TF* staging_g = nullptr;
+        std::function<void(void*, const void*, size_t)> to_host;
+        std::function<void()> barrier;
+
+        // Cross::create (:323-460): a location outside the domain throws, and the message names it
+        void create()
+        {
+            mhh_grid g = grid.abi(true);
+            auto run = [&](int kind, const std::vector<TF>& loc, std::vector<int>& full, std::vector<int>& half)
+            {
+                std::vector<double> l(loc.begin(), loc.end());
+                full.assign(loc.size(), 0); half.assign(loc.size(), 0);
+                int nf = 0, nh = 0;
+                mhh_check(mhh_cross_indices_host(&g, kind, l.data(), (int)l.size(), full.data(), &nf, half.data(), &nh));
+                full.resize(nf); half.resize(nh);
+            };
+            run(MHH_CROSS_XY, xy, kxy, kxyh); run(MHH_CROSS_XZ, xz, jxz, jxzh); run(MHH_CROSS_YZ, yz, ixz, ixzh);
+        }
+        // the planes of the largest call: every section of one variable
+        size_t staging_elems() const
+        {
+            const auto& gd = grid.gd;
+            const size_t nj = std::max(jxz.size(), jxzh.size()), ni = std::max(ixz.size(), ixzh.size()), nk = std::max(kxy.size(), kxyh.size());
+            return std::max<size_t>(1, nj*gd.kmax*gd.imax + ni*gd.kmax*gd.jmax + nk*gd.jmax*gd.imax) + (size_t)gd.jmax*gd.imax;
+        }
+
+        // Cross::cross_simple (:564-636); loc = {1,0,0} u, {0,1,0} v, {0,0,1} w: the half-level list of that direction
+        int cross_simple(const TF* data, TF offset, const std::string& name, int iotime, const std::array<int,3>& loc, void* stream = nullptr)
+        {
+            return sections(data, offset, name, iotime, 0, loc[1] ? jxzh : jxz, loc[0] ? ixzh : ixz, loc[2] ? kxyh : kxy, stream);
+        }
+        // Cross::cross_lngrad (:653-703): order 2 calc_lngrad_2nd, 4 calc_lngrad_4th, on the cells of the sections alone
+        int cross_lngrad(const TF* a, const std::string& name, int iotime, int order, void* stream = nullptr)
+        {
+            return sections(a, TF(0), name, iotime, order, jxz, ixz, kxy, stream);
+        }
+        // Cross::cross_plane (:638-651): data is a 2-D array [ijcells]
+        int cross_plane(const TF* data, TF offset, const std::string& name, int iotime, void* stream = nullptr)
+        {
+            mhh_grid g = grid.abi();
+            mhh_cross_job j{}; j.fld = data; j.kind = MHH_CROSS_PLANE; j.offset = offset; j.out = staging_g;
+            mhh_check(mhh_cross_gather(&g, &j, 1, stream));
+            return write_plane(name, iotime);
+        }
+        // Cross::cross_path (:705-725)
+        int cross_path(const TF* data, const std::string& name, int iotime, void* stream = nullptr)
+        {
+            mhh_grid g = grid.abi();
+            mhh_check(mhh_cross_path(&g, data, fields.rhoref_g, staging_g, stream));
+            return write_plane(name, iotime);
+        }
+        // Cross::cross_height_threshold (:738-760)
+        int cross_height_threshold(const TF* data, TF threshold, Cross_direction direction, const std::string& name, int iotime, void* stream = nullptr)
+        {
+            mhh_grid g = grid.abi();
+            mhh_check(mhh_cross_height_threshold(&g, data, threshold, direction == Cross_direction::Bottom_to_top, staging_g, stream));
+            return write_plane(name, iotime);
+        }
+
+    private:
+        std::string filename(const std::string& name, const char* sect, int index, int iotime) const
+        {
+            char buf[512];
+            if (index < 0) std::snprintf(buf, sizeof(buf), "%s/%s.%s.%07d", path.c_str(), name.c_str(), sect, iotime);
+            else           std::snprintf(buf, sizeof(buf), "%s/%s.%s.%05d.%07d", path.c_str(), name.c_str(), sect, index, iotime);
+            return buf;
+        }
+        void fetch(size_t n)
+        {
+            if (!to_host) throw std::runtime_error("Cross: to_host, the copy of device memory to the host, is not set");
+            host.resize(n);
+            to_host(host.data(), staging_g, n*sizeof(TF));
+        }
+        void meet() const
+        {
+            if (grid.gd.npy == 1) return;
+            if (!barrier) throw std::runtime_error("Cross: a slab rank (npy > 1) needs barrier");
+            barrier();
+        }
+        // One file written by this rank alone, exclusively ("wbx", src/field3d_io.cxx:779-785)
+        static int write_own(const std::string& fn, const TF* data, size_t n)
+        {
+            FILE* f = std::fopen(fn.c_str(), "wbx");
+            if (!f) return 1;
+            int nerror = (std::fwrite(data, sizeof(TF), n, f) != n);
+            if (std::fclose(f)) ++nerror;
+            return nerror;
+        }
+        // One global file of rows x (cols per rank) x npy: rank 0 creates it exclusively and writes its share, the others follow after
+        // a barrier (MPI_File_open with MPI_MODE_CREATE | MPI_MODE_EXCL and the subarray view, :320-350)
+        int write_shared(const std::string& fn, const TF* data, int rows, int cols, bool split_rows)
+        {
+            const auto& gd = grid.gd;
+            if (gd.npy == 1) return write_own(fn, data, (size_t)rows*cols);
+            int nerror = 0;
+            auto put = [&](const char* mode)
+            {
+                FILE* f = std::fopen(fn.c_str(), mode);
+                if (!f) { ++nerror; return; }
+                if (split_rows)                 // xy: [jtot][itot], this rank's rows in one piece
+                {
+                    if (std::fseek(f, (long)((size_t)gd.mpicoordy*rows*cols*sizeof(TF)), SEEK_SET) || std::fwrite(data, sizeof(TF), (size_t)rows*cols, f) != (size_t)rows*cols) ++nerror;
+                }
+                else                            // yz: [kmax][jtot], this rank's columns of every row
+                    for (int r=0; r<rows && !nerror; ++r)
+                        if (std::fseek(f, (long)(((size_t)r*cols*gd.npy + (size_t)gd.mpicoordy*cols)*sizeof(TF)), SEEK_SET) ||
+                            std::fwrite(data + (size_t)r*cols, sizeof(TF), cols, f) != (size_t)cols) ++nerror;
+                if (std::fclose(f)) ++nerror;
+            };
+            if (gd.mpicoordy == 0) put("wbx");
+            meet();
+            if (gd.mpicoordy != 0) put("r+b");
+            meet();
+            return nerror;
+        }
+        int write_plane(const std::string& name, int iotime)
+        {
+            const auto& gd = grid.gd;
+            fetch((size_t)gd.jmax*gd.imax);
+            return write_shared(filename(name, "xy", -1, iotime), host.data(), gd.jmax, gd.imax, true);
+        }
+        int sections(const TF* data, TF offset, const std::string& name, int iotime, int order, const std::vector<int>& jlist, const std::vector<int>& ilist,
+                     const std::vector<int>& klist, void* stream)
+        {
+            const auto& gd = grid.gd;
+            mhh_grid g = grid.abi();
+            std::vector<mhh_cross_job> jobs; std::vector<long long> jpos(jlist.size(), -1);
+            size_t pos = 0;
+            auto add = [&](int kind, int index, size_t cells)
+            {
+                mhh_cross_job j{}; j.fld = data; j.kind = kind; j.index = index; j.k0 = gd.kstart; j.k1 = gd.kend; j.offset = offset; j.out = staging_g + pos;
+                jobs.push_back(j); pos += cells;
+            };
+            const int jtot = gd.jmax*gd.npy;
+            for (size_t n=0; n<jlist.size(); ++n)
+            {
+                // the row's owner; the half-level row jtot is the cyclic image of row 0: the last rank's north ghost row
+                const bool top = (jlist[n] == jtot);
+                if ((top ? gd.npy - 1 : jlist[n]/gd.jmax) != gd.mpicoordy) continue;
+                jpos[n] = (long long)pos;
+                add(MHH_CROSS_XZ, top ? gd.jend : jlist[n] % gd.jmax + gd.jgc, (size_t)gd.kmax*gd.imax);
+            }
+            const size_t ipos = pos;
+            for (int i : ilist) add(MHH_CROSS_YZ, i % gd.imax + gd.igc, (size_t)gd.kmax*gd.jmax);
+            const size_t kpos = pos;
+            for (int k : klist) add(MHH_CROSS_XY, k + gd.kgc, (size_t)gd.jmax*gd.imax);
+            if (!jobs.empty())
+            {
+                if (order == 0) mhh_check(mhh_cross_gather(&g, jobs.data(), (int)jobs.size(), stream));
+                else            mhh_check(mhh_cross_lngrad(&g, order, jobs.data(), (int)jobs.size(), stream));
+                fetch(pos);
+            }
+            int nerror = 0;
+            for (size_t n=0; n<jlist.size(); ++n)
+                if (jpos[n] >= 0) nerror += write_own(filename(name, "xz", jlist[n], iotime), host.data() + jpos[n], (size_t)gd.kmax*gd.imax);
+            for (size_t n=0; n<ilist.size(); ++n)
+                nerror += write_shared(filename(name, "yz", ilist[n], iotime), host.data() + ipos + n*(size_t)gd.kmax*gd.jmax, gd.kmax, gd.jmax, false);
+            for (size_t n=0; n<klist.size(); ++n)
+                nerror += write_shared(filename(name, "xy", klist[n], iotime), host.data() + kpos + n*(size_t)gd.jmax*gd.imax, gd.jmax, gd.imax, true);
+            return nerror;
+        }
+        Grid<TF>& grid; Fields<TF>& fields; std::string path;
+        std::vector<TF> host;
 };
 
 } // namespace mhh_host

@@ -111,7 +111,7 @@ class HotPath:
 
     def __init__(self, case, itot, jtot, ktot, dtype=np.float64, device="cuda:0", seed=666, dt=1.0,
                  lib=None, npy=1, rank=0, group=None, global_init=None, force_slab=False, slim_halos=True, overlap=None, pres_chunks=None, igc=None,
-                 nscalars=None, forcing=None, surface=None, thermo=None, micro=None, radiation=None, stats=None, budget=None):
+                 nscalars=None, forcing=None, surface=None, thermo=None, micro=None, radiation=None, stats=None, budget=None, cross=None):
         import torch
         if budget is not None and stats is None:
             raise ValueError("budget= needs stats=Stats(...): the budget profiles are averaged under the masks of the statistics")
@@ -281,6 +281,8 @@ class HotPath:
         self.stats = stats.bind(self) if stats is not None else None
         # Budget_2 (budget.Budget2): the budget group of the statistics, sampled with them after Stats' own passes
         self.budget = budget.bind(self) if budget is not None else None
+        # Cross (cross.Cross): the index lists, the job table and the staging buffers; sampled outside the step by hp.cross.sample(iotime)
+        self.cross = cross.bind(self) if cross is not None else None
         self.cyclic_prognostic()
         self.sync()
 
