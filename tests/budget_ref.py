@@ -9,21 +9,16 @@ not write and a model-profile level without a cell are 0. Grid::interpolate_2nd 
 reached without an object: one expression, restated here in float64 (what its double literals make of it) and narrowed once.
 """
 import ctypes as C
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 import common as cm
-import moist_ref as M
+import refshim
 import stats_ref as R
+from refshim import Dims, code, dims_of, f32exact, tag
 from microhh_amd import budget as B
 from microhh_amd import stats as S
 
-GOLDEN = os.path.join(cm.ROOT, "tests", "golden", "budget_ref.npz")
-RECORD = os.environ.get("MHH_RECORD_BUDGET_GOLDEN") == "1"
 MASKS = R.MASKS
 # (shape, ghost cells, kind): the second ghost layout; 37 rows make two row chunks, the second partial; the exact fixture
 LAYOUTS = [((17, 9, 8), (2, 2, 1), "seeded"), ((17, 9, 8), (3, 3, 1), "seeded"), ((24, 37, 8), (2, 2, 1), "seeded")]
@@ -78,21 +73,18 @@ class BudgetCase:
             f["evisc"] = (rs.randint(1, 8, size=n3)/4.).astype(np.float64)
             f["u_fluxbot"], f["v_fluxbot"] = q4(n2, -1, 1), q4(n2, -1, 1)
         else:
-            f["u"] = R.f32exact(2. + 0.3*lev + (rs.random_sample(n3) - 0.5))
-            f["v"] = R.f32exact(-1. + 0.2*lev + (rs.random_sample(n3) - 0.5))
-            f["w"] = R.f32exact(rs.random_sample(n3) - 0.5)
-            f["p"] = R.f32exact(5.*(rs.random_sample(n3) - 0.5))
-            f["evisc"] = R.f32exact(0.05 + rs.random_sample(n3))
-            f["b"] = R.f32exact(0.1*lev + 0.5*(rs.random_sample(n3) - 0.5))
-            f["u_fluxbot"] = R.f32exact(0.1*(rs.random_sample(n2) - 0.5))
-            f["v_fluxbot"] = R.f32exact(0.1*(rs.random_sample(n2) - 0.5))
+            f["u"] = f32exact(2. + 0.3*lev + (rs.random_sample(n3) - 0.5))
+            f["v"] = f32exact(-1. + 0.2*lev + (rs.random_sample(n3) - 0.5))
+            f["w"] = f32exact(rs.random_sample(n3) - 0.5)
+            f["p"] = f32exact(5.*(rs.random_sample(n3) - 0.5))
+            f["evisc"] = f32exact(0.05 + rs.random_sample(n3))
+            f["b"] = f32exact(0.1*lev + 0.5*(rs.random_sample(n3) - 0.5))
+            f["u_fluxbot"] = f32exact(0.1*(rs.random_sample(n2) - 0.5))
+            f["v_fluxbot"] = f32exact(0.1*(rs.random_sample(n2) - 0.5))
         self.f = f
 
     def digest(self):
-        h = hashlib.sha256()
-        for k in sorted(self.f):
-            h.update(np.ascontiguousarray(self.f[k], dtype=np.float64).tobytes())
-        return h.hexdigest()
+        return refshim.digest(*[np.asarray(self.f[k], dtype=np.float64) for k in sorted(self.f)])
 
     def host(self, g):
         """Host arrays of grid g's dtype and layout with the horizontal ghost cells filled periodically."""
@@ -114,29 +106,13 @@ def case_of(shape, kind):
 
 
 # ---- the shim ---------------------------------------------------------------------------------------------------------------
-_shim = {}
+def _bind(lib):
+    VPP = C.POINTER(C.c_void_p)
+    lib.ref_budget_2_group.argtypes = [C.c_int, C.POINTER(Dims), C.c_int, VPP, VPP, VPP, C.POINTER(C.c_double)]
+    lib.ref_budget_2_group.restype = None
 
 
-def shim():
-    """tests/cpp/ref_budget_2_shim.cpp compiled like stats_ref's shims; None without the reference tree."""
-    if "lib" not in _shim:
-        if not R.have_reference():
-            _shim["lib"] = None
-        else:
-            _shim["tmp"] = tempfile.TemporaryDirectory()
-            so = os.path.join(_shim["tmp"].name, "libref_budget_2.so")
-            src = os.path.join(R.REF_ROOT, "src")
-            subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-DRESTRICTKEYWORD=__restrict__",
-                            "-DNC_FILL_DOUBLE=9.9692099683868690e+36", "-DNC_FILL_FLOAT=9.9692099683868690e+36f", "-I" + M.REF_INC, "-I" + src,
-                            "-I" + os.path.join(cm.ROOT, "tests", "stubs_syntax_only"),
-                            "-fPIC", "-shared", "-fvisibility=hidden", "-ffunction-sections", "-fdata-sections", "-Wl,--gc-sections", "-o", so,
-                            os.path.join(cm.ROOT, "tests", "cpp", "ref_budget_2_shim.cpp")], check=True)
-            lib = C.CDLL(so)
-            VPP = C.POINTER(C.c_void_p)
-            lib.ref_budget_2_group.argtypes = [C.c_int, C.POINTER(M.Dims), C.c_int, VPP, VPP, VPP, C.POINTER(C.c_double)]
-            lib.ref_budget_2_group.restype = None
-            _shim["lib"] = lib
-    return _shim["lib"]
+shim = refshim.Shim("budget_2", ["ref_budget_2_shim.cpp"], _bind, defines=refshim.NC_FILL, stubs=True)
 
 
 def _ptrs(arrays):
@@ -161,7 +137,7 @@ def interp_w(w, g, axis):
 
 def ref_masks(c, g):
     """The mask words after the thresholds and the cyclic fill, and nmask[mask][2][kcells], as stats_ref.ref_case makes them."""
-    lib, h, d, cd = R.shim(), c.stat.host(g), M.dims_of(g), R.code(g.np_dtype)
+    lib, h, d, cd = R.shim(), c.stat.host(g), dims_of(g), code(g.np_dtype)
     nm = len(MASKS)
     flagmax = np.uint32(sum(int(f) for n in range(nm) for f in R.flags(n)))
     mf, mb = np.full(g.shape3, flagmax, dtype=np.uint32), np.full(g.shape2, flagmax, dtype=np.uint32)
@@ -182,10 +158,10 @@ def ref_masks(c, g):
 def mean_all(g, fld, mf, flag, nmk):
     """calc_mean over 0 .. kcells-1 (Stats::calc_mask_mean_profile, src/stats.cxx:1328-1347) into a zeroed profile: a level
     without a cell keeps 0."""
-    d = M.dims_of(g)
+    d = dims_of(g)
     d.kstart, d.kend = 0, g.kcells - 1
     p = np.zeros(g.kcells, dtype=g.np_dtype)
-    R.shim().ref_stats_prof(R.code(g.np_dtype), C.byref(d), 0, cm.ptr(p), cm.ptr(fld), None, 0., 0., cm.ptr(mf), int(flag), cm.ptr(np.ascontiguousarray(nmk)))
+    R.shim().ref_stats_prof(code(g.np_dtype), C.byref(d), 0, cm.ptr(p), cm.ptr(fld), None, 0., 0., cm.ptr(mf), int(flag), cm.ptr(np.ascontiguousarray(nmk)))
     p[np.asarray(nmk) == 0] = 0
     return p
 
@@ -211,7 +187,7 @@ def cube_scale(g, h, wm, k):
 def term_fields(g, h, um, vm, wm, bmean, pmean, par, groups=None):
     """The reference's term FIELDS of one mask over zero-filled tmp fields: yields (name, [kcells][jcells][icells]). h: host arrays
     u, v, w, p, evisc, b, u_fluxbot, v_fluxbot of grid g with their cyclic ghost cells; the profiles of the grid's dtype."""
-    lib, t, d, cd = shim(), g.np_dtype, M.dims_of(g), R.code(g.np_dtype)
+    lib, t, d, cd = shim(), g.np_dtype, dims_of(g), code(g.np_dtype)
     wx, wy = interp_w(h["w"], g, 2), interp_w(h["w"], g, 1)
     pars = (C.c_double*5)(par["utrans"], par["vtrans"], par["fc"], float(t.type(1.)/t.type(g.dx)), float(t.type(1.)/t.type(g.dy)))
     inp = _ptrs([np.ascontiguousarray(h[n]) for n in ("u", "v", "w", "p", "evisc", "b", "u_fluxbot", "v_fluxbot")] + [wx, wy])
@@ -229,7 +205,7 @@ def term_fields(g, h, um, vm, wm, bmean, pmean, par, groups=None):
 def ref_case(shape, gc, dtype, kind):
     """Everything the reference gives on one case: {key: array}."""
     c, g = case_of(shape, kind), grid_of(shape, gc, dtype, kind)
-    h, d, cd, t = c.host(g), M.dims_of(g), R.code(dtype), g.np_dtype
+    h, d, cd, t = c.host(g), dims_of(g), code(dtype), g.np_dtype
     nm, kc = len(MASKS), g.kcells
     js, ie = slice(g.jstart, g.jend), slice(g.istart, g.iend)
     mf, nmask = ref_masks(c, g)
@@ -271,10 +247,7 @@ def all_cases():
 
 
 def case_key(shape, gc, dtype, kind):
-    return "%s/%d%d%d/%s/" % (case_of(shape, kind).key, gc[0], gc[1], gc[2], R.tag(dtype))
-
-
-_all, _golden = {}, {}
+    return "%s/%d%d%d/%s/" % (case_of(shape, kind).key, gc[0], gc[1], gc[2], tag(dtype))
 
 
 def _compute_all():
@@ -287,32 +260,13 @@ def _compute_all():
     return rec
 
 
-def golden():
-    if "z" not in _golden:
-        _golden["z"] = np.load(GOLDEN) if os.path.exists(GOLDEN) else None
-    return _golden["z"]
-
-
-def computed():
-    if "rec" not in _all:
-        _all["rec"] = _compute_all() if R.have_reference() else None
-    return _all["rec"]
+GOLD = refshim.Golden("budget", _compute_all, "tests/test_budget_terms.py")
+RECORD, golden, computed, record_if_asked = GOLD.record, GOLD.golden, GOLD.computed, GOLD.record_if_asked
 
 
 def ref(shape, gc, dtype, kind, name, be=None):
-    """A reference result by name: from the shim on this host, else (and always on the GPU backend) from the golden file."""
-    key = case_key(shape, gc, dtype, kind) + name
-    if R.have_reference() and (be is None or be.name == "emul") and not RECORD:
-        return computed()[key]
-    z = golden()
-    assert z is not None, "tests/golden/budget_ref.npz is missing: record it where the reference tree exists"
-    return z[key]
-
-
-def record_if_asked():
-    if RECORD:
-        np.savez_compressed(GOLDEN, **_compute_all())
-        _golden.clear()
+    """A reference result by name (Golden.ref)."""
+    return GOLD.ref(case_key(shape, gc, dtype, kind) + name, be)
 
 
 def bound(g, want, scale, cube=None):

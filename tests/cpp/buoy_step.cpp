@@ -7,7 +7,7 @@
 //   3. the overlapped slab sub-step Substep_slab::halo_visc_rhs (mhh_host_rccl.h) on a one-rank RCCL communicator against the
 //      single-GPU sub-step, within 1e-10 of the largest value.
 // Exit status 0 and "buoy_step ok" on success.
-#include <hip/hip_runtime.h>
+#include "host_prog.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -20,9 +20,6 @@
 using namespace mhh_host;
 typedef double TF;
 
-#define HIPCHK(x) do { hipError_t e = (x); if (e != hipSuccess) { std::fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e)); std::exit(2); } } while (0)
-
-static TF* up(const std::vector<TF>& v) { TF* d; HIPCHK(hipMalloc(&d, v.size()*sizeof(TF))); HIPCHK(hipMemcpy(d, v.data(), v.size()*sizeof(TF), hipMemcpyHostToDevice)); return d; }
 static std::vector<TF> dn(const TF* d, size_t n) { std::vector<TF> v(n); HIPCHK(hipMemcpy(v.data(), d, n*sizeof(TF), hipMemcpyDeviceToHost)); return v; }
 
 struct Lcg

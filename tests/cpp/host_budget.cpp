@@ -6,43 +6,26 @@
 // Masks default, wpos (w > 0 on both levels, Plus), wneg (Min). Every group, diff_smag2.
 // OUT, per mask: umodel vmodel wmodel, then every profile in the order of mhh_budget_2_prof_name [kcells each].
 // gc = (3, 3, 1), second order, double.
-#include <hip/hip_runtime.h>
-#include <cstdio>
-#include <cstdlib>
-#include <iostream>
-#include "../../microhh_amd/host/mhh_host.h"
+#include "host_prog.h"
 
 using namespace mhh_host;
 typedef double TF;
-#define HIPCHK(x) do { hipError_t e = (x); if (e != hipSuccess) { std::fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e)); std::exit(2); } } while (0)
-static TF* up(const std::vector<TF>& v) { TF* d; HIPCHK(hipMalloc(&d, v.size()*sizeof(TF))); HIPCHK(hipMemcpy(d, v.data(), v.size()*sizeof(TF), hipMemcpyHostToDevice)); return d; }
-template<class T> static T* dev(size_t n) { T* d; HIPCHK(hipMalloc(&d, n*sizeof(T))); HIPCHK(hipMemset(d, 0, n*sizeof(T))); return d; }
 
 int main(int argc, char** argv)
 {
-    if (argc != 9) { std::fprintf(stderr, "usage\n"); return 3; }
-    try
+    return run_main(argc, argv, 9, [&]() -> int
     {
         Grid<TF> grid; auto& gd = grid.gd;
-        gd.itot = std::atoi(argv[3]); gd.jtot = std::atoi(argv[4]); gd.ktot = std::atoi(argv[5]); gd.igc = gd.jgc = 3; gd.kgc = 1;
-        gd.imax = gd.itot; gd.jmax = gd.jtot; gd.kmax = gd.ktot;
-        gd.icells = gd.itot + 6; gd.jcells = gd.jtot + 6; gd.kcells = gd.ktot + 2; gd.ijcells = gd.icells*gd.jcells; gd.ncells = gd.ijcells*gd.kcells;
-        gd.istart = gd.jstart = 3; gd.kstart = 1; gd.iend = 3 + gd.itot; gd.jend = 3 + gd.jtot; gd.kend = 1 + gd.ktot;
-        gd.xsize = gd.ysize = 3200.; gd.zsize = 1200.; gd.dx = gd.xsize/gd.itot; gd.dy = gd.ysize/gd.jtot;
+        make_grid(grid, std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]), 3, 3, 1, 3200., 3200., 1200.);
         const size_t nk = gd.kcells, n3 = gd.ncells, n2 = gd.ijcells;
-        FILE* in = std::fopen(argv[1], "rb");
-        if (!in) return 4;
-        auto rd = [&](size_t n) { std::vector<TF> v(n); if (std::fread(v.data(), sizeof(TF), n, in) != n) { std::fprintf(stderr, "short input\n"); std::exit(4); } return v; };
+        Reader rd(argv[1]);
         Fields<TF> fields;
         for (const char* n : {"u", "v", "w"}) { auto f = std::make_shared<Field3d<TF>>(); f->fld_g = up(rd(n3)); fields.mp[n] = f; }
         for (const char* n : {"p", "evisc"}) { auto f = std::make_shared<Field3d<TF>>(); f->fld_g = up(rd(n3)); fields.sd[n] = f; }
         TF* b = up(rd(n3));
         fields.mp.at("u")->flux_bot_g = up(rd(n2)); fields.mp.at("v")->flux_bot_g = up(rd(n2));
-        for (std::vector<TF>* v : {&gd.z, &gd.zh, &gd.dz, &gd.dzh, &gd.dzi, &gd.dzhi}) *v = rd(nk);
-        gd.dzi4.assign(nk, 0); gd.dzhi4.assign(nk, 0);
-        std::fclose(in);
-        gd.z_g = up(gd.z); gd.zh_g = up(gd.zh); gd.dz_g = up(gd.dz); gd.dzh_g = up(gd.dzh); gd.dzi_g = up(gd.dzi); gd.dzhi_g = up(gd.dzhi);
-        gd.dzi4_g = up(gd.dzi4); gd.dzhi4_g = up(gd.dzhi4);
+        read_metrics(grid, rd);
+        rd.close();
 
         Stats_sampler<TF> stats(grid, fields);
         const char* masks[3] = {"default", "wpos", "wneg"};
@@ -72,18 +55,14 @@ int main(int argc, char** argv)
             if (!refused) return 7;
         }
 
-        FILE* out = std::fopen(argv[2], "wb");
-        if (!out) return 4;
-        auto wr = [&](const TF* d, size_t n) { std::vector<TF> v(n); HIPCHK(hipMemcpy(v.data(), d, n*sizeof(TF), hipMemcpyDeviceToHost));
-                                               if (std::fwrite(v.data(), sizeof(TF), n, out) != n) std::exit(4); };
+        Writer wr(argv[2]);
         for (const char* m : masks)
         {
             for (int i=0; i<3; ++i) wr(budget.get_model(i, m), nk);
             for (int n=0; n<budget.nprofs(); ++n) wr(budget.get_prof(m, mhh_budget_2_prof_name(budget.groups, n, nullptr)), nk);
         }
-        std::fclose(out);
+        wr.close();
         std::printf("host_budget ok\n");
-    }
-    catch (const std::exception& e) { std::cerr << "EXCEPTION: " << e.what() << std::endl; return 5; }
-    return 0;
+        return 0;
+    });
 }

@@ -6,36 +6,21 @@
 // exec(thermo, dt), Limiter::exec(subdt) for qr and nr, get_time_limit(idt, dt). OUT: qr nr thlt qtt qrt nrt [ncells each], rr_bot
 // [ijcells], the time limit as a double.
 // gc = (3, 3, 1), second order, double, the domain of rico (12800 x 12800 x 4000 m).
-#include <hip/hip_runtime.h>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <iostream>
-#include "../../microhh_amd/host/mhh_host.h"
+#include "host_prog.h"
 
 using namespace mhh_host;
 typedef double TF;
-#define HIPCHK(x) do { hipError_t e = (x); if (e != hipSuccess) { std::fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e)); std::exit(2); } } while (0)
-static TF* up(const std::vector<TF>& v) { TF* d; HIPCHK(hipMalloc(&d, v.size()*sizeof(TF))); HIPCHK(hipMemcpy(d, v.data(), v.size()*sizeof(TF), hipMemcpyHostToDevice)); return d; }
-template<class T> static T* dev(size_t n) { T* d; HIPCHK(hipMalloc(&d, n*sizeof(T))); HIPCHK(hipMemset(d, 0, n*sizeof(T))); return d; }
 
 int main(int argc, char** argv)
 {
-    if (argc != 10) { std::fprintf(stderr, "usage\n"); return 3; }
-    try
+    return run_main(argc, argv, 10, [&]() -> int
     {
         Grid<TF> grid; auto& gd = grid.gd;
-        gd.itot = std::atoi(argv[3]); gd.jtot = std::atoi(argv[4]); gd.ktot = std::atoi(argv[5]); gd.igc = gd.jgc = 3; gd.kgc = 1;
-        gd.imax = gd.itot; gd.jmax = gd.jtot; gd.kmax = gd.ktot;
-        gd.icells = gd.itot + 6; gd.jcells = gd.jtot + 6; gd.kcells = gd.ktot + 2; gd.ijcells = gd.icells*gd.jcells; gd.ncells = gd.ijcells*gd.kcells;
-        gd.istart = gd.jstart = 3; gd.kstart = 1; gd.iend = 3 + gd.itot; gd.jend = 3 + gd.jtot; gd.kend = 1 + gd.ktot;
-        gd.xsize = gd.ysize = 12800.; gd.zsize = 4000.; gd.dx = gd.xsize/gd.itot; gd.dy = gd.ysize/gd.jtot;
+        make_grid(grid, std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]), 3, 3, 1, 12800., 12800., 4000.);
         const size_t nk = gd.kcells, n3 = gd.ncells, n2 = gd.ijcells;
         const double Nc0 = std::atof(argv[6]), dt = std::atof(argv[7]), subdt = std::atof(argv[8]);
         const unsigned long idt = std::strtoul(argv[9], nullptr, 10);
-        FILE* in = std::fopen(argv[1], "rb");
-        if (!in) return 4;
-        auto rd = [&](size_t n) { std::vector<TF> v(n); if (std::fread(v.data(), sizeof(TF), n, in) != n) { std::fprintf(stderr, "short input\n"); std::exit(4); } return v; };
+        Reader rd(argv[1]);
         Fields<TF> fields;
         auto mk = [&]() { auto f = std::make_shared<Field3d<TF>>(); f->fld_g = up(rd(n3)); return f; };
         for (const char* n : {"thl", "qt", "qr", "nr"}) fields.sp[n] = mk();
@@ -43,11 +28,8 @@ int main(int argc, char** argv)
         Thermo_moist<TF> thermo(grid, fields);
         thermo.pref_g = up(rd(nk)); thermo.exnref_g = up(rd(nk)); fields.rhoref_g = up(rd(nk));
         thermo.nonconv_g = dev<int>(1);
-        for (std::vector<TF>* v : {&gd.z, &gd.zh, &gd.dz, &gd.dzh, &gd.dzi, &gd.dzhi}) *v = rd(nk);
-        gd.dzi4.assign(nk, 0); gd.dzhi4.assign(nk, 0);
-        std::fclose(in);
-        gd.z_g = up(gd.z); gd.zh_g = up(gd.zh); gd.dz_g = up(gd.dz); gd.dzh_g = up(gd.dzh); gd.dzi_g = up(gd.dzi); gd.dzhi_g = up(gd.dzhi);
-        gd.dzi4_g = up(gd.dzi4); gd.dzhi4_g = up(gd.dzhi4);
+        read_metrics(grid, rd);
+        rd.close();
 
         Microphys_2mom_warm<TF> micro(grid, fields);
         micro.Nc0 = Nc0;
@@ -68,18 +50,13 @@ int main(int argc, char** argv)
         HIPCHK(hipDeviceSynchronize());
         int nonconv = 0; HIPCHK(hipMemcpy(&nonconv, thermo.nonconv_g, sizeof(int), hipMemcpyDeviceToHost));
         if (nonconv) return 8;
-        FILE* out = std::fopen(argv[2], "wb");
-        if (!out) return 4;
-        auto wr = [&](const TF* d, size_t n) { std::vector<TF> v(n); HIPCHK(hipMemcpy(v.data(), d, n*sizeof(TF), hipMemcpyDeviceToHost));
-                                               if (std::fwrite(v.data(), sizeof(TF), n, out) != n) std::exit(4); };
+        Writer wr(argv[2]);
         wr(fields.sp["qr"]->fld_g, n3); wr(fields.sp["nr"]->fld_g, n3);
         for (const char* n : {"thl", "qt", "qr", "nr"}) wr(fields.st[n]->fld_g, n3);
         wr(micro.rr_bot_g, n2);
-        const double lim = (double)limit;
-        if (std::fwrite(&lim, sizeof(double), 1, out) != 1) return 4;
-        std::fclose(out);
+        wr.host({(double)limit});
+        wr.close();
         std::printf("host_micro ok\n");
-    }
-    catch (const std::exception& e) { std::cerr << "EXCEPTION: " << e.what() << std::endl; return 5; }
-    return 0;
+        return 0;
+    });
 }

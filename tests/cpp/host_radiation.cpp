@@ -5,36 +5,21 @@
 // IN: thl qt thlt [ncells each], then pref exnref rhoref [kcells each], then z zh dz dzh dzi dzhi [kcells each].
 // exec(thermo, day_of_year), get_radiation_field for lflx and sflx. OUT: thlt lflx sflx [ncells each], mu as a double.
 // gc = (3, 3, 1), second order, double, the domain of dycoms (6400 x 6400 x 1500 m).
-#include <hip/hip_runtime.h>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <iostream>
-#include "../../microhh_amd/host/mhh_host.h"
+#include "host_prog.h"
 
 using namespace mhh_host;
 typedef double TF;
-#define HIPCHK(x) do { hipError_t e = (x); if (e != hipSuccess) { std::fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e)); std::exit(2); } } while (0)
-static TF* up(const std::vector<TF>& v) { TF* d; HIPCHK(hipMalloc(&d, v.size()*sizeof(TF))); HIPCHK(hipMemcpy(d, v.data(), v.size()*sizeof(TF), hipMemcpyHostToDevice)); return d; }
-template<class T> static T* dev(size_t n) { T* d; HIPCHK(hipMalloc(&d, n*sizeof(T))); HIPCHK(hipMemset(d, 0, n*sizeof(T))); return d; }
 
 int main(int argc, char** argv)
 {
-    if (argc != 13) { std::fprintf(stderr, "usage\n"); return 3; }
-    try
+    return run_main(argc, argv, 13, [&]() -> int
     {
         Grid<TF> grid; auto& gd = grid.gd;
-        gd.itot = std::atoi(argv[3]); gd.jtot = std::atoi(argv[4]); gd.ktot = std::atoi(argv[5]); gd.igc = gd.jgc = 3; gd.kgc = 1;
-        gd.imax = gd.itot; gd.jmax = gd.jtot; gd.kmax = gd.ktot;
-        gd.icells = gd.itot + 6; gd.jcells = gd.jtot + 6; gd.kcells = gd.ktot + 2; gd.ijcells = gd.icells*gd.jcells; gd.ncells = gd.ijcells*gd.kcells;
-        gd.istart = gd.jstart = 3; gd.kstart = 1; gd.iend = 3 + gd.itot; gd.jend = 3 + gd.jtot; gd.kend = 1 + gd.ktot;
-        gd.xsize = gd.ysize = 6400.; gd.zsize = 1500.; gd.dx = gd.xsize/gd.itot; gd.dy = gd.ysize/gd.jtot;
+        make_grid(grid, std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]), 3, 3, 1, 6400., 6400., 1500.);
         gd.lat = std::atof(argv[10]); gd.lon = std::atof(argv[11]);
         const double day_of_year = std::atof(argv[12]);
         const size_t nk = gd.kcells, n3 = gd.ncells;
-        FILE* in = std::fopen(argv[1], "rb");
-        if (!in) return 4;
-        auto rd = [&](size_t n) { std::vector<TF> v(n); if (std::fread(v.data(), sizeof(TF), n, in) != n) { std::fprintf(stderr, "short input\n"); std::exit(4); } return v; };
+        Reader rd(argv[1]);
         Fields<TF> fields;
         auto mk = [&]() { auto f = std::make_shared<Field3d<TF>>(); f->fld_g = up(rd(n3)); return f; };
         for (const char* n : {"thl", "qt"}) fields.sp[n] = mk();
@@ -42,11 +27,8 @@ int main(int argc, char** argv)
         Thermo_moist<TF> thermo(grid, fields);
         thermo.pref_g = up(rd(nk)); thermo.exnref_g = up(rd(nk)); fields.rhoref_g = up(rd(nk));
         thermo.nonconv_g = dev<int>(1);
-        for (std::vector<TF>* v : {&gd.z, &gd.zh, &gd.dz, &gd.dzh, &gd.dzi, &gd.dzhi}) *v = rd(nk);
-        gd.dzi4.assign(nk, 0); gd.dzhi4.assign(nk, 0);
-        std::fclose(in);
-        gd.z_g = up(gd.z); gd.zh_g = up(gd.zh); gd.dz_g = up(gd.dz); gd.dzh_g = up(gd.dzh); gd.dzi_g = up(gd.dzi); gd.dzhi_g = up(gd.dzhi);
-        gd.dzi4_g = up(gd.dzi4); gd.dzhi4_g = up(gd.dzhi4);
+        read_metrics(grid, rd);
+        rd.close();
 
         Radiation_gcss<TF> radiation(grid, fields);
         radiation.xka = std::atof(argv[6]); radiation.fr0 = std::atof(argv[7]); radiation.fr1 = std::atof(argv[8]); radiation.div = std::atof(argv[9]);
@@ -63,16 +45,11 @@ int main(int argc, char** argv)
         HIPCHK(hipDeviceSynchronize());
         int nonconv = 0; HIPCHK(hipMemcpy(&nonconv, thermo.nonconv_g, sizeof(int), hipMemcpyDeviceToHost));
         if (nonconv) return 8;
-        FILE* out = std::fopen(argv[2], "wb");
-        if (!out) return 4;
-        auto wr = [&](const TF* d, size_t n) { std::vector<TF> v(n); HIPCHK(hipMemcpy(v.data(), d, n*sizeof(TF), hipMemcpyDeviceToHost));
-                                               if (std::fwrite(v.data(), sizeof(TF), n, out) != n) std::exit(4); };
+        Writer wr(argv[2]);
         wr(fields.st["thl"]->fld_g, n3); wr(lflx, n3); wr(sflx, n3);
-        const double mu = radiation.calc_zenith(day_of_year);
-        if (std::fwrite(&mu, sizeof(double), 1, out) != 1) return 4;
-        std::fclose(out);
+        wr.host({(double)radiation.calc_zenith(day_of_year)});
+        wr.close();
         std::printf("host_radiation ok\n");
-    }
-    catch (const std::exception& e) { std::cerr << "EXCEPTION: " << e.what() << std::endl; return 5; }
-    return 0;
+        return 0;
+    });
 }

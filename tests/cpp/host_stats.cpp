@@ -9,34 +9,20 @@
 // OUT, per mask: nmask nmaskh (as doubles) area areah u u_2 u_3 u_4 u_grad w w_2 w_grad q q_frac w_adv u_w u_diff u_flux [kcells each], then
 // q_cover q_path bot nmask_bot.
 // gc = (3, 3, 1), second order, double.
-#include <hip/hip_runtime.h>
-#include <cstdio>
-#include <cstdlib>
-#include <iostream>
-#include "../../microhh_amd/host/mhh_host.h"
+#include "host_prog.h"
 
 using namespace mhh_host;
 typedef double TF;
-#define HIPCHK(x) do { hipError_t e = (x); if (e != hipSuccess) { std::fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e)); std::exit(2); } } while (0)
-static TF* up(const std::vector<TF>& v) { TF* d; HIPCHK(hipMalloc(&d, v.size()*sizeof(TF))); HIPCHK(hipMemcpy(d, v.data(), v.size()*sizeof(TF), hipMemcpyHostToDevice)); return d; }
-template<class T> static T* dev(size_t n) { T* d; HIPCHK(hipMalloc(&d, n*sizeof(T))); HIPCHK(hipMemset(d, 0, n*sizeof(T))); return d; }
 
 int main(int argc, char** argv)
 {
-    if (argc != 8) { std::fprintf(stderr, "usage\n"); return 3; }
-    try
+    return run_main(argc, argv, 8, [&]() -> int
     {
         Grid<TF> grid; auto& gd = grid.gd;
-        gd.itot = std::atoi(argv[3]); gd.jtot = std::atoi(argv[4]); gd.ktot = std::atoi(argv[5]); gd.igc = gd.jgc = 3; gd.kgc = 1;
-        gd.imax = gd.itot; gd.jmax = gd.jtot; gd.kmax = gd.ktot;
-        gd.icells = gd.itot + 6; gd.jcells = gd.jtot + 6; gd.kcells = gd.ktot + 2; gd.ijcells = gd.icells*gd.jcells; gd.ncells = gd.ijcells*gd.kcells;
-        gd.istart = gd.jstart = 3; gd.kstart = 1; gd.iend = 3 + gd.itot; gd.jend = 3 + gd.jtot; gd.kend = 1 + gd.ktot;
-        gd.xsize = gd.ysize = 3200.; gd.zsize = 1200.; gd.dx = gd.xsize/gd.itot; gd.dy = gd.ysize/gd.jtot;
+        make_grid(grid, std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]), 3, 3, 1, 3200., 3200., 1200.);
         const TF threshold = std::atof(argv[6]), offset = std::atof(argv[7]);
         const size_t nk = gd.kcells, n3 = gd.ncells, n2 = gd.ijcells;
-        FILE* in = std::fopen(argv[1], "rb");
-        if (!in) return 4;
-        auto rd = [&](size_t n) { std::vector<TF> v(n); if (std::fread(v.data(), sizeof(TF), n, in) != n) { std::fprintf(stderr, "short input\n"); std::exit(4); } return v; };
+        Reader rd(argv[1]);
         Fields<TF> fields;
         Field3d<TF> u, w, q;
         u.fld_g = up(rd(n3)); w.fld_g = up(rd(n3)); q.fld_g = up(rd(n3));
@@ -45,11 +31,8 @@ int main(int argc, char** argv)
         TF* bot = up(rd(n2));
         u.flux_bot_g = up(rd(n2)); u.flux_top_g = up(rd(n2));
         fields.rhoref_g = up(rd(nk));
-        for (std::vector<TF>* v : {&gd.z, &gd.zh, &gd.dz, &gd.dzh, &gd.dzi, &gd.dzhi}) *v = rd(nk);
-        gd.dzi4.assign(nk, 0); gd.dzhi4.assign(nk, 0);
-        std::fclose(in);
-        gd.z_g = up(gd.z); gd.zh_g = up(gd.zh); gd.dz_g = up(gd.dz); gd.dzh_g = up(gd.dzh); gd.dzi_g = up(gd.dzi); gd.dzhi_g = up(gd.dzhi);
-        gd.dzi4_g = up(gd.dzi4); gd.dzhi4_g = up(gd.dzhi4);
+        read_metrics(grid, rd);
+        rd.close();
 
         Stats_sampler<TF> stats(grid, fields);
         const char* masks[3] = {"default", "wpos", "wneg"};
@@ -85,12 +68,9 @@ int main(int argc, char** argv)
         stats.calc_tend(w, "w", "adv");
         HIPCHK(hipDeviceSynchronize());
 
-        FILE* out = std::fopen(argv[2], "wb");
-        if (!out) return 4;
-        auto wr = [&](const TF* d, size_t n) { std::vector<TF> v(n); HIPCHK(hipMemcpy(v.data(), d, n*sizeof(TF), hipMemcpyDeviceToHost));
-                                               if (std::fwrite(v.data(), sizeof(TF), n, out) != n) std::exit(4); };
+        Writer wr(argv[2]);
         auto wri = [&](const int* d, size_t n) { std::vector<int> v(n); HIPCHK(hipMemcpy(v.data(), d, n*sizeof(int), hipMemcpyDeviceToHost));
-                                                 std::vector<TF> f(v.begin(), v.end()); if (std::fwrite(f.data(), sizeof(TF), n, out) != n) std::exit(4); };
+                                                 wr.host(std::vector<TF>(v.begin(), v.end())); };
         for (const char* m : masks)
         {
             wri(stats.get_nmask(m, false), nk); wri(stats.get_nmask(m, true), nk);
@@ -98,9 +78,8 @@ int main(int argc, char** argv)
             wr(stats.get_time_series(m, "q_cover"), 1); wr(stats.get_time_series(m, "q_path"), 1); wr(stats.get_time_series(m, "bot"), 1);
             wri(stats.get_nmask_bot(m), 1);
         }
-        std::fclose(out);
+        wr.close();
         std::printf("host_stats ok\n");
-    }
-    catch (const std::exception& e) { std::cerr << "EXCEPTION: " << e.what() << std::endl; return 5; }
-    return 0;
+        return 0;
+    });
 }

@@ -2,7 +2,7 @@
 // microhh_amd/host/mhh_host.h (the reference's Advec/Diff/Pres/Boundary_cyclic interfaces over the C ABI), the way
 // Model<TF>::exec does (src/model.cxx:346-411). Input and output are raw binary files written/read by
 // tests/test_cpp_host.py, which checks the result against the CPU oracle.
-#include <hip/hip_runtime.h>
+#include "host_prog.h"
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -12,10 +12,7 @@
 using namespace mhh_host;
 typedef double TF;
 
-#define HIPCHK(x) do { hipError_t e = (x); if (e != hipSuccess) { std::fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e)); std::exit(2); } } while (0)
-
 static std::vector<TF> rd(FILE* f, size_t n) { std::vector<TF> v(n); if (std::fread(v.data(), sizeof(TF), n, f) != n) { std::fprintf(stderr, "short read\n"); std::exit(3); } return v; }
-static TF* up(const std::vector<TF>& v) { TF* d; HIPCHK(hipMalloc(&d, v.size()*sizeof(TF))); HIPCHK(hipMemcpy(d, v.data(), v.size()*sizeof(TF), hipMemcpyHostToDevice)); return d; }
 static void dn(FILE* f, const TF* d, size_t n) { std::vector<TF> v(n); HIPCHK(hipMemcpy(v.data(), d, n*sizeof(TF), hipMemcpyDeviceToHost)); std::fwrite(v.data(), sizeof(TF), n, f); }
 
 int main(int argc, char** argv)

@@ -6,42 +6,28 @@
 // wrap as the 2-D exchange (one rank through the slab sequence); both must agree here, and OUT holds the first:
 // dutot ustar obuk ufluxbot vfluxbot ugradbot vgradbot thbot thgradbot dudz dvdz dbdz [ijcells doubles each], then nobuk as doubles.
 // gc = (3, 3, 1), second order, double, mbcbot = noslip, th with sbcbot = flux (Thermo_dry).
-#include <hip/hip_runtime.h>
-#include <cstdio>
-#include <cstdlib>
+#include "host_prog.h"
 #include <cstring>
-#include <iostream>
-#include "../../microhh_amd/host/mhh_host.h"
 
 using namespace mhh_host;
 typedef double TF;
-#define HIPCHK(x) do { hipError_t e = (x); if (e != hipSuccess) { std::fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e)); std::exit(2); } } while (0)
-static TF* up(const std::vector<TF>& v) { TF* d; HIPCHK(hipMalloc(&d, v.size()*sizeof(TF))); HIPCHK(hipMemcpy(d, v.data(), v.size()*sizeof(TF), hipMemcpyHostToDevice)); return d; }
-template<class T> static T* dev(size_t n) { T* d; HIPCHK(hipMalloc(&d, n*sizeof(T))); HIPCHK(hipMemset(d, 0, n*sizeof(T))); return d; }
 
 int main(int argc, char** argv)
 {
-    if (argc != 13) { std::fprintf(stderr, "usage\n"); return 3; }
-    try
+    return run_main(argc, argv, 13, [&]() -> int
     {
         Grid<TF> grid; auto& gd = grid.gd;
-        gd.itot = std::atoi(argv[3]); gd.jtot = std::atoi(argv[4]); gd.ktot = std::atoi(argv[5]); gd.igc = gd.jgc = 3; gd.kgc = 1;
-        gd.imax = gd.itot; gd.jmax = gd.jtot; gd.kmax = gd.ktot;
-        gd.icells = gd.itot + 6; gd.jcells = gd.jtot + 6; gd.kcells = gd.ktot + 2; gd.ijcells = gd.icells*gd.jcells; gd.ncells = gd.ijcells*gd.kcells;
-        gd.istart = gd.jstart = 3; gd.kstart = 1; gd.iend = 3 + gd.itot; gd.jend = 3 + gd.jtot; gd.kend = 1 + gd.ktot;
-        gd.xsize = gd.ysize = 3200.; gd.zsize = 2.*std::atof(argv[6])*gd.ktot; gd.dx = gd.xsize/gd.itot; gd.dy = gd.ysize/gd.jtot;
+        make_grid(grid, std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]), 3, 3, 1, 3200., 3200., 2.*std::atof(argv[6])*std::atoi(argv[5]));
         const size_t nk = gd.kcells, n3 = gd.ncells, n2 = gd.ijcells;
         gd.z.assign(nk, 0); for (int k=0; k<gd.kcells; ++k) gd.z[k] = (2.*(k - gd.kstart) + 1.)*std::atof(argv[6]);      // z[kstart] = zsl
         gd.z_g = up(gd.z);
-        FILE* in = std::fopen(argv[1], "rb");
-        if (!in) return 4;
-        auto rd = [&](size_t n) { std::vector<TF> v(n); if (std::fread(v.data(), sizeof(TF), n, in) != n) { std::fprintf(stderr, "short input\n"); std::exit(4); } return v; };
+        Reader rd(argv[1]);
         Fields<TF> fields;
         auto mk = [&](bool read) { auto f = std::make_shared<Field3d<TF>>(); f->fld_g = read ? up(rd(n3)) : nullptr;
                                    f->fld_bot_g = dev<TF>(n2); f->grad_bot_g = dev<TF>(n2); f->flux_bot_g = dev<TF>(n2); return f; };
         fields.mp["u"] = mk(true); fields.mp["v"] = mk(true); fields.sp["th"] = mk(true);
         fields.mp["w"] = mk(false); fields.mt["u"] = mk(false); fields.mt["v"] = mk(false); fields.mt["w"] = mk(false); fields.st["th"] = mk(false);
-        std::fclose(in);
+        rd.close();
 
         Thermo<TF> thermo; thermo.swthermo = "dry";
         auto upload = [](void* d, const void* s, size_t n) { HIPCHK(hipMemcpy(d, s, n, hipMemcpyHostToDevice)); };
@@ -80,11 +66,10 @@ int main(int argc, char** argv)
         bool refused = false;
         try { Boundary_surface<TF> bad(grid, fields); bad.sw_charnock = true; bad.init(); } catch (const std::runtime_error&) { refused = true; }
         if (!refused) return 7;
-        FILE* out = std::fopen(argv[2], "wb");
-        if (!out || std::fwrite(a.data(), sizeof(TF), a.size(), out) != a.size()) return 4;
-        std::fclose(out);
+        Writer wr(argv[2]);
+        wr.host(a);
+        wr.close();
         std::printf("host_surface ok\n");
-    }
-    catch (const std::exception& e) { std::cerr << "EXCEPTION: " << e.what() << std::endl; return 5; }
-    return 0;
+        return 0;
+    });
 }

@@ -2,7 +2,7 @@
 // of microhh_amd/host/mhh_host.h and the slab driver Pres_slab(master, grid, fields, 4) of microhh_amd/host/mhh_host_rccl.h on a
 // one-rank RCCL communicator (the halos of vt and p and both transposes go through ncclSend / ncclRecv to self). Input and output
 // are raw binary files written / read by tests/test_slab4_gpu_ranks.py, which compares the two.
-#include <hip/hip_runtime.h>
+#include "host_prog.h"
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -12,10 +12,7 @@
 using namespace mhh_host;
 typedef double TF;
 
-#define HIPCHK(x) do { hipError_t e = (x); if (e != hipSuccess) { std::fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e)); std::exit(2); } } while (0)
-
 static std::vector<TF> rd(FILE* f, size_t n) { std::vector<TF> v(n); if (std::fread(v.data(), sizeof(TF), n, f) != n) { std::fprintf(stderr, "short read\n"); std::exit(3); } return v; }
-static TF* up(const std::vector<TF>& v) { TF* d; HIPCHK(hipMalloc(&d, v.size()*sizeof(TF))); HIPCHK(hipMemcpy(d, v.data(), v.size()*sizeof(TF), hipMemcpyHostToDevice)); return d; }
 static void dn(FILE* f, const TF* d, size_t n) { std::vector<TF> v(n); HIPCHK(hipMemcpy(v.data(), d, n*sizeof(TF), hipMemcpyDeviceToHost)); std::fwrite(v.data(), sizeof(TF), n, f); }
 
 int main(int argc, char** argv)

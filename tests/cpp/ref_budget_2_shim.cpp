@@ -7,11 +7,10 @@
 // only, with the arguments Budget_2<TF>::exec_stats (:1414-1818) passes. Grid::interpolate_2nd (wx, wy) is a member of Grid<TF> and
 // cannot be reached without an object: tests/budget_ref.py restates that one expression in NumPy float64.
 #include "budget_2.cxx"
+#include "ref_shim.h"
 
 namespace
 {
-    struct Dims { int istart, iend, jstart, jend, kstart, kend, icells, ijcells, kcells; };
-
     // out: the term fields of the group, in the library's order (the LES diffusion group: two more, the helper fields wz and evisch);
     // in: u, v, w, p, evisc, b, ufluxbot, vfluxbot, wx, wy;
     // prof: umodel, vmodel, wmodel, bmean, pmean, dzi, dzhi; par: utrans, vtrans, fc, dxi, dyi
@@ -52,8 +51,6 @@ namespace
         }
     }
 }
-
-#define REF_API extern "C" __attribute__((visibility("default")))
 
 REF_API void ref_budget_2_group(int dtype, const Dims* d, int grp, void* const* out, const void* const* in, const void* const* prof, const double* par)
 {

@@ -7,11 +7,10 @@
 // is written here is the calls only, with the arguments Cross::cross_lngrad (:653-703), cross_path (:705-725) and
 // cross_height_threshold (:738-760) pass. Cross::create is a member behind Master and Grid: tests/test_cross_indices.py restates it.
 #include "cross.cxx"
+#include "ref_shim.h"
 
 namespace
 {
-    struct Dims { int istart, iend, jstart, jend, kstart, kend, icells, ijcells, kcells; };
-
     template<typename TF>
     void lngrad(const Dims& d, int order, const TF* a, TF* out, double dxi, double dyi, const TF* dzi)
     {
@@ -41,7 +40,6 @@ namespace
 #define F32(x) static_cast<float*>(x)
 #define C64(x) static_cast<const double*>(x)
 #define C32(x) static_cast<const float*>(x)
-#define REF_API extern "C" __attribute__((visibility("default")))
 
 REF_API void ref_cross_lngrad(int dtype, const Dims* d, int order, const void* a, void* out, double dxi, double dyi, const void* dzi)
 {

@@ -10,10 +10,10 @@
 #include "limiter.cxx"
 
 #include <vector>
+#include "ref_shim.h"
 
 namespace
 {
-    struct Dims { int istart, iend, jstart, jend, kstart, kend, icells, ijcells, kcells; };
     enum { AUTO = 1, ACCR = 2, EVAP = 4, SCBR = 8, SEDI = 16, CLIP = 32 };
 
     template<typename TF>
@@ -74,7 +74,6 @@ namespace
 #define F32(x) static_cast<float*>(x)
 #define C64(x) static_cast<const double*>(x)
 #define C32(x) static_cast<const float*>(x)
-#define REF_API extern "C" __attribute__((visibility("default")))
 
 REF_API void ref_micro_exec(int dtype, const Dims* d, int mask, double Nc0, double dt, void* qr, void* nr, const void* thl, const void* qt, void* ql,
                             void* qrt, void* nrt, void* thlt, void* qtt, void* rr_bot, const void* rho, const void* rhoh, const void* p,

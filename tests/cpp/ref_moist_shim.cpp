@@ -1,7 +1,7 @@
 // ref_moist_shim.cpp -- TEST infrastructure: the reference's own Thermo_moist_functions behind a C interface.
 //
-// Compiled by tests/moist_ref.py into a temporary directory with the reference's include directory on the include path
-// (g++ -std=c++17 -O2 -ffp-contract=off -I<reference>/include); nothing compiled from it is kept. What comes from the reference at
+// Compiled by tests/moist_ref.py (tests/refshim.py holds the command) into a temporary directory with the reference's include
+// directory on the include path; nothing compiled from it is kept. What comes from the reference at
 // compile time: thermo_moist_functions.h (sat_adjust and every point function, exner, calc_base_state) with constants.h and
 // fast_math.h. What is written here: the file-local loops of src/thermo_moist.cxx, which sit in an anonymous namespace and cannot
 // be linked (calc_top_and_bot, calc_buoyancy_tend_2nd, calc_buoyancy, calc_liquid_water, calc_ice, calc_T, calc_N2), restated with
@@ -13,13 +13,12 @@
 
 #define restrict __restrict__
 #include "thermo_moist_functions.h"
+#include "ref_shim.h"
 
 namespace tmf = Thermo_moist_functions;
 
 namespace
 {
-    struct Dims { int istart, iend, jstart, jend, kstart, kend, icells, ijcells, kcells; };
-
     template<typename TF>
     int sat_cells(long long n, const TF* thl, const TF* qt, const TF* p, const TF* exn, TF* ql, TF* qi, TF* t, TF* qs, int* threw)
     {
@@ -143,6 +142,7 @@ void surf_hooks(int n, const TF* thl, const TF* qt, const TF* thlbot, const TF* 
 #define C64(x) static_cast<const double*>(x)
 #define C32(x) static_cast<const float*>(x)
 
+#pragma GCC visibility push(default)      // the entry points: every function of this block
 extern "C"
 {
 int ref_moist_sat_adjust(int dtype, long long n, const void* thl, const void* qt, const void* p, const void* exn,
@@ -189,3 +189,4 @@ void ref_moist_base_state(int dtype, int kstart, int kend, int top_bot, void* th
                                F32(pref), F32(prefh), F32(rho), F32(rhoh), F32(thv), F32(thvh), F32(ex), F32(exh));
 }
 }
+#pragma GCC visibility pop

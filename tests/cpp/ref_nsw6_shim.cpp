@@ -10,11 +10,10 @@
 #include "microphys_nsw6.cxx"
 
 #include <vector>
+#include "ref_shim.h"
 
 namespace
 {
-    struct Dims { int istart, iend, jstart, jend, kstart, kend, icells, ijcells, kcells; };
-
     template<typename TF>
     void nsw6_conversion(const Dims& d, double Nc0, double dt, TF* qrt, TF* qst, TF* qgt, TF* qtt, TF* thlt, const TF* qr, const TF* qs, const TF* qg,
                          const TF* qt, const TF* thl, const TF* ql, const TF* qi, const TF* rho, const TF* exner, const TF* p, const TF* dzi, const TF* dzhi)
@@ -79,7 +78,6 @@ namespace
 #define F32(x) static_cast<float*>(x)
 #define C64(x) static_cast<const double*>(x)
 #define C32(x) static_cast<const float*>(x)
-#define REF_API extern "C" __attribute__((visibility("default")))
 
 REF_API void ref_nsw6_conversion(int dtype, const Dims* d, double Nc0, double dt, void* qrt, void* qst, void* qgt, void* qtt, void* thlt, const void* qr,
                                  const void* qs, const void* qg, const void* qt, const void* thl, const void* ql, const void* qi, const void* rho,

@@ -8,11 +8,10 @@
 #include "radiation_gcss.cxx"
 
 #include <vector>
+#include "ref_shim.h"
 
 namespace
 {
-    struct Dims { int istart, iend, jstart, jend, kstart, kend, icells, ijcells, kcells; };
-
     template<typename TF>
     void rad_exec(const Dims& d, double xka, double fr0, double fr1, double div, double mu, TF* tt, const TF* ql, const TF* qt, TF* flx, TF* swn,
                   const TF* rhoref, const TF* z, const TF* dzhi)
@@ -40,7 +39,6 @@ namespace
 #define F32(x) static_cast<float*>(x)
 #define C64(x) static_cast<const double*>(x)
 #define C32(x) static_cast<const float*>(x)
-#define REF_API extern "C" __attribute__((visibility("default")))
 
 REF_API double ref_rad_zenith(int dtype, double lat, double lon, double day_of_year)
 {

@@ -3,9 +3,9 @@
 // compiled from it is kept); src/advec_2i5.cxx is included in place so that the kernels of its anonymous namespace are visible. What is
 // written here is the call only, with the arguments Advec_2i5::get_advec_flux passes. kind: 0 scalar, 1 u, 2 v, 3 a scalar of fluxlimit_list.
 #include "advec_2i5.cxx"
+#include "ref_shim.h"
 namespace
 {
-    struct Dims { int istart, iend, jstart, jend, kstart, kend, icells, ijcells, kcells; };
     template<typename TF> void flux(const Dims& d, int kind, TF* st, const TF* s, const TF* w)
     {
         if (kind == 1)      advec_flux_u(st, s, w, d.istart, d.iend, d.jstart, d.jend, d.kstart, d.kend, d.icells, d.ijcells);
@@ -14,8 +14,7 @@ namespace
         else                advec_flux_s(st, s, w, d.istart, d.iend, d.jstart, d.jend, d.kstart, d.kend, d.icells, d.ijcells);
     }
 }
-extern "C" __attribute__((visibility("default")))
-void ref_stats_flux_advec_2i5(int dtype, const Dims* d, int kind, void* st, const void* s, const void* w)
+REF_API void ref_stats_flux_advec_2i5(int dtype, const Dims* d, int kind, void* st, const void* s, const void* w)
 {
     if (dtype == 0) flux(*d, kind, static_cast<double*>(st), static_cast<const double*>(s), static_cast<const double*>(w));
     else            flux(*d, kind, static_cast<float*>(st), static_cast<const float*>(s), static_cast<const float*>(w));

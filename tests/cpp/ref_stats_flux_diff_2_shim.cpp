@@ -2,9 +2,8 @@
 // A translation unit of the statistics shim (tests/stats_ref.py compiles it with the others into a temporary directory; nothing
 // compiled from it is kept); src/diff_2.cxx is included in place. The call is Diff_2::diff_flux's (:192-196).
 #include "diff_2.cxx"
-namespace { struct Dims { int istart, iend, jstart, jend, kstart, kend, icells, ijcells, kcells; }; }
-extern "C" __attribute__((visibility("default")))
-void ref_stats_flux_diff_2(int dtype, const Dims* d, void* out, const void* data, double visc, const void* dzhi)
+#include "ref_shim.h"
+REF_API void ref_stats_flux_diff_2(int dtype, const Dims* d, void* out, const void* data, double visc, const void* dzhi)
 {
     if (dtype == 0) calc_diff_flux(static_cast<double*>(out), static_cast<const double*>(data), visc, static_cast<const double*>(dzhi),
                                    d->istart, d->iend, d->jstart, d->jend, d->kstart, d->kend, d->icells, d->ijcells);

@@ -3,9 +3,9 @@
 // nothing compiled from it is kept); src/diff_smag2.cxx is included in place. The calls are Diff_smag2::diff_flux's (:1217-1276) in
 // both of its forms. kind: 0 scalar, 1 u, 2 v; di is gd.dxi for u and gd.dyi for v.
 #include "diff_smag2.cxx"
+#include "ref_shim.h"
 namespace
 {
-    struct Dims { int istart, iend, jstart, jend, kstart, kend, icells, ijcells, kcells; };
     template<typename TF> void flux(const Dims& d, int kind, int sm, TF* out, const TF* data, const TF* w, const TF* evisc, const TF* bot, const TF* top,
                                     TF di, const TF* dzhi, TF tPr, TF visc)
     {
@@ -27,8 +27,7 @@ namespace
 }
 #define P64(x) static_cast<const double*>(x)
 #define P32(x) static_cast<const float*>(x)
-extern "C" __attribute__((visibility("default")))
-void ref_stats_flux_diff_smag2(int dtype, const Dims* d, int kind, int sm, void* out, const void* data, const void* w, const void* evisc, const void* bot,
+REF_API void ref_stats_flux_diff_smag2(int dtype, const Dims* d, int kind, int sm, void* out, const void* data, const void* w, const void* evisc, const void* bot,
                                const void* top, double di, const void* dzhi, double tPr, double visc)
 {
     if (dtype == 0) flux(*d, kind, sm, static_cast<double*>(out), P64(data), P64(w), P64(evisc), P64(bot), P64(top), di, P64(dzhi), tPr, visc);

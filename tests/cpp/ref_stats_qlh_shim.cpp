@@ -8,11 +8,10 @@
 #include "thermo_moist.cxx"
 
 #include <vector>
+#include "ref_shim.h"
 
 namespace
 {
-    struct Dims { int istart, iend, jstart, jend, kstart, kend, icells, ijcells, kcells; };
-
     template<typename TF>
     void qlh(const Dims& d, TF* out, const TF* thl, const TF* qt, const TF* prefh)
     {
@@ -22,8 +21,7 @@ namespace
     }
 }
 
-extern "C" __attribute__((visibility("default")))
-void ref_stats_ql_h(int dtype, const Dims* d, void* out, const void* thl, const void* qt, const void* prefh)
+REF_API void ref_stats_ql_h(int dtype, const Dims* d, void* out, const void* thl, const void* qt, const void* prefh)
 {
     if (dtype == 0) qlh(*d, static_cast<double*>(out), static_cast<const double*>(thl), static_cast<const double*>(qt), static_cast<const double*>(prefh));
     else            qlh(*d, static_cast<float*>(out), static_cast<const float*>(thl), static_cast<const float*>(qt), static_cast<const float*>(prefh));

@@ -9,11 +9,10 @@
 // calc_grad_2nd is a member of Stats<TF> and cannot be reached without an object: tests/stats_ref.py restates that one loop in NumPy
 // float64, in row order. calc_liquid_water_h of thermo_moist.cxx is behind ref_stats_qlh_shim.cpp, a translation unit of its own.
 #include "stats.cxx"
+#include "ref_shim.h"
 
 namespace
 {
-    struct Dims { int istart, iend, jstart, jend, kstart, kend, icells, ijcells, kcells; };
-
     template<typename TF>
     void thres(const Dims& d, int mode, unsigned int* mfield, unsigned int* mfield_bot, unsigned int flag, unsigned int flagh,
                const TF* fld, const TF* fldh, const TF* fld_bot, double threshold)
@@ -75,7 +74,6 @@ namespace
 #define F32(x) static_cast<float*>(x)
 #define C64(x) static_cast<const double*>(x)
 #define C32(x) static_cast<const float*>(x)
-#define REF_API extern "C" __attribute__((visibility("default")))
 
 REF_API void ref_stats_thres(int dtype, const Dims* d, int mode, unsigned int* mfield, unsigned int* mfield_bot, unsigned int flag, unsigned int flagh,
                              const void* fld, const void* fldh, const void* fld_bot, double threshold)

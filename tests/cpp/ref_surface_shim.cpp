@@ -1,7 +1,7 @@
 // ref_surface_shim.cpp -- TEST infrastructure: the reference's own surface-layer templates behind a C interface.
 //
-// Compiled by tests/surface_ref.py into a temporary directory with the reference's include directory on the include path
-// (g++ -std=c++17 -O2 -ffp-contract=off -I<reference>/include); nothing compiled from it is kept. What comes from the reference
+// Compiled by tests/surface_ref.py (tests/refshim.py holds the command) into a temporary directory with the reference's include
+// directory on the include path; nothing compiled from it is kept. What comes from the reference
 // at compile time: Boundary_surface_kernels (prepare_lut, calc_dutot, the lookup solvers, calc_duvdz_mo, calc_dbdz_mo) and
 // Monin_obukhov. What is written here: four stub lines that let that header compile alone, a Boundary_cyclic whose exec_2d wraps a
 // 2-D array, the file-local loops of src/boundary_surface.cxx (stability, stability_neutral, surfm, surfs) and of
@@ -36,6 +36,7 @@ template<typename TF> struct Boundary_cyclic
     }
 };
 #include "boundary_surface_kernels.h"
+#include "ref_shim.h"
 
 namespace bsk = Boundary_surface_kernels;
 namespace most = Monin_obukhov;
@@ -243,12 +244,12 @@ void exec(const ref_surface_io& io)
 }
 }
 
-extern "C" void ref_surface_exec(const ref_surface_io* io)
+REF_API void ref_surface_exec(const ref_surface_io* io)
 {
     if (io->dtype == 0) exec<double>(*io); else exec<float>(*io);
 }
 // Boundary_surface::init_solver (:812-826)
-extern "C" void ref_surface_lut(double zsl, double z0m, double z0h, int mbcbot, int thermobc, int dtype, float* zL, float* f)
+REF_API void ref_surface_lut(double zsl, double z0m, double z0h, int mbcbot, int thermobc, int dtype, float* zL, float* f)
 {
     const Boundary_type m = static_cast<Boundary_type>(mbcbot), t = static_cast<Boundary_type>(thermobc);
     if (dtype == 0) bsk::prepare_lut<double>(zL, f, z0m, z0h, zsl, nzL_lut, m, t);

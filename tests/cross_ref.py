@@ -8,20 +8,14 @@ uses + - * / only and is narrowed to values a float holds exactly, so they are t
 the file holds their digest per case. The gather has NumPy slicing as its reference and needs no shim.
 """
 import ctypes as C
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 import common as cm
-import moist_ref as M
+import refshim
+from refshim import Dims, code, dims_of, f32exact, have_reference, tag
 from microhh_amd.grid import Grid
 
-REF_ROOT = os.path.dirname(os.path.normpath(M.REF_INC))
-GOLDEN = os.path.join(cm.ROOT, "tests", "golden", "cross_ref.npz")
-RECORD = os.environ.get("MHH_RECORD_CROSS_GOLDEN") == "1"
 ZSIZE = 3000.
 KGMAX = 3                      # vertical ghost levels the inputs are drawn with
 
@@ -35,8 +29,6 @@ THRESHOLD = 0.25               # of the threshold heights: a value a float holds
 # the kinds of column of the thresholded field q, by (i + j*itot) % NKIND
 NONE, ONLY_KSTART, ONLY_TOP, TWO_LAYERS, EQUAL, RANDOM = range(6)
 NKIND = 6
-
-tag, code, f32exact, have_reference = M.tag, M.code, M.f32exact, M.have_reference
 
 
 XY, XZ, YZ, PLANE = 0, 1, 2, 3
@@ -86,10 +78,7 @@ class CrossCase:
         self.f = f
 
     def digest(self):
-        h = hashlib.sha256()
-        for k in sorted(self.f):
-            h.update(np.ascontiguousarray(self.f[k], dtype=np.float64).tobytes())
-        return h.hexdigest()
+        return refshim.digest(*[np.asarray(self.f[k], dtype=np.float64) for k in sorted(self.f)])
 
     def host(self, g):
         """Host arrays of grid g's dtype and layout: the vertical ghost levels hold the seeded values, the horizontal ghost cells the
@@ -115,30 +104,15 @@ def case_of(shape):
 
 
 # ---- the shim ---------------------------------------------------------------------------------------------------------------
-_shim = {}
+def _bind(lib):
+    vp, ci, cd = C.c_void_p, C.c_int, C.c_double
+    DP = C.POINTER(Dims)
+    lib.ref_cross_lngrad.argtypes = [ci, DP, ci, vp, vp, cd, cd, vp]; lib.ref_cross_lngrad.restype = None
+    lib.ref_cross_path.argtypes = [ci, DP, vp, vp, vp, vp]; lib.ref_cross_path.restype = None
+    lib.ref_cross_height.argtypes = [ci, DP, vp, vp, vp, cd, ci]; lib.ref_cross_height.restype = None
 
 
-def shim():
-    """The shim compiled against the reference's tree into a temporary directory (kept for the session); None without the tree."""
-    if "lib" not in _shim:
-        if not have_reference():
-            _shim["lib"] = None
-        else:
-            _shim["tmp"] = tempfile.TemporaryDirectory()
-            so = os.path.join(_shim["tmp"].name, "libref_cross.so")
-            src = os.path.join(REF_ROOT, "src")
-            subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-DRESTRICTKEYWORD=__restrict__", "-I" + M.REF_INC, "-I" + src,
-                            "-I" + os.path.join(cm.ROOT, "tests", "stubs_syntax_only"),
-                            "-fPIC", "-shared", "-fvisibility=hidden", "-ffunction-sections", "-fdata-sections", "-Wl,--gc-sections", "-o", so,
-                            os.path.join(cm.ROOT, "tests", "cpp", "ref_cross_shim.cpp")], check=True)
-            lib = C.CDLL(so)
-            vp, ci, cd = C.c_void_p, C.c_int, C.c_double
-            DP = C.POINTER(M.Dims)
-            lib.ref_cross_lngrad.argtypes = [ci, DP, ci, vp, vp, cd, cd, vp]; lib.ref_cross_lngrad.restype = None
-            lib.ref_cross_path.argtypes = [ci, DP, vp, vp, vp, vp]; lib.ref_cross_path.restype = None
-            lib.ref_cross_height.argtypes = [ci, DP, vp, vp, vp, cd, ci]; lib.ref_cross_height.restype = None
-            _shim["lib"] = lib
-    return _shim["lib"]
+shim = refshim.Shim("cross", ["ref_cross_shim.cpp"], _bind, stubs=True)
 
 
 def inverse(g, d):
@@ -150,7 +124,7 @@ def inverse(g, d):
 def ref_lngrad(g, a):
     """calc_lngrad_2nd / calc_lngrad_4th of the whole field a (host array of grid g), as Cross::cross_lngrad calls them."""
     out = np.zeros(g.shape3, dtype=g.np_dtype)
-    d = M.dims_of(g)
+    d = dims_of(g)
     shim().ref_cross_lngrad(code(g.np_dtype), C.byref(d), g.order, cm.ptr(np.ascontiguousarray(a)), cm.ptr(out), inverse(g, g.dx), inverse(g, g.dy),
                             cm.ptr(g.dzi if g.order == 2 else g.dzi4))
     return out
@@ -158,14 +132,14 @@ def ref_lngrad(g, a):
 
 def ref_path(g, a, rho):
     tmp = np.zeros(g.shape3, dtype=g.np_dtype)
-    d = M.dims_of(g)
+    d = dims_of(g)
     shim().ref_cross_path(code(g.np_dtype), C.byref(d), cm.ptr(np.ascontiguousarray(a)), cm.ptr(tmp), cm.ptr(np.ascontiguousarray(rho)), cm.ptr(g.dz))
     return tmp[g.kstart, g.jstart:g.jend, g.istart:g.iend].copy()
 
 
 def ref_height(g, a, threshold, upward):
     out = np.full(g.shape2, 777., dtype=g.np_dtype)
-    d = M.dims_of(g)
+    d = dims_of(g)
     shim().ref_cross_height(code(g.np_dtype), C.byref(d), cm.ptr(np.ascontiguousarray(a)), cm.ptr(out), cm.ptr(g.z), threshold, int(upward))
     return out[g.jstart:g.jend, g.istart:g.iend].copy()
 
@@ -192,36 +166,13 @@ def _compute_all():
     return rec
 
 
-_all, _golden = {}, {}
-
-
-def golden():
-    if "z" not in _golden:
-        _golden["z"] = np.load(GOLDEN) if os.path.exists(GOLDEN) else None
-    return _golden["z"]
-
-
-def computed():
-    if "rec" not in _all:
-        _all["rec"] = _compute_all() if have_reference() else None
-    return _all["rec"]
+GOLD = refshim.Golden("cross", _compute_all, "tests/test_cross_kernels.py")
+RECORD, golden, computed, record_if_asked = GOLD.record, GOLD.golden, GOLD.computed, GOLD.record_if_asked
 
 
 def ref(shape, gc, order, dtype, name, be=None):
-    """A reference result by name: from the shim on this host, else (and always on the GPU backend) from the golden file."""
-    key = case_key(shape, gc, order, dtype) + name
-    if have_reference() and (be is None or be.name == "emul") and not RECORD:
-        return computed()[key]
-    z = golden()
-    assert z is not None, "tests/golden/cross_ref.npz is missing: record it where the reference tree exists"
-    return z[key]
-
-
-def record_if_asked():
-    """MHH_RECORD_CROSS_GOLDEN=1: write the golden file from the shim (the first test of tests/test_cross_kernels.py calls this)."""
-    if RECORD:
-        np.savez_compressed(GOLDEN, **_compute_all())
-        _golden.clear()
+    """A reference result by name (Golden.ref)."""
+    return GOLD.ref(case_key(shape, gc, order, dtype) + name, be)
 
 
 # ---- what the tests hold the library against -------------------------------------------------------------------------------------

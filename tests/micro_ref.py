@@ -8,20 +8,15 @@ is numpy's seeded legacy generator, everything derived from a draw uses + - * / 
 exactly, so they are the same numbers on every host; the file holds their digest per case.
 """
 import ctypes as C
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 import common as cm
 import moist_ref as M
+import refshim
+from refshim import Dims, code, dims_of, f32exact, have_reference, tag
 from microhh_amd.grid import Grid
 
-REF_ROOT = os.path.dirname(os.path.normpath(M.REF_INC))
-GOLDEN = os.path.join(cm.ROOT, "tests", "golden", "micro_ref.npz")
-RECORD = os.environ.get("MHH_RECORD_MICRO_GOLDEN") == "1"
 PBOT = 101540.
 NC0 = 70.e6
 ZSIZE = 4000.
@@ -47,8 +42,6 @@ def stored(shape, mask):
     """The outputs of a run that the golden file holds."""
     names = WRITES[ALL if mask == ALL else mask & ~CLIP]
     return tuple(n for n in names if not (shape == SHAPES[3] and n == "qtt"))
-
-tag, code, f32exact = M.tag, M.code, M.f32exact
 
 
 def grid_of(shape, gc, dtype):
@@ -106,11 +99,8 @@ class RainCase:
         self.dt = {name: float(np.float32(cfl*dzmin/6.6)) for name, cfl in CFLS.items()}
 
     def digest(self):
-        h = hashlib.sha256()
-        for a in (self.thl, self.qt, self.qr, self.nr, self.p, self.exn, self.rho, self.tend0["qrt"], self.tend0["nrt"], self.tend0["thlt"],
-                  self.tend0["qtt"], np.array([self.dt["lo"], self.dt["hi"]])):
-            h.update(np.ascontiguousarray(a).tobytes())
-        return h.hexdigest()
+        return refshim.digest(self.thl, self.qt, self.qr, self.nr, self.p, self.exn, self.rho, self.tend0["qrt"], self.tend0["nrt"], self.tend0["thlt"],
+                              self.tend0["qtt"], np.array([self.dt["lo"], self.dt["hi"]]))
 
     def embed(self, a3, g, fill=777.):
         """The (ktot+2, jtot, itot) block inside a [kcells][jcells][icells] array of g's dtype; the horizontal ghost cells hold
@@ -141,37 +131,21 @@ def rain_case(shape):
 
 
 # ---- the shim ---------------------------------------------------------------------------------------------------------------
-_shim = {}
-have_reference = M.have_reference
+def _bind(lib):
+    vp, ci, cd = C.c_void_p, C.c_int, C.c_double
+    lib.ref_micro_exec.argtypes = [ci, C.POINTER(Dims), ci, cd, cd] + [vp]*17; lib.ref_micro_exec.restype = None
+    lib.ref_micro_cfl.argtypes = [ci, C.POINTER(Dims), vp, vp, vp, vp, cd]; lib.ref_micro_cfl.restype = cd
+    lib.ref_limiter.argtypes = [ci, C.POINTER(Dims), vp, vp, cd]; lib.ref_limiter.restype = None
 
 
-def shim():
-    """The shim compiled against the reference's tree into a temporary directory (kept for the session); None without the tree."""
-    if "lib" not in _shim:
-        if not have_reference():
-            _shim["lib"] = None
-        else:
-            _shim["tmp"] = tempfile.TemporaryDirectory()
-            so = os.path.join(_shim["tmp"].name, "libref_micro.so")
-            src = os.path.join(REF_ROOT, "src")
-            subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-DRESTRICTKEYWORD=__restrict__", "-I" + M.REF_INC, "-I" + src,
-                            "-fPIC", "-shared", "-fvisibility=hidden", "-ffunction-sections", "-fdata-sections", "-Wl,--gc-sections", "-o", so,
-                            os.path.join(cm.ROOT, "tests", "cpp", "ref_micro_shim.cpp"), os.path.join(src, "master.cxx"),
-                            os.path.join(src, "master_serial.cxx")], check=True)
-            lib = C.CDLL(so)
-            vp, ci, cd = C.c_void_p, C.c_int, C.c_double
-            lib.ref_micro_exec.argtypes = [ci, C.POINTER(M.Dims), ci, cd, cd] + [vp]*17; lib.ref_micro_exec.restype = None
-            lib.ref_micro_cfl.argtypes = [ci, C.POINTER(M.Dims), vp, vp, vp, vp, cd]; lib.ref_micro_cfl.restype = cd
-            lib.ref_limiter.argtypes = [ci, C.POINTER(M.Dims), vp, vp, cd]; lib.ref_limiter.restype = None
-            _shim["lib"] = lib
-    return _shim["lib"]
+shim = refshim.Shim("micro", ["ref_micro_shim.cpp"], _bind, ref_sources=refshim.MASTER)
 
 
 def ref_exec(shape, dtype, mask, dtname, zero_tend=False, gc=(1, 1, 1)):
     """The reference on the case: {qr, nr (clipped), qrt, nrt, thlt, qtt, rr_bot, ql, dr} as arrays of the grid's shape."""
     c, g = rain_case(shape), grid_of(shape, gc, dtype)
     h = c.inputs(g, zero_tend)
-    d = M.dims_of(g)
+    d = dims_of(g)
     ql, dr = np.zeros(g.shape3, dtype=dtype), np.zeros(g.shape3, dtype=dtype)
     shim().ref_micro_exec(code(dtype), C.byref(d), mask, NC0, c.dt[dtname], *[cm.ptr(h[n]) for n in ("qr", "nr", "thl", "qt")], cm.ptr(ql),
                           *[cm.ptr(h[n]) for n in OUT], cm.ptr(h["rr_bot"]), cm.ptr(h["rho"]), cm.ptr(h["rho"]), cm.ptr(h["p"]), cm.ptr(h["exn"]),
@@ -183,13 +157,13 @@ def ref_exec(shape, dtype, mask, dtname, zero_tend=False, gc=(1, 1, 1)):
 def ref_cfl(shape, dtype, dtname):
     c, g = rain_case(shape), grid_of(shape, (1, 1, 1), dtype)
     h = c.inputs(g)
-    d = M.dims_of(g)
+    d = dims_of(g)
     return shim().ref_micro_cfl(code(dtype), C.byref(d), cm.ptr(h["qr"]), cm.ptr(h["nr"]), cm.ptr(h["rho"]), cm.ptr(g.dzi), c.dt[dtname])
 
 
 def ref_limiter(g, at, a, dt):
     at = at.copy()
-    d = M.dims_of(g)
+    d = dims_of(g)
     shim().ref_limiter(code(g.np_dtype), C.byref(d), cm.ptr(at), cm.ptr(a), dt)
     return at
 
@@ -241,33 +215,8 @@ def _compute_all():
     return rec
 
 
-_all, _golden = {}, {}
-
-
-def golden():
-    if "z" not in _golden:
-        _golden["z"] = np.load(GOLDEN) if os.path.exists(GOLDEN) else None
-    return _golden["z"]
-
-
-def computed():
-    if "rec" not in _all:
-        _all["rec"] = _compute_all() if have_reference() else None
-    return _all["rec"]
-
-
-def exact_here(be):
-    """emul with the shim compiled on this host: the same C library and no contraction, so what passes through pow, exp and sqrt
-    must agree bit for bit too."""
-    return be.name == "emul" and have_reference() and not RECORD
-
-
-def ref(key, be=None):
-    if have_reference() and (be is None or be.name == "emul") and not RECORD:
-        return computed()[key]
-    z = golden()
-    assert z is not None, "tests/golden/micro_ref.npz is missing: record it where the reference tree exists"
-    return z[key]
+GOLD = refshim.Golden("micro", _compute_all, "tests/test_micro_exec.py")
+RECORD, golden, computed, exact_here, ref, record_if_asked = GOLD.record, GOLD.golden, GOLD.computed, GOLD.exact_here, GOLD.ref, GOLD.record_if_asked
 
 
 # ---- the device -------------------------------------------------------------------------------------------------------------
@@ -310,11 +259,3 @@ class Dev:
         self.capi.check(be.lib.mhh_micro_2mom_warm_cfl(self.G, be.ptr(d["qr"]), be.ptr(d["nr"]), be.ptr(d["rho"]), dt, be.ptr(self.work), C.byref(out),
                                                        be.stream), be.lib)
         return out.value
-
-
-def record_if_asked():
-    """MHH_RECORD_MICRO_GOLDEN=1: write the golden file from the shim (the first test of tests/test_micro_exec.py calls this)."""
-    if RECORD:
-        rec = _compute_all()
-        np.savez_compressed(GOLDEN, **rec)
-        _golden.clear()

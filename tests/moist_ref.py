@@ -8,20 +8,15 @@ numpy's seeded legacy generator, narrowed to values a float holds exactly, and e
 they are the same numbers on every host; the file holds their digest per case.
 """
 import ctypes as C
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 import common as cm
+import refshim
+from refshim import Dims, code, dims_of, f32exact, have_reference, tag
 from microhh_amd.grid import Grid
 from microhh_amd.thermo import bomex_profiles, bomex_synthetic
 
-REF_INC = os.environ.get("MHH_REFERENCE_INCLUDE", "/root/reference/include")     # point it elsewhere to run against the golden file
-GOLDEN = os.path.join(cm.ROOT, "tests", "golden", "moist_ref.npz")
-RECORD = os.environ.get("MHH_RECORD_MOIST_GOLDEN") == "1"
 T0 = 273.15
 PBOT = 101500.
 NPOINT = 2048
@@ -29,14 +24,6 @@ NPOINT = 2048
 # (itot, jtot, ktot); the last one runs with 8 levels per chunk, so that several chunks meet
 SHAPES = [(70, 9, 10), (17, 9, 8), (20, 1, 12), (130, 6, 40)]
 GCS = [(1, 1, 1), (3, 3, 1)]
-
-
-def tag(dtype):
-    return "f64" if np.dtype(dtype) == np.float64 else "f32"
-
-
-def f32exact(a):
-    return np.asarray(a, dtype=np.float64).astype(np.float32).astype(np.float64)
 
 
 def exn_like(p):
@@ -111,10 +98,7 @@ class FieldCase:
         self.thvref = f32exact(300. + 0.004*g.z); self.thvrefh = f32exact(300. + 0.004*g.zh)
 
     def digest(self):
-        h = hashlib.sha256()
-        for a in (self.thl, self.qt, self.wt, self.pref, self.prefh, self.thvref, self.thvrefh):
-            h.update(np.ascontiguousarray(a).tobytes())
-        return h.hexdigest()
+        return refshim.digest(self.thl, self.qt, self.wt, self.pref, self.prefh, self.thvref, self.thvrefh)
 
     def embed(self, a3, g, fill=777.):
         """The (ktot+2, jtot, itot) block inside a [kcells][jcells][icells] array of g's dtype; the horizontal ghost cells hold
@@ -157,49 +141,18 @@ BASE_OUT = ["pref", "prefh", "rhoref", "rhorefh", "thvref", "thvrefh", "exnref",
 
 
 # ---- the shim ---------------------------------------------------------------------------------------------------------------
-class Dims(C.Structure):
-    _fields_ = [(n, C.c_int) for n in ("istart", "iend", "jstart", "jend", "kstart", "kend", "icells", "ijcells", "kcells")]
+def _bind(lib):
+    vp, ci = C.c_void_p, C.c_int
+    lib.ref_moist_sat_adjust.argtypes = [ci, C.c_longlong] + [vp]*9; lib.ref_moist_sat_adjust.restype = ci
+    lib.ref_moist_exner.argtypes = [ci, ci, vp, vp]; lib.ref_moist_exner.restype = None
+    lib.ref_moist_tend.argtypes = [ci, C.POINTER(Dims)] + [vp]*5; lib.ref_moist_tend.restype = ci
+    lib.ref_moist_fields.argtypes = [ci, C.POINTER(Dims)] + [vp]*9; lib.ref_moist_fields.restype = None
+    lib.ref_moist_N2.argtypes = [ci, C.POINTER(Dims)] + [vp]*4; lib.ref_moist_N2.restype = None
+    lib.ref_moist_surf_hooks.argtypes = [ci, ci] + [vp]*6 + [C.c_double]*2 + [vp]*4; lib.ref_moist_surf_hooks.restype = None
+    lib.ref_moist_base_state.argtypes = [ci, ci, ci, ci, vp, vp, C.c_double] + [vp]*13; lib.ref_moist_base_state.restype = None
 
 
-def dims_of(g):
-    d = Dims()
-    for n, _ in Dims._fields_:
-        setattr(d, n, getattr(g, n))
-    return d
-
-
-_shim = {}
-
-
-def have_reference():
-    return os.path.isdir(REF_INC)
-
-
-def shim():
-    """The shim compiled against the reference's headers into a temporary directory (kept for the session); None without the tree."""
-    if "lib" not in _shim:
-        if not have_reference():
-            _shim["lib"] = None
-        else:
-            _shim["tmp"] = tempfile.TemporaryDirectory()
-            so = os.path.join(_shim["tmp"].name, "libref_moist.so")
-            subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-I" + REF_INC, "-o", so,
-                            os.path.join(cm.ROOT, "tests", "cpp", "ref_moist_shim.cpp")], check=True)
-            lib = C.CDLL(so)
-            vp, ci = C.c_void_p, C.c_int
-            lib.ref_moist_sat_adjust.argtypes = [ci, C.c_longlong] + [vp]*9; lib.ref_moist_sat_adjust.restype = ci
-            lib.ref_moist_exner.argtypes = [ci, ci, vp, vp]; lib.ref_moist_exner.restype = None
-            lib.ref_moist_tend.argtypes = [ci, C.POINTER(Dims)] + [vp]*5; lib.ref_moist_tend.restype = ci
-            lib.ref_moist_fields.argtypes = [ci, C.POINTER(Dims)] + [vp]*9; lib.ref_moist_fields.restype = None
-            lib.ref_moist_N2.argtypes = [ci, C.POINTER(Dims)] + [vp]*4; lib.ref_moist_N2.restype = None
-            lib.ref_moist_surf_hooks.argtypes = [ci, ci] + [vp]*6 + [C.c_double]*2 + [vp]*4; lib.ref_moist_surf_hooks.restype = None
-            lib.ref_moist_base_state.argtypes = [ci, ci, ci, ci, vp, vp, C.c_double] + [vp]*13; lib.ref_moist_base_state.restype = None
-            _shim["lib"] = lib
-    return _shim["lib"]
-
-
-def code(dtype):
-    return 0 if np.dtype(dtype) == np.float64 else 1
+shim = refshim.Shim("moist", ["ref_moist_shim.cpp"], _bind)
 
 
 def typed(master, dtype):
@@ -279,10 +232,7 @@ def _compute_all():
     for shape in SHAPES:
         rec["digest/field/%s" % field_case(shape).key] = np.array(field_case(shape).digest())
     for name in ("warm", "mixed"):
-        h = hashlib.sha256()
-        for k in ("thl", "qt", "p", "exn"):
-            h.update(point_set(name)[k].tobytes())
-        rec["digest/point/%s" % name] = np.array(h.hexdigest())
+        rec["digest/point/%s" % name] = np.array(refshim.digest(*[point_set(name)[k] for k in ("thl", "qt", "p", "exn")]))
     return rec
 
 
@@ -318,36 +268,8 @@ def bomex_reference():
     return _bomex["r"]
 
 
-_all = {}
-_golden = {}
-
-
-def golden():
-    if "z" not in _golden:
-        _golden["z"] = np.load(GOLDEN) if os.path.exists(GOLDEN) else None
-    return _golden["z"]
-
-
-def computed():
-    """Every reference array from the shim (once per session); None without the reference tree."""
-    if "rec" not in _all:
-        _all["rec"] = _compute_all() if have_reference() else None
-    return _all["rec"]
-
-
-def exact_here(be):
-    """emul with the shim compiled on this host: the same C library and no contraction, so even what passes through exp and pow
-    must agree bit for bit."""
-    return be.name == "emul" and have_reference() and not RECORD
-
-
-def ref(key, be=None):
-    """The reference array `key`: from the shim where it is built and the backend runs on this host, otherwise from the golden file."""
-    if have_reference() and (be is None or be.name == "emul") and not RECORD:
-        return computed()[key]
-    z = golden()
-    assert z is not None, "tests/golden/moist_ref.npz is missing: record it where the reference tree exists"
-    return z[key]
+GOLD = refshim.Golden("moist", _compute_all, "tests/test_moist_cell.py")       # its first test records: it holds computed() against the file
+RECORD, golden, computed, exact_here, ref = GOLD.record, GOLD.golden, GOLD.computed, GOLD.exact_here, GOLD.ref
 
 
 def rel(got, want):

@@ -10,19 +10,15 @@ Two ways to feed ql and qi, as the entry point has them: "given" (seeded arrays 
 on exactly representable inputs) and "sat" (both null: sat_adjust inline; the reference is fed by its own sat_adjust).
 """
 import ctypes as C
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 import common as cm
 import micro_ref as MR
 import moist_ref as M
+import refshim
+from refshim import Dims, code, dims_of, f32exact, have_reference, tag
 
-GOLDEN = os.path.join(cm.ROOT, "tests", "golden", "nsw6_ref.npz")
-RECORD = os.environ.get("MHH_RECORD_NSW6_GOLDEN") == "1"
 PBOT = 101480.
 NC0 = 100.e6
 T0 = 273.15
@@ -47,8 +43,6 @@ CFLS = {"lo": 0.3, "hi": 3.5}
 SEED_BUMP = {(130, 6, 40): 16}
 STRIDE = 5          # of the two large shapes the golden file keeps every fifth column in i
 grid_of = MR.grid_of
-tag, code, f32exact = M.tag, M.code, M.f32exact
-have_reference = M.have_reference
 
 
 def exp_like(x):
@@ -119,11 +113,8 @@ class IceCase:
         self.dt = {name: float(np.float32(cfl*dzmin/7.)) for name, cfl in CFLS.items()}
 
     def digest(self):
-        h = hashlib.sha256()
-        for a in [getattr(self, n) for n in ("thl", "qt", "ql", "qi") + SPECIES + ("p", "exn", "rho")] + [self.tend0[n] for n in OUT] + \
-                 [np.array([self.dt["lo"], self.dt["hi"]])]:
-            h.update(np.ascontiguousarray(a).tobytes())
-        return h.hexdigest()
+        return refshim.digest(*[getattr(self, n) for n in ("thl", "qt", "ql", "qi") + SPECIES + ("p", "exn", "rho")], *[self.tend0[n] for n in OUT],
+                              np.array([self.dt["lo"], self.dt["hi"]]))
 
     def embed(self, a3, g, fill=777.):
         out = np.full(g.shape3, fill, dtype=g.np_dtype)
@@ -241,35 +232,20 @@ def diagnose(c, dt):
 
 
 # ---- the shim ---------------------------------------------------------------------------------------------------------------
-_shim = {}
+def _bind(lib):
+    vp, ci, cd = C.c_void_p, C.c_int, C.c_double
+    lib.ref_nsw6_conversion.argtypes = [ci, C.POINTER(Dims), cd, cd] + [vp]*17; lib.ref_nsw6_conversion.restype = None
+    lib.ref_nsw6_sedimentation.argtypes = [ci, C.POINTER(Dims), ci, cd] + [vp]*6; lib.ref_nsw6_sedimentation.restype = None
+    lib.ref_nsw6_cfl.argtypes = [ci, C.POINTER(Dims), ci, cd] + [vp]*4; lib.ref_nsw6_cfl.restype = cd
+    lib.ref_nsw6_ql_qi.argtypes = [ci, C.POINTER(Dims)] + [vp]*7; lib.ref_nsw6_ql_qi.restype = ci
 
 
-def shim():
-    """The shim compiled against the reference's tree into a temporary directory (kept for the session); None without the tree."""
-    if "lib" not in _shim:
-        if not have_reference():
-            _shim["lib"] = None
-        else:
-            _shim["tmp"] = tempfile.TemporaryDirectory()
-            so = os.path.join(_shim["tmp"].name, "libref_nsw6.so")
-            src = os.path.join(MR.REF_ROOT, "src")
-            subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-DRESTRICTKEYWORD=__restrict__", "-I" + M.REF_INC, "-I" + src,
-                            "-fPIC", "-shared", "-fvisibility=hidden", "-ffunction-sections", "-fdata-sections", "-Wl,--gc-sections", "-o", so,
-                            os.path.join(cm.ROOT, "tests", "cpp", "ref_nsw6_shim.cpp"), os.path.join(src, "master.cxx"),
-                            os.path.join(src, "master_serial.cxx")], check=True)
-            lib = C.CDLL(so)
-            vp, ci, cd = C.c_void_p, C.c_int, C.c_double
-            lib.ref_nsw6_conversion.argtypes = [ci, C.POINTER(M.Dims), cd, cd] + [vp]*17; lib.ref_nsw6_conversion.restype = None
-            lib.ref_nsw6_sedimentation.argtypes = [ci, C.POINTER(M.Dims), ci, cd] + [vp]*6; lib.ref_nsw6_sedimentation.restype = None
-            lib.ref_nsw6_cfl.argtypes = [ci, C.POINTER(M.Dims), ci, cd] + [vp]*4; lib.ref_nsw6_cfl.restype = cd
-            lib.ref_nsw6_ql_qi.argtypes = [ci, C.POINTER(M.Dims)] + [vp]*7; lib.ref_nsw6_ql_qi.restype = ci
-            _shim["lib"] = lib
-    return _shim["lib"]
+shim = refshim.Shim("nsw6", ["ref_nsw6_shim.cpp"], _bind, ref_sources=refshim.MASTER)
 
 
 def ref_ql_qi(g, h):
     """ql, qi and T of the reference's sat_adjust on the interior (zero elsewhere); asserts that it converged everywhere."""
-    d = M.dims_of(g)
+    d = dims_of(g)
     ql, qi, T = (np.zeros(g.shape3, dtype=g.np_dtype) for _ in range(3))
     threw = shim().ref_nsw6_ql_qi(code(g.np_dtype), C.byref(d), cm.ptr(h["thl"]), cm.ptr(h["qt"]), cm.ptr(h["p"]), cm.ptr(h["exn"]), cm.ptr(ql), cm.ptr(qi),
                                   cm.ptr(T))
@@ -282,7 +258,7 @@ def ref_exec(shape, dtype, mask, dtname, mode, zero_tend=False, gc=(1, 1, 1)):
     rates, and the ql, qi, T it ran on."""
     c, g = ice_case(shape), grid_of(shape, gc, dtype)
     h = c.inputs(g, zero_tend)
-    d = M.dims_of(g)
+    d = dims_of(g)
     lib = shim()
     if mode == "sat":
         h["ql"], h["qi"], h["T"] = ref_ql_qi(g, h)
@@ -300,7 +276,7 @@ def ref_cfl(shape, dtype, dtname):
     """get_time_limit's cfl (:1125-1174): the largest of the three, at least 1e-5, a double."""
     c, g = ice_case(shape), grid_of(shape, (1, 1, 1), dtype)
     h = c.inputs(g)
-    d = M.dims_of(g)
+    d = dims_of(g)
     cfl = max(shim().ref_nsw6_cfl(code(dtype), C.byref(d), s, c.dt[dtname], cm.ptr(h[SPECIES[s]]), cm.ptr(h["rho"]), cm.ptr(g.dzi), cm.ptr(g.dz))
               for s in range(3))
     return max(cfl, 1.e-5)
@@ -369,33 +345,8 @@ def _compute_all():
     return rec
 
 
-_all, _golden = {}, {}
-
-
-def golden():
-    if "z" not in _golden:
-        _golden["z"] = np.load(GOLDEN) if os.path.exists(GOLDEN) else None
-    return _golden["z"]
-
-
-def computed():
-    if "rec" not in _all:
-        _all["rec"] = _compute_all() if have_reference() else None
-    return _all["rec"]
-
-
-def exact_here(be):
-    """emul with the shim compiled on this host: the same C library, the same compiler's folding of std::tgamma and no contraction,
-    so what passes through pow, exp, log and sqrt must agree bit for bit too."""
-    return be.name == "emul" and have_reference() and not RECORD
-
-
-def ref(key, be=None):
-    if have_reference() and (be is None or be.name == "emul") and not RECORD:
-        return computed()[key]
-    z = golden()
-    assert z is not None, "tests/golden/nsw6_ref.npz is missing: record it where the reference tree exists"
-    return z[key]
+GOLD = refshim.Golden("nsw6", _compute_all, "tests/test_nsw6_exec.py")
+RECORD, golden, computed, exact_here, ref, record_if_asked = GOLD.record, GOLD.golden, GOLD.computed, GOLD.exact_here, GOLD.ref, GOLD.record_if_asked
 
 
 # ---- the device -------------------------------------------------------------------------------------------------------------
@@ -444,9 +395,3 @@ class Dev:
         return out.value
 
 
-def record_if_asked():
-    """MHH_RECORD_NSW6_GOLDEN=1: write the golden file from the shim (the first test of tests/test_nsw6_exec.py calls this)."""
-    if RECORD:
-        rec = _compute_all()
-        np.savez_compressed(GOLDEN, **rec)
-        _golden.clear()

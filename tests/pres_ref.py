@@ -14,21 +14,17 @@ library's solve is held against), the mean profiles, the stretched z profiles (m
 SHA-256 of every array that is compared bit for bit. The inputs are common.Case's seeded draws on every host."""
 import contextlib
 import ctypes as C
-import hashlib
 import json
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 import common as cm
+import refshim
 from common import ptr, dbl
+from refshim import have_reference, tag, typed_digest as digest  # noqa: F401
 
-REF_INC = os.environ.get("MHH_REFERENCE_INCLUDE", "/root/reference/include")     # point it elsewhere to run against the golden file
-REF_ROOT = os.path.dirname(os.path.normpath(REF_INC))
-GOLDEN = os.path.join(cm.ROOT, "tests", "golden", "pres_ref.npz")
-RECORD = os.environ.get("MHH_RECORD_PRES_GOLDEN") == "1"
+GOLD = refshim.Golden("pres", None, "tests/test_pres_ref.py")       # recorded piece by piece, by the src=reference cases of the tests
+RECORD, golden = GOLD.record, GOLD.need
 DT = 0.7
 
 # (order, (itot, jtot, ktot), (igc, jgc, kgc)): the shapes of test_pres (tests/test_parity.py), an odd itot and jtot (the n/2+1 mirror
@@ -51,36 +47,22 @@ THERMO_SHAPES = [(70, 9, 10), (17, 9, 8), (20, 1, 12)]          # tests/test_the
 GRAV = 9.81                                                      # Constants::grav, which the reference's kernels read themselves
 
 
-def tag(dtype):
-    return "f64" if np.dtype(dtype) == np.float64 else "f32"
-
-
 def case_id(case):
     order, shape, gc = case
     return "o%d-%dx%dx%d-gc%d%d%d" % ((order,) + shape + gc)
 
 
-def have_reference():
-    return os.path.isdir(REF_INC) and os.path.isdir(os.path.join(REF_ROOT, "src"))
-
-
 # ---- the golden file ------------------------------------------------------------------------------------------------------------
-_golden = {}
+_digests = {}
 REC = {"arrays": {}, "digests": {}}
 
 
-def golden():
-    if "z" not in _golden:
-        assert os.path.exists(GOLDEN), "tests/golden/pres_ref.npz is missing: record it where the reference tree exists"
-        z = np.load(GOLDEN)
-        _golden["z"] = z
-        _golden["digests"] = json.loads(str(z["digests"]))
-    return _golden["z"]
-
-
-def digest(a):
-    a = np.ascontiguousarray(a)
-    return "%s %s %s" % (a.dtype.str, "x".join(map(str, a.shape)), hashlib.sha256(a.tobytes()).hexdigest())
+def golden_digest(key):
+    """The recorded digest of the reference's output `key` (the file's JSON table, parsed once per loaded file)."""
+    z = golden()
+    if _digests.get("of") is not z:
+        _digests.update(of=z, table=json.loads(str(z["digests"])))
+    return _digests["table"][key]
 
 
 def zprofile(ktot, zsize):
@@ -94,8 +76,7 @@ def zprofile(ktot, zsize):
 
 
 def write_record():
-    np.savez_compressed(GOLDEN, digests=np.array(json.dumps(REC["digests"], sort_keys=True)), **REC["arrays"])
-    _golden.clear()
+    GOLD.save(dict(digests=np.array(json.dumps(REC["digests"], sort_keys=True)), **REC["arrays"]))
 
 
 def expect_bits(src, key, got, run_ref):
@@ -108,8 +89,7 @@ def expect_bits(src, key, got, run_ref):
             REC["digests"][key] = digest(want)
         ok = got.shape == want.shape and got.dtype == want.dtype and np.array_equal(got, want)
         return ok, (key, "ulp", cm.ulp_diff(got, want)) if not ok and got.shape == want.shape and got.dtype.kind == "f" else (key,)
-    golden()
-    return digest(got) == _golden["digests"][key], MISMATCH % key
+    return digest(got) == golden_digest(key), MISMATCH % key
 
 
 def expect_values(src, key, run_ref):
@@ -129,14 +109,7 @@ MISMATCH = ("%s differs from the recorded reference output. The golden file hold
 
 def same_as_golden(key, got):
     """(equal, message) of the library's array got against the recorded digest of the reference's output."""
-    golden()
-    return digest(got) == _golden["digests"][key], MISMATCH % key
-
-
-def golden_digest(key):
-    """For the tests of the library, which never run the reference: the recorded digest."""
-    golden()
-    return _golden["digests"][key]
+    return digest(got) == golden_digest(key), MISMATCH % key
 
 
 # ---- grids and inputs ---------------------------------------------------------------------------------------------------------------
@@ -195,32 +168,15 @@ def field_with_packed(g, packed):
 
 
 # ---- the shim ---------------------------------------------------------------------------------------------------------------------
-_shim = {}
+def _bind(lib):
+    lib.ref_pres_divergence.restype = C.c_double
+    lib.ref_thermo_dry_grav.restype = C.c_double
+    lib.ref_calc_mean.restype = C.c_double
+    lib.ref_pres_set_fft.argtypes = [C.c_void_p, C.c_void_p]
 
 
-def shim():
-    """The shim compiled against the reference's tree into a temporary directory (kept for the session); None without the tree."""
-    if "lib" not in _shim:
-        if not have_reference():
-            _shim["lib"] = None
-        else:
-            _shim["tmp"] = tempfile.TemporaryDirectory()
-            so = os.path.join(_shim["tmp"].name, "libref_pres.so")
-            src = os.path.join(REF_ROOT, "src")
-            subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-DRESTRICTKEYWORD=__restrict__",
-                            "-I" + os.path.join(cm.ROOT, "tests", "stubs_syntax_only"), "-I" + REF_INC, "-I" + src, "-I" + os.path.join(cm.ROOT, "include"),
-                            "-fPIC", "-shared", "-fvisibility=hidden", "-ffunction-sections", "-fdata-sections", "-Wl,--gc-sections", "-Wl,-z,defs",
-                            "-o", so, os.path.join(cm.ROOT, "tests", "cpp", "ref_pres_shim.cpp"),
-                            os.path.join(cm.ROOT, "tests", "cpp", "ref_thermo_dry_shim.cpp"),
-                            os.path.join(cm.ROOT, "tests", "cpp", "ref_force_shim.cpp"), os.path.join(src, "master.cxx"),
-                            os.path.join(src, "master_serial.cxx")], check=True)
-            lib = C.CDLL(so)
-            lib.ref_pres_divergence.restype = C.c_double
-            lib.ref_thermo_dry_grav.restype = C.c_double
-            lib.ref_calc_mean.restype = C.c_double
-            lib.ref_pres_set_fft.argtypes = [C.c_void_p, C.c_void_p]
-            _shim["lib"] = lib
-    return _shim["lib"]
+shim = refshim.Shim("pres", ["ref_pres_shim.cpp", "ref_thermo_dry_shim.cpp", "ref_force_shim.cpp"], _bind, ref_sources=refshim.MASTER,
+                    stubs=True, project_include=True)
 
 
 @contextlib.contextmanager

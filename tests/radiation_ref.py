@@ -9,20 +9,15 @@ digest per case. ql and qt are INPUTS here (handed to the ql pointer), so that e
 and in the kernel and no cell has to be left out of a comparison.
 """
 import ctypes as C
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 import common as cm
 import moist_ref as M
+import refshim
+from refshim import Dims, code, dims_of, f32exact, have_reference, tag
 from microhh_amd.grid import Grid
 
-REF_ROOT = os.path.dirname(os.path.normpath(M.REF_INC))
-GOLDEN = os.path.join(cm.ROOT, "tests", "golden", "radiation_ref.npz")
-RECORD = os.environ.get("MHH_RECORD_RADIATION_GOLDEN") == "1"
 ZSIZE = 1500.
 LW, SW = 1, 2
 SWEEP, PLAIN = 0, 1
@@ -45,9 +40,6 @@ ZENITH_DAYS = (160.0, 160.25, 160.5)
 ZENITH_LONS = (0., -120.)
 # (parameters, sun) of every run; the golden file holds all of them for the SMALL shapes and the first for the others
 RUNS = [("dycoms", "day"), ("div0", "day"), ("divneg", "day"), ("dycoms", "low"), ("dycoms", "night"), ("dycoms", "edge")]
-
-tag, code, f32exact = M.tag, M.code, M.f32exact
-
 
 KGC2 = ((17, 9, 8), (1, 1, 2))       # the one layout with two vertical ghost levels: the literal-1 layer depth reads the ghost z
 
@@ -115,10 +107,7 @@ class CloudCase:
         self.thlt = f32exact(1.e-3*(rs.random_sample(n3) - 0.5))
 
     def digest(self):
-        h = hashlib.sha256()
-        for a in (self.ql, self.qt, self.thlt):
-            h.update(np.ascontiguousarray(a).tobytes())
-        return h.hexdigest()
+        return refshim.digest(self.ql, self.qt, self.thlt)
 
     def embed(self, a3, g, fill):
         """The (ktot, jtot, itot) block inside a [kcells][jcells][icells] array of g's dtype; every ghost cell holds `fill`, which no
@@ -149,31 +138,15 @@ def cloud_case(shape):
 
 
 # ---- the shim ---------------------------------------------------------------------------------------------------------------
-_shim = {}
-have_reference = M.have_reference
+def _bind(lib):
+    vp, ci, cd = C.c_void_p, C.c_int, C.c_double
+    lib.ref_rad_zenith.argtypes = [ci, cd, cd, cd]; lib.ref_rad_zenith.restype = cd
+    lib.ref_rad_exec.argtypes = [ci, C.POINTER(Dims)] + [cd]*5 + [vp]*8; lib.ref_rad_exec.restype = None
+    lib.ref_rad_lw.argtypes = [ci, C.POINTER(Dims)] + [cd]*4 + [vp]*6; lib.ref_rad_lw.restype = None
+    lib.ref_rad_sw.argtypes = [ci, C.POINTER(Dims), cd] + [vp]*6; lib.ref_rad_sw.restype = None
 
 
-def shim():
-    """The shim compiled against the reference's tree into a temporary directory (kept for the session); None without the tree."""
-    if "lib" not in _shim:
-        if not have_reference():
-            _shim["lib"] = None
-        else:
-            _shim["tmp"] = tempfile.TemporaryDirectory()
-            so = os.path.join(_shim["tmp"].name, "libref_radiation.so")
-            src = os.path.join(REF_ROOT, "src")
-            subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-DRESTRICTKEYWORD=__restrict__", "-I" + M.REF_INC, "-I" + src,
-                            "-fPIC", "-shared", "-fvisibility=hidden", "-ffunction-sections", "-fdata-sections", "-Wl,--gc-sections", "-o", so,
-                            os.path.join(cm.ROOT, "tests", "cpp", "ref_radiation_shim.cpp"), os.path.join(src, "master.cxx"),
-                            os.path.join(src, "master_serial.cxx")], check=True)
-            lib = C.CDLL(so)
-            vp, ci, cd = C.c_void_p, C.c_int, C.c_double
-            lib.ref_rad_zenith.argtypes = [ci, cd, cd, cd]; lib.ref_rad_zenith.restype = cd
-            lib.ref_rad_exec.argtypes = [ci, C.POINTER(M.Dims)] + [cd]*5 + [vp]*8; lib.ref_rad_exec.restype = None
-            lib.ref_rad_lw.argtypes = [ci, C.POINTER(M.Dims)] + [cd]*4 + [vp]*6; lib.ref_rad_lw.restype = None
-            lib.ref_rad_sw.argtypes = [ci, C.POINTER(M.Dims), cd] + [vp]*6; lib.ref_rad_sw.restype = None
-            _shim["lib"] = lib
-    return _shim["lib"]
+shim = refshim.Shim("radiation", ["ref_radiation_shim.cpp"], _bind, ref_sources=refshim.MASTER)
 
 
 def ref_zenith(dtype, lon, day):
@@ -196,7 +169,7 @@ def ref_exec(shape, dtype, par, mu, parts=LW | SW, zero_tend=False, gc=(1, 1, 1)
     reference runs and keeping the wanted one), lflx and sflx as get_radiation_field gives them."""
     c, g = cloud_case(shape), grid_of(shape, gc, dtype)
     h = c.inputs(g, zero_tend)
-    d = M.dims_of(g)
+    d = dims_of(g)
     p = PARAMS[par]
     lib = shim()
     t = np.dtype(dtype).type
@@ -253,33 +226,8 @@ def _compute_all():
     return rec
 
 
-_all, _golden = {}, {}
-
-
-def golden():
-    if "z" not in _golden:
-        _golden["z"] = np.load(GOLDEN) if os.path.exists(GOLDEN) else None
-    return _golden["z"]
-
-
-def computed():
-    if "rec" not in _all:
-        _all["rec"] = _compute_all() if have_reference() else None
-    return _all["rec"]
-
-
-def exact_here(be):
-    """emul with the shim compiled on this host: the same C library and no contraction, so what passes through exp, pow and sqrt
-    must agree bit for bit too."""
-    return be.name == "emul" and have_reference() and not RECORD
-
-
-def ref(key, be=None):
-    if have_reference() and (be is None or be.name == "emul") and not RECORD:
-        return computed()[key]
-    z = golden()
-    assert z is not None, "tests/golden/radiation_ref.npz is missing: record it where the reference tree exists"
-    return z[key]
+GOLD = refshim.Golden("radiation", _compute_all, "tests/test_radiation_exec.py")
+RECORD, golden, computed, exact_here, ref, record_if_asked = GOLD.record, GOLD.golden, GOLD.computed, GOLD.exact_here, GOLD.ref, GOLD.record_if_asked
 
 
 # ---- the device -------------------------------------------------------------------------------------------------------------
@@ -322,11 +270,3 @@ class Dev:
 
     def out(self):
         return {n: self.be.host(self.d[n]).reshape(self.g.shape3) for n in OUT}
-
-
-def record_if_asked():
-    """MHH_RECORD_RADIATION_GOLDEN=1: write the golden file from the shim (the first test of tests/test_radiation_exec.py calls this)."""
-    if RECORD:
-        rec = _compute_all()
-        np.savez_compressed(GOLDEN, **rec)
-        _golden.clear()

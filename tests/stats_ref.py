@@ -10,21 +10,16 @@ their digest per case. Two things are restated in NumPy: the cyclic fill of the 
 Stats<TF> that cannot be reached without an object (one loop, float64, in row order).
 """
 import ctypes as C
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 import common as cm
 import moist_ref as M
+import refshim
+from refshim import Dims, code, dims_of, f32exact, have_reference, tag
 from microhh_amd.grid import Grid
 from microhh_amd import stats as S
 
-REF_ROOT = os.path.dirname(os.path.normpath(M.REF_INC))
-GOLDEN = os.path.join(cm.ROOT, "tests", "golden", "stats_ref.npz")
-RECORD = os.environ.get("MHH_RECORD_STATS_GOLDEN") == "1"
 ZSIZE = 3000.
 
 # (itot, jtot, ktot): 70 crosses a 64-lane row; jtot = 1 is the degenerate row; 37 rows make two row chunks with a ragged second one
@@ -37,8 +32,6 @@ VARS = [("a", 0, 0.5, 0., ("mean", "2", "3", "4", "grad")), ("wh", 1, 0., 0., ("
         ("q", 0, 0., 1.e-5, ("mean", "frac", "path", "cover"))]
 BOT_OFFSET = 0.25
 OPCODE = {"mean": S.MEAN, "2": S.MOMENT2, "3": S.MOMENT3, "4": S.MOMENT4, "frac": S.FRAC, "grad": S.GRAD}
-
-tag, code, f32exact, have_reference = M.tag, M.code, M.f32exact, M.have_reference
 
 
 def flags(n):
@@ -95,10 +88,7 @@ class StatCase:
         self.f = f
 
     def digest(self):
-        h = hashlib.sha256()
-        for k in sorted(self.f):
-            h.update(np.ascontiguousarray(self.f[k], dtype=np.float64).tobytes())
-        return h.hexdigest()
+        return refshim.digest(*[np.asarray(self.f[k], dtype=np.float64) for k in sorted(self.f)])
 
     def host(self, g):
         """Host arrays of grid g's dtype and layout; horizontal ghost cells hold 777, which no kernel may read into a result."""
@@ -154,48 +144,30 @@ def case_grid(shape, gc, dtype, kind):
 
 
 # ---- the shim ---------------------------------------------------------------------------------------------------------------
-_shim = {}
+def _bind(lib):
+    vp, ci, cd, cu = C.c_void_p, C.c_int, C.c_double, C.c_uint
+    DP = C.POINTER(Dims)
+    lib.ref_stats_thres.argtypes = [ci, DP, ci, vp, vp, cu, cu, vp, vp, vp, cd]; lib.ref_stats_thres.restype = None
+    lib.ref_stats_counts.argtypes = [ci, DP, ci, vp, vp, cu, cu, vp, vp, vp, vp, vp]; lib.ref_stats_counts.restype = None
+    lib.ref_stats_prof.argtypes = [ci, DP, ci, vp, vp, vp, cd, cd, vp, cu, vp]; lib.ref_stats_prof.restype = None
+    lib.ref_stats_columns.argtypes = [ci, DP, vp, vp, vp, vp, cd, cd, vp, cu, vp]; lib.ref_stats_columns.restype = None
+    lib.ref_stats_mean_2d.argtypes = [ci, DP, ci, ci, vp, cd]; lib.ref_stats_mean_2d.restype = cd
+    lib.ref_stats_ql_h.argtypes = [ci, DP, vp, vp, vp, vp]; lib.ref_stats_ql_h.restype = None
+    lib.ref_stats_flux_advec_2.argtypes = [ci, DP, ci, vp, vp, vp]; lib.ref_stats_flux_advec_2.restype = None
+    lib.ref_stats_flux_advec_2i5.argtypes = [ci, DP, ci, vp, vp, vp]; lib.ref_stats_flux_advec_2i5.restype = None
+    lib.ref_stats_flux_diff_2.argtypes = [ci, DP, vp, vp, cd, vp]; lib.ref_stats_flux_diff_2.restype = None
+    lib.ref_stats_flux_diff_smag2.argtypes = [ci, DP, ci, ci, vp, vp, vp, vp, vp, vp, cd, vp, cd, cd]; lib.ref_stats_flux_diff_smag2.restype = None
 
 
-def shim():
-    """The shim compiled against the reference's tree into a temporary directory (kept for the session); None without the tree.
-    The two NetCDF fill values are the constants of netcdf.h, which the one-macro stub of tests/stubs_syntax_only does not carry."""
-    if "lib" not in _shim:
-        if not have_reference():
-            _shim["lib"] = None
-        else:
-            _shim["tmp"] = tempfile.TemporaryDirectory()
-            so = os.path.join(_shim["tmp"].name, "libref_stats.so")
-            src = os.path.join(REF_ROOT, "src")
-            subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-DRESTRICTKEYWORD=__restrict__",
-                            "-DNC_FILL_DOUBLE=9.9692099683868690e+36", "-DNC_FILL_FLOAT=9.9692099683868690e+36f", "-I" + M.REF_INC, "-I" + src,
-                            "-I" + os.path.join(cm.ROOT, "tests", "stubs_syntax_only"),
-                            "-fPIC", "-shared", "-fvisibility=hidden", "-ffunction-sections", "-fdata-sections", "-Wl,--gc-sections", "-o", so,
-                            os.path.join(cm.ROOT, "tests", "cpp", "ref_stats_shim.cpp"),
-                            os.path.join(cm.ROOT, "tests", "cpp", "ref_stats_qlh_shim.cpp")] +
-                           [os.path.join(cm.ROOT, "tests", "cpp", "ref_stats_flux_%s_shim.cpp" % n) for n in ("advec_2", "advec_2i5", "diff_2", "diff_smag2")],
-                           check=True)
-            lib = C.CDLL(so)
-            vp, ci, cd, cu = C.c_void_p, C.c_int, C.c_double, C.c_uint
-            DP = C.POINTER(M.Dims)
-            lib.ref_stats_thres.argtypes = [ci, DP, ci, vp, vp, cu, cu, vp, vp, vp, cd]; lib.ref_stats_thres.restype = None
-            lib.ref_stats_counts.argtypes = [ci, DP, ci, vp, vp, cu, cu, vp, vp, vp, vp, vp]; lib.ref_stats_counts.restype = None
-            lib.ref_stats_prof.argtypes = [ci, DP, ci, vp, vp, vp, cd, cd, vp, cu, vp]; lib.ref_stats_prof.restype = None
-            lib.ref_stats_columns.argtypes = [ci, DP, vp, vp, vp, vp, cd, cd, vp, cu, vp]; lib.ref_stats_columns.restype = None
-            lib.ref_stats_mean_2d.argtypes = [ci, DP, ci, ci, vp, cd]; lib.ref_stats_mean_2d.restype = cd
-            lib.ref_stats_ql_h.argtypes = [ci, DP, vp, vp, vp, vp]; lib.ref_stats_ql_h.restype = None
-            lib.ref_stats_flux_advec_2.argtypes = [ci, DP, ci, vp, vp, vp]; lib.ref_stats_flux_advec_2.restype = None
-            lib.ref_stats_flux_advec_2i5.argtypes = [ci, DP, ci, vp, vp, vp]; lib.ref_stats_flux_advec_2i5.restype = None
-            lib.ref_stats_flux_diff_2.argtypes = [ci, DP, vp, vp, cd, vp]; lib.ref_stats_flux_diff_2.restype = None
-            lib.ref_stats_flux_diff_smag2.argtypes = [ci, DP, ci, ci, vp, vp, vp, vp, vp, vp, cd, vp, cd, cd]; lib.ref_stats_flux_diff_smag2.restype = None
-            _shim["lib"] = lib
-    return _shim["lib"]
+shim = refshim.Shim("stats", ["ref_stats_shim.cpp", "ref_stats_qlh_shim.cpp"] +
+                    ["ref_stats_flux_%s_shim.cpp" % n for n in ("advec_2", "advec_2i5", "diff_2", "diff_smag2")], _bind,
+                    defines=refshim.NC_FILL, stubs=True)
 
 
 def ref_ql_h(g, thl, qt, prefh):
     """calc_liquid_water_h (src/thermo_moist.cxx:368-411) on host arrays of grid g: ql_h over a zero field."""
     out = np.zeros(g.shape3, dtype=g.np_dtype)
-    d = M.dims_of(g)
+    d = dims_of(g)
     shim().ref_stats_ql_h(code(g.np_dtype), C.byref(d), cm.ptr(out), cm.ptr(np.ascontiguousarray(thl)), cm.ptr(np.ascontiguousarray(qt)),
                           cm.ptr(np.ascontiguousarray(prefh)))
     return out
@@ -269,7 +241,7 @@ def ref_case(shape, gc, dtype, kind="seeded"):
     """Everything the reference gives on one case: {key: array}."""
     lib = shim()
     c, g = case_of(shape, kind), case_grid(shape, gc, dtype, kind)
-    h, d, cd = c.host(g), M.dims_of(g), code(dtype)
+    h, d, cd = c.host(g), dims_of(g), code(dtype)
     t = g.np_dtype
     nm = len(MASKS)
     out = {}
@@ -345,7 +317,7 @@ def flux_host(c, g):
 def ref_flux_fields(g, h, mean, wmean):
     """The reference's flux FIELDS of one mask: {key: [kcells][jcells][icells]}. fld' and w' are subtract_mean's (stats.cxx:514-535,
     a subtraction in the dtype, restated here) over zero-filled tmp fields: fld' on kstart .. kend-1, w' on kstart .. kend."""
-    lib, t, d, cd_ = shim(), g.np_dtype, M.dims_of(g), code(g.np_dtype)
+    lib, t, d, cd_ = shim(), g.np_dtype, dims_of(g), code(g.np_dtype)
     ks, ke = g.kstart, g.kend
     ap, wp = np.zeros(g.shape3, dtype=t), np.zeros(g.shape3, dtype=t)
     with np.errstate(over="ignore", invalid="ignore"):
@@ -375,7 +347,7 @@ def ref_fluxes(shape, gc, dtype, base):
     bound, the masked mean of |flux| per level."""
     lib = shim()
     c, g = case_of(shape), grid_of(shape, gc, dtype)
-    h, d, cd_, t = flux_host(c, g), M.dims_of(g), code(dtype), g.np_dtype
+    h, d, cd_, t = flux_host(c, g), dims_of(g), code(dtype), g.np_dtype
     nm = len(MASKS)
     mf = np.ascontiguousarray(base["mfield"].astype(np.uint32))
     out = {}
@@ -430,38 +402,13 @@ def _compute_all():
     return rec
 
 
-_all, _golden = {}, {}
-
-
-def golden():
-    if "z" not in _golden:
-        _golden["z"] = np.load(GOLDEN) if os.path.exists(GOLDEN) else None
-    return _golden["z"]
-
-
-def computed():
-    if "rec" not in _all:
-        _all["rec"] = _compute_all() if have_reference() else None
-    return _all["rec"]
+GOLD = refshim.Golden("stats", _compute_all, "tests/test_stats_masks.py")
+RECORD, golden, computed, record_if_asked = GOLD.record, GOLD.golden, GOLD.computed, GOLD.record_if_asked
 
 
 def ref(shape, gc, dtype, kind, name, be=None):
-    """A reference result by name: from the shim on this host, else (and always on the GPU backend) from the golden file."""
-    if name.startswith("mfield"):
-        dtype = cm.DTYPES[0]
-    key = case_key(shape, gc, dtype, kind) + name
-    if have_reference() and (be is None or be.name == "emul") and not RECORD:
-        return computed()[key]
-    z = golden()
-    assert z is not None, "tests/golden/stats_ref.npz is missing: record it where the reference tree exists"
-    return z[key]
-
-
-def record_if_asked():
-    """MHH_RECORD_STATS_GOLDEN=1: write the golden file from the shim (the first test of tests/test_stats_masks.py calls this)."""
-    if RECORD:
-        np.savez_compressed(GOLDEN, **_compute_all())
-        _golden.clear()
+    """A reference result by name (Golden.ref); the mask words are stored once, under the first dtype."""
+    return GOLD.ref(case_key(shape, gc, cm.DTYPES[0] if name.startswith("mfield") else dtype, kind) + name, be)
 
 
 # ---- the device -------------------------------------------------------------------------------------------------------------

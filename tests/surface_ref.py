@@ -6,19 +6,15 @@ tests/golden/surface_ref.npz, recorded with MHH_RECORD_SURFACE_GOLDEN=1 python -
 and the reference outputs of every case, and the digests of the four lookup tables (the tables themselves are 80 kB each).
 """
 import ctypes as C
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 import common as cm
+import refshim
+from refshim import digest, have_reference  # noqa: F401
 from microhh_amd import capi
 from microhh_amd.grid import Grid
 
-REF_INC = os.environ.get("MHH_REFERENCE_INCLUDE", "/root/reference/include")     # point it elsewhere to run against the golden file
-GOLDEN = os.path.join(cm.ROOT, "tests", "golden", "surface_ref.npz")
 NZL = 10000
 DIRICHLET, NEUMANN, FLUX, USTAR = 0, 1, 2, 3
 NONE, DRY, BUOY = 0, 1, 2
@@ -126,28 +122,12 @@ class RefIO(C.Structure):
                 ("dudz", C.c_void_p), ("dvdz", C.c_void_p), ("dbdz", C.c_void_p)]
 
 
-_shim = {}
+def _bind(lib):
+    lib.ref_surface_exec.argtypes = [C.POINTER(RefIO)]; lib.ref_surface_exec.restype = None
+    lib.ref_surface_lut.argtypes = [C.c_double]*3 + [C.c_int]*3 + [C.c_void_p]*2; lib.ref_surface_lut.restype = None
 
 
-def have_reference():
-    return os.path.isdir(REF_INC)
-
-
-def shim():
-    """The shim compiled against the reference's headers into a temporary directory (kept for the session); None without the tree."""
-    if "lib" not in _shim:
-        if not have_reference():
-            _shim["lib"] = None
-        else:
-            _shim["tmp"] = tempfile.TemporaryDirectory()
-            so = os.path.join(_shim["tmp"].name, "libref_surface.so")
-            subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-I" + REF_INC, "-o", so,
-                            os.path.join(cm.ROOT, "tests", "cpp", "ref_surface_shim.cpp")], check=True)
-            lib = C.CDLL(so)
-            lib.ref_surface_exec.argtypes = [C.POINTER(RefIO)]; lib.ref_surface_exec.restype = None
-            lib.ref_surface_lut.argtypes = [C.c_double]*3 + [C.c_int]*3 + [C.c_void_p]*2; lib.ref_surface_lut.restype = None
-            _shim["lib"] = lib
-    return _shim["lib"]
+shim = refshim.Shim("surface", ["ref_surface_shim.cpp"], _bind)
 
 
 def zsl_of(g):
@@ -160,13 +140,6 @@ def lut(fn, g, mbcbot, thermobc):
     rc = fn(zsl_of(g), Z0M, Z0H, mbcbot, thermobc, g.dtype, cm.ptr(zL), cm.ptr(f))
     assert not rc, rc
     return zL, f
-
-
-def digest(*arrays):
-    h = hashlib.sha256()
-    for a in arrays:
-        h.update(np.ascontiguousarray(a).tobytes())
-    return h.hexdigest()
 
 
 def ref_exec(case, inp, st, table, dutot=None):
@@ -202,19 +175,13 @@ def ref_exec(case, inp, st, table, dutot=None):
     return out
 
 
-_golden = {}
-
-
-def golden():
-    if "z" not in _golden:
-        _golden["z"] = np.load(GOLDEN) if os.path.exists(GOLDEN) else None
-    return _golden["z"]
+GOLD = refshim.Golden("surface", None, "tests/test_surface_ref.py")      # its first test holds every case and records them
+RECORD, golden = GOLD.record, GOLD.golden
 
 
 def golden_case(case):
     """(inputs, reference outputs) of a case from the golden file."""
-    z = golden()
-    assert z is not None, "tests/golden/surface_ref.npz is missing: record it where the reference tree exists"
+    z = GOLD.need()
     mid = case.id.rsplit("-", 1)[0]
     master = {k: z["%s/in/%s" % (mid, k)] for k in case.master}
     return case.inputs(master), {k: z["%s/out/%s" % (case.id, k)] for k in case.out_names()}

@@ -2,36 +2,26 @@
 masks of a Stats_sampler and exec_stats with every group on 32 x 8 x 16 from inputs this test writes, and gives the bits of the same
 calls made through the Python driver (microhh_amd.budget.Budget2Sampler). Built here with hipcc into a temporary directory."""
 import os
-import subprocess
 import tempfile
 
 import numpy as np
 import pytest
 
-import common as cm
+import hostprog
 import stats_ref as R
 from microhh_amd import budget as BU
 from microhh_amd import stats as S
 from microhh_amd.grid import DIFF_SMAG2, Grid
 
-CPP = os.path.join(cm.ROOT, "tests", "cpp")
-LIBDIR = os.path.join(cm.ROOT, "microhh_amd")
 GRID = (32, 8, 16)
 UTRANS, VTRANS, FC = 1.5, -0.5, 1.e-4
 MASKS = ("default", "wpos", "wneg")
 ALL = 0x7ff
 
 
-def _compile(out):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-o", out, os.path.join(CPP, "host_budget.cpp"),
-                    "-L" + LIBDIR, "-lmhh_hip", "-Wl,-rpath," + LIBDIR], check=True)
-
-
 def test_budget_host_program_compiles():
     """not gpu: the program and the host class it drives build against the library."""
-    with tempfile.TemporaryDirectory() as tmp:
-        _compile(os.path.join(tmp, "host_budget"))
+    hostprog.compile("host_budget")
 
 
 @pytest.mark.gpu
@@ -57,14 +47,10 @@ def test_cpp_host_budget_gives_the_bits_of_the_python_driver():
     want, model = want.cpu().numpy(), model.cpu().numpy()
     names = bs.names(ALL)
     with tempfile.TemporaryDirectory() as tmp:
-        exe, fin, fout = (os.path.join(tmp, n) for n in ("host_budget", "in.bin", "out.bin"))
-        _compile(exe)
-        with open(fin, "wb") as fh:
-            for x in [f3[n] for n in ("u", "v", "w", "p", "evisc", "b")] + [f2["u_fluxbot"], f2["v_fluxbot"], g.z, g.zh, g.dz, g.dzh, g.dzi, g.dzhi]:
-                np.ascontiguousarray(x, dtype=np.float64).tofile(fh)
-        r = subprocess.run([exe, fin, fout, *[str(n) for n in GRID], repr(UTRANS), repr(VTRANS), repr(FC)], capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0 and "host_budget ok" in r.stdout, r.stdout + r.stderr
-        got = np.fromfile(fout, dtype=np.float64)
+        fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
+        hostprog.write_doubles(fin, [f3[n] for n in ("u", "v", "w", "p", "evisc", "b")] + [f2["u_fluxbot"], f2["v_fluxbot"], g.z, g.zh, g.dz, g.dzh, g.dzi, g.dzhi])
+        hostprog.run(hostprog.compile("host_budget"), fin, fout, *GRID, repr(UTRANS), repr(VTRANS), repr(FC))
+        got = hostprog.read_doubles(fout)
     kc = g.kcells
     per = (3 + len(names))*kc
     assert got.size == len(MASKS)*per and len(names) == 43

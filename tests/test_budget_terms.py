@@ -196,8 +196,8 @@ def test_dry_buoyancy(be, dtype):
     t = g.np_dtype
     th = (300. + BR.case_of(shape, kind).host(g)["b"]).astype(t)
     thref = (300. + 0.01*np.arange(g.kcells)).astype(t)
-    b = be.zeros(g.shape3, dtype)
-    B.ok(be, be.lib.mhh_thermo_dry_buoyancy(be.grid(g), be.ptr(b), be.ptr(be.arr(th)), be.ptr(be.arr(thref)), GRAV, be.stream))
+    b, dth, dthref = be.zeros(g.shape3, dtype), be.arr(th), be.arr(thref)         # held until the call has run: ptr keeps no reference
+    B.ok(be, be.lib.mhh_thermo_dry_buoyancy(be.grid(g), be.ptr(b), be.ptr(dth), be.ptr(dthref), GRAV, be.stream))
     be.sync()
     want = (t.type(GRAV)/thref)[:, None, None] * (th - thref[:, None, None])
     js, ie = slice(g.jstart, g.jend), slice(g.istart, g.iend)

@@ -3,31 +3,21 @@ of u, w, th, thlngrad and the planes thpath, thfluxbot, thbase, thtop on 32 x 8 
 the ones the Python driver (microhh_amd.cross.Cross behind a HotPath) writes from the same fields, byte for byte. Built here with
 hipcc into a temporary directory."""
 import os
-import subprocess
 import tempfile
 
 import numpy as np
 import pytest
 
-import common as cm
+import hostprog
 
-CPP = os.path.join(cm.ROOT, "tests", "cpp")
-LIBDIR = os.path.join(cm.ROOT, "microhh_amd")
 GRID = (32, 8, 16)
 IOTIME, UTRANS, THRESHOLD = 3600, 2.5, 301.9125      # the threshold: the mean of th on level 8, so that the base varies over the columns
 LOC = dict(xy=[0., 610., 1200.], xz=[0., 1700., 3200.], yz=[1650., 3200.])
 
 
-def _compile(out):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-o", out, os.path.join(CPP, "host_cross.cpp"),
-                    "-L" + LIBDIR, "-lmhh_hip", "-Wl,-rpath," + LIBDIR], check=True)
-
-
 def test_cross_host_program_compiles():
     """not gpu: the program and the host class it drives build against the library."""
-    with tempfile.TemporaryDirectory() as tmp:
-        _compile(os.path.join(tmp, "host_cross"))
+    hostprog.compile("host_cross")
 
 
 @pytest.mark.gpu
@@ -49,14 +39,10 @@ def test_cpp_host_cross_writes_the_files_of_the_python_driver():
             fieldio.save_xy_slice(fieldio.cross_filename(pydir, name, "xy", None, IOTIME), out.cpu().numpy(), g)
         base = fieldio.load_xy_slice(fieldio.cross_filename(pydir, "thbase", "xy", None, IOTIME), g)
         assert (base > 0).any() and len(np.unique(base)) > 1
-        exe, fin = os.path.join(tmp, "host_cross"), os.path.join(tmp, "in.bin")
-        _compile(exe)
+        fin = os.path.join(tmp, "in.bin")
         host = lambda t: t.detach().cpu().numpy()      # noqa: E731
-        with open(fin, "wb") as fh:
-            for x in (host(hp.u), host(hp.w), host(hp.s[0]), host(hp.surf["s_fluxbot"]), host(hp.rhoref), g.z, g.zh, g.dz, g.dzh, g.dzi, g.dzhi):
-                np.ascontiguousarray(x, dtype=np.float64).tofile(fh)
-        r = subprocess.run([exe, fin, cppdir, *[str(n) for n in GRID], str(IOTIME), repr(UTRANS), repr(THRESHOLD)], capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0 and "host_cross ok" in r.stdout, r.stdout + r.stderr
+        hostprog.write_doubles(fin, (host(hp.u), host(hp.w), host(hp.s[0]), host(hp.surf["s_fluxbot"]), host(hp.rhoref), g.z, g.zh, g.dz, g.dzh, g.dzi, g.dzhi))
+        hostprog.run(hostprog.compile("host_cross"), fin, cppdir, *GRID, IOTIME, repr(UTRANS), repr(THRESHOLD))
         hp.close()
         want = sorted(os.listdir(pydir))
         assert sorted(os.listdir(cppdir)) == want and len(want) == 4*8 + 4

@@ -3,7 +3,6 @@ Force::exec (the sponge with fixed profiles, geostrophic wind + Coriolis, large-
 writes, and gives the bits of the same calls made through the Python binding. Built here with hipcc into a temporary directory."""
 import ctypes as C
 import os
-import subprocess
 import tempfile
 
 import numpy as np
@@ -11,24 +10,16 @@ import pytest
 
 import backends as B
 import common as cm
+import hostprog
 from common import same_bits as same
 from microhh_amd import capi, forcing
 
-CPP = os.path.join(cm.ROOT, "tests", "cpp")
-LIBDIR = os.path.join(cm.ROOT, "microhh_amd")
 NAMES = ["u", "v", "w", "s0", "s1"]
-
-
-def _compile(out):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-o", out, os.path.join(CPP, "host_force.cpp"),
-                    "-L" + LIBDIR, "-lmhh_hip", "-Wl,-rpath," + LIBDIR], check=True)
 
 
 def test_force_host_program_compiles():
     """not gpu: the program and the host classes it drives build against the library."""
-    with tempfile.TemporaryDirectory() as tmp:
-        _compile(os.path.join(tmp, "host_force"))
+    hostprog.compile("host_force")
 
 
 @pytest.mark.gpu
@@ -58,15 +49,11 @@ def test_cpp_host_buffer_and_force_give_the_bits_of_the_python_calls():
     assert not same(want[0], c.ut) and not same(want[2], c.wt)
     # the C++ program on the same inputs
     with tempfile.TemporaryDirectory() as tmp:
-        exe, fin, fout = (os.path.join(tmp, n) for n in ("host_force", "in.bin", "out.bin"))
-        _compile(exe)
-        with open(fin, "wb") as fh:
-            for a in [g.z, g.zh, g.dz, g.dzh, g.dzi, g.dzhi, c.u, c.v, c.w, c.s[0], c.s[1], c.ut, c.vt, c.wt, c.st[0], c.st[1]] + profs:
-                np.ascontiguousarray(a, dtype=np.float64).tofile(fh)
-        args = [exe, fin, fout, "17", "9", "8"] + [repr(float(x)) for x in (g.xsize, g.ysize, g.zsize, zstart, sigma, beta, fc, utrans, vtrans)]
-        r = subprocess.run(args, capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0 and "host_force ok" in r.stdout, r.stdout + r.stderr
-        assert "bufferkstart %d bufferkstarth %d" % (b.bufferkstart, b.bufferkstarth) in r.stdout
-        got = np.fromfile(fout, dtype=np.float64).reshape((5,) + tuple(g.shape3))
+        fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
+        hostprog.write_doubles(fin, [g.z, g.zh, g.dz, g.dzh, g.dzi, g.dzhi, c.u, c.v, c.w, c.s[0], c.s[1], c.ut, c.vt, c.wt, c.st[0], c.st[1]] + profs)
+        out = hostprog.run(hostprog.compile("host_force"), fin, fout, "17", "9", "8",
+                           *[repr(float(x)) for x in (g.xsize, g.ysize, g.zsize, zstart, sigma, beta, fc, utrans, vtrans)])
+        assert "bufferkstart %d bufferkstarth %d" % (b.bufferkstart, b.bufferkstarth) in out
+        got = hostprog.read_doubles(fout).reshape((5,) + tuple(g.shape3))
     for n, a, w in zip(NAMES, got, want):
         assert same(a, w), (n, cm.ulp_diff(a, w))

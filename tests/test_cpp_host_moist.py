@@ -3,31 +3,22 @@ exec (the base state on the device and the buoyancy tendency) and get_thermo_fie
 and gives the bits of the same calls made through the Python driver (HotPath with thermo=Moist). Built here with hipcc into a
 temporary directory."""
 import os
-import subprocess
 import tempfile
 
 import numpy as np
 import pytest
 
 import common as cm
+import hostprog
 from common import same_bits as same
 
-CPP = os.path.join(cm.ROOT, "tests", "cpp")
-LIBDIR = os.path.join(cm.ROOT, "microhh_amd")
 GRID = (32, 8, 24)
 PBOT = 101500.
 
 
-def _compile(out):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-o", out, os.path.join(CPP, "host_moist.cpp"),
-                    "-L" + LIBDIR, "-lmhh_hip", "-Wl,-rpath," + LIBDIR], check=True)
-
-
 def test_moist_host_program_compiles():
     """not gpu: the program and the host class it drives build against the library."""
-    with tempfile.TemporaryDirectory() as tmp:
-        _compile(os.path.join(tmp, "host_moist"))
+    hostprog.compile("host_moist")
 
 
 @pytest.mark.gpu
@@ -39,19 +30,15 @@ def test_cpp_host_thermo_moist_gives_the_bits_of_the_python_driver():
     host = lambda t: t.detach().cpu().numpy().astype(np.float64)          # noqa: E731
     thl0, qt0 = thermo.bomex_profiles(g.z[g.kstart:g.kend])
     with tempfile.TemporaryDirectory() as tmp:
-        exe, fin, fout = (os.path.join(tmp, n) for n in ("host_moist", "in.bin", "out.bin"))
-        _compile(exe)
-        with open(fin, "wb") as fh:
-            for a in (host(hp.s[0]), host(hp.s[1]), host(hp.wt), thl0, qt0, g.z, g.zh, g.dz, g.dzh, g.dzi, g.dzhi):
-                np.ascontiguousarray(a, dtype=np.float64).tofile(fh)
+        fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
+        hostprog.write_doubles(fin, (host(hp.s[0]), host(hp.s[1]), host(hp.wt), thl0, qt0, g.z, g.zh, g.dz, g.dzh, g.dzi, g.dzhi))
         th.means(); hp.thermo_moist()
         ql = th.field("ql")
         th.check()
         want = [host(hp.wt), host(ql)] + [host(th.tab[n]) for n in thermo.BASE_STATE]
         hp.close()
-        r = subprocess.run([exe, fin, fout, *[str(n) for n in GRID], repr(PBOT)], capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0 and "host_moist ok" in r.stdout, r.stdout + r.stderr
-        got = np.fromfile(fout, dtype=np.float64)
+        hostprog.run(hostprog.compile("host_moist"), fin, fout, *GRID, repr(PBOT))
+        got = hostprog.read_doubles(fout)
     n3 = int(np.prod(g.shape3))
     parts = [got[:n3].reshape(g.shape3), got[n3:2*n3].reshape(g.shape3)] + [got[2*n3 + k*g.kcells:2*n3 + (k+1)*g.kcells] for k in range(8)]
     assert float(want[1].max()) > 0

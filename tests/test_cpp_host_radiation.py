@@ -2,31 +2,22 @@
 get_radiation_field on 64 x 8 x 32 from inputs this test writes, and gives the bits of the same calls made through the Python driver
 (HotPath("dycoms", ..., radiation=Gcss(...))). Built here with hipcc into a temporary directory."""
 import os
-import subprocess
 import tempfile
 
 import numpy as np
 import pytest
 
 import common as cm
+import hostprog
 from common import same_bits as same
 
-CPP = os.path.join(cm.ROOT, "tests", "cpp")
-LIBDIR = os.path.join(cm.ROOT, "microhh_amd")
 GRID = (64, 8, 32)
 DAY = 160.5
 
 
-def _compile(out):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-o", out, os.path.join(CPP, "host_radiation.cpp"),
-                    "-L" + LIBDIR, "-lmhh_hip", "-Wl,-rpath," + LIBDIR], check=True)
-
-
 def test_radiation_host_program_compiles():
     """not gpu: the program and the host class it drives build against the library."""
-    with tempfile.TemporaryDirectory() as tmp:
-        _compile(os.path.join(tmp, "host_radiation"))
+    hostprog.compile("host_radiation")
 
 
 @pytest.mark.gpu
@@ -41,12 +32,9 @@ def test_cpp_host_radiation_gives_the_bits_of_the_python_driver():
     g, th, rad = hp.grid, hp.thermo, hp.radiation
     host = lambda t: t.detach().cpu().numpy().astype(np.float64)          # noqa: E731
     with tempfile.TemporaryDirectory() as tmp:
-        exe, fin, fout = (os.path.join(tmp, n) for n in ("host_radiation", "in.bin", "out.bin"))
-        _compile(exe)
-        with open(fin, "wb") as fh:
-            for a in ([host(hp.s[0]), host(hp.s[1]), host(hp.st[0]), host(th.tab["pref"]), host(th.tab["exnref"]), host(hp.rhoref)] +
-                      [g.z, g.zh, g.dz, g.dzh, g.dzi, g.dzhi]):
-                np.ascontiguousarray(a, dtype=np.float64).tofile(fh)
+        fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
+        hostprog.write_doubles(fin, [host(hp.s[0]), host(hp.s[1]), host(hp.st[0]), host(th.tab["pref"]), host(th.tab["exnref"]), host(hp.rhoref)] +
+                               [g.z, g.zh, g.dz, g.dzh, g.dzi, g.dzhi])
         before = host(hp.st[0])
         rad.exec()
         f = rad.fields()
@@ -54,10 +42,8 @@ def test_cpp_host_radiation_gives_the_bits_of_the_python_driver():
         want = [host(hp.st[0]), host(f["lflx"]), host(f["sflx"])]
         mu = rad.mu
         hp.close()
-        r = subprocess.run([exe, fin, fout, *[str(n) for n in GRID], *[repr(c[k]) for k in ("xka", "fr0", "fr1", "div", "lat", "lon")], repr(DAY)],
-                           capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0 and "host_radiation ok" in r.stdout, r.stdout + r.stderr
-        got = np.fromfile(fout, dtype=np.float64)
+        hostprog.run(hostprog.compile("host_radiation"), fin, fout, *GRID, *[repr(c[k]) for k in ("xka", "fr0", "fr1", "div", "lat", "lon")], repr(DAY))
+        got = hostprog.read_doubles(fout)
     n3 = int(np.prod(g.shape3))
     assert got.size == 3*n3 + 1 and not same(want[0], before) and float(want[2].max()) > 100.
     for k, (name, w) in enumerate(zip(["thlt", "lflx", "sflx"], want)):

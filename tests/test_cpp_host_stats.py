@@ -2,34 +2,24 @@
 calc_stats, calc_tend and calc_stats_2d on 32 x 8 x 16 from inputs this test writes, and gives the bits of the same calls made
 through the Python driver (microhh_amd.stats.Sampler). Built here with hipcc into a temporary directory."""
 import os
-import subprocess
 import tempfile
 
 import numpy as np
 import pytest
 
-import common as cm
+import hostprog
 from microhh_amd import stats as S
 from microhh_amd.grid import Grid
 
-CPP = os.path.join(cm.ROOT, "tests", "cpp")
-LIBDIR = os.path.join(cm.ROOT, "microhh_amd")
 GRID = (32, 8, 16)
 THRESHOLD, OFFSET = 2.e-4, 1.5
 MASKS = ("default", "wpos", "wneg")
 PROFS = ("area", "areah", "u", "u_2", "u_3", "u_4", "u_grad", "w", "w_2", "w_grad", "q", "q_frac", "w_adv", "u_w", "u_diff", "u_flux")
 
 
-def _compile(out):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-o", out, os.path.join(CPP, "host_stats.cpp"),
-                    "-L" + LIBDIR, "-lmhh_hip", "-Wl,-rpath," + LIBDIR], check=True)
-
-
 def test_stats_host_program_compiles():
     """not gpu: the program and the host class it drives build against the library."""
-    with tempfile.TemporaryDirectory() as tmp:
-        _compile(os.path.join(tmp, "host_stats"))
+    hostprog.compile("host_stats")
 
 
 @pytest.mark.gpu
@@ -63,14 +53,10 @@ def test_cpp_host_stats_gives_the_bits_of_the_python_driver():
     want = {"area": sm.area.cpu().numpy(), "areah": sm.areah.cpu().numpy(), "u": a[0], "u_2": b[0], "u_3": b[1], "u_4": b[2], "u_grad": b[3],
             "w": a[1], "w_2": b[4], "w_grad": b[5], "q": a[2], "q_frac": b[6], "w_adv": a[4], "u_w": c[0], "u_diff": c[1], "u_flux": c[2]}
     with tempfile.TemporaryDirectory() as tmp:
-        exe, fin, fout = (os.path.join(tmp, n) for n in ("host_stats", "in.bin", "out.bin"))
-        _compile(exe)
-        with open(fin, "wb") as fh:
-            for x in (u, w, q, ev, bot, fbot, ftop, rho, g.z, g.zh, g.dz, g.dzh, g.dzi, g.dzhi):
-                np.ascontiguousarray(x, dtype=np.float64).tofile(fh)
-        r = subprocess.run([exe, fin, fout, *[str(n) for n in GRID], repr(THRESHOLD), repr(OFFSET)], capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0 and "host_stats ok" in r.stdout, r.stdout + r.stderr
-        got = np.fromfile(fout, dtype=np.float64)
+        fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
+        hostprog.write_doubles(fin, (u, w, q, ev, bot, fbot, ftop, rho, g.z, g.zh, g.dz, g.dzh, g.dzi, g.dzhi))
+        hostprog.run(hostprog.compile("host_stats"), fin, fout, *GRID, repr(THRESHOLD), repr(OFFSET))
+        got = hostprog.read_doubles(fout)
     kc = g.kcells
     per = (2 + len(PROFS))*kc + 4
     assert got.size == len(MASKS)*per

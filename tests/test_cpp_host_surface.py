@@ -3,7 +3,6 @@ set_values, init_solver and two exec calls -- the fused call, and the slab seque
 agree -- on (17, 9, 8) from inputs this test writes, and gives the bits of the same calls made through the Python binding. Built
 here with hipcc into a temporary directory."""
 import os
-import subprocess
 import tempfile
 
 import numpy as np
@@ -11,24 +10,16 @@ import pytest
 
 import backends as B
 import common as cm
+import hostprog
 import surface_ref as S
 from common import same_bits as same
 
-CPP = os.path.join(cm.ROOT, "tests", "cpp")
-LIBDIR = os.path.join(cm.ROOT, "microhh_amd")
 NAMES = ["dutot", "ustar", "obuk", "ufluxbot", "vfluxbot", "ugradbot", "vgradbot", "sbot0", "sgradbot0", "dudz", "dvdz", "dbdz", "nobuk"]
-
-
-def _compile(out):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-o", out, os.path.join(CPP, "host_surface.cpp"),
-                    "-L" + LIBDIR, "-lmhh_hip", "-Wl,-rpath," + LIBDIR], check=True)
 
 
 def test_surface_host_program_compiles():
     """not gpu: the program and the host class it drives build against the library."""
-    with tempfile.TemporaryDirectory() as tmp:
-        _compile(os.path.join(tmp, "host_surface"))
+    hostprog.compile("host_surface")
 
 
 @pytest.mark.gpu
@@ -41,15 +32,11 @@ def test_cpp_host_surface_layer_gives_the_bits_of_the_python_calls():
     d.fused(); d.fused()
     want = d.outputs()
     with tempfile.TemporaryDirectory() as tmp:
-        exe, fin, fout = (os.path.join(tmp, n) for n in ("host_surface", "in.bin", "out.bin"))
-        _compile(exe)
-        with open(fin, "wb") as fh:
-            for k in ("u", "v", "s0"):
-                be.host(d.a[k]).astype(np.float64).tofile(fh)
-        args = [exe, fin, fout, str(g.itot), str(g.jtot), str(g.ktot)] + [repr(float(x)) for x in (S.zsl_of(g), S.UBOT, S.VBOT, 0.07, S.Z0M, S.THREF, S.THREFH)]
-        r = subprocess.run(args, capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0 and "host_surface ok" in r.stdout, r.stdout + r.stderr
-        got = np.fromfile(fout, dtype=np.float64).reshape((len(NAMES),) + tuple(g.shape2))
+        fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
+        hostprog.write_doubles(fin, [be.host(d.a[k]) for k in ("u", "v", "s0")])
+        hostprog.run(hostprog.compile("host_surface"), fin, fout, g.itot, g.jtot, g.ktot,
+                     *[repr(float(x)) for x in (S.zsl_of(g), S.UBOT, S.VBOT, 0.07, S.Z0M, S.THREF, S.THREFH)])
+        got = hostprog.read_doubles(fout).reshape((len(NAMES),) + tuple(g.shape2))
     core = (slice(g.jstart, g.jend), slice(g.istart, g.iend))
     for n, a in zip(NAMES, got):
         w = want[n].astype(np.float64)

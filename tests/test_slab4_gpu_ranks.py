@@ -4,18 +4,17 @@ the full BASELINE size runs the slab code path on one rank, and the C++ slab dri
 Every run is compared with the single-GPU path on the same fields: RHS tendencies bit-exact, p and the pressure-corrected tendencies
 to 1e-10 (fp64) / 2e-4 (fp32)."""
 import os
-import subprocess
 import tempfile
 
 import numpy as np
 import pytest
 
+import hostprog
 from ranks import run_ranks
 
 pytestmark = pytest.mark.gpu
 CASE = "moser600"
 GRID = (128, 64, 32)
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _interior(hp, t):
@@ -129,25 +128,12 @@ def test_pres4_slab_full_size_matches_single_gpu():
         assert float((a - b).abs().max()) <= 1e-10 * float(a.abs().max()), (n, float((a - b).abs().max()) / float(a.abs().max()))
 
 
-def _build_driver():
-    """tests/cpp/pres4_slab.cpp -> tests/cpp/pres4_slab (rebuilt when the source, the host headers or the library are newer)."""
-    cpp = os.path.join(ROOT, "tests", "cpp")
-    exe, src = os.path.join(cpp, "pres4_slab"), os.path.join(cpp, "pres4_slab.cpp")
-    deps = [src, os.path.join(ROOT, "microhh_amd", "host", "mhh_host.h"), os.path.join(ROOT, "microhh_amd", "host", "mhh_host_rccl.h"),
-            os.path.join(ROOT, "include", "mhh_hip.h"), os.path.join(ROOT, "microhh_amd", "libmhh_hip.so")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-        subprocess.run([hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-o", exe, src, "-L" + os.path.join(ROOT, "microhh_amd"), "-lmhh_hip",
-                        "-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,$ORIGIN/../../microhh_amd"], check=True, cwd=cpp)
-    return exe
-
-
 @pytest.mark.parametrize("chunks", [1, 4], ids=["whole-transposes", "sliced-transposes"])
 def test_cpp_pres_slab_order4_matches_single_gpu_pres(chunks):
     """Pres_slab<TF>(master, grid, fields, 4) of microhh_amd/host/mhh_host_rccl.h on a one-rank RCCL communicator against
     Pres<TF>(grid, fields, 4) of microhh_amd/host/mhh_host.h on the same fields: p, ut, vt, wt to 1e-10, the same divergence."""
     from microhh_amd.model import HotPath
-    exe = _build_driver()
+    exe = hostprog.compile("pres4_slab", libs=("rccl",))
     hp = HotPath(CASE, 64, 32, 32, device="cuda:0", dt=0.5)
     hp.cyclic_prognostic(); hp.rhs(); hp.sync()
     g = hp.grid
@@ -161,8 +147,7 @@ def test_cpp_pres_slab_order4_matches_single_gpu_pres(chunks):
             for t in (hp.u, hp.v, hp.w, hp.ut, hp.vt, hp.wt):
                 t.cpu().numpy().astype(np.float64).tofile(f)
         hp.close()
-        r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stdout + r.stderr
+        hostprog.run(exe, fin, fout, timeout=300)
         raw = np.fromfile(fout, dtype=np.float64)
     div1, div2 = raw[:2]
     n3 = g.ncells

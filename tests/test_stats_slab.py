@@ -94,7 +94,7 @@ def test_two_ranks_against_one():
             first, count = 0., 0.
             for rank, p in enumerate(parts):
                 gr = Grid(GRID[0], GRID[1], GRID[2], *CASES["drycblles"]["size"], order=2, igc=g.igc, jgc=g.jgc, kgc=g.kgc, npy=2, mpicoordy=rank)
-                d = SR.M.dims_of(gr)
+                d = SR.dims_of(gr)
                 col = np.zeros(4)
                 nm = np.ones(gr.kcells, dtype=np.int32)
                 lib.ref_stats_columns(0, C.byref(d), cm.ptr(col), cm.ptr(p["th"]), cm.ptr(gr.dz), cm.ptr(p["rho"]), 0., COVER, cm.ptr(p["mfield"]), int(fl[m]), cm.ptr(nm))

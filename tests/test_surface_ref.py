@@ -12,7 +12,6 @@ Toleranced: everything that passes through pow / log / exp. On emul with the shi
 too (same C library, no contraction); elsewhere max|got - ref| / max|ref| per array stays under BOUND.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -31,7 +30,7 @@ from microhh_amd import capi
 BOUND = {np.dtype(np.float64): 8*5.804e-16, np.dtype(np.float32): 8*5.149e-7}
 CEILING = {np.dtype(np.float64): 1e-10, np.dtype(np.float32): 1e-4}     # beyond this a difference is not rounding
 
-RECORD = os.environ.get("MHH_RECORD_SURFACE_GOLDEN") == "1"
+RECORD = S.RECORD
 CASES = [pytest.param(c, s, id=i) for (c, s), i in zip(S.CASES, S.CASE_IDS)]
 _ref, _dev = {}, {}
 
@@ -107,8 +106,7 @@ def test_shim_compiles_and_golden_is_current(tmp_path):
             rec["lut/%s" % case.id] = np.array(S.digest(*table_of(case, True)))
     rec.update(state_reference(True))
     if RECORD:
-        np.savez_compressed(S.GOLDEN, **rec)
-        S._golden.clear()
+        S.GOLD.save(rec)
     z = S.golden()
     assert z is not None, "record tests/golden/surface_ref.npz first (MHH_RECORD_SURFACE_GOLDEN=1)"
     assert sorted(z.files) == sorted(rec)
