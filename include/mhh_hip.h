@@ -902,6 +902,71 @@ int mhh_cross_height_threshold(const mhh_grid* g, const void* fld, double thresh
  * of g are HOST pointers. A location outside the domain is refused and the message names it.                                      */
 int mhh_cross_indices_host(const mhh_grid* g, int kind, const double* loc, int nloc, int* full, int* nfull, int* half, int* nhalf);
 
+/* ---- Immersed_boundary (src/immersed_boundary.cxx, src/immersed_boundary.cu; sw_immersed_boundary=dem) --------------------------------
+ * Flow over terrain: the cells just inside the wall (ghost cells) are set from an inverse-distance-weighted interpolation of cells
+ * outside it, twice per sub-step (src/model.cxx:380, :407). The set-up (Immersed_boundary::create) runs on the HOST and touches no
+ * GPU: every pointer of the three *_host entries is a host pointer. IB_type::User and the fourth order are not built. */
+#define MHH_IB_DIRICHLET 0   /* Boundary_type::Dirichlet_type: n_idw-1 points and the boundary value, 2*bv - vI                          */
+#define MHH_IB_NEUMANN   1   /* Boundary_type::Neumann_type:   vI - bv*di                                                               */
+#define MHH_IB_FLUX      2   /* Boundary_type::Flux_type:      vI - (-bv/visc)*di                                                       */
+#define MHH_IB_MAX_JOBS  8   /* jobs that travel with one launch; a call takes any number and launches per batch                         */
+/* Ghost_cells<TF> (include/immersed_boundary.h:39-76) as calc_ghost_cells leaves it: nghost entries each, nghost*n_idw for ip_* and
+ * c_idw ([n][q], the reference's layout); i, j, k are array indices of this rank; the void* arrays are of the grid's dtype. */
+typedef struct mhh_ib_ghost_lists
+{
+    int* i; int* j; int* k;
+    void* xb; void* yb; void* zb;
+    void* xi; void* yi; void* zi;
+    void* di;
+    int* ip_i; int* ip_j; int* ip_k;
+    void* ip_d; void* c_idw; void* c_idw_sum;
+} mhh_ib_ghost_lists;
+/* calc_ghost_cells (src/immersed_boundary.cxx:334-426) for one staggered location: is_ghost_cell (:107-185), find_nearest_location_wall
+ * (:188-220) with the image point and di, find_interpolation_points (:223-285), precalculate_idw (:288-331), bit for bit on one host.
+ * dem [ijcells] with filled halos; x, y [icells], [jcells] and z, dz [kcells] are the location's own (u: xh, y, z, dz; v: x, yh, z, dz;
+ * w: x, y, zh, dzh; s: x, y, z, dz); dx, dy are g's. Two calls: out == NULL stores the count in *nghost; with out, *nghost must hold that
+ * count and the lists are filled. The counting call keeps its scan (per thread) for a filling call with the same grid and values. Refused with a reason: "IB dem interpolation out of bounds!"; fewer than n_idw neighbours (naming
+ * i, j, k); n_idw < 1; an unknown boundary type; igc < 2 or jgc < 2 (:622); a ghost cell with k+5 >= kcells (the reference reads past its
+ * arrays there); a grid of more than 2^31-1 cells. */
+int mhh_ib_ghost_cells_host(const mhh_grid* g, const void* dem, const void* x, const void* y, const void* z, const void* dz, int n_idw, int bc,
+                            int mpi_offset_x, int mpi_offset_y, int* nghost, mhh_ib_ghost_lists* out);
+/* find_k_dem (src/immersed_boundary.cxx:516-537): k_dem[ij] = the first level with z[k] > dem[ij], kend where there is none; interior
+ * columns (the halos come from mhh_boundary_cyclic_2d_u32, :916) */
+int mhh_ib_k_dem_host(const mhh_grid* g, const void* dem, const void* z, unsigned int* k_dem);
+/* interp2_dem (src/immersed_boundary.cxx:65-103) of plane [ijcells] at the points (xp[n], yp[n]): the sbot_spatial boundary values at
+ * (xb, yb) (:891-897) */
+int mhh_ib_interp_dem_host(const mhh_grid* g, const void* plane, const void* x, const void* y, const void* xp, const void* yp, int n,
+                           int mpi_offset_x, int mpi_offset_y, void* out);
+/* One field's ghost cells. The DEVICE tables are not the reference's: cell[n] = i + j*icells + k*ijcells of ghost cell n (the list keeps
+ * the k-j-i order of calc_ghost_cells), ip[q*nghost + n] the same of its q-th interpolation point, c_idw[q*nghost + n] its weight
+ * (TRANSPOSED, [q][n]). Every offset must lie inside the field; interpolation points are never ghost cells of the same list. */
+typedef struct mhh_ib_job
+{
+    void* fld;                      /* [ncells], written at cell[]                                                                 */
+    const void* boundary_value;     /* [nghost]: mbot, or sbot of the scalar                                                        */
+    int bc;                         /* MHH_IB_*                                                                                      */
+    int nghost;                     /* 0: the job is a no-op                                                                         */
+    double visc;                    /* Fields::visc or the scalar's; read by MHH_IB_FLUX                                             */
+    const int* cell;                /* [nghost]                                                                                      */
+    const int* ip;                  /* [n_idw][nghost]; the last row is not read by MHH_IB_DIRICHLET                                 */
+    const void* c_idw;              /* [n_idw][nghost]                                                                               */
+    const void* c_idw_sum;          /* [nghost]                                                                                      */
+    const void* di;                 /* [nghost]                                                                                      */
+} mhh_ib_job;
+/* set_ghost_cells (src/immersed_boundary.cxx:441-485; set_ghost_cells_g, src/immersed_boundary.cu:33-78) for every job in ONE launch:
+ * u, v, w of exec_momentum (:640-669, .cu:108-133), all scalars of exec_scalars (:677-696, .cu:140-168); the reference launches once
+ * per field. Same bits: the sum over q in index order from 0, the Dirichlet term last, one division by c_idw_sum. Only enqueues: no
+ * allocation, no synchronisation. The cyclic fills that follow (.cu:134-136, :166) are mhh_boundary_cyclic_n, issued by the caller.
+ * Refused: a null pointer in a job with nghost > 0, an unknown boundary type, n_idw < 1. */
+int mhh_ib_set_ghost_cells(const mhh_grid* g, int n_idw, const mhh_ib_job* jobs, int njobs, void* stream);
+/* calc_mask (src/immersed_boundary.cxx:489-512) of get_mask (:930-946): mask = z[k] > dem, maskh = zh[k] > dem as 0 / 1 of the dtype on
+ * the interior cells; dem [ijcells] on the device */
+int mhh_ib_mask(const mhh_grid* g, const void* dem, void* mask, void* maskh, void* stream);
+/* calc_fluxes (src/immersed_boundary.cxx:541-597) of exec_cross (:950-985): flux [ijcells] on the interior columns = the vertical flux
+ * at k_dem plus the fluxes through the side faces shared with higher neighbours, / (dx*dy); one thread per column, the reference's
+ * operand order. k_dem [ijcells] with filled halos, on the device. */
+int mhh_ib_fluxbot(const mhh_grid* g, void* flux, const unsigned int* k_dem, const void* s, double svisc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

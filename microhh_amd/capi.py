@@ -75,6 +75,19 @@ class MhhCrossJob(C.Structure):
     _fields_ = [("fld", vp), ("kind", ci), ("index", ci), ("k0", ci), ("k1", ci), ("offset", cd), ("out", vp)]
 
 
+IP = C.POINTER(C.c_int)
+
+
+class MhhIbGhostLists(C.Structure):
+    _fields_ = [("i", IP), ("j", IP), ("k", IP), ("xb", vp), ("yb", vp), ("zb", vp), ("xi", vp), ("yi", vp), ("zi", vp), ("di", vp),
+                ("ip_i", IP), ("ip_j", IP), ("ip_k", IP), ("ip_d", vp), ("c_idw", vp), ("c_idw_sum", vp)]
+
+
+class MhhIbJob(C.Structure):
+    _fields_ = [("fld", vp), ("boundary_value", vp), ("bc", ci), ("nghost", ci), ("visc", cd), ("cell", vp), ("ip", vp),
+                ("c_idw", vp), ("c_idw_sum", vp), ("di", vp)]
+
+
 class MhhBudget2Desc(C.Structure):
     _fields_ = [("u", vp), ("v", vp), ("w", vp), ("p", vp), ("evisc", vp), ("b", vp), ("u_fluxbot", vp), ("v_fluxbot", vp),
                 ("umodel", vp), ("vmodel", vp), ("wmodel", vp), ("bmean", vp), ("pmean", vp),
@@ -91,6 +104,8 @@ RP = C.POINTER(MhhRadiationGcssParams)
 SJP = C.POINTER(MhhStatsJob)
 BDP = C.POINTER(MhhBudget2Desc)
 CJP = C.POINTER(MhhCrossJob)
+IGP = C.POINTER(MhhIbGhostLists)
+IJP = C.POINTER(MhhIbJob)
 PLAN = vp
 
 SIGNATURES = {
@@ -243,6 +258,12 @@ SIGNATURES = {
     "mhh_cross_path": (ci, [GP, vp, vp, vp, vp]),
     "mhh_cross_height_threshold": (ci, [GP, vp, cd, ci, vp, vp]),
     "mhh_cross_indices_host": (ci, [GP, ci, C.POINTER(cd), ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),
+    "mhh_ib_ghost_cells_host": (ci, [GP, vp, vp, vp, vp, vp, ci, ci, ci, ci, C.POINTER(ci), IGP]),
+    "mhh_ib_k_dem_host": (ci, [GP, vp, vp, vp]),
+    "mhh_ib_interp_dem_host": (ci, [GP, vp, vp, vp, vp, vp, ci, ci, ci, vp]),
+    "mhh_ib_set_ghost_cells": (ci, [GP, ci, IJP, ci, vp]),
+    "mhh_ib_mask": (ci, [GP, vp, vp, vp, vp]),
+    "mhh_ib_fluxbot": (ci, [GP, vp, vp, vp, cd, vp]),
 }
 
 

@@ -14,6 +14,7 @@ pinned host buffer, and the writes of fieldio.save_*_slice. What is built, by th
   Microphys (src/microphys_2mom_warm.cxx:950-960, src/microphys_nsw6.cxx:1098-1114)   rr_bot, rs_bot, rg_bot
   Boundary_surface (src/boundary_surface.cxx:688-712)     ustar, obuk
   Radiation_gcss (src/radiation_gcss.cxx:555-560)         lflx, sflx
+  Immersed_boundary (src/immersed_boundary.cxx:950-985)   <scalar>fluxbot_ib, with HotPath(..., ib=Dem(...))
 
 A scalar goes by HotPath's names (th, s1, s2, ...; s0 is th) and by the reference's name in the case (thl, qt, qr, nr, qs, qg; b in
 a Thermo_buoy case). A name the case cannot provide raises ValueError("... is illegal") at bind time; the reference only warns
@@ -123,6 +124,12 @@ class Cross:
             both = lambda: rad.fields()                              # noqa: E731   one call gives both
             out["lflx"] = ("simple", lambda: self._now(both)["lflx"], "s", 0.)
             out["sflx"] = ("simple", lambda: self._now(both)["sflx"], "s", 0.)
+        # Immersed_boundary::exec_cross (src/immersed_boundary.cxx:950-985): <scalar>fluxbot_ib, a plane with no offset
+        if getattr(hp, "ib", None) is not None:
+            for name, row in list(prog.items()):
+                if row[1] == "s":
+                    n = next(m for m, t in enumerate(hp.s) if t is row[0])
+                    out[name + "fluxbot_ib"] = ("plane", (lambda n=n: hp.ib.fluxbot(n)), "s", 0.)
         return out
 
     def _now(self, x):

@@ -845,3 +845,8 @@ MHH_API int mhh_boundary_ghost_cells_w(const mhh_grid* g, void* w, int type, voi
 // Cross: the planes of the cross-sections, lngrad, path and threshold heights (src/cross.cxx)
 // =======================================================================================================
 #include "cross.h"
+
+// =======================================================================================================
+// Immersed_boundary: DEM ghost cells, the ib mask and the wall flux (src/immersed_boundary.cxx)
+// =======================================================================================================
+#include "immersed_boundary.h"

@@ -1526,4 +1526,238 @@ class Cross_sampler
         std::vector<TF> host;
 };
 
+// ---- Immersed_boundary (include/immersed_boundary.h; src/immersed_boundary.cxx, src/immersed_boundary.cu) -----------------------
+// sw_immersed_boundary=dem on one rank or a y-slab. create() is the host set-up of Immersed_boundary::create (:766-918) over
+// mhh_ib_ghost_cells_host, _interp_dem_host and _k_dem_host: `dem` [ijcells] and the planes of `sbot_spatial` hold the data WITH
+// filled halos (boundary_cyclic.exec_2d, :800, is the caller's, as is the reading of the files). prepare_device() builds the device
+// tables of mhh_ib_job (one cell offset per point, the per-point arrays transposed) through the caller's alloc / upload / release.
+// exec_momentum and exec_scalars are one launch each; the cyclic fills that follow (.cu:134-136, :166) go through `cyclic`, which a
+// slab rank sets to its exchange (default: Boundary_cyclic::exec_g of every field). The halos of k_dem (boundary_cyclic.exec_2d, :916)
+// are filled on the host in create(): east-west by a local wrap, north-south by a local wrap on one rank and through
+// `exchange_k_dem` on a slab, without which create() throws there.
+template<typename TF>
+struct Ghost_cells
+{
+    int nghost = 0;
+    std::vector<int> i, j, k, ip_i, ip_j, ip_k;
+    std::vector<TF> xb, yb, zb, xi, yi, zi, di, ip_d, c_idw, c_idw_sum;
+    std::map<std::string, std::vector<TF>> sbot;
+    std::vector<TF> mbot;
+    int* cell_g = nullptr; int* ip_g = nullptr;                                 // [nghost], [n_idw][nghost]
+    TF* c_idw_g = nullptr; TF* c_idw_sum_g = nullptr; TF* di_g = nullptr;      // [n_idw][nghost], [nghost], [nghost]
+    std::map<std::string, TF*> sbot_g;
+    TF* mbot_g = nullptr;
+};
+
+template<typename TF>
+class Immersed_boundary
+{
+    public:
+        Immersed_boundary(Grid<TF>& grid_in, Fields<TF>& fields_in) : grid(grid_in), fields(fields_in) {}
+        int n_idw_points = 0;                                        // [IB] n_idw_points
+        int sbcbot = MHH_IB_DIRICHLET;                               // [IB] sbcbot: MHH_IB_*
+        std::map<std::string, TF> sbc;                               // [IB] sbot[scalar]
+        std::map<std::string, std::vector<TF>> sbot_spatial;         // <scalar>_sbot.0000000 as [ijcells], halos filled
+        std::vector<TF> dem;                                         // dem.0000000 as [ijcells], halos filled
+        std::vector<unsigned int> k_dem;                             // [ijcells], halos filled
+        unsigned int* k_dem_g = nullptr; TF* dem_g = nullptr;
+        std::map<std::string, Ghost_cells<TF>> ghost;
+        std::function<void*(size_t)> alloc;                          // device memory of that many bytes
+        std::function<void(void*, const void*, size_t)> upload;      // host to device
+        std::function<void(void*)> release;
+        std::function<void(const std::vector<TF*>&, void*)> cyclic;  // the cyclic fills of these fields on the stream
+        // slab ranks: fill the jgc south and jgc north ghost rows of this host plane [jcells][icells] from the ring neighbours' interior
+        // rows (the rows arrive with their east-west halos filled)
+        std::function<void(unsigned int*)> exchange_k_dem;
+
+        void create()
+        {
+            const auto& gd = grid.gd;
+            if ((int)dem.size() != gd.ijcells) throw std::runtime_error("Immersed_boundary: dem holds ijcells values, halos filled");
+            std::vector<TF> x(gd.icells), xh(gd.icells), y(gd.jcells), yh(gd.jcells);
+            const double yoff = gd.mpicoordy * gd.ysize / gd.npy;            // src/grid.cxx:248-262
+            for (int i=0; i<gd.icells; ++i) { x[i] = 0.5*gd.dx + (i-gd.igc)*gd.dx + 0.; xh[i] = (i-gd.igc)*gd.dx + 0.; }
+            for (int j=0; j<gd.jcells; ++j) { y[j] = 0.5*gd.dy + (j-gd.jgc)*gd.dy + yoff; yh[j] = (j-gd.jgc)*gd.dy + yoff; }
+            offx = gd.igc; offy = -gd.mpicoordy*gd.jmax + gd.jgc;             // :781-782
+            ghost.clear();
+            calc(ghost["u"], xh, y, gd.z, gd.dz, MHH_IB_DIRICHLET);
+            calc(ghost["v"], x, yh, gd.z, gd.dz, MHH_IB_DIRICHLET);
+            calc(ghost["w"], x, y, gd.zh, gd.dzh, MHH_IB_DIRICHLET);
+            for (const char* n : {"u", "v", "w"}) ghost.at(n).mbot.assign(ghost.at(n).nghost, TF(0));
+            mhh_grid g = grid.abi(true);
+            if (!fields.sp.empty())
+            {
+                Ghost_cells<TF>& gs = ghost["s"];
+                calc(gs, x, y, gd.z, gd.dz, sbcbot);
+                for (auto& it : fields.sp)
+                {
+                    std::vector<TF>& bv = gs.sbot[it.first];
+                    bv.assign(gs.nghost, sbc.count(it.first) ? sbc.at(it.first) : TF(0));
+                    if (sbot_spatial.count(it.first))           // interp2_dem at (xb, yb) (:891-897)
+                        mhh_check(mhh_ib_interp_dem_host(&g, sbot_spatial.at(it.first).data(), x.data(), y.data(), gs.xb.data(), gs.yb.data(), gs.nghost, offx, offy, bv.data()));
+                }
+            }
+            k_dem.assign(gd.ijcells, 0u);
+            mhh_check(mhh_ib_k_dem_host(&g, dem.data(), gd.z.data(), k_dem.data()));
+            const int ic = gd.icells;
+            for (int j=gd.jstart; j<gd.jend; ++j)
+                for (int i=0; i<gd.igc; ++i)
+                {
+                    k_dem[j*ic + i] = k_dem[j*ic + gd.iend-gd.igc + i];
+                    k_dem[j*ic + gd.iend + i] = k_dem[j*ic + gd.istart + i];
+                }
+            if (gd.npy == 1)
+                for (int j=0; j<gd.jgc; ++j)
+                    for (int i=0; i<ic; ++i)
+                    {
+                        // (jtot == 1 replicates the row, as Boundary_cyclic does)
+                        k_dem[j*ic + i] = k_dem[(gd.jtot == 1 ? gd.jstart : gd.jend - gd.jgc + j)*ic + i];
+                        k_dem[(gd.jend + j)*ic + i] = k_dem[(gd.jtot == 1 ? gd.jstart : gd.jstart + j)*ic + i];
+                    }
+            else if (exchange_k_dem) exchange_k_dem(k_dem.data());
+            else throw std::runtime_error("Immersed_boundary: a slab rank (npy > 1) needs exchange_k_dem for the north-south halos of k_dem");
+        }
+
+        void prepare_device()
+        {
+            if (!alloc || !upload) throw std::runtime_error("Immersed_boundary: alloc and upload are not set");
+            const auto& gd = grid.gd;
+            const int nq = n_idw_points;
+            for (auto& it : ghost)
+            {
+                Ghost_cells<TF>& gh = it.second;
+                const size_t n = gh.nghost;
+                std::vector<int> cell(n), ip(n*nq);
+                std::vector<TF> c(n*nq);
+                for (size_t m=0; m<n; ++m)
+                {
+                    cell[m] = gh.i[m] + gh.j[m]*gd.icells + gh.k[m]*gd.ijcells;
+                    for (int q=0; q<nq; ++q)
+                    {
+                        ip[q*n + m] = gh.ip_i[m*nq + q] + gh.ip_j[m*nq + q]*gd.icells + gh.ip_k[m*nq + q]*gd.ijcells;
+                        c[q*n + m] = gh.c_idw[m*nq + q];
+                    }
+                }
+                gh.cell_g = put(cell); gh.ip_g = put(ip); gh.c_idw_g = put(c); gh.c_idw_sum_g = put(gh.c_idw_sum); gh.di_g = put(gh.di);
+                gh.mbot_g = put(gh.mbot);
+                for (auto& sb : gh.sbot) gh.sbot_g[sb.first] = put(sb.second);
+            }
+            dem_g = put(dem);
+            k_dem_g = put(k_dem);
+        }
+
+        void clear_device()
+        {
+            auto drop = [&](auto*& p) { if (p && release) release(p); p = nullptr; };
+            for (auto& it : ghost)
+            {
+                Ghost_cells<TF>& gh = it.second;
+                drop(gh.cell_g); drop(gh.ip_g); drop(gh.c_idw_g); drop(gh.c_idw_sum_g); drop(gh.di_g); drop(gh.mbot_g);
+                for (auto& sb : gh.sbot_g) drop(sb.second);
+                gh.sbot_g.clear();
+            }
+            drop(dem_g); drop(k_dem_g);
+        }
+
+        // Immersed_boundary::exec_momentum (:640-674, .cu:108-137)
+        void exec_momentum(void* stream = nullptr)
+        {
+            if (ghost.empty()) return;
+            mhh_grid g = grid.abi();
+            mhh_ib_job jobs[3];
+            std::vector<TF*> flds;
+            int n = 0;
+            for (const char* name : {"u", "v", "w"})
+            {
+                const Ghost_cells<TF>& gh = ghost.at(name);
+                jobs[n++] = job(fields.mp.at(name)->fld_g, gh.mbot_g, MHH_IB_DIRICHLET, fields.visc, gh);
+                flds.push_back(fields.mp.at(name)->fld_g);
+            }
+            mhh_check(mhh_ib_set_ghost_cells(&g, n_idw_points, jobs, 3, stream));
+            fill(flds, stream);
+        }
+        // Immersed_boundary::exec_scalars (:677-696, .cu:140-168)
+        void exec_scalars(void* stream = nullptr)
+        {
+            if (ghost.empty() || fields.sp.empty()) return;
+            mhh_grid g = grid.abi();
+            const Ghost_cells<TF>& gh = ghost.at("s");
+            std::vector<mhh_ib_job> jobs;
+            std::vector<TF*> flds;
+            for (auto& it : fields.sp)
+            {
+                jobs.push_back(job(it.second->fld_g, gh.sbot_g.at(it.first), sbcbot, it.second->visc, gh));
+                flds.push_back(it.second->fld_g);
+            }
+            mhh_check(mhh_ib_set_ghost_cells(&g, n_idw_points, jobs.data(), (int)jobs.size(), stream));
+            fill(flds, stream);
+        }
+        // Immersed_boundary::get_mask (:930-946): calc_mask into two device fields; the caller hands them to
+        // Stats_sampler::set_mask_thres("ib", mask, maskh, 0.5, Plus) (:942)
+        bool has_mask(const std::string& name) const { return name == "ib"; }
+        void get_mask(TF* mask_g, TF* maskh_g, void* stream = nullptr)
+        {
+            mhh_grid g = grid.abi();
+            mhh_check(mhh_ib_mask(&g, dem_g, mask_g, maskh_g, stream));
+        }
+        // Immersed_boundary::exec_cross (:950-985): <scalar>fluxbot_ib of every listed scalar, a plane with no offset; flux_g [ijcells]
+        // is the caller's scratch (tmp->flux_bot)
+        int exec_cross(Cross_sampler<TF>& cross, const std::vector<std::string>& crosslist, int iotime, TF* flux_g, void* stream = nullptr)
+        {
+            mhh_grid g = grid.abi();
+            int nerror = 0;
+            const std::string ending = "fluxbot_ib";
+            for (const std::string& s : crosslist)
+            {
+                if (s.size() < ending.size() || s.compare(s.size() - ending.size(), ending.size(), ending)) continue;
+                const std::string scalar = s.substr(0, s.size() - ending.size());
+                if (!fields.sp.count(scalar)) continue;
+                mhh_check(mhh_ib_fluxbot(&g, flux_g, k_dem_g, fields.sp.at(scalar)->fld_g, fields.sp.at(scalar)->visc, stream));
+                nerror += cross.cross_plane(flux_g, TF(0.), s, iotime, stream);
+            }
+            return nerror;
+        }
+
+    private:
+        void calc(Ghost_cells<TF>& gh, const std::vector<TF>& x, const std::vector<TF>& y, const std::vector<TF>& z, const std::vector<TF>& dz, int bc)
+        {
+            mhh_grid g = grid.abi(true);
+            int n = 0;
+            mhh_check(mhh_ib_ghost_cells_host(&g, dem.data(), x.data(), y.data(), z.data(), dz.data(), n_idw_points, bc, offx, offy, &n, nullptr));
+            const size_t np = (size_t)n*n_idw_points;
+            gh.nghost = n;
+            for (auto* v : {&gh.i, &gh.j, &gh.k}) v->assign(n, 0);
+            for (auto* v : {&gh.ip_i, &gh.ip_j, &gh.ip_k}) v->assign(np, 0);
+            for (auto* v : {&gh.xb, &gh.yb, &gh.zb, &gh.xi, &gh.yi, &gh.zi, &gh.di, &gh.c_idw_sum}) v->assign(n, TF(0));
+            for (auto* v : {&gh.ip_d, &gh.c_idw}) v->assign(np, TF(0));
+            mhh_ib_ghost_lists l{gh.i.data(), gh.j.data(), gh.k.data(), gh.xb.data(), gh.yb.data(), gh.zb.data(), gh.xi.data(), gh.yi.data(), gh.zi.data(),
+                                 gh.di.data(), gh.ip_i.data(), gh.ip_j.data(), gh.ip_k.data(), gh.ip_d.data(), gh.c_idw.data(), gh.c_idw_sum.data()};
+            mhh_check(mhh_ib_ghost_cells_host(&g, dem.data(), x.data(), y.data(), z.data(), dz.data(), n_idw_points, bc, offx, offy, &n, &l));
+        }
+        // (an empty vector still gets one element: a null table pointer would be refused where nghost > 0 only, but a valid address
+        // keeps every job uniform)
+        template<class T> T* put(const std::vector<T>& v)
+        {
+            T* d = static_cast<T*>(alloc(std::max<size_t>(1, v.size())*sizeof(T)));
+            if (!v.empty()) upload(d, v.data(), v.size()*sizeof(T));
+            return d;
+        }
+        mhh_ib_job job(TF* fld, const TF* bv, int bc, TF visc, const Ghost_cells<TF>& gh) const
+        {
+            mhh_ib_job j{};
+            j.fld = fld; j.boundary_value = bv; j.bc = bc; j.nghost = gh.nghost; j.visc = visc;
+            j.cell = gh.cell_g; j.ip = gh.ip_g; j.c_idw = gh.c_idw_g; j.c_idw_sum = gh.c_idw_sum_g; j.di = gh.di_g;
+            return j;
+        }
+        void fill(const std::vector<TF*>& flds, void* stream)
+        {
+            if (cyclic) { cyclic(flds, stream); return; }
+            mhh_grid g = grid.abi();
+            std::vector<void*> p(flds.begin(), flds.end());
+            mhh_check(mhh_boundary_cyclic_n(&g, p.data(), (int)p.size(), MHH_EDGE_BOTH, stream));
+        }
+        Grid<TF>& grid; Fields<TF>& fields;
+        int offx = 0, offy = 0;
+};
+
 } // namespace mhh_host

@@ -7,6 +7,7 @@ that this package accelerates, expressed as calls into the C ABI.
     microphys->exec ; limiter->exec       -> mhh_micro_2mom_warm_exec or mhh_micro_nsw6_exec, mhh_limiter_exec (micro=..., opt-in) (:369, :415)
     radiation->exec (Radiation_gcss)      -> mhh_radiation_gcss_exec (radiation=..., opt-in)      (:372)
     boundary->exec ; set_ghost_cells      -> mhh_boundary_surface_exec, mhh_boundary_ghost_cells (surface=..., opt-in) (:374-375)
+    ib->exec_scalars ; ib->exec_momentum  -> mhh_ib_set_ghost_cells + the cyclic fills (ib=..., opt-in)  (:380, :407)
     advec->exec ; diff->exec              -> mhh_rhs_exec (fused, same bits)                     (:388, :392)
     fields->exec ; buffer->exec ; force->exec -> mhh_field_mean_*, mhh_buffer_force_exec (forcing=..., opt-in) (:351, :395, :404)
     pres->exec(dt)                        -> mhh_pres_exec, or its slab form around 2 all-to-alls (:411)
@@ -111,7 +112,7 @@ class HotPath:
 
     def __init__(self, case, itot, jtot, ktot, dtype=np.float64, device="cuda:0", seed=666, dt=1.0,
                  lib=None, npy=1, rank=0, group=None, global_init=None, force_slab=False, slim_halos=True, overlap=None, pres_chunks=None, igc=None,
-                 nscalars=None, forcing=None, surface=None, thermo=None, micro=None, radiation=None, stats=None, budget=None, cross=None):
+                 nscalars=None, forcing=None, surface=None, thermo=None, micro=None, radiation=None, stats=None, budget=None, cross=None, ib=None):
         import torch
         if budget is not None and stats is None:
             raise ValueError("budget= needs stats=Stats(...): the budget profiles are averaged under the masks of the statistics")
@@ -277,6 +278,8 @@ class HotPath:
         self.micro = micro.bind(self) if micro is not None else None
         # Radiation_gcss (radiation.Gcss): the zenith angle, two scratch fields
         self.radiation = radiation.bind(self) if radiation is not None else None
+        # Immersed_boundary (ib.Dem): the ghost-cell tables of u, v, w and s, the mask fields and k_dem, made once on the host
+        self.ib = ib.bind(self) if ib is not None else None
         # Stats (stats.Stats): the mask words, counts and reduction scratch; sampled outside the step by hp.stats.sample()
         self.stats = stats.bind(self) if stats is not None else None
         # Budget_2 (budget.Budget2): the budget group of the statistics, sampled with them after Stats' own passes
@@ -558,7 +561,9 @@ class HotPath:
         cyclic fills, exec_viscosity (which reads the PREVIOUS sub-step's dudz, dvdz, dbdz, as the reference does), the surface
         layer, the vertical ghost cells, then the RHS -- the plain sequence on a slab too (the overlapped sub-step fuses
         exec_viscosity with the RHS, and the surface layer sits between them). With `thermo` (thermo.Moist), the same plain sequence
-        with the means of thl and qt in front of exec_viscosity and Thermo_moist::exec behind it."""
+        with the means of thl and qt in front of exec_viscosity and Thermo_moist::exec behind it. With `ib` (ib.Dem), the plain
+        sequence on a slab too, with the two calls of src/model.cxx:380 and :407: the scalars' ghost cells after the surface layer and
+        in front of the RHS, those of u, v, w after Buffer and Force and in front of the pressure solve."""
         means_done = False
         if self.thermo is not None:
             # Thermo_moist, in the order of Model::exec (src/model.cxx:346-392): the cyclic fills; fields->exec, the means of thl and qt
@@ -575,11 +580,20 @@ class HotPath:
                 self.radiation.exec()
             if self.surface is not None:       # boundary->exec (:376) reads the thvref, thvrefh thermo->exec has just written
                 self.surface_layer()
+            if self.ib is not None:            # ib->exec_scalars (:380), after the vertical ghost cells
+                self.ib.exec_scalars()
             self.rhs()
         elif self.surface is not None:
             self.cyclic_prognostic()
             self.exec_viscosity()
             self.surface_layer()
+            if self.ib is not None:
+                self.ib.exec_scalars()
+            self.rhs()
+        elif self.ib is not None:
+            self.cyclic_prognostic()
+            self.exec_viscosity()
+            self.ib.exec_scalars()
             self.rhs()
         elif self.can_overlap:
             self.halo_visc_rhs()
@@ -591,6 +605,8 @@ class HotPath:
             if not means_done:
                 self.forcing_means()
             self.buffer_force()
+        if self.ib is not None:                # ib->exec_momentum (:407), after buffer->exec and force->exec
+            self.ib.exec_momentum()
         self.pres()
         if self.micro is not None:             # limiter->exec with the sub-step (:415), the last tendency
             self.micro.limit()

@@ -180,6 +180,10 @@ class Stats:
                 if hp.thermo is None or not hasattr(hp.thermo, "field"):
                     raise ValueError("Stats: the ql mask needs thermo=Moist(pbot)")
                 self.mask_thres(m, self.ql, self.ql_h, None, 0., PLUS)
+            elif m == "ib" and getattr(hp, "ib", None) is not None:
+                # Immersed_boundary::get_mask (src/immersed_boundary.cxx:930-946): calc_mask's two fields at threshold 0.5; without
+                # ib= the name stays a mask of the caller's
+                self.mask_thres(m, hp.ib.mask, hp.ib.maskh, None, 0.5, PLUS)
         std = ("mean", "2", "3", "4", "grad")
         fo = hp.forcing
         self.utrans = float(self.utrans if self.utrans is not None else (fo.utrans if fo is not None else 0.))
