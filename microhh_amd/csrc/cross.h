@@ -111,42 +111,44 @@ __global__ void __launch_bounds__(256) cross_lngrad_kernel(const CrossArgs<TF> A
 // calc_cross_path (src/cross.cxx:170-197): one thread per column marching up, tmp += rhoref[k] * data[ijk] * dz[k] serially in TF in
 // exactly that operand order ((rho*data)*dz; Stats' calc_path multiplies data*rho*dz, which rounds differently). out [jmax][imax].
 template<class TF>
-__global__ void __launch_bounds__(BX*BY) cross_path_kernel(const TF* __restrict__ data, const TF* __restrict__ rho, const TF* __restrict__ dz,
-                                                           TF* __restrict__ out, int imax, int jmax, int igc, int jgc, int icells, int ijcells,
-                                                           int kstart, int kend)
+struct CrossPathOp
 {
-    const int ci = blockIdx.x*BX + threadIdx.x, cj = blockIdx.y*BY + threadIdx.y;
-    if (ci >= imax || cj >= jmax) return;
-    const size_t ij = (size_t)(ci + igc) + (size_t)(cj + jgc)*icells;
-    TF acc = TF(0.);
-    for (int k=kstart; k<kend; ++k)
-        acc += rho[k] * data[ij + (size_t)k*ijcells] * dz[k];
-    out[(size_t)ci + (size_t)cj*imax] = acc;
-}
+    const TF* __restrict__ data; const TF* __restrict__ rho; const TF* __restrict__ dz; TF* __restrict__ out;
+    int istart, jstart, imax, ijcells, kstart, kend;
+    __device__ void operator()(int i, int j, int, int col) const
+    {
+        const size_t ij = (size_t)col;
+        TF acc = TF(0.);
+        for (int k=kstart; k<kend; ++k)
+            acc += rho[k] * data[ij + (size_t)k*ijcells] * dz[k];
+        out[(size_t)(i-istart) + (size_t)(j-jstart)*imax] = acc;
+    }
+};
 
 // calc_cross_height_threshold (src/cross.cxx:200-250): z[k] of the lowest (upward) or highest level with data > threshold, the
 // fill value where no level qualifies. out [jmax][imax].
 template<class TF>
-__global__ void __launch_bounds__(BX*BY) cross_height_kernel(const TF* __restrict__ data, const TF* __restrict__ z, TF* __restrict__ out,
-                                                             TF threshold, int upward, TF fillvalue, int imax, int jmax, int igc, int jgc,
-                                                             int icells, int ijcells, int kstart, int kend)
+struct CrossHeightOp
 {
-    const int ci = blockIdx.x*BX + threadIdx.x, cj = blockIdx.y*BY + threadIdx.y;
-    if (ci >= imax || cj >= jmax) return;
-    const size_t ij = (size_t)(ci + igc) + (size_t)(cj + jgc)*icells;
-    TF h = fillvalue;
-    if (upward)
+    const TF* __restrict__ data; const TF* __restrict__ z; TF* __restrict__ out; TF threshold; int upward; TF fillvalue;
+    int istart, jstart, imax, ijcells, kstart, kend;
+    __device__ void operator()(int i, int j, int, int col) const
     {
-        for (int k=kstart; k<kend; ++k)
-            if (data[ij + (size_t)k*ijcells] > threshold) { h = z[k]; break; }
+        const size_t ij = (size_t)col;
+        TF h = fillvalue;
+        if (upward)
+        {
+            for (int k=kstart; k<kend; ++k)
+                if (data[ij + (size_t)k*ijcells] > threshold) { h = z[k]; break; }
+        }
+        else
+        {
+            for (int k=kend-1; k>kstart-1; --k)
+                if (data[ij + (size_t)k*ijcells] > threshold) { h = z[k]; break; }
+        }
+        out[(size_t)(i-istart) + (size_t)(j-jstart)*imax] = h;
     }
-    else
-    {
-        for (int k=kend-1; k>kstart-1; --k)
-            if (data[ij + (size_t)k*ijcells] > threshold) { h = z[k]; break; }
-    }
-    out[(size_t)ci + (size_t)cj*imax] = h;
-}
+};
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 // What every job must satisfy before a kernel indexes with it; lngrad: the planes lie in the interior, where the stencils of
@@ -278,13 +280,10 @@ MHH_API int mhh_cross_path(const mhh_grid* g, const void* fld, const void* rhore
 {
     if (int e = check_grid(g)) return e;
     MHH_REQUIRE(fld && rhoref && g->dz && out, "null pointer");
-    const dim3 grid((g->imax + BX-1)/BX, (g->jmax + BY-1)/BY), block(BX, BY, 1);
-#define CALL(TF) hipLaunchKernelGGL(cross_path_kernel<TF>, grid, block, 0, as_stream(stream), cp<TF>(fld), cp<TF>(rhoref), cp<TF>(g->dz), mp<TF>(out), \
-                                    g->imax, g->jmax, g->igc, g->jgc, g->icells, g->ijcells, g->kstart, g->kend)
-    if (g->dtype == MHH_F64) CALL(double); else CALL(float);
+#define CALL(TF) launch_columns(as_stream(stream), make_grid<TF>(g), 1, CrossPathOp<TF>{cp<TF>(fld), cp<TF>(rhoref), cp<TF>(g->dz), mp<TF>(out), \
+                                g->istart, g->jstart, g->imax, g->ijcells, g->kstart, g->kend})
+    return MHH_DISPATCH(g, CALL);
 #undef CALL
-    MHH_LAUNCH_CHECK();
-    return MHH_OK;
 }
 
 // calc_cross_height_threshold (src/cross.cxx:200-250) with the fill value TF(-1e-9) of Cross::cross_height_threshold (:738-760);
@@ -293,13 +292,10 @@ MHH_API int mhh_cross_height_threshold(const mhh_grid* g, const void* fld, doubl
 {
     if (int e = check_grid(g)) return e;
     MHH_REQUIRE(fld && g->z && out, "null pointer");
-    const dim3 grid((g->imax + BX-1)/BX, (g->jmax + BY-1)/BY), block(BX, BY, 1);
-#define CALL(TF) hipLaunchKernelGGL(cross_height_kernel<TF>, grid, block, 0, as_stream(stream), cp<TF>(fld), cp<TF>(g->z), mp<TF>(out), TF(threshold), \
-                                    upward ? 1 : 0, TF(-1e-9), g->imax, g->jmax, g->igc, g->jgc, g->icells, g->ijcells, g->kstart, g->kend)
-    if (g->dtype == MHH_F64) CALL(double); else CALL(float);
+#define CALL(TF) launch_columns(as_stream(stream), make_grid<TF>(g), 1, CrossHeightOp<TF>{cp<TF>(fld), cp<TF>(g->z), mp<TF>(out), TF(threshold), \
+                                upward ? 1 : 0, TF(-1e-9), g->istart, g->jstart, g->imax, g->ijcells, g->kstart, g->kend})
+    return MHH_DISPATCH(g, CALL);
 #undef CALL
-    MHH_LAUNCH_CHECK();
-    return MHH_OK;
 }
 
 // The search of Cross::create (src/cross.cxx:323-460) for the locations of one direction (MHH_CROSS_XY: [cross] xy, heights; XZ: xz,

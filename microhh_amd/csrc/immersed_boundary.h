@@ -58,46 +58,47 @@ __global__ void __launch_bounds__(256) ib_set_ghost_cells_kernel(const IbArgs<TF
 
 // calc_mask (src/immersed_boundary.cxx:489-512): 1 where the level lies above the DEM of the column, interior cells only
 template<class TF>
-__global__ void __launch_bounds__(BX*BY) ib_mask_kernel(TF* __restrict__ mask, TF* __restrict__ maskh, const TF* __restrict__ dem,
-                                                        const TF* __restrict__ z, const TF* __restrict__ zh,
-                                                        int istart, int iend, int jstart, int jend, int kstart, int icells, int ijcells)
+struct IbMaskOp
 {
-    const int i = istart + blockIdx.x*BX + threadIdx.x, j = jstart + blockIdx.y*BY + threadIdx.y, k = kstart + blockIdx.z;
-    if (i >= iend || j >= jend) return;
-    const size_t ij = (size_t)i + (size_t)j*icells, ijk = ij + (size_t)k*ijcells;
-    const int is_not_ib = z[k] > dem[ij], is_not_ib_h = zh[k] > dem[ij];
-    mask[ijk] = static_cast<TF>(is_not_ib);
-    maskh[ijk] = static_cast<TF>(is_not_ib_h);
-}
+    TF* __restrict__ mask; TF* __restrict__ maskh; const TF* __restrict__ dem; const TF* __restrict__ z; const TF* __restrict__ zh; int icells;
+    __device__ void operator()(int i, int j, int k, int ijk) const
+    {
+        const int ij = i + j*icells;
+        const int is_not_ib = z[k] > dem[ij], is_not_ib_h = zh[k] > dem[ij];
+        mask[ijk] = static_cast<TF>(is_not_ib);
+        maskh[ijk] = static_cast<TF>(is_not_ib_h);
+    }
+};
 
 // calc_fluxes (src/immersed_boundary.cxx:541-597): one thread per column, serial in k, the reference's operand order: the vertical
 // flux, then west, east, south, north through the faces shared with a neighbour whose first level above the DEM is higher, then
 // / (dx*dy). k_dem is held inside [kstart, kend] (what find_k_dem writes), so that a foreign plane cannot index outside the field.
 template<class TF>
-__global__ void __launch_bounds__(BX*BY) ib_fluxbot_kernel(TF* __restrict__ flux, const unsigned int* __restrict__ k_dem, const TF* __restrict__ s,
-                                                           TF dx, TF dy, const TF* __restrict__ dz, TF dxi, TF dyi, const TF* __restrict__ dzhi, TF svisc,
-                                                           int istart, int iend, int jstart, int jend, int kstart, int kend, int icells, int ijcells)
+struct IbFluxbotOp
 {
-    const int i = istart + blockIdx.x*BX + threadIdx.x, j = jstart + blockIdx.y*BY + threadIdx.y;
-    if (i >= iend || j >= jend) return;
-    const int ii = 1, jj = icells;
-    const size_t kk = ijcells;
-    const int ij = i + j*jj;
-    auto kd = [&](int c) { const int v = (int)k_dem[c]; return v < kstart ? kstart : (v > kend ? kend : v); };
-    const int k0 = kd(ij);
-    const size_t col = (size_t)ij;
-    TF f;
+    TF* __restrict__ flux; const unsigned int* __restrict__ k_dem; const TF* __restrict__ s;
+    TF dx, dy; const TF* __restrict__ dz; TF dxi, dyi; const TF* __restrict__ dzhi; TF svisc;
+    int kstart, kend, icells, ijcells;
+    __device__ void operator()(int, int, int, int ij) const
     {
-        const size_t ijk = col + k0*kk;
-        f = -svisc*(s[ijk]-s[ijk-kk])*dzhi[k0] * dx*dy;
+        const int ii = 1, jj = icells;
+        const size_t kk = ijcells;
+        auto kd = [&](int c) { const int v = (int)k_dem[c]; return v < kstart ? kstart : (v > kend ? kend : v); };
+        const int k0 = kd(ij);
+        const size_t col = (size_t)ij;
+        TF f;
+        {
+            const size_t ijk = col + k0*kk;
+            f = -svisc*(s[ijk]-s[ijk-kk])*dzhi[k0] * dx*dy;
+        }
+        for (int k=k0; k<kd(ij-ii); ++k) { const size_t ijk = col + k*kk; f += -svisc*(s[ijk]-s[ijk-ii])*dxi * dy*dz[k]; }
+        for (int k=k0; k<kd(ij+ii); ++k) { const size_t ijk = col + k*kk; f +=  svisc*(s[ijk+ii]-s[ijk])*dxi * dy*dz[k]; }
+        for (int k=k0; k<kd(ij-jj); ++k) { const size_t ijk = col + k*kk; f += -svisc*(s[ijk]-s[ijk-jj])*dyi * dx*dz[k]; }
+        for (int k=k0; k<kd(ij+jj); ++k) { const size_t ijk = col + k*kk; f +=  svisc*(s[ijk+jj]-s[ijk])*dyi * dx*dz[k]; }
+        f /= dx*dy;
+        flux[ij] = f;
     }
-    for (int k=k0; k<kd(ij-ii); ++k) { const size_t ijk = col + k*kk; f += -svisc*(s[ijk]-s[ijk-ii])*dxi * dy*dz[k]; }
-    for (int k=k0; k<kd(ij+ii); ++k) { const size_t ijk = col + k*kk; f +=  svisc*(s[ijk+ii]-s[ijk])*dxi * dy*dz[k]; }
-    for (int k=k0; k<kd(ij-jj); ++k) { const size_t ijk = col + k*kk; f += -svisc*(s[ijk]-s[ijk-jj])*dyi * dx*dz[k]; }
-    for (int k=k0; k<kd(ij+jj); ++k) { const size_t ijk = col + k*kk; f +=  svisc*(s[ijk+jj]-s[ijk])*dyi * dx*dz[k]; }
-    f /= dx*dy;
-    flux[ij] = f;
-}
+};
 
 // ---- host side: the set-up of Immersed_boundary::create ----------------------------------------------------------------------
 // What the reference throws (std::runtime_error, `throw 1`) is thrown here as well and becomes the error string at the entry point.
@@ -427,13 +428,10 @@ MHH_API int mhh_ib_mask(const mhh_grid* g, const void* dem, void* mask, void* ma
 {
     if (int e = check_grid(g)) return e;
     MHH_REQUIRE(dem && mask && maskh && g->z && g->zh, "null pointer");
-    const dim3 grid((g->imax + BX-1)/BX, (g->jmax + BY-1)/BY, g->kmax), block(BX, BY, 1);
-#define CALL(TF) hipLaunchKernelGGL(ib_mask_kernel<TF>, grid, block, 0, as_stream(stream), mp<TF>(mask), mp<TF>(maskh), cp<TF>(dem), cp<TF>(g->z), cp<TF>(g->zh), \
-                                    g->istart, g->iend, g->jstart, g->jend, g->kstart, g->icells, g->ijcells)
-    if (g->dtype == MHH_F64) CALL(double); else CALL(float);
+#define CALL(TF) launch_interior(as_stream(stream), make_grid<TF>(g), g->kstart, g->kend, \
+                                 IbMaskOp<TF>{mp<TF>(mask), mp<TF>(maskh), cp<TF>(dem), cp<TF>(g->z), cp<TF>(g->zh), g->icells})
+    return MHH_DISPATCH(g, CALL);
 #undef CALL
-    MHH_LAUNCH_CHECK();
-    return MHH_OK;
 }
 
 // calc_fluxes (src/immersed_boundary.cxx:541-597) of Immersed_boundary::exec_cross (:950-985): flux [ijcells], interior columns
@@ -442,12 +440,9 @@ MHH_API int mhh_ib_fluxbot(const mhh_grid* g, void* flux, const unsigned int* k_
     if (int e = check_grid(g)) return e;
     MHH_REQUIRE(flux && k_dem && s && g->dz && g->dzhi, "null pointer");
     MHH_REQUIRE(g->igc >= 1 && g->jgc >= 1 && g->kgc >= 1, "calc_fluxes reads one ghost cell in every direction");
-    const dim3 grid((g->imax + BX-1)/BX, (g->jmax + BY-1)/BY), block(BX, BY, 1);
     // gd.dxi = 1./gd.dx (src/grid.cxx:244): a double quotient of the narrowed spacing, narrowed
-#define CALL(TF) hipLaunchKernelGGL(ib_fluxbot_kernel<TF>, grid, block, 0, as_stream(stream), mp<TF>(flux), k_dem, cp<TF>(s), TF(g->dx), TF(g->dy), cp<TF>(g->dz), \
-                                    TF(1./TF(g->dx)), TF(1./TF(g->dy)), cp<TF>(g->dzhi), TF(svisc), g->istart, g->iend, g->jstart, g->jend, g->kstart, g->kend, g->icells, g->ijcells)
-    if (g->dtype == MHH_F64) CALL(double); else CALL(float);
+#define CALL(TF) launch_columns(as_stream(stream), make_grid<TF>(g), 1, IbFluxbotOp<TF>{mp<TF>(flux), k_dem, cp<TF>(s), TF(g->dx), TF(g->dy), cp<TF>(g->dz), \
+                                TF(1./TF(g->dx)), TF(1./TF(g->dy)), cp<TF>(g->dzhi), TF(svisc), g->kstart, g->kend, g->icells, g->ijcells})
+    return MHH_DISPATCH(g, CALL);
 #undef CALL
-    MHH_LAUNCH_CHECK();
-    return MHH_OK;
 }

@@ -1,5 +1,5 @@
 // k_common.h -- host-side plumbing shared by the HIP translation units of libmhh_hip.so:
-// error reporting, mhh_grid -> GridDev<TF> narrowing, the generic cell-kernel launcher.
+// error reporting, mhh_grid -> GridDev<TF> narrowing, the generic cell-kernel and column-kernel launchers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -148,6 +148,27 @@ template<class TF, class Op>
 inline int launch_interior(hipStream_t st, const GridDev<TF>& g, int k0, int k1, const Op& op)
 {
     return launch_cells(st, op, g.istart, g.iend, g.jstart, g.jend, k0, k1, g.icells, g.ijcells);
+}
+
+// ---- generic one-thread-per-column kernel ------------------------------------------------------------
+// The other shape of the physics modules: a thread owns the column (i, j) and walks it serially in k inside the Op, a wave on 64
+// consecutive i of a row. Blocks map to columns in plain grid order (no decode_tile: a column pass touches every plane once, so
+// there is no strip to keep in an L2). blockIdx.z is handed to the Op as z: nz independent passes (species, fields) in one launch.
+template<class Op>
+__global__ void __launch_bounds__(BX*BY) column_kernel(const Op op, int i0, int i1, int j0, int j1, int jj)
+{
+    const int i = i0 + (int)blockIdx.x*BX + (int)threadIdx.x, j = j0 + (int)blockIdx.y*BY + (int)threadIdx.y;
+    if (i >= i1 || j >= j1) return;                              // a ragged row or tile: the lane sits out (no barrier in a column Op)
+    op(i, j, (int)blockIdx.z, i + j*jj);
+}
+template<class TF, class Op>
+inline int launch_columns(hipStream_t st, const GridDev<TF>& g, int nz, const Op& op)
+{
+    if (nz < 1 || g.imax < 1 || g.jmax < 1) return MHH_OK;       // (check_grid refuses an empty interior; the callers pass 1 or 3)
+    hipLaunchKernelGGL(column_kernel<Op>, dim3((g.imax + BX-1)/BX, (g.jmax + BY-1)/BY, nz), dim3(BX, BY, 1), 0, st, op,
+                       g.istart, g.iend, g.jstart, g.jend, g.icells);
+    MHH_LAUNCH_CHECK();
+    return MHH_OK;
 }
 
 #define MHH_DISPATCH(g, CALL) ((g)->dtype == MHH_F64 ? CALL(double) : CALL(float))

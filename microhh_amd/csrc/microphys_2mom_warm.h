@@ -26,7 +26,7 @@ struct MicroArgs
     const TF* rho; const TF* p; const TF* exn; const TF* dz; const TF* dzi;
     TF* c_qr; TF* c_nr; TF* s_qr; TF* s_nr; int* nonconv;
     TF nc; double dt; int mask;
-    int icells, ijcells, istart, iend, jstart, jend, kstart, kend;
+    int icells, ijcells, istart, iend, kstart, kend;          // the i bounds and icells: the marching kernel's own frame
 };
 
 // qr or nr of level k as the processes see it: remove_negative_values (:51-64) covers the interior levels only, the slopes read
@@ -186,28 +186,29 @@ __device__ __forceinline__ TF micro_gather(const MicroArgs<TF>& A, int col, int 
     return ftot;
 }
 template<class TF>
-__global__ void __launch_bounds__(64*MICRO_NJ) micro_flux_kernel(const MicroArgs<TF> A)
+struct MicroFluxOp
 {
-    const int i = A.istart + (int)blockIdx.x*64 + (int)threadIdx.x, j = A.jstart + (int)blockIdx.y*MICRO_NJ + (int)threadIdx.y;
-    if (i >= A.iend || j >= A.jend) return;
-    const int col = i + j*A.icells;
-    TF fq_up = TF(0.), fn_up = TF(0.), fq = TF(0.), fn = TF(0.);           // the flux at kend is zero
-    for (int k=A.kend-1; k>A.kstart-1; --k)
+    MicroArgs<TF> A;
+    __device__ void operator()(int, int, int, int col) const
     {
-        const int c = col + k*A.ijcells;
-        const TF rho = A.rho[k], dz = A.dz[k], dzi = A.dzi[k];
-        TF ftot = micro_gather(A, col, k, A.qr, A.c_qr, A.s_qr, false);
-        ftot = tmin(ftot, rho * dz * A.qr[c] - fq_up * TF(A.dt));
-        fq = TF(-ftot / A.dt);
-        ftot = micro_gather(A, col, k, A.nr, A.c_nr, A.s_nr, true);
-        ftot = tmin(ftot, rho * dz * A.nr[c] - fn_up * TF(A.dt));
-        fn = TF(-ftot / A.dt);
-        A.qrt[c] += -(fq_up - fq) / rho * dzi;
-        A.nrt[c] += -(fn_up - fn) / rho * dzi;
-        fq_up = fq; fn_up = fn;
+        TF fq_up = TF(0.), fn_up = TF(0.), fq = TF(0.), fn = TF(0.);           // the flux at kend is zero
+        for (int k=A.kend-1; k>A.kstart-1; --k)
+        {
+            const int c = col + k*A.ijcells;
+            const TF rho = A.rho[k], dz = A.dz[k], dzi = A.dzi[k];
+            TF ftot = micro_gather(A, col, k, A.qr, A.c_qr, A.s_qr, false);
+            ftot = tmin(ftot, rho * dz * A.qr[c] - fq_up * TF(A.dt));
+            fq = TF(-ftot / A.dt);
+            ftot = micro_gather(A, col, k, A.nr, A.c_nr, A.s_nr, true);
+            ftot = tmin(ftot, rho * dz * A.nr[c] - fn_up * TF(A.dt));
+            fn = TF(-ftot / A.dt);
+            A.qrt[c] += -(fq_up - fq) / rho * dzi;
+            A.nrt[c] += -(fn_up - fn) / rho * dzi;
+            fq_up = fq; fn_up = fn;
+        }
+        A.rr_bot[col] = -fq;
     }
-    A.rr_bot[col] = -fq;
-}
+};
 
 template<class TF>
 static int micro_exec(const mhh_grid* g, int impl, const mhh_micro_params* P, void* qr, void* nr, const void* thl, const void* qt, void* qrt, void* nrt,
@@ -219,10 +220,10 @@ static int micro_exec(const mhh_grid* g, int impl, const mhh_micro_params* P, vo
                           cp<TF>(rhoref), cp<TF>(pref), cp<TF>(exnref), cp<TF>(g->dz), cp<TF>(g->dzi),
                           sedi ? mp<TF>(scratch[0]) : nullptr, sedi ? mp<TF>(scratch[1]) : nullptr, sedi ? mp<TF>(scratch[2]) : nullptr, sedi ? mp<TF>(scratch[3]) : nullptr, nonconv,
                           TF(P->Nc0), P->dt, P->processes,
-                          g->icells, g->ijcells, g->istart, g->iend, g->jstart, g->jend, g->kstart, g->kend};
+                          g->icells, g->ijcells, g->istart, g->iend, g->kstart, g->kend};
+    const GridDev<TF> gd = make_grid<TF>(g);
     if (impl == MHH_MICRO_IMPL_CELL)
     {
-        const GridDev<TF> gd = make_grid<TF>(g);
         if (P->processes & MICRO_CLIP)
         {
             MicroClipOp<TF> clip{mp<TF>(qr), mp<TF>(nr)};
@@ -241,10 +242,7 @@ static int micro_exec(const mhh_grid* g, int impl, const mhh_micro_params* P, vo
         MHH_LAUNCH_CHECK();
     }
     if (sedi)
-    {
-        hipLaunchKernelGGL(micro_flux_kernel<TF>, dim3((g->imax + 63)/64, (g->jmax + MICRO_NJ-1)/MICRO_NJ, 1), dim3(64, MICRO_NJ, 1), 0, st, A);
-        MHH_LAUNCH_CHECK();
-    }
+        return launch_columns(st, gd, 1, MicroFluxOp<TF>{A});
     return MHH_OK;
 }
 
