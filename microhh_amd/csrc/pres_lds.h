@@ -309,8 +309,9 @@ __global__ void __launch_bounds__(BT, (BT >= 128 ? 4 : 1)) pres_in_fftx_kernel(c
         }
         else
         {
-            // rows fastest, modes kx = 0 .. nh; kx = 0 and kx = nh (Nyquist) are real
-            for (int e=(int)tl; e<8*(nh + 1); e+=itot)
+            // rows fastest, modes kx = 0 .. nh; kx = 0 and kx = nh (Nyquist) are real; the columns nh < kx < npy*nxb are the zero
+            // padding of the all-to-all (as xbuf_x_kernel of k_slab.hip writes it): the buffer need not come zeroed
+            for (int e=(int)tl; e<8*a.sl.npy*a.sl.nxb; e+=itot)
             {
                 const int kx = e >> 3, r = e & 7;
                 const int ka = kx & (nh-1);
@@ -320,6 +321,7 @@ __global__ void __launch_bounds__(BT, (BT >= 128 ? 4 : 1)) pres_in_fftx_kernel(c
                 C2<TF> x = ev + mul_tw<-1>(od, T[ka]);
                 if (kx == 0) x = C2<TF>{za.x + za.y, TF(0)};
                 if (kx == nh) x = C2<TF>{za.x - za.y, TF(0)};
+                if (kx > nh) x = C2<TF>{TF(0), TF(0)};
                 a.S[lds_xbuf_index<TF>(a.sl, k, kx, j0 + r, a.nrows)] = x;
             }
         }

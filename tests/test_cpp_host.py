@@ -27,6 +27,18 @@ def test_host_header_is_self_contained():
                                                                           "slab-rccl-two-calls", "slab-rccl-fused", "slab-rccl-overlapped-halos", "slab-rccl-sliced-transposes",
                                                                           "slab-rccl-overlapped-and-sliced"])
 def test_cpp_host_substep_matches_oracle(mode):
+    """The sub-step of the C++ driver on a uniform grid with rhoref = 1; the modes are those of substep_against_the_oracle."""
+    substep_against_the_oracle(mode)
+
+
+@pytest.mark.gpu
+def test_cpp_host_slab_substep_on_a_stretched_grid_with_a_density_profile():
+    """The slab code path (mode 9: slab-rccl-fused) where z is moser_z and rhoref, rhorefh are random and differ: the tables of the
+    slab pressure plan (a != c) and the density factors of the LDS x stage, which the uniform modes above cannot tell apart."""
+    substep_against_the_oracle(9, stretched=True, rho="random")
+
+
+def substep_against_the_oracle(mode, stretched=False, rho="one"):
     """mode bit 0: advec->exec + diff->exec as the fused pass; bit 1: "th" in advec.fluxlimit_list (kgc = 2);
     bit 2: Thermo_dry buoyancy (thermo->exec before advec, or folded into the fused pass); bit 3: the slab code path of
     microhh_amd/host/mhh_host_rccl.h (north-south halos by ncclSend / ncclRecv, the pressure solve around two grouped all-to-alls,
@@ -35,8 +47,8 @@ def test_cpp_host_substep_matches_oracle(mode):
     launch per operator); bit 5: the pressure solve in four k-slices whose all-to-alls run on a second stream (Pres_slab::set_chunks).
     The grid has 24 rows = three strips of eight, so the slab solves take the x stages with the transforms in LDS."""
     subprocess.run(["make", "-s", "-C", CPP], check=True)
-    g = cm.grid_2nd(32, 24, 16, gc=(3, 3, 2 if mode & 2 else 1), stretched=False)
-    c = cm.Case(g, rho="one")
+    g = cm.grid_2nd(32, 24, 16, gc=(3, 3, 2 if mode & 2 else 1), stretched=stretched)
+    c = cm.Case(g, rho=rho)
     sm, dt, visc = 1, 0.6, 1e-5
     thref = np.full(g.kcells, 300.)
     threfh = 300. + 0.37*np.arange(g.kcells)

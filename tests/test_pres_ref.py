@@ -735,7 +735,9 @@ def test_oracle_exec_on_the_slab_case(src, dtype):
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_library_slab_pressure(be, dtype):
     """Pressure through mhh_pres_exec and through the slab path on one rank (mhh_pres_slab_*, the exchanges local copies) against the
-    recorded reference solve: interior of p and of the tendencies within the stated pressure tolerance."""
+    recorded reference solve: interior of p and of the tendencies within the stated pressure tolerance. The case is a uniform grid
+    with rhoref = 1, where the two off-diagonals of the solve are equal: it holds the call sequence of the slab path, not the tables of
+    its plan. Stretched grids, density profiles and more than one rank: tests/test_slab_vranks.py."""
     tol = 1e-11 if dtype == np.float64 else 2e-4
     gi, hps = slab_hotpaths(be, dtype, [False, True])
     z = R.golden()
