@@ -233,7 +233,9 @@ MHH_HD TF advec25_hor_f0(const P& f, TF f0, int jj, TF ue, TF uw, TF vn, TF vs, 
 // rounded by < 2^-53 of itself, the correction term carries the 2^-53 relative error of r: together < 2^-51 ulp); from a
 // faithful quotient a second correction with the exact residual RN(x - d q) gives RN(x/d) (Markstein's theorem; it needs
 // r = RN(1/d) and a significand of d that is not all ones -- the host checks that, known_divisor_ok). Exact for x = 0 and for
-// every x whose residual does not underflow (|x| > 2^-960 in fp64): eddy viscosities are never that small.
+// every x whose residual does not underflow (|x| > 2^-960 in fp64, |x| >= 2^-100 in fp32: the last bit of the residual of a
+// faithful quotient is 2^-47 |x| at the least and has to stay at or above 2^-149; tests/cpp/tiling_probe.cpp, mode divknown, finds
+// the first fp32 mismatches in the binade 2^-112 for d = 0.4 and 0.8, 2^-113 for d = 1/3, 2/3): eddy viscosities are never that small.
 MHH_HD double tfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 MHH_HD float  tfma(float a, float b, float c)    { return __builtin_fmaf(a, b, c); }
 template<class VT, class TF>

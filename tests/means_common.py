@@ -9,6 +9,15 @@ import backends as B
 import common as cm
 
 SHAPES = [(70, 9, 10), (20, 1, 12), (130, 37, 6)]
+# The shapes of tests/test_reduction_order.py, by the level tiling (level_reduce.h) of their chunks of 32 rows; the classes are
+# asserted from the headers by tests/test_launch_geometry.py::test_matrix_reaches_every_geometry_class:
+LEVEL_SHAPES = [(130, 37, 4),     # 2 chunks: sr 1, several k-segments (the class of jtot = 64 and 128)
+                (6, 260, 5),      # 9 chunks: sr 1, 9 strips, a last round of units with idle slots
+                (6, 250, 3),      # 8 chunks: sr 1, 8 strips (the class of jtot = 256)
+                (6, 484, 3),      # 16 chunks: sr 2, 8 strips (the class of jtot = 512)
+                (6, 520, 3),      # 17 chunks: sr 2, the last strip cut
+                (6, 780, 2),      # 25 chunks: sr 3, the last strip cut
+                (6, 1000, 2)]     # 32 chunks: sr 4, 8 strips (the class of jtot = 1024)
 U = 2.0**-53
 
 

@@ -30,7 +30,8 @@ WRITES = {AUTO: OUT, ACCR: ("qrt", "thlt", "qtt"), EVAP: OUT, SCBR: ("nrt",), SE
 
 # (itot, jtot, ktot) and whether the grid is stretched; the last one runs with 8 levels per chunk, so that a gather crosses a seam
 SHAPES = M.SHAPES
-STRETCHED = {(70, 9, 10): False, (17, 9, 8): True, (20, 1, 12): False, (130, 6, 40): True}
+STRETCHED = {(70, 9, 10): False, (17, 9, 8): True, (20, 1, 12): False, (130, 6, 40): True,
+             (66, 100, 40): True, (130, 132, 9): False}       # the last two: tests/test_launch_geometry.py (no reference results, not in SHAPES)
 GCS = M.GCS
 CFLS = {"lo": 0.3, "hi": 3.5}
 # the runs the golden file holds: every mask on the two small shapes (sedimentation with both steps), everything at once with the

@@ -13,18 +13,25 @@ not exist, and the gradient's q*dzhi is the one product that is added, so it pin
 It is the fp64 cases that tell one order from another: a few thousand fp32 values add exactly in double, in any order, and what the
 fp32 cases pin is where a value is rounded to fp32 (the product with dz, the difference of the gradient, the quotient of a mean).
 
+The chunks of a level are dealt to the blocks by level_tiling / level_tile (strips of sr chunks, units round-robin over the 8 XCDs).
+SHAPE has 2 chunks; MORE (means_common.LEVEL_SHAPES) has 8, 9, 16, 17, 25 and 32 of them on 6 columns: sr = 1, 2, 3 and 4, whole and
+cut last strips, a last round of units with idle slots -- the tilings of jtot = 256, 512 and 1024. A chunk decoded twice, not at all
+or with the wrong rows changes a level's sum.
+
 Runs on the ``emul`` backend and on the ``hip`` backend (marked gpu)."""
 import numpy as np
 import pytest
 
 from backends import be  # noqa: F401
 from common import DTYPES, same_bits as same
-from means_common import grid, fields, profiles, sums
+from means_common import grid, fields, profiles, sums, LEVEL_SHAPES
 from microhh_amd import stats as S
 
 BX, BY, ROWS = 64, 4, 32
 SHAPE = (130, 37, 4)
 TALL = (2, 1, 260)
+MORE = [s for s in LEVEL_SHAPES if s != SHAPE]
+MORE_IDS = ["%dx%dx%d" % s for s in MORE]
 THRESHOLDS = (0.2, 0.4, 0.6, 0.8)
 
 
@@ -78,9 +85,8 @@ def test_the_chunk_rows_are_the_one_constant(be):
     assert int(be.lib.mhh_field_mean_chunk_rows()) == ROWS and int(be.lib.mhh_stats_chunk_rows()) == ROWS
 
 
-@pytest.mark.parametrize("dtype", DTYPES)
-def test_mean_profile_is_the_tree_order(be, dtype):
-    g = grid(SHAPE, dtype)
+def mean_profile_is_the_tree_order(be, dtype, shape):
+    g = grid(shape, dtype)
     host = fields(g, 2)
     got = profiles(be, g, be.grid(g), [be.arr(a) for a in host])
     n = float(g.itot * g.jtot)
@@ -90,7 +96,18 @@ def test_mean_profile_is_the_tree_order(be, dtype):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("shape", [SHAPE, TALL])
+def test_mean_profile_is_the_tree_order(be, dtype):
+    mean_profile_is_the_tree_order(be, dtype, SHAPE)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("shape", MORE, ids=MORE_IDS)
+def test_mean_profile_is_the_tree_order_over_many_chunks(be, dtype, shape):
+    mean_profile_is_the_tree_order(be, dtype, shape)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("shape", [SHAPE, TALL] + MORE)
 def test_mean_sum_is_the_tree_order_and_the_finish_kernels(be, dtype, shape):
     g = grid(shape, dtype)
     host = fields(g, 2)
@@ -111,10 +128,10 @@ def test_mean_sum_is_the_tree_order_and_the_finish_kernels(be, dtype, shape):
 class Masked:
     """u, v, w and two mask fields on a backend, a Sampler whose masks are final, the mask words on the host."""
 
-    def __init__(self, be, dtype, nm):
+    def __init__(self, be, dtype, nm, shape=SHAPE):
         import torch
         self.be, self.torch = be, torch
-        self.g = g = grid(SHAPE, dtype)
+        self.g = g = grid(shape, dtype)
         self.G = be.grid(g)
         self.device = torch.device("cpu") if be.name == "emul" else be.dev
         self.h = dict(zip(("u", "v", "w", "m", "mh"), fields(g, 5, seed=11)))
@@ -142,10 +159,10 @@ class Masked:
 _masked = {}
 
 
-def masked(be, dtype, nm):
-    key = (be.name, np.dtype(dtype).name, nm)
+def masked(be, dtype, nm, shape=SHAPE):
+    key = (be.name, np.dtype(dtype).name, nm, shape)
     if key not in _masked:
-        _masked[key] = Masked(be, dtype, nm)
+        _masked[key] = Masked(be, dtype, nm, shape)
     return _masked[key]
 
 
@@ -156,10 +173,8 @@ def inside(g, a, k0, k1):
     return out
 
 
-@pytest.mark.parametrize("nm", [1, 2, 3, 5])
-@pytest.mark.parametrize("dtype", DTYPES)
-def test_stats_sums_are_the_16x16_order(be, dtype, nm):
-    m = masked(be, dtype, nm)
+def stats_sums_are_the_16x16_order(be, dtype, nm, shape):
+    m = masked(be, dtype, nm, shape)
     g, d = m.g, m.d
     jobs = [(d["u"], 0, S.MEAN, 0., 0., None), (d["u"], 0, S.GRAD, 0., 0., None), (d["v"], 0, S.MEAN, 0., 0., None),
             (d["w"], 1, S.MEAN, 0., 0., None), (d["u"], 0, S.COUNT, 0., 0., None), (d["u"], 1, S.COUNT, 0., 0., None)]
@@ -189,8 +204,19 @@ def test_stats_sums_are_the_16x16_order(be, dtype, nm):
 
 @pytest.mark.parametrize("nm", [1, 2, 3, 5])
 @pytest.mark.parametrize("dtype", DTYPES)
-def test_budget_model_sums_are_the_16x16_order_and_the_stats_means(be, dtype, nm):
-    m = masked(be, dtype, nm)
+def test_stats_sums_are_the_16x16_order(be, dtype, nm):
+    stats_sums_are_the_16x16_order(be, dtype, nm, SHAPE)
+
+
+@pytest.mark.parametrize("nm", [2, 5])
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("shape", MORE, ids=MORE_IDS)
+def test_stats_sums_are_the_16x16_order_over_many_chunks(be, dtype, nm, shape):
+    stats_sums_are_the_16x16_order(be, dtype, nm, shape)
+
+
+def budget_model_sums_are_the_16x16_order_and_the_stats_means(be, dtype, nm, shape):
+    m = masked(be, dtype, nm, shape)
     g, d, t = m.g, m.d, m.torch
     got = t.zeros((3, nm, g.kcells), device=m.device, dtype=t.float64)
     scratch = t.zeros((int(be.lib.mhh_budget_2_scratch_elems(m.G, nm)),), device=m.device, dtype=t.float64)
@@ -202,3 +228,15 @@ def test_budget_model_sums_are_the_16x16_order_and_the_stats_means(be, dtype, nm
     for n, (var, half) in enumerate((("u", 0), ("v", 0), ("w", 1))):
         assert same(got[n], m.mean_sums(var, half)), var           # calc_mask_mean_profile: every level of kcells
     assert same(got[:, :, g.kstart:g.kend+1], stats[:, :, g.kstart:g.kend+1])
+
+
+@pytest.mark.parametrize("nm", [1, 2, 3, 5])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_budget_model_sums_are_the_16x16_order_and_the_stats_means(be, dtype, nm):
+    budget_model_sums_are_the_16x16_order_and_the_stats_means(be, dtype, nm, SHAPE)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("shape", MORE, ids=MORE_IDS)
+def test_budget_model_sums_are_the_16x16_order_over_many_chunks(be, dtype, shape):
+    budget_model_sums_are_the_16x16_order_and_the_stats_means(be, dtype, 2, shape)
