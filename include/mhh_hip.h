@@ -967,6 +967,66 @@ int mhh_ib_mask(const mhh_grid* g, const void* dem, void* mask, void* maskh, voi
  * operand order. k_dem [ijcells] with filled halos, on the device. */
 int mhh_ib_fluxbot(const mhh_grid* g, void* flux, const unsigned int* k_dem, const void* s, double svisc, void* stream);
 
+/* ---- Source and Decay (src/source.cxx, src/decay.cxx; src/model.cxx:398, :401) ---------------------------------------------------
+ * Tracer emissions into the tendencies of passive scalars (Gaussian blobs, line segments, blobs with a vertical emission profile)
+ * and their exponential decay. The set-up of Source::create runs on the HOST inside the library; the target is the reference's CPU
+ * path, which has the moving and time-varying sources its GPU path refuses (src/source.cu:134). */
+typedef struct mhh_source_desc
+{
+    int scalar;                 /* index of the target in mhh_fields.st (sourcelist[n])                                          */
+    int swvmr;                  /* != 0: strength in kmol s-1, scaling rhoref[k]/xmair; 0: kg s-1, scaling rhoref[k]              */
+    int profile_index;          /* row of the emission profiles, < 0: none (sw_profile)                                          */
+    int reserved;
+    double x0, y0, z0, sigma_x, sigma_y, sigma_z, line_x, line_y, line_z, strength;    /* narrowed to the grid's dtype first    */
+} mhh_source_desc;
+typedef struct mhh_source mhh_source;
+/* Source::create (src/source.cxx:266-316) for nsrc sources: per source the index ranges of calc_shape (:44-75) or, in z of a profile
+ * source, calc_shape_profile (:77-98), and the norm of Source::calc_norm (:435-547), as the reference has them: no periodic wrap, the
+ * ranges clipped to the interior; the norm's test INCLUSIVE (i <= range[1]) where the emission loop is exclusive; only the first
+ * non-zero of line_x, line_y, line_z gets the three-branch segment. g holds HOST metric pointers (z and dz are read), profiles is host
+ * memory [nprofiles][kcells], rhoref host memory [kcells], all of the grid's dtype. The norm is summed over the source's box alone
+ * in k, j, i order with the host's exp: the reference adds +0 elsewhere. On a slab (npy > 1) x and y are those of the one-rank grid
+ * (src/grid.cxx:252-262 with no offset) and every rank sums the norm of the WHOLE domain, so no exchange is needed and a rank's
+ * tendencies are rows of the one-rank result. The device tables are uploaded on the stream, which is synchronised.
+ * Refused with a reason: a profile source with a line length != 0 (the reference refuses > 0, :239-244), a scalar or profile index out of range, sigma <= 0. */
+int mhh_source_create(const mhh_grid* g, const mhh_source_desc* src, int nsrc, const void* profiles, int nprofiles, const void* rhoref,
+                      void* stream, mhh_source** out);
+void mhh_source_destroy(mhh_source* h);
+/* What Source::exec does under swtimedep_location and swtimedep_strength (src/source.cxx:362-401) once Timedep has interpolated: new
+ * x0, y0, z0 and / or strength (NULL: kept) for source n (one value each) or, n < 0, for every source (arrays of the source count).
+ * A move redoes the ranges and the norm; the tables are rebuilt and uploaded on the stream, which is synchronised: host work, not
+ * part of a captured graph (the launch's size changes with the tables). Refused: a source with a profile ("Emission profiles with
+ * time dependent location/strength are not (yet) supported!", :236, :381). */
+int mhh_source_update(mhh_source* h, int n, const double* x0, const double* y0, const double* z0, const double* strength, void* stream);
+int mhh_source_count(const mhh_source* h);
+int mhh_source_tiles(const mhh_source* h);                      /* blocks of the launch                                           */
+/* shape[n].range_x, range_y, range_z (array indices of this rank) and norm[n] (src/source.cxx:292-315) */
+int mhh_source_ranges(const mhh_source* h, int n, int* range6);
+int mhh_source_norm(const mhh_source* h, int n, double* norm);
+/* calc_source (src/source.cxx:100-190) of Source::exec (:403-431) for all sources of all scalars in ONE launch; calc_source_g of
+ * src/source.cu launches once per source. A cell of f->st[scalar] is read and written once and the sources whose box holds it are
+ * added in source order: the bits of the reference's loops where the host's exp is the reference's. Only enqueues: no allocation,
+ * no synchronisation, no host round trip. */
+int mhh_source_exec(mhh_source* h, const mhh_grid* g, const mhh_fields* f, void* stream);
+typedef struct mhh_decay_params
+{
+    int    exponential[MHH_MAX_SCALARS];   /* swdecay[name] = exponential; all zero: the call does nothing                       */
+    double timescale[MHH_MAX_SCALARS];     /* [decay] timescale[name]                                                            */
+} mhh_decay_params;
+/* enforce_exponential_decay (src/decay.cxx:35-51) of Decay::exec (:97-111) for every decaying scalar in ONE launch over the interior:
+ * st -= rate*s with rate = 1./max(timescale, dt_sub), the quotient in double and narrowed (the reference's `1.` is a double literal);
+ * dt_sub is timeloop->get_sub_time_step() (src/model.cxx:398). Same bits, fp64 and fp32. stats.calc_tend is not built. */
+int mhh_decay_exec(const mhh_grid* g, const mhh_fields* f, const mhh_decay_params* p, double dt_sub, void* stream);
+/* Decay::get_mask("couvreux") (src/decay.cxx:123-187) in two halves, so that a slab can sum over its ranks between them as master.sum
+ * does. _sums: sums [2][kcells] DOUBLES = the sums of s and of s*s (the square in the grid's dtype) over the rank's interior of each
+ * level, through the deterministic two-stage reduction of the horizontal means; scratch holds
+ * mhh_decay_couvreux_scratch_elems(g) doubles. _field: mean = sums/(itot*jtot) and var = sumsq/(itot*jtot) - mean*mean narrowed,
+ * out = s - mean - nstd*sqrt(var) on the interior and zero elsewhere, outh = grid.interpolate_2nd(out) to the half levels
+ * (src/grid.cxx:455-499). The mask is then mhh_stats_mask_thres(out, outh, threshold 0, MHH_STATS_MASK_PLUS). Only enqueue. */
+unsigned long long mhh_decay_couvreux_scratch_elems(const mhh_grid* g);
+int mhh_decay_couvreux_sums(const mhh_grid* g, const void* s, void* scratch, void* sums, void* stream);
+int mhh_decay_couvreux_field(const mhh_grid* g, const void* s, const void* sums, double nstd, void* out, void* outh, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,6 +94,15 @@ class MhhBudget2Desc(C.Structure):
                 ("utrans", cd), ("vtrans", cd), ("fc", cd), ("order", ci), ("diff_scheme", ci), ("groups", C.c_uint)]
 
 
+class MhhSourceDesc(C.Structure):
+    _fields_ = [("scalar", ci), ("swvmr", ci), ("profile_index", ci), ("reserved", ci)] + \
+               [(n, cd) for n in ("x0", "y0", "z0", "sigma_x", "sigma_y", "sigma_z", "line_x", "line_y", "line_z", "strength")]
+
+
+class MhhDecayParams(C.Structure):
+    _fields_ = [("exponential", ci * MAX_SCALARS), ("timescale", cd * MAX_SCALARS)]
+
+
 FP = C.POINTER(MhhFields)
 SP = C.POINTER(MhhSurfaceParams)
 DP = C.POINTER(MhhDiffParams)
@@ -106,6 +115,9 @@ BDP = C.POINTER(MhhBudget2Desc)
 CJP = C.POINTER(MhhCrossJob)
 IGP = C.POINTER(MhhIbGhostLists)
 IJP = C.POINTER(MhhIbJob)
+SDP = C.POINTER(MhhSourceDesc)
+DCP = C.POINTER(MhhDecayParams)
+CDP = C.POINTER(cd)
 PLAN = vp
 
 SIGNATURES = {
@@ -264,6 +276,18 @@ SIGNATURES = {
     "mhh_ib_set_ghost_cells": (ci, [GP, ci, IJP, ci, vp]),
     "mhh_ib_mask": (ci, [GP, vp, vp, vp, vp]),
     "mhh_ib_fluxbot": (ci, [GP, vp, vp, vp, cd, vp]),
+    "mhh_source_create": (ci, [GP, SDP, ci, vp, ci, vp, vp, C.POINTER(vp)]),
+    "mhh_source_destroy": (None, [vp]),
+    "mhh_source_update": (ci, [vp, ci, CDP, CDP, CDP, CDP, vp]),
+    "mhh_source_count": (ci, [vp]),
+    "mhh_source_tiles": (ci, [vp]),
+    "mhh_source_ranges": (ci, [vp, ci, C.POINTER(ci)]),
+    "mhh_source_norm": (ci, [vp, ci, CDP]),
+    "mhh_source_exec": (ci, [vp, GP, FP, vp]),
+    "mhh_decay_exec": (ci, [GP, FP, DCP, cd, vp]),
+    "mhh_decay_couvreux_scratch_elems": (C.c_ulonglong, [GP]),
+    "mhh_decay_couvreux_sums": (ci, [GP, vp, vp, vp, vp]),
+    "mhh_decay_couvreux_field": (ci, [GP, vp, vp, cd, vp, vp, vp]),
 }
 
 

@@ -850,3 +850,8 @@ MHH_API int mhh_boundary_ghost_cells_w(const mhh_grid* g, void* w, int type, voi
 // Immersed_boundary: DEM ghost cells, the ib mask and the wall flux (src/immersed_boundary.cxx)
 // =======================================================================================================
 #include "immersed_boundary.h"
+
+// =======================================================================================================
+// Source and Decay: tracer emissions in one launch, exponential decay (src/source.cxx, src/decay.cxx)
+// =======================================================================================================
+#include "source_decay.h"

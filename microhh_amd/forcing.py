@@ -166,3 +166,13 @@ class Forcing:
         """buffer->exec and force->exec (src/model.cxx:395,404) as one pass over the tendencies."""
         hp = self.hp
         capi.check(hp.lib.mhh_buffer_force_exec(hp.G, C.byref(hp.fields), C.byref(self.bparams), C.byref(self.fparams), hp.stream), hp.lib)
+
+    def exec_buffer(self):
+        """buffer->exec (src/model.cxx:395) on its own: a stage sits between it and force->exec."""
+        hp = self.hp
+        capi.check(hp.lib.mhh_buffer_exec(hp.G, C.byref(hp.fields), C.byref(self.bparams), hp.stream), hp.lib)
+
+    def exec_force(self):
+        """force->exec (src/model.cxx:404) on its own."""
+        hp = self.hp
+        capi.check(hp.lib.mhh_force_exec(hp.G, C.byref(hp.fields), C.byref(self.fparams), hp.stream), hp.lib)

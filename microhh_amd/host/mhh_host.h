@@ -1760,4 +1760,117 @@ class Immersed_boundary
         int offx = 0, offy = 0;
 };
 
+// ---- Source (include/source.h:33-100; src/source.cxx) ------------------------------------------------------------------------------
+// The reference's lists as public members (what its constructor reads from [source]), init / create / exec with its meaning.
+// create() hands them to mhh_source_create, which redoes calc_shape / calc_shape_profile / calc_norm on the host; exec() is
+// Source::exec (:355-432) after the Timedep interpolation, which stays the caller's: set source_x0 .. strength and call update().
+template<typename TF>
+class Source
+{
+    public:
+        Source(Grid<TF>& gridin, Fields<TF>& fieldsin) : grid(gridin), fields(fieldsin) {}
+        ~Source() { if (handle) mhh_source_destroy(handle); }
+        Source(const Source&) = delete;
+        bool swsource = false, sw_emission_profile = false;
+        std::vector<std::string> sourcelist;
+        std::vector<TF> source_x0, source_y0, source_z0, sigma_x, sigma_y, sigma_z, strength, line_x, line_y, line_z;
+        std::vector<bool> sw_vmr;
+        std::vector<int> profile_index;
+        std::map<int, std::vector<TF>> profile_z;                    // [kcells] each, as Source::create reads them (:280-286)
+        void init() {}
+        void create(void* stream = nullptr)
+        {
+            if (!swsource) return;
+            auto& gd = grid.get_grid_data();
+            const size_t n = source_x0.size();
+            std::vector<int> rows;                                   // the unique profile indices in order -> rows of the table
+            std::vector<TF> prof;
+            for (auto& it : profile_z)
+            {
+                if ((int)it.second.size() != gd.kcells) throw std::runtime_error("mhh: an emission profile holds kcells elements");
+                rows.push_back(it.first); prof.insert(prof.end(), it.second.begin(), it.second.end());
+            }
+            std::vector<mhh_source_desc> d(n);
+            for (size_t m=0; m<n; ++m)
+            {
+                d[m] = mhh_source_desc{};
+                d[m].scalar = scalar_index(fields, sourcelist[m]);
+                d[m].swvmr = sw_vmr[m]; d[m].profile_index = -1;
+                if (sw_emission_profile)
+                    d[m].profile_index = (int)(std::find(rows.begin(), rows.end(), profile_index[m]) - rows.begin());
+                d[m].x0 = source_x0[m]; d[m].y0 = source_y0[m]; d[m].z0 = source_z0[m];
+                d[m].sigma_x = sigma_x[m]; d[m].sigma_y = sigma_y[m]; d[m].sigma_z = sigma_z[m];
+                d[m].line_x = line_x[m]; d[m].line_y = line_y[m]; d[m].line_z = line_z[m]; d[m].strength = strength[m];
+            }
+            mhh_grid gh = grid.abi(true);
+            if (handle) { mhh_source_destroy(handle); handle = nullptr; }
+            mhh_check(mhh_source_create(&gh, d.data(), (int)n, prof.empty() ? nullptr : prof.data(), (int)rows.size(), fields.rhoref.data(), stream, &handle));
+        }
+        // swtimedep_location / swtimedep_strength (:362-401): the members hold what Timedep interpolated
+        void update(bool location, bool strength_too, void* stream = nullptr)
+        {
+            if (!swsource || !(location || strength_too)) return;
+            std::vector<double> x(source_x0.begin(), source_x0.end()), y(source_y0.begin(), source_y0.end()), z(source_z0.begin(), source_z0.end()),
+                                q(strength.begin(), strength.end());
+            mhh_check(mhh_source_update(handle, -1, location ? x.data() : nullptr, location ? y.data() : nullptr, location ? z.data() : nullptr,
+                                        strength_too ? q.data() : nullptr, stream));
+        }
+        void exec(void* stream = nullptr)
+        {
+            if (!swsource) return;
+            mhh_grid g = grid.abi(); mhh_fields f = abi_fields(fields);
+            mhh_check(mhh_source_exec(handle, &g, &f, stream));
+        }
+        TF get_norm(int n) const { double v; mhh_check(mhh_source_norm(handle, n, &v)); return TF(v); }
+        std::array<int, 6> get_ranges(int n) const { std::array<int, 6> r; mhh_check(mhh_source_ranges(handle, n, r.data())); return r; }
+    private:
+        Grid<TF>& grid; Fields<TF>& fields;
+        mhh_source* handle = nullptr;
+};
+
+// ---- Decay (include/decay.h:42-78; src/decay.cxx) -------------------------------------------------------------------------------------
+enum class Decay_type {disabled, enabled, exponential};
+template<typename TF>
+class Decay
+{
+    public:
+        Decay(Grid<TF>& gridin, Fields<TF>& fieldsin) : grid(gridin), fields(fieldsin) {}
+        struct Decay_var { double timescale; Decay_type type; };
+        std::map<std::string, Decay_var> dmap;                      // what init() reads from [decay] (:66-88)
+        TF nstd_couvreux = 1.;
+        void init() {}
+        void create(Stats&) {}
+        void exec(double dt, Stats&, void* stream = nullptr)        // (:97-111); stats.calc_tend is a no-op off sampling steps
+        {
+            mhh_decay_params p{};
+            for (auto& it : dmap)
+                if (it.second.type == Decay_type::exponential)
+                {
+                    const int n = scalar_index(fields, it.first);
+                    if (n < 0) throw std::runtime_error("mhh: decay of an unknown scalar " + it.first);
+                    p.exponential[n] = 1; p.timescale[n] = it.second.timescale;
+                }
+            mhh_grid g = grid.abi(); mhh_fields f = abi_fields(fields);
+            mhh_check(mhh_decay_exec(&g, &f, &p, dt, stream));
+        }
+        bool has_mask(std::string name) { return name == "couvreux"; }
+        // (:123-187). couvreux, couvreuxh: the two tmp fields; work: mhh_decay_couvreux_scratch_elems + 2*kcells device doubles;
+        // sum_ranks: the sum over the ranks, in place, of device doubles (empty on one rank), as master.sum
+        void get_mask(Stats_sampler<TF>& stats, std::string mask_name, Field3d<TF>& couvreux, Field3d<TF>& couvreuxh, double* work,
+                      std::function<void(double*, size_t)> sum_ranks = nullptr, void* stream = nullptr)
+        {
+            if (mask_name != "couvreux") throw std::runtime_error("Decay cannot provide mask: \"" + mask_name + "\"");
+            if (fields.sp.find("couvreux") == fields.sp.end()) throw std::runtime_error("Couvreux mask not available without couvreux scalar");
+            mhh_grid g = grid.abi();
+            double* sums = work + mhh_decay_couvreux_scratch_elems(&g);
+            const TF* s = fields.sp.at("couvreux")->fld_g;
+            mhh_check(mhh_decay_couvreux_sums(&g, s, work, sums, stream));
+            if (sum_ranks) sum_ranks(sums, 2*(size_t)grid.get_grid_data().kcells);
+            mhh_check(mhh_decay_couvreux_field(&g, s, sums, nstd_couvreux, couvreux.fld_g, couvreuxh.fld_g, stream));
+            stats.set_mask_thres(mask_name, couvreux, couvreuxh, TF(0.), Stats_mask_type::Plus, stream);
+        }
+    private:
+        Grid<TF>& grid; Fields<TF>& fields;
+};
+
 } // namespace mhh_host

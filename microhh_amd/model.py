@@ -112,7 +112,8 @@ class HotPath:
 
     def __init__(self, case, itot, jtot, ktot, dtype=np.float64, device="cuda:0", seed=666, dt=1.0,
                  lib=None, npy=1, rank=0, group=None, global_init=None, force_slab=False, slim_halos=True, overlap=None, pres_chunks=None, igc=None,
-                 nscalars=None, forcing=None, surface=None, thermo=None, micro=None, radiation=None, stats=None, budget=None, cross=None, ib=None):
+                 nscalars=None, forcing=None, surface=None, thermo=None, micro=None, radiation=None, stats=None, budget=None, cross=None, ib=None,
+                 source=None, decay=None):
         import torch
         if budget is not None and stats is None:
             raise ValueError("budget= needs stats=Stats(...): the budget profiles are averaged under the masks of the statistics")
@@ -280,6 +281,10 @@ class HotPath:
         self.radiation = radiation.bind(self) if radiation is not None else None
         # Immersed_boundary (ib.Dem): the ghost-cell tables of u, v, w and s, the mask fields and k_dem, made once on the host
         self.ib = ib.bind(self) if ib is not None else None
+        # Source and Decay (source.Sources, source.Decay): the sources' ranges, norms and device tables, made once on the host;
+        # in front of Stats, whose couvreux mask asks the decay for its scalar
+        self.source = source.bind(self) if source is not None else None
+        self.decay = decay.bind(self) if decay is not None else None
         # Stats (stats.Stats): the mask words, counts and reduction scratch; sampled outside the step by hp.stats.sample()
         self.stats = stats.bind(self) if stats is not None else None
         # Budget_2 (budget.Budget2): the budget group of the statistics, sampled with them after Stats' own passes
@@ -543,6 +548,13 @@ class HotPath:
         """buffer->exec and force->exec (src/model.cxx:395,404) in one pass over the tendencies."""
         self.forcing.exec()
 
+    def decay_source(self):
+        """decay->exec and source->exec (src/model.cxx:398,401), one launch each."""
+        if self.decay is not None:
+            self.decay.exec()
+        if self.source is not None:
+            self.source.exec()
+
     def thermo_moist(self):
         """thermo->exec (src/model.cxx:366; Thermo_moist::exec, src/thermo_moist.cxx:1273-1303): with swupdatebasestate the base state
         from the means on the device, then the buoyancy tendency of w."""
@@ -563,7 +575,9 @@ class HotPath:
         exec_viscosity with the RHS, and the surface layer sits between them). With `thermo` (thermo.Moist), the same plain sequence
         with the means of thl and qt in front of exec_viscosity and Thermo_moist::exec behind it. With `ib` (ib.Dem), the plain
         sequence on a slab too, with the two calls of src/model.cxx:380 and :407: the scalars' ghost cells after the surface layer and
-        in front of the RHS, those of u, v, w after Buffer and Force and in front of the pressure solve."""
+        in front of the RHS, those of u, v, w after Buffer and Force and in front of the pressure solve. With `source` or `decay`
+        (source.Sources, source.Decay), the order of src/model.cxx:395-404: Buffer, decay, source, Force -- Buffer and Force as their own
+        passes, which have the bits of the fused one; without the two nothing changes."""
         means_done = False
         if self.thermo is not None:
             # Thermo_moist, in the order of Model::exec (src/model.cxx:346-392): the cyclic fills; fields->exec, the means of thl and qt
@@ -604,7 +618,14 @@ class HotPath:
         if self.forcing is not None:
             if not means_done:
                 self.forcing_means()
-            self.buffer_force()
+            if self.source is None and self.decay is None:
+                self.buffer_force()
+            else:
+                self.forcing.exec_buffer()
+                self.decay_source()
+                self.forcing.exec_force()
+        elif self.source is not None or self.decay is not None:
+            self.decay_source()
         if self.ib is not None:                # ib->exec_momentum (:407), after buffer->exec and force->exec
             self.ib.exec_momentum()
         self.pres()
@@ -622,7 +643,14 @@ class HotPath:
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             self.step()
+        self._graphs = getattr(self, "_graphs", []) + [graph]      # source.update() resets them: they hold the old tables' launch
         return graph
+
+    def drop_graphs(self):
+        """Reset every graph capture_step() has returned: a replay then raises instead of launching over tables that are gone."""
+        for g in getattr(self, "_graphs", []):
+            g.reset()
+        self._graphs = []
 
     # -- reductions (local max, then Master.max over ranks) ------------------------------------------------------
     def divergence(self):

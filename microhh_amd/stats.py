@@ -151,7 +151,8 @@ class Stats:
     bind() registers what Fields::exec_stats (src/fields.cxx:647-665) and Diff_smag2::exec_stats register, as far as their
     operations are built: w; u and v with utrans / vtrans as offsets; every scalar and its _bot; p; evisc. add() registers more, e.g.
     a ql field with ("mean", "frac", "path", "cover") at its threshold. Built-in masks: "default"; "wplus" and "wmin" as
-    Fields::get_mask builds them; "ql" as Thermo_moist::get_mask does (needs thermo=Moist). Any other name is a mask whose thresholds
+    Fields::get_mask builds them; "ql" as Thermo_moist::get_mask does (needs thermo=Moist); "couvreux" as Decay::get_mask does (needs
+    decay=Decay(..., names={"couvreux": n})). Any other name is a mask whose thresholds
     the caller registers with mask_thres(); all are applied, in the order given, at every sample()."""
 
     def __init__(self, masks=("default",), utrans=None, vtrans=None):
@@ -180,6 +181,13 @@ class Stats:
                 if hp.thermo is None or not hasattr(hp.thermo, "field"):
                     raise ValueError("Stats: the ql mask needs thermo=Moist(pbot)")
                 self.mask_thres(m, self.ql, self.ql_h, None, 0., PLUS)
+            elif m == "couvreux":
+                # Decay::get_mask (src/decay.cxx:123-187): the decaying tracer less its level mean and nstd_couvreux standard
+                # deviations, and its interpolation to the half levels, at threshold 0; the reference throws without the scalar
+                dec = getattr(hp, "decay", None)
+                if dec is None or dec.couvreux_index is None:
+                    raise ValueError("Couvreux mask not available without couvreux scalar")
+                self.mask_thres(m, dec.couvreux, dec.couvreux_h, None, 0., PLUS)
             elif m == "ib" and getattr(hp, "ib", None) is not None:
                 # Immersed_boundary::get_mask (src/immersed_boundary.cxx:930-946): calc_mask's two fields at threshold 0.5; without
                 # ib= the name stays a mask of the caller's
