@@ -1027,6 +1027,35 @@ unsigned long long mhh_decay_couvreux_scratch_elems(const mhh_grid* g);
 int mhh_decay_couvreux_sums(const mhh_grid* g, const void* s, void* scratch, void* sums, void* stream);
 int mhh_decay_couvreux_field(const mhh_grid* g, const void* s, const void* sums, double nstd, void* out, void* outh, void* stream);
 
+/* ---- Boundary_outflow (src/boundary_outflow.cxx; src/model.cxx:347, :383) -------------------------------------------------------------
+ * Open lateral boundaries for scalars: Boundary::set_prognostic_outflow_bcs (src/boundary.cxx:464-469) loops over the scalars of
+ * scalar_outflow; momentum and the pressure solve stay periodic. */
+#define MHH_OUTFLOW_WEST   1   /* Edge_location (include/boundary_outflow.h): the bits of edges_mask; dirs[] is indexed West, East, South, North */
+#define MHH_OUTFLOW_EAST   2
+#define MHH_OUTFLOW_SOUTH  4
+#define MHH_OUTFLOW_NORTH  8
+#define MHH_OUTFLOW_OUTFLOW 0  /* Flow_direction::Outflow: a[gc] = a[mirror interior cell]                                           */
+#define MHH_OUTFLOW_INFLOW  1  /* Flow_direction::Inflow:  a[gc] = a_d - (n+1)*2*(a_d - inflow_prof[k])                               */
+/* The inflow table of Boundary::process_time_dependent_outflow / Boundary::create (src/boundary.cxx:411-426): the ktot values of
+ * prof_ktot at kstart .. kend-1 of table_kcells, its ghost levels ZERO (the zero-initialised vector and std::rotate of :421-424).
+ * Both are host memory of the grid's dtype; the caller uploads the table. */
+int mhh_boundary_outflow_profile_host(const mhh_grid* g, const void* prof_ktot, void* table_kcells);
+/* Boundary_outflow<TF>::exec (src/boundary_outflow.cxx:236-343; GPU src/boundary_outflow.cu:147-291) for nfields scalars at once.
+ * order 2: compute_inoutflow_2nd (:85-149) on the edges of edges_mask in the order West, East, South, North, West / East over all
+ * jcells x kcells and South / North over all icells, so the corner ghost cells are the South / North rule applied to what West / East
+ * wrote. South and North set kgc ghost rows, not jgc: the reference passes gd.kgc where the loops expect jgc (:311, :333). dirs[4]:
+ * MHH_OUTFLOW_OUTFLOW or _INFLOW per edge; profiles[n]: device table [kcells] of field n, read on inflow edges only (may be NULL
+ * without one). order 4: compute_inflow_4th with value 0 at West and compute_outflow_4th at East (:151-193), three ghost columns
+ * each; dirs, profiles and the South / North bits are ignored. edges_mask: the edges this rank owns (the reference's mpicoordx == 0,
+ * mpicoordy == 0, ... tests); 0 does nothing. At most TWO launches whatever nfields and edges_mask are, where the reference launches
+ * once per scalar and edge. Bit for bit the reference's CPU loops. Only enqueues: no allocation, no synchronisation.
+ * Refused with a reason, nothing launched: itot < igc, kgc > jgc, jmax < kgc with a South or North edge (the reference's serial loops
+ * would read cells they also write, or index outside the field); order 4 with igc < 3 or itot < 3. */
+int mhh_boundary_outflow_exec(const mhh_grid* g, int order, void* const* fields, int nfields, const void* const* profiles, const int* dirs,
+                              int edges_mask, void* stream);
+/* the launches the calling thread's last mhh_boundary_outflow_exec made (the reference: one per scalar and edge, src/boundary_outflow.cu:209-287) */
+int mhh_boundary_outflow_last_launches(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -288,6 +288,9 @@ SIGNATURES = {
     "mhh_decay_couvreux_scratch_elems": (C.c_ulonglong, [GP]),
     "mhh_decay_couvreux_sums": (ci, [GP, vp, vp, vp, vp]),
     "mhh_decay_couvreux_field": (ci, [GP, vp, vp, cd, vp, vp, vp]),
+    "mhh_boundary_outflow_profile_host": (ci, [GP, vp, vp]),
+    "mhh_boundary_outflow_exec": (ci, [GP, ci, C.POINTER(vp), ci, C.POINTER(vp), C.POINTER(ci), ci, vp]),
+    "mhh_boundary_outflow_last_launches": (ci, []),
 }
 
 

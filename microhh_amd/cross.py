@@ -201,6 +201,11 @@ class Cross:
                     seen.add(id(t)); need_halo.append(t)
         if need_halo:
             hp.halo(need_halo)                # through the communicator, as Stats' fills
+            # the cyclic fill has overwritten the lateral ghost cells of an open scalar (outflow.Outflow): the reference's sections
+            # read them as set_prognostic_outflow_bcs left them (cross_lngrad, src/cross.cxx), so the outflow fill follows
+            out = getattr(hp, "outflow", None)
+            if out is not None and any(t is hp.s[n] for t in need_halo for n in out.index):
+                hp.outflow_bcs()
         gather, lngrad = [], []
         for p in self.pieces:
             t, out = self._now(p["src"]), self.staging.data_ptr() + p["pos"]*es

@@ -855,3 +855,8 @@ MHH_API int mhh_boundary_ghost_cells_w(const mhh_grid* g, void* w, int type, voi
 // Source and Decay: tracer emissions in one launch, exponential decay (src/source.cxx, src/decay.cxx)
 // =======================================================================================================
 #include "source_decay.h"
+
+// =======================================================================================================
+// Boundary_outflow: open lateral boundaries for scalars in two launches (src/boundary_outflow.cxx)
+// =======================================================================================================
+#include "boundary_outflow.h"

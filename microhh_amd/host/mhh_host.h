@@ -1873,4 +1873,73 @@ class Decay
         Grid<TF>& grid; Fields<TF>& fields;
 };
 
+// ---- Boundary_outflow (include/boundary_outflow.h:33-51; src/boundary_outflow.cxx) ---------------------------------------------------
+// Open lateral boundaries for scalars. The constructor takes what the reference's reads from [boundary] (flow_direction[west ..
+// north], :207-225) and the scalar_outflow list that Boundary holds (src/boundary.cxx:464-469); exec(data, inflow_prof) is the
+// reference's member, exec_all is Boundary::set_prognostic_outflow_bcs for all scalars of the list in the launches of one. The
+// sequence of Model::exec calls exec_all directly after the cyclic fills (src/model.cxx:347) and, with an immersed boundary, once
+// more after ib->exec_scalars (:383). swspatialorder: grid.get_spatial_order().
+enum class Edge_location {West, East, South, North};
+enum class Flow_direction {Inflow, Outflow};
+template<typename TF>
+class Boundary_outflow
+{
+    public:
+        Boundary_outflow(Grid<TF>& gridin, std::map<Edge_location, Flow_direction> flow_directionin, std::vector<std::string> scalar_outflowin,
+                         int swspatialorderin = 2) :
+            scalar_outflow(std::move(scalar_outflowin)), swspatialorder(swspatialorderin), grid(gridin), flow_direction(std::move(flow_directionin))
+        {
+            if (!scalar_outflow.empty())
+                for (Edge_location e : {Edge_location::West, Edge_location::East, Edge_location::South, Edge_location::North})
+                    if (!flow_direction.count(e)) throw std::runtime_error("Boundary_outflow: a flow_direction is missing");
+        }
+        std::vector<std::string> scalar_outflow;
+        int swspatialorder;
+        // Boundary::process_inflow (src/boundary.cxx:411-426): ktot values at kstart .. kend-1 of a zeroed kcells vector (host)
+        std::vector<TF> inflow_profile(const std::vector<TF>& prof_ktot) const
+        {
+            const auto& gd = grid.get_grid_data();
+            if ((int)prof_ktot.size() != gd.ktot) throw std::runtime_error("Boundary_outflow: an inflow profile holds ktot values");
+            std::vector<TF> table(gd.kcells);
+            mhh_grid g = grid.abi(true);
+            mhh_check(mhh_boundary_outflow_profile_host(&g, prof_ktot.data(), table.data()));
+            return table;
+        }
+        // the edges this rank owns: mpicoordx == 0 == npx-1; mpicoordy == 0, mpicoordy == npy-1 (:247-323)
+        int edges() const
+        {
+            const auto& gd = grid.get_grid_data();
+            return MHH_OUTFLOW_WEST | MHH_OUTFLOW_EAST | (gd.mpicoordy == 0 ? MHH_OUTFLOW_SOUTH : 0) | (gd.mpicoordy == gd.npy-1 ? MHH_OUTFLOW_NORTH : 0);
+        }
+        // Boundary_outflow<TF>::exec (:236-343): data and inflow_prof [kcells] are device memory
+        void exec(TF* data, const TF* inflow_prof, void* stream = nullptr)
+        {
+            void* f[1] = {data}; const void* p[1] = {inflow_prof};
+            launch(f, p, 1, edges(), stream);
+        }
+        // Boundary::set_prognostic_outflow_bcs (src/boundary.cxx:464-469): every scalar of scalar_outflow, at most two launches
+        void exec_all(Fields<TF>& fields, const std::map<std::string, TF*>& inflow_profiles_g, void* stream = nullptr) { exec_all(fields, inflow_profiles_g, edges(), stream); }
+        void exec_all(Fields<TF>& fields, const std::map<std::string, TF*>& inflow_profiles_g, int edges_mask, void* stream = nullptr)
+        {
+            if (scalar_outflow.empty()) return;
+            if (scalar_outflow.size() > MHH_MAX_SCALARS) throw std::runtime_error("mhh: more than MHH_MAX_SCALARS scalars");
+            void* f[MHH_MAX_SCALARS]; const void* p[MHH_MAX_SCALARS];
+            int n = 0;
+            for (auto& s : scalar_outflow) { f[n] = fields.sp.at(s)->fld_g; p[n] = inflow_profiles_g.at(s); ++n; }
+            launch(f, p, n, edges_mask, stream);
+        }
+    private:
+        void launch(void* const* f, const void* const* p, int n, int edges_mask, void* stream)
+        {
+            int dirs[4];
+            int e = 0;
+            for (Edge_location loc : {Edge_location::West, Edge_location::East, Edge_location::South, Edge_location::North})
+                dirs[e++] = flow_direction.at(loc) == Flow_direction::Inflow ? MHH_OUTFLOW_INFLOW : MHH_OUTFLOW_OUTFLOW;
+            mhh_grid g = grid.abi();
+            mhh_check(mhh_boundary_outflow_exec(&g, swspatialorder, f, n, p, dirs, edges_mask, stream));
+        }
+        Grid<TF>& grid;
+        std::map<Edge_location, Flow_direction> flow_direction;
+};
+
 } // namespace mhh_host

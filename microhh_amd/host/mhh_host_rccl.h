@@ -285,9 +285,23 @@ class Substep_slab
             if (ev_done) (void)hipEventDestroy(ev_done);
             if (comm_stream) (void)hipStreamDestroy(comm_stream);
         }
+        // Open lateral boundaries (Boundary_outflow): the fill has to follow the north-south exchange that the overlapped sub-step
+        // hides behind the interior rows, so with it can_overlap() is false and the sub-step is the plain sequence, which starts with
+        // cyclic_outflow(). inflow_profiles_g: the device tables [kcells] per scalar of outflow.scalar_outflow
+        void set_outflow(Boundary_outflow<TF>* o, std::map<std::string, TF*> inflow_profiles_g) { outflow = o; inflow_profiles = std::move(inflow_profiles_g); }
+        // set_prognostic_cyclic_bcs + set_prognostic_outflow_bcs (src/model.cxx:346-347) on the slab: the exchange of all prognostic
+        // fields, then exec_all with this rank's edge mask (West and East on every rank, South on rank 0, North on rank npy-1)
+        void cyclic_outflow()
+        {
+            std::vector<TF*> prog{fields.mp.at("u")->fld_g, fields.mp.at("v")->fld_g, fields.mp.at("w")->fld_g};
+            for (auto& it : fields.sp) prog.push_back(it.second->fld_g);
+            halo.exec_g(prog);
+            if (outflow) outflow->exec_all(fields, inflow_profiles, outflow->edges(), master.stream);
+        }
         bool can_overlap(const Advec<TF>& advec, const Diff<TF>& diff) const
         {
             const auto& gd = grid.get_grid_data();
+            if (outflow && !outflow->scalar_outflow.empty()) return false;
             return advec.get_scheme() == MHH_ADVEC_2I5 && diff.get_scheme() == MHH_DIFF_SMAG2 && !fields.sp.empty() && fields.sp.size() <= MHH_MAX_SCALARS
                    && advec.fluxlimit_list.empty() && gd.jgc >= 3 && gd.jmax >= 12;
         }
@@ -318,5 +332,6 @@ class Substep_slab
     private:
         Master_rccl& master; Grid<TF>& grid; Fields<TF>& fields; Boundary_cyclic_slab<TF>& halo;
         hipStream_t comm_stream = nullptr; hipEvent_t ev_ready = nullptr, ev_done = nullptr;
+        Boundary_outflow<TF>* outflow = nullptr; std::map<std::string, TF*> inflow_profiles;
 };
 } // namespace mhh_host

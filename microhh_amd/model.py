@@ -113,7 +113,7 @@ class HotPath:
     def __init__(self, case, itot, jtot, ktot, dtype=np.float64, device="cuda:0", seed=666, dt=1.0,
                  lib=None, npy=1, rank=0, group=None, global_init=None, force_slab=False, slim_halos=True, overlap=None, pres_chunks=None, igc=None,
                  nscalars=None, forcing=None, surface=None, thermo=None, micro=None, radiation=None, stats=None, budget=None, cross=None, ib=None,
-                 source=None, decay=None):
+                 source=None, decay=None, outflow=None):
         import torch
         if budget is not None and stats is None:
             raise ValueError("budget= needs stats=Stats(...): the budget profiles are averaged under the masks of the statistics")
@@ -266,7 +266,10 @@ class HotPath:
         self._prog = [self.u, self.v, self.w] + self.s
         # (with a surface layer dudz, dvdz, dbdz change every sub-step and are written on the interior only, as in the reference:
         # evisc is then exchanged like any field instead of being re-evaluated on the ghost rows)
-        self.evisc_local_ghosts = self.slab and self.slim and cfg["diff"] == DIFF_SMAG2 and g.jgc >= 2 and surface is None
+        # (with open boundaries for scalar 0, which feeds N2, the re-evaluated ghost rows would differ from the reference's cyclic
+        # fill of evisc at South and North: exchanged too, see outflow.py)
+        self.evisc_local_ghosts = (self.slab and self.slim and cfg["diff"] == DIFF_SMAG2 and g.jgc >= 2 and surface is None
+                                   and not (outflow is not None and 0 in outflow.scalars))
         if self.evisc_local_ghosts:
             p.evisc_ghost_rows = 1
             for k in ("dudz", "dvdz", "dbdz", "z0m"):
@@ -285,6 +288,8 @@ class HotPath:
         # in front of Stats, whose couvreux mask asks the decay for its scalar
         self.source = source.bind(self) if source is not None else None
         self.decay = decay.bind(self) if decay is not None else None
+        # Boundary_outflow (outflow.Outflow): the inflow tables of the open scalars on the device, the edges this rank owns
+        self.outflow = outflow.bind(self) if outflow is not None else None
         # Stats (stats.Stats): the mask words, counts and reduction scratch; sampled outside the step by hp.stats.sample()
         self.stats = stats.bind(self) if stats is not None else None
         # Budget_2 (budget.Budget2): the budget group of the statistics, sampled with them after Stats' own passes
@@ -383,11 +388,16 @@ class HotPath:
     def cyclic_prognostic(self):
         self.halo(self._prog)
 
+    def outflow_bcs(self):
+        """boundary->set_prognostic_outflow_bcs (src/model.cxx:347, :383): nothing without `outflow`."""
+        if self.outflow is not None:
+            self.outflow.exec()
+
     # -- the north-south exchange of the prognostic fields hidden behind the rows that do not need it -------------------
     @property
     def can_overlap(self):
         g = self.grid
-        return (self.slab and self.overlap and self.evisc_local_ghosts and self.cfg["advec"] == ADVEC_2I5 and self.cfg["diff"] == DIFF_SMAG2
+        return (self.slab and self.overlap and self.evisc_local_ghosts and self.outflow is None and self.cfg["advec"] == ADVEC_2I5 and self.cfg["diff"] == DIFF_SMAG2
                 and len(self.s) >= 1 and g.jgc >= 3 and g.jmax >= 12)      # 1 .. MHH_MAX_SCALARS scalars, none flux-limited (HotPath limits none): as Substep_slab::can_overlap
 
     def halo_visc_rhs(self, ev=None):
@@ -577,13 +587,16 @@ class HotPath:
         sequence on a slab too, with the two calls of src/model.cxx:380 and :407: the scalars' ghost cells after the surface layer and
         in front of the RHS, those of u, v, w after Buffer and Force and in front of the pressure solve. With `source` or `decay`
         (source.Sources, source.Decay), the order of src/model.cxx:395-404: Buffer, decay, source, Force -- Buffer and Force as their own
-        passes, which have the bits of the fused one; without the two nothing changes."""
+        passes, which have the bits of the fused one; without the two nothing changes. With `outflow` (outflow.Outflow), the open scalars'
+        lateral ghost cells directly after the cyclic fills (:347) and once more after ib->exec_scalars (:383) -- the plain sequence on
+        a slab too: the overlapped sub-step hides the exchange behind interior rows, and the fill has to follow that exchange."""
         means_done = False
         if self.thermo is not None:
             # Thermo_moist, in the order of Model::exec (src/model.cxx:346-392): the cyclic fills; fields->exec, the means of thl and qt
             # (:351); exec_viscosity, whose N2 reads the thvref the previous sub-step left (:354); thermo->exec, the base state from
             # the means and the buoyancy tendency in front of advec->exec (:366, :388)
             self.cyclic_prognostic()
+            self.outflow_bcs()
             if self.thermo.swupdate:
                 means_done = self.thermo.means()
             self.exec_viscosity()
@@ -596,23 +609,29 @@ class HotPath:
                 self.surface_layer()
             if self.ib is not None:            # ib->exec_scalars (:380), after the vertical ghost cells
                 self.ib.exec_scalars()
+                self.outflow_bcs()
             self.rhs()
         elif self.surface is not None:
             self.cyclic_prognostic()
+            self.outflow_bcs()
             self.exec_viscosity()
             self.surface_layer()
             if self.ib is not None:
                 self.ib.exec_scalars()
+                self.outflow_bcs()
             self.rhs()
         elif self.ib is not None:
             self.cyclic_prognostic()
+            self.outflow_bcs()
             self.exec_viscosity()
             self.ib.exec_scalars()
+            self.outflow_bcs()
             self.rhs()
         elif self.can_overlap:
             self.halo_visc_rhs()
         else:
             self.cyclic_prognostic()
+            self.outflow_bcs()
             self.exec_viscosity()
             self.rhs()
         if self.forcing is not None:
